@@ -1,11 +1,16 @@
 #!/usr/bin/env python3
 """Headline benchmark: denoising steps/s of the W8A8 Wan2.1-T2V-1.3B DiT at 832x480x81f on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 One step = conditional DiT pass + unconditional DiT pass + classifier-free-guidance combine + scheduler update
 (ViDiT-Q/examples/Wan2.1/wan/text2video.py:248-269) on synthetic latents / text context / random-init weights
 of the named architecture, all resident in HBM before the timed region.  Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times the K steps and prints the headline figure.  --full adds what takes work of its own:
+the timed calibration pass, an instrumented repeat of the K steps (rooflines, int8 fraction of the step), the quantized-vs-FP
+output quality and the CPU baseline.  --dump-outputs DIR writes the latent the last timed step returned as DIR/latent.npy
+(float32); the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -181,6 +186,11 @@ def main():
     ap.add_argument("--size", default="832*480")
     ap.add_argument("--frames", type=int, default=81)
     ap.add_argument("--guide", type=float, default=5.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also the timed calibration pass, the instrumented repeat of the K steps (rooflines), the quality figures and the "
+                         "CPU baseline; --no-cpu-baseline / --no-quality / --no-instrumented-repeat drop parts of it")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write the latent returned by the last timed step to DIR/latent.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-quality", action="store_true")
     ap.add_argument("--quant-config", dest="quant_config", default="w8a8_all_linears.yaml", help="file under quant_configs/")
@@ -285,7 +295,7 @@ def main():
     # (W/get_calib_data_wanx.py:262-267: one per-channel absmax of every Linear input per call)
     from viditq_extension import _C as wanq_C
     calib_report = None
-    if rank == 0:
+    if rank == 0 and args.full:
         ctimer = {}
         wanq_C.set_call_timer(ctimer)
         torch.cuda.synchronize()
@@ -327,7 +337,7 @@ def main():
     sharded = None
     if args.dit_fsdp and world > 1:
         sharded = model.shard_blocks(None)  # all ranks hold the same model: FULL_SHARD over the world
-    if world > 1 or args.no_quality:
+    if world > 1 or args.no_quality or not args.full:
         del fp
         torch.cuda.empty_cache()
 
@@ -381,33 +391,14 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = tmax.item()
     assert torch.isfinite(latent).all(), "non-finite latent after the timed steps"
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "latent.npy"), latent.float().cpu().numpy())
 
-    # ---- per-kernel timing for the roofline objects: the same K steps once more, with a HIP event pair around every GEMM /
-    # attention launch on the launch stream (about 1400 pairs per step, which is why they stay out of the headline region
-    # above; `instrumented_ms_per_step` shows what they cost).  share_of_step = kernel time / wall time of THIS region.
-    use_graph[0] = False  # launches must be eager to be bracketed by events
-    two.enabled = False   # ... and on ONE stream: beside another pass's kernels an event pair times the sharing, not the kernel
-    timer = GemmTimer()
-    atimer = GemmTimer()
-    qgemm.set_timer(timer)
-    wan_ops.set_attention_timer(atimer)
-    htimer = {}
-    wanq_C.set_call_timer(htimer)  # the HBM-bound row-wise kernels of the step (an event pair around each launch)
-    torch.cuda.synchronize()
-    tp0 = time.perf_counter()
-    for i in range(total, total + (0 if args.no_repeat else args.steps)):
-        latent = step(latent, i)
-    torch.cuda.synchronize()
-    dt_prof = max(time.perf_counter() - tp0, 1e-9)
-    qgemm.set_timer(None)
-    wan_ops.set_attention_timer(None)
-    wanq_C.set_call_timer(None)
-
-    gs = timer.summary()
     out = {
         "metric": "denoising steps/sec Wan2.1-%s %s %sx%df" % (args.model.split("-")[-1], "W4A8-mixed" if n_w4 else "W8A8", args.size.replace("*", "x"), args.frames), "value": args.steps / dt, "unit": "steps/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-        "instrumented_ms_per_step": dt_prof / args.steps * 1e3,
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "int8", "data": "synthetic",
         "config": {"workload": f"Wan2.1-{args.model} DiT, {n_quant} Linears W8A8{f' of which {n_w4} W4A8 (packed 4-bit weights)' if n_w4 else ''} (W asym per-channel static, A sym per-token dynamic; "
                                f"ViDiT-Q scale+rotate alpha=0.5665 on {n_vidit} self-attn q/k/v layers), "
@@ -426,71 +417,95 @@ def main():
                    # all_to_all_single): bytes leaving the GPU over xGMI per step, and the number of all-to-alls
                    "a2a_per_step": int(a2a[0]), "a2a_bytes_per_step": int(a2a[1])},
     }
-    # Two MFMA-bound kernels carry the step: the bf16 flash attention (the dominant one at L = 32760) and the int8 GEMM
-    # behind every W8A8 Linear.  `roofline` is whichever took more of the timed region; the other is reported beside it.
-    # `traffic`: HBM bytes per launch from the committed PMC passes (profiles/*_traffic.json: FETCH_SIZE x2 + WRITE_SIZE,
-    # one counter per rocprofv3 pass, averaged over the same launch mix); counters cannot be read inside this process.
-    lines = []
-    wkey = f"{args.model} {args.size} {args.frames}f n{world}"
-    g_traffic, g_src = pmc_traffic("gemm", wkey)
-    a_traffic, a_src = pmc_traffic("attention", wkey)
-    if attn_desc != "bf16" and a_traffic is not None:
-        a_traffic, a_src = None, a_src + " was taken on the bf16 attention kernel, not on this run's attention configuration"
-    if gs:
-        ach = gs["ops"] / gs["seconds"]
-        lines.append({"bound": "mfma", "kernel": "gemm_w8a8_pp_kernel (ping-pong persistent, W8) / gemm_w8a8_big_kernel (W4, GELU or 16-bit residual forms) / gemm_w8a8_kernel (small shapes): int8 MFMA, every quantised linear",
-                      "achieved": ach / 1e12, "peak": INT8_MFMA_PEAK / 1e12, "unit": "TOP/s", "frac": ach / INT8_MFMA_PEAK,
-                      "traffic": g_traffic, "traffic_source": g_src, "traffic_unit": "HBM bytes per launch (PMC)", "launches": gs["launches"],
-                      "avg_launch_us": gs["seconds"] / gs["launches"] * 1e6, "share_of_step": gs["seconds"] / dt_prof})
-    asum = atimer.summary()
-    if asum:
-        ach = asum["ops"] / asum["seconds"]
-        lines.append({"bound": "mfma", "kernel": "attn_fwd16_kernel (bf16 MFMA 16x16x32 flash attention, self + cross; WANQ_ATTN_M16=0: attn_fwd_kernel, 32x32x16)" if attn_desc == "bf16" else f"attn_fwd_kernel ({attn_desc})", "achieved": ach / 1e12,
-                      "peak": BF16_MFMA_PEAK / 1e12, "unit": "TFLOP/s", "frac": ach / BF16_MFMA_PEAK,
-                      "traffic": a_traffic, "traffic_source": a_src, "traffic_unit": "HBM bytes per launch (PMC)",
-                      "launches": asum["launches"], "avg_launch_us": asum["seconds"] / asum["launches"] * 1e6,
-                      "share_of_step": asum["seconds"] / dt_prof})
-    # whole-step int8 matrix work against the int8 MFMA roofline (north star: "throughput ... as fraction of the int8-MFMA roofline"):
-    # every W8A8 / W4A8 GEMM of the step, plus the Q.K^T half of the attention FLOPs where that runs on the int8 matrix cores
-    # (attn.qk configs).  With bf16 attention (the reference's Wan wiring) most of the step's time is not int8 work at all.
-    if gs:
-        qk_share = sum(1 for b_ in model.hip_blocks for f_ in (b_.attn_qk8,) if f_) / max(1, len(model.hip_blocks))
-        int8_ops = gs["ops"] / args.steps + (0.5 * asum["ops"] / args.steps * qk_share if (asum and qk_share) else 0.0)
-        out["int8_step"] = {"int8_ops_per_step": int8_ops, "achieved_TOPs": int8_ops * args.steps / dt / 1e12,
-                            "frac_of_int8_mfma_peak": int8_ops * args.steps / dt / INT8_MFMA_PEAK,
-                            "what": "all int8 MFMA work of a step / the step's wall time / 5.03 POP/s"}
-    lines.sort(key=lambda r: -r["share_of_step"])
-    if lines:
-        out["roofline"] = lines[0]
-    if len(lines) > 1:
-        out["roofline_second_kernel"] = lines[1]
-    # HBM-bound kernels of the step (north star: "HBM GB/s against gfx950 peak"): algorithmic bytes per launch (what the wrapper
-    # hands over: rows x cols x (input + output element sizes) + the per-token vectors / the rotary table) / the launch's
-    # duration between its own HIP events, against the 8 TB/s spec
-    hb = []
-    names = {"gelu_quant_sum": "quant_rows_wave_kernel<BF16,18,GELU> (GELU + per-token quantise of the FFN hidden)",
-             "quant_sum": "rowwise_kernel<..., false> (per-token quantise: attention output -> o, cross-attention output)",
-             "layernorm_quant": "rowwise_kernel<..., LN> (LayerNorm + modulate + per-token quantise)",
-             "layernorm_rotate_quant_x3": "rotate_kernel<12,1,4,LN,MULTI> (LayerNorm + modulate + ViDiT scale / rotate + quantise for q, k, v)",
-             "layernorm_rotate_quant": "rotate_kernel<..., LN> (LayerNorm + modulate + ViDiT scale / rotate + quantise, one consumer)",
-             "rotate_quant": "rotate_kernel / rotate140_kernel (ViDiT scale / rotate + quantise)",
-             "rmsnorm_rope": "rmsnorm_rope_kernel (RMSNorm + RoPE on q / k, in place)",
-             "rmsnorm_rope_scatter": "rmsnorm_rope_kernel<..., SC> (RMSNorm + RoPE stored into the Ulysses send images)",
-             "rmsnorm_rope_q8": "rmsnorm_rope_kernel<..., Q8> (RMSNorm + RoPE + per-(token, head) int8 codes for the int8 Q.K^T attention)", "rmsnorm": "rmsnorm_rope_kernel (RMSNorm only: cross-attention q / k)",
-             "layernorm": "rowwise_kernel<..., LN> (LayerNorm, fp output)"}
-    for tag, ev in htimer.items():
-        secs = sum(a.elapsed_time(b) for a, b, _ in ev) * 1e-3
-        nbytes = float(sum(n for _, _, n in ev))
-        if secs > 0:
-            hb.append({"kernel": names.get(tag, tag), "entry": tag, "launches_per_step": len(ev) / args.steps, "bytes_per_launch": nbytes / len(ev),
-                       "avg_us": secs / len(ev) * 1e6, "TBps": nbytes / secs / 1e12, "frac": nbytes / secs / HBM_PEAK,
-                       "share_of_step": secs / dt_prof})
-    hb.sort(key=lambda r: -r["share_of_step"])
-    if hb:
-        out["roofline_hbm"] = hb
+    if args.full:
+        # ---- per-kernel timing for the roofline objects: the same K steps once more, with a HIP event pair around every GEMM /
+        # attention launch on the launch stream (about 1400 pairs per step, which is why they stay out of the headline region
+        # above; `instrumented_ms_per_step` shows what they cost).  share_of_step = kernel time / wall time of THIS region.
+        use_graph[0] = False  # launches must be eager to be bracketed by events
+        two.enabled = False   # ... and on ONE stream: beside another pass's kernels an event pair times the sharing, not the kernel
+        timer = GemmTimer()
+        atimer = GemmTimer()
+        qgemm.set_timer(timer)
+        wan_ops.set_attention_timer(atimer)
+        htimer = {}
+        wanq_C.set_call_timer(htimer)  # the HBM-bound row-wise kernels of the step (an event pair around each launch)
+        torch.cuda.synchronize()
+        tp0 = time.perf_counter()
+        for i in range(total, total + (0 if args.no_repeat else args.steps)):
+            latent = step(latent, i)
+        torch.cuda.synchronize()
+        dt_prof = max(time.perf_counter() - tp0, 1e-9)
+        qgemm.set_timer(None)
+        wan_ops.set_attention_timer(None)
+        wanq_C.set_call_timer(None)
+
+        gs = timer.summary()
+        out["instrumented_ms_per_step"] = dt_prof / args.steps * 1e3
+        # Two MFMA-bound kernels carry the step: the bf16 flash attention (the dominant one at L = 32760) and the int8 GEMM
+        # behind every W8A8 Linear.  `roofline` is whichever took more of the timed region; the other is reported beside it.
+        # `traffic`: HBM bytes per launch from the committed PMC passes (profiles/*_traffic.json: FETCH_SIZE x2 + WRITE_SIZE,
+        # one counter per rocprofv3 pass, averaged over the same launch mix); counters cannot be read inside this process.
+        lines = []
+        wkey = f"{args.model} {args.size} {args.frames}f n{world}"
+        g_traffic, g_src = pmc_traffic("gemm", wkey)
+        a_traffic, a_src = pmc_traffic("attention", wkey)
+        if attn_desc != "bf16" and a_traffic is not None:
+            a_traffic, a_src = None, a_src + " was taken on the bf16 attention kernel, not on this run's attention configuration"
+        if gs:
+            ach = gs["ops"] / gs["seconds"]
+            lines.append({"bound": "mfma", "kernel": "gemm_w8a8_pp_kernel (ping-pong persistent, W8) / gemm_w8a8_big_kernel (W4, GELU or 16-bit residual forms) / gemm_w8a8_kernel (small shapes): int8 MFMA, every quantised linear",
+                          "achieved": ach / 1e12, "peak": INT8_MFMA_PEAK / 1e12, "unit": "TOP/s", "frac": ach / INT8_MFMA_PEAK,
+                          "traffic": g_traffic, "traffic_source": g_src, "traffic_unit": "HBM bytes per launch (PMC)", "launches": gs["launches"],
+                          "avg_launch_us": gs["seconds"] / gs["launches"] * 1e6, "share_of_step": gs["seconds"] / dt_prof})
+        asum = atimer.summary()
+        if asum:
+            ach = asum["ops"] / asum["seconds"]
+            lines.append({"bound": "mfma", "kernel": "attn_fwd16_kernel (bf16 MFMA 16x16x32 flash attention, self + cross; WANQ_ATTN_M16=0: attn_fwd_kernel, 32x32x16)" if attn_desc == "bf16" else f"attn_fwd_kernel ({attn_desc})", "achieved": ach / 1e12,
+                          "peak": BF16_MFMA_PEAK / 1e12, "unit": "TFLOP/s", "frac": ach / BF16_MFMA_PEAK,
+                          "traffic": a_traffic, "traffic_source": a_src, "traffic_unit": "HBM bytes per launch (PMC)",
+                          "launches": asum["launches"], "avg_launch_us": asum["seconds"] / asum["launches"] * 1e6,
+                          "share_of_step": asum["seconds"] / dt_prof})
+        # whole-step int8 matrix work against the int8 MFMA roofline (north star: "throughput ... as fraction of the int8-MFMA roofline"):
+        # every W8A8 / W4A8 GEMM of the step, plus the Q.K^T half of the attention FLOPs where that runs on the int8 matrix cores
+        # (attn.qk configs).  With bf16 attention (the reference's Wan wiring) most of the step's time is not int8 work at all.
+        if gs:
+            qk_share = sum(1 for b_ in model.hip_blocks for f_ in (b_.attn_qk8,) if f_) / max(1, len(model.hip_blocks))
+            int8_ops = gs["ops"] / args.steps + (0.5 * asum["ops"] / args.steps * qk_share if (asum and qk_share) else 0.0)
+            out["int8_step"] = {"int8_ops_per_step": int8_ops, "achieved_TOPs": int8_ops * args.steps / dt / 1e12,
+                                "frac_of_int8_mfma_peak": int8_ops * args.steps / dt / INT8_MFMA_PEAK,
+                                "what": "all int8 MFMA work of a step / the step's wall time / 5.03 POP/s"}
+        lines.sort(key=lambda r: -r["share_of_step"])
+        if lines:
+            out["roofline"] = lines[0]
+        if len(lines) > 1:
+            out["roofline_second_kernel"] = lines[1]
+        # HBM-bound kernels of the step (north star: "HBM GB/s against gfx950 peak"): algorithmic bytes per launch (what the wrapper
+        # hands over: rows x cols x (input + output element sizes) + the per-token vectors / the rotary table) / the launch's
+        # duration between its own HIP events, against the 8 TB/s spec
+        hb = []
+        names = {"gelu_quant_sum": "quant_rows_wave_kernel<BF16,18,GELU> (GELU + per-token quantise of the FFN hidden)",
+                 "quant_sum": "rowwise_kernel<..., false> (per-token quantise: attention output -> o, cross-attention output)",
+                 "layernorm_quant": "rowwise_kernel<..., LN> (LayerNorm + modulate + per-token quantise)",
+                 "layernorm_rotate_quant_x3": "rotate_kernel<12,1,4,LN,MULTI> (LayerNorm + modulate + ViDiT scale / rotate + quantise for q, k, v)",
+                 "layernorm_rotate_quant": "rotate_kernel<..., LN> (LayerNorm + modulate + ViDiT scale / rotate + quantise, one consumer)",
+                 "rotate_quant": "rotate_kernel / rotate140_kernel (ViDiT scale / rotate + quantise)",
+                 "rmsnorm_rope": "rmsnorm_rope_kernel (RMSNorm + RoPE on q / k, in place)",
+                 "rmsnorm_rope_scatter": "rmsnorm_rope_kernel<..., SC> (RMSNorm + RoPE stored into the Ulysses send images)",
+                 "rmsnorm_rope_q8": "rmsnorm_rope_kernel<..., Q8> (RMSNorm + RoPE + per-(token, head) int8 codes for the int8 Q.K^T attention)", "rmsnorm": "rmsnorm_rope_kernel (RMSNorm only: cross-attention q / k)",
+                 "layernorm": "rowwise_kernel<..., LN> (LayerNorm, fp output)"}
+        for tag, ev in htimer.items():
+            secs = sum(a.elapsed_time(b) for a, b, _ in ev) * 1e-3
+            nbytes = float(sum(n for _, _, n in ev))
+            if secs > 0:
+                hb.append({"kernel": names.get(tag, tag), "entry": tag, "launches_per_step": len(ev) / args.steps, "bytes_per_launch": nbytes / len(ev),
+                           "avg_us": secs / len(ev) * 1e6, "TBps": nbytes / secs / 1e12, "frac": nbytes / secs / HBM_PEAK,
+                           "share_of_step": secs / dt_prof})
+        hb.sort(key=lambda r: -r["share_of_step"])
+        if hb:
+            out["roofline_hbm"] = hb
     if calib_report is not None:
         out["calibration"] = calib_report
-    if rank == 0 and world == 1 and not args.no_quality:
+    if args.full and rank == 0 and world == 1 and not args.no_quality:
         # deviation of the quantized DiT output from the FP (bf16-autocast) output of the same synthetic model
         t = sched.timesteps[0:1]
         with torch.no_grad():
@@ -501,7 +516,7 @@ def main():
         rng = (yf.max() - yf.min()).item()
         out["quality"] = {"tensor": "DiT output latent (noise_pred)", "rel_l2_vs_fp": ((yq - yf).norm() / yf.norm()).item(),
                           "psnr_db_vs_fp": 10 * torch.log10(torch.tensor(rng * rng / mse)).item()}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:  # reported at N = 1 only
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:  # reported at N = 1 only
         out["cpu_baseline"] = cpu_baseline(cfg, seq_len, n_vidit_per_block=n_vidit // max(1, cfg["num_layers"]))
     if rank == 0:
         if rehearse:

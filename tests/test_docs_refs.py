@@ -42,15 +42,12 @@ def test_every_cited_path_exists():
 
 def test_reference_citations_name_real_files_and_lines():
     """Every `file:line` citation of the reference -- the header's "replaces ..." notes, the product's and the oracle's docstrings, the
-    documents -- names a file of the reference tree and lines inside it (tools/check_citations.py).  Needs /root/reference: skipped on a
-    box without it (the GPU box)."""
+    documents -- names a file of the reference tree and lines inside it (tools/check_citations.py), checked against the recorded file
+    list and line counts of that tree (tests/golden/reference_tree.json)."""
     import subprocess
     import sys
 
-    import pytest
-
-    if not os.path.isdir("/root/reference"):
-        pytest.skip("the reference tree is not on this box")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_citations.py"), "--all"], capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_citations.py"), "--all",
+                        "--index", os.path.join(ROOT, "tests", "golden", "reference_tree.json")], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-3000:]
     assert int(r.stdout.split()[0]) > 300

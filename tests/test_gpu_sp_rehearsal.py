@@ -98,7 +98,7 @@ def test_bench_multi_rank_control_flow_rehearsal(gpus, plan, extra, launcher):
     import json
 
     root = os.path.dirname(HERE)
-    args = ["--gpus", str(gpus), "--steps", "1", "--warmup", "0", "--frames", "9", "--no-cpu-baseline", "--no-quality", *extra]
+    args = ["--gpus", str(gpus), "--steps", "1", "--warmup", "0", "--frames", "9", "--full", "--no-cpu-baseline", "--no-quality", *extra]
     if launcher == "self":
         cmd = [sys.executable, os.path.join(root, "bench.py"), *args]
     else:
@@ -132,7 +132,7 @@ def test_bench_single_rank_line_has_every_key_of_the_contract():
     env = dict(os.environ, OMP_NUM_THREADS="8")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "WANQ_BENCH_REHEARSE_ON_ONE_GPU"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--frames", "9"], env=env,
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--frames", "9", "--full"], env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -147,6 +147,36 @@ def test_bench_single_rank_line_has_every_key_of_the_contract():
     assert all(abs(h["frac"] - h["TBps"] / 8.0) < 1e-9 for h in out["roofline_hbm"])
     cb = out["cpu_baseline"]
     assert cb["kind"] == "port" and 1 <= cb["cores"] <= cb["cores_available"] and cb["value"] > 0 and cb["cfg_a"]["value"] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs_match_the_full_run(tmp_path):
+    """`python bench.py` without --full carries the headline keys only; --dump-outputs writes the latent of the last timed step, and the
+    plain and the --full run (timed calibration pass, instrumented repeat after the dump) dump the same values."""
+    import json
+
+    import numpy as np
+
+    root = os.path.dirname(HERE)
+    env = dict(os.environ, OMP_NUM_THREADS="8")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "WANQ_BENCH_REHEARSE_ON_ONE_GPU"):
+        env.pop(k, None)
+    outs = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-quality"])):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--frames", "9",
+                            "--dump-outputs", str(tmp_path / mode), *extra], env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        outs[mode] = json.loads(lines[0])
+    plain = outs["plain"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in plain, k
+    assert plain["steps"] == 2 and abs(plain["value"] * plain["ms_per_step"] - 1e3) < 1e-6
+    assert not {"roofline", "roofline_hbm", "calibration", "int8_step", "quality", "cpu_baseline", "instrumented_ms_per_step"} & set(plain)
+    assert "roofline" in outs["full"] and "calibration" in outs["full"]
+    a, b = np.load(tmp_path / "plain" / "latent.npy"), np.load(tmp_path / "full" / "latent.npy")
+    assert a.dtype == np.float32 and a.shape == (16, 3, 60, 104) and np.isfinite(a).all()
+    np.testing.assert_array_equal(a, b)
 
 
 def test_rccl_backend_single_rank_collective_forms():

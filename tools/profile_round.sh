@@ -1,7 +1,7 @@
 #!/bin/bash
 # Everything profiles/rNN_<tag>_* is made from, in one gpurun call:  tools/profile_round.sh r02_b <code tag>
 #   1. full pytest -m gpu                      -> gpurun_out/<tag>_tests.log
-#   2. bench.py (default flags)                -> gpurun_out/<tag>_bench_line.txt
+#   2. bench.py --full                         -> <tag>_bench_line.txt in the output folder
 #   3. rocprofv3 --kernel-trace --stats of a 2-step bench.py  -> gpurun_out/<tag>_prof/  (+ step breakdown)
 #   4. PMC passes (FETCH_SIZE, WRITE_SIZE separately; never together with a trace domain) over the GEMM and attention
 #      launches of one cfg-B block            -> gpurun_out/<tag>_{gemm,attention}_traffic.{csv,json}
@@ -17,14 +17,14 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
   rc=$?; echo "pytest rc=$rc" >> "$OUT/${TAG}_tests.log"; tail -4 "$OUT/${TAG}_tests.log"
   [ $rc -eq 0 ] || exit $rc
 fi
-timeout -k 10 600 python bench.py > "$OUT/${TAG}_bench_line.txt" 2> "$OUT/${TAG}_bench.err" || { tail -5 "$OUT/${TAG}_bench.err"; exit 1; }
+timeout -k 10 600 python bench.py --full > "$OUT/${TAG}_bench_line.txt" 2> "$OUT/${TAG}_bench.err" || { tail -5 "$OUT/${TAG}_bench.err"; exit 1; }
 cat "$OUT/${TAG}_bench_line.txt"
 # per-kernel statistics and the step breakdown are taken with the two passes of a step on ONE stream (--pass-streams 1): on two streams
 # (what the default, auto, may pick: wan/utils/two_pass.py) kernels of the two passes share the GPU and a kernel's traced duration is no
 # longer its own time
-timeout -k 10 600 python bench.py --pass-streams 1 --no-cpu-baseline --no-quality > "$OUT/${TAG}_bench_line_one_stream.txt" 2>> "$OUT/${TAG}_bench.err" || { tail -5 "$OUT/${TAG}_bench.err"; exit 1; }
+timeout -k 10 600 python bench.py --full --pass-streams 1 --no-cpu-baseline --no-quality > "$OUT/${TAG}_bench_line_one_stream.txt" 2>> "$OUT/${TAG}_bench.err" || { tail -5 "$OUT/${TAG}_bench.err"; exit 1; }
 MS=$(python3 -c "import json,sys; print(json.loads(open('$OUT/${TAG}_bench_line_one_stream.txt').read().strip().splitlines()[-1])['ms_per_step'])")
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_prof" -o "$TAG" -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-quality --pass-streams 1 > "$OUT/${TAG}_prof_bench.log" 2>&1 || { tail -5 "$OUT/${TAG}_prof_bench.log"; exit 1; }
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_prof" -o "$TAG" -- python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-quality --pass-streams 1 > "$OUT/${TAG}_prof_bench.log" 2>&1 || { tail -5 "$OUT/${TAG}_prof_bench.log"; exit 1; }
 TRACE=$(find "$OUT/${TAG}_prof" -name "*kernel_trace.csv" | head -1)
 python3 tools/step_breakdown.py "$TRACE" --ms "$MS" --title "$TAG, $CODE" > "$OUT/${TAG}_step_breakdown.txt" && head -14 "$OUT/${TAG}_step_breakdown.txt"
 for W in gemm attention; do
