@@ -222,7 +222,7 @@ int64_t wanq_attention_select_form(int64_t nw4_keys);
  *   o[q,h,:] = softmax_k( (q8[q,h,:] . k8[k,h,:]) * delta_q[h][q] * delta_k[h][k] * scale ) v[k,h,:]
  * q8 / k8: int8 [tokens, heads*128] with byte strides q8_stride / k8_stride; q_scale: fp32 [heads][qs_stride]; k_scale: fp32
  * two planes [heads][ks_stride] (delta_k, then -12582912*delta_k: the layout wanq_rmsnorm_rope_q8 writes), ks_stride >= Lk
- * rounded up to 64.  S = K8.Q8^T on v_mfma_i32_32x32x32_i8 (integer-exact), P.V in bf16 as above; v / o bf16.
+ * rounded up to 64.  S = K8.Q8^T on v_mfma_i32_16x16x64_i8 (integer-exact), P.V in bf16 as above; v / o bf16.
  * splits as in wanq_attention_fwd_split (1 = none; workspace from wanq_attention_split_workspace).
  * The reference wires this recipe for OpenSORA only (Q/base/quant_attn.py is imported, not used, by its Wan model). */
 int wanq_attention_qk8_fwd(const int8_t* q8, const float* q_scale, int64_t qs_stride, const int8_t* k8,
