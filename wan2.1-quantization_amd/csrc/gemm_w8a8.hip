@@ -14,63 +14,18 @@
 // ds_read_b128 fragment reads and ds_write_b128 staging writes are both bank-conflict free.
 // Workgroup ids are remapped so that each XCD's L2 sees a compact (8 m-tiles x n) panel.
 #include "gemm_params.h"
-#include <stdlib.h>
 
 namespace wanq {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
-template <int OUT>
-__device__ __forceinline__ uint2 pack16x4(const float (&y)[4]) {
-  uint2 v;
-  if (OUT == WANQ_F16) {
-    // the fp32 value first, then its cast (the reference's order, w8a8_gemm_cuda.cu:416-442): without the opaque copies hipcc may
-    // contract the last fma and the cast into v_fma_mixlo_f16 -- one rounding instead of two, a different half in rare cases, and
-    // which of the two a kernel gets depends on the code around it
-    float z[4] = {y[0], y[1], y[2], y[3]};
-    asm volatile("" : "+v"(z[0]), "+v"(z[1]), "+v"(z[2]), "+v"(z[3]));
-    __half2* h = reinterpret_cast<__half2*>(&v);
-    h[0] = __floats2half2_rn(z[0], z[1]);
-    h[1] = __floats2half2_rn(z[2], z[3]);
-  } else {
-    uint16_t b[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const __hip_bfloat16 t = __float2bfloat16(y[j]);
-      b[j] = *reinterpret_cast<const uint16_t*>(&t);
-    }
-    v = make_uint2((uint32_t)b[0] | ((uint32_t)b[1] << 16), (uint32_t)b[2] | ((uint32_t)b[3] << 16));
-  }
-  return v;
-}
-
 constexpr int BM = 128, BN = 128, BK = 128;
 constexpr int STAGE_BYTES = (BM + BN) * BK;  // 32 KiB
-constexpr int GROUP_M = 4;  // m-tiles per L2 panel (sweep 2..32 on cfg-B: 4 best, 8 within 1-3 %; WANQ_GEMM_GROUP_M overrides)
-// kernel selection (wanq_gemm_select_kernel; environment at start-up: WANQ_GEMM_V1=1 -> 1, WANQ_GEMM_PP=0 -> 2)
-static int g_kernel_sel = [] {
-  const char* v1 = getenv("WANQ_GEMM_V1");
-  const char* pp = getenv("WANQ_GEMM_PP");
-  return (v1 && v1[0] == '1') ? 1 : (pp && pp[0] == '0') ? 2 : 0;
-}();
+constexpr int GROUP_M = 4;  // m-tiles per L2 panel (sweep 2..32 on cfg-B: 4 best, 8 within 1-3 %)
+static int g_kernel_sel = 0;  // kernel selection, set by wanq_gemm_select_kernel
 
 __device__ __forceinline__ int lds_off(int row, int chunk) { return row * BK + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
-__device__ __forceinline__ void load4_ch(const void* p, int dt, int idx, float (&o)[4]) {
-  if (dt == WANQ_F32) {
-    const float4 v = *reinterpret_cast<const float4*>(static_cast<const float*>(p) + idx);
-    o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-  } else if (dt == WANQ_F16) {
-    const uint2 v = *reinterpret_cast<const uint2*>(static_cast<const __half*>(p) + idx);
-    const __half2* h = reinterpret_cast<const __half2*>(&v);
-    const float2 a = __half22float2(h[0]), b = __half22float2(h[1]);
-    o[0] = a.x; o[1] = a.y; o[2] = b.x; o[3] = b.y;
-  } else {  // WANQ_I16
-    const short4 v = *reinterpret_cast<const short4*>(static_cast<const short*>(p) + idx);
-    o[0] = (float)v.x; o[1] = (float)v.y; o[2] = (float)v.z; o[3] = (float)v.w;
-  }
-}
 
 template <int OUT>
 struct OutIo;
@@ -280,7 +235,7 @@ __global__ __launch_bounds__(256, 2) void gemm_w8a8_kernel(const GemmParams p) {
 // v2 (large M): persistent kernel, 256(M) x 256(N) tile, 8 waves as 2(M) x 4(N), each wave 128 tokens x 64
 // channels = 8 x 4 blocks of v_mfma_i32_16x16x64_i8 (12 ds_read_b128 per 32 MFMAs).
 //  * MFMA shape: the 16x16x64 form does the same work per cycle as 32x32x32 but the part holds a higher clock under it (the
-//    chip is clock/power-limited in this kernel: 1.45-1.85 GHz measured inside it, tools/probes/clock_probe_run.py; bare
+//    chip is clock/power-limited in this kernel: 1.45-1.85 GHz measured inside it, profiles/r02_g_kernel_clock_probe.txt; bare
 //    streams: 4.25 vs 3.74 POP/s, tools/probes/mfma_shape_clock.hip).  Same LDS bytes per MFMA cycle, same LDS image.
 //  * Both operands go global -> LDS directly (global_load_lds_dwordx4, 16 B per lane, one 1-KiB wave
 //    instruction = 8 rows x 128 B); the LDS image stays lane-linear and the bank swizzle is applied on the
@@ -293,9 +248,6 @@ __global__ __launch_bounds__(256, 2) void gemm_w8a8_kernel(const GemmParams p) {
 //    stores), so the epilogue's stores drain to HBM underneath the next tile's main loop instead of stalling
 //    every CU at the same time.
 // Used when M >= 512 and K % 128 == 0; everything else takes the v1 kernel.
-#ifdef WANQ_CLOCK_PROBE  // diagnostic build only: shader clock held by one workgroup of the persistent kernel
-__device__ unsigned long long g_gemm_clk[2];
-#endif
 constexpr int B2M = 256, B2N = 256, B2K = 128;
 constexpr int B2_STAGE = (B2M + B2N) * B2K;  // 64 KiB
 
@@ -454,9 +406,6 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_big_kernel(const GemmParams 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave & 1, wn = wave >> 1;
-#ifdef WANQ_CLOCK_PROBE
-  const unsigned long long clk_c0 = clock64(), clk_w0 = wall_clock64();
-#endif
   const int fr = lane & 31, fh = lane >> 5;
   const int K = p.K;
   const int nk = K / B2K;
@@ -757,9 +706,6 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_big_kernel(const GemmParams 
         }
       }
     }
-#ifdef WANQ_CLOCK_PROBE
-    if (next >= ntiles && blockIdx.x == 77 && tid == 0) { g_gemm_clk[0] = clock64() - clk_c0; g_gemm_clk[1] = wall_clock64() - clk_w0; }
-#endif
     if (next >= ntiles) break;
     // A full tile issues exactly 16 (16-bit output) or 32 store instructions per wave after the LDS-DMA above; a ragged
     // tile may issue fewer (whole-wave skips), so it falls back to a full drain.
@@ -794,14 +740,6 @@ static int launch_gemm(GemmParams p, hipStream_t st) {
     const int tiles = p.mt * p.nt;
     const int grid = tiles < 256 ? ((tiles + 7) & ~7) : 256;  // one workgroup per CU; % 8 == 0 for the XCD ranges
     hipLaunchKernelGGL((gemm_w8a8_big_kernel<OUT, W4>), dim3((unsigned)grid), dim3(512), 2 * B2_STAGE, st, p);
-#ifdef WANQ_CLOCK_PROBE
-    {
-      (void)hipStreamSynchronize(st);
-      unsigned long long h[2];
-      (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_gemm_clk), sizeof(h));
-      printf("[clock] gemm M=%d N=%d K=%d: %llu cycles in %.1f us -> %.0f MHz\n", p.M, p.N, p.K, h[0], h[1] / 100.0, h[0] / (h[1] / 100.0));
-    }
-#endif
   } else {
     hipLaunchKernelGGL((gemm_w8a8_kernel<OUT, W4>), dim3((unsigned)(p.mt * p.nt)), dim3(256), 2 * STAGE_BYTES, st, p);
   }
@@ -830,11 +768,10 @@ static int gemm_entry(bool w4, const int8_t* a, const void* w, void* out, int ou
   }
   WANQ_REQUIRE((epi_flags & ~(WANQ_EPI_GELU | WANQ_EPI_GATE_RES)) == 0, WANQ_E_ARG, "%s: unknown epilogue flag", what);
   if (M == 0) return WANQ_OK;
-  static const int group_m = [] { const char* e = getenv("WANQ_GEMM_GROUP_M"); const int v = e ? atoi(e) : 0; return v > 0 ? v : GROUP_M; }();
   GemmParams p{};
   p.a = a; p.w = static_cast<const int8_t*>(w); p.out = out; p.sa = sa; p.asum = asum; p.sw = sw; p.bias = bias; p.zp = zp; p.gate = gate;
   p.residual = residual; p.tok_dtype = tok_dtype; p.ch_dtype = ch_dtype; p.zp_dtype = zp_dtype; p.epi = epi_flags;
-  p.M = (int)M; p.N = N; p.K = K; p.group_m = group_m;
+  p.M = (int)M; p.N = N; p.K = K; p.group_m = GROUP_M;
   p.mt = (int)((M + BM - 1) / BM);
   p.nt = (N + BN - 1) / BN;
   WANQ_REQUIRE((int64_t)p.mt * p.nt < (1ll << 31), WANQ_E_SHAPE, "%s: too many tiles", what);

@@ -20,7 +20,7 @@
 //   * The issue stream runs two K-tiles ahead of the compute stream and does not know about tile boundaries: the first
 //     K-tiles of the workgroup's NEXT output tile arrive under the last K-tiles of this one.
 //
-// Schedule of one K-tile t, WANQ_PP_BURST = 32 (shipped; slots relative to group 0's first burst, G0 bursts in even slots):
+// Schedule of one K-tile t (slots relative to group 0's first burst, G0 bursts in even slots):
 //   slot  group  phase  fragment reads                 LDS-DMA issued (4 pieces per wave)
 //   -1    G0     LA     X0a(t), Wa(t), Wb(t)  (16)     X0a, X0b (t+1)
 //    0    G1     LA     X1a(t), Wa(t), Wb(t)           X1a, X1b (t+1)
@@ -31,8 +31,8 @@
 // one before it (vmcnt(4)): W(t+1) behind QA(t), X(t+1) behind QB(t) -- 3.5 slots after its issue, one barrier before its first
 // reader (the issuing waves' wait, then the barrier every reader passes).  Write-after-read: W is re-filled ONE slot after its
 // last reader (G1's LA), so load phases finish their reads (lgkmcnt(0)) in front of their barrier; X two slots after.
-// WANQ_PP_BURST = 16 builds the first form (four phases per K-tile, 16-MFMA bursts, one 8-KiB chunk per slot, vmcnt(10) at the
-// end of every load phase: 2775 cycles per K-tile against 2500-2600; kept for the A/B of profiles/r04_l_*, r04_m_*).
+// Why 32-MFMA bursts: the first form (four phases per K-tile, 16-MFMA bursts, one 8-KiB chunk per slot) paid ~90 cycles of
+// barrier / refill per 256: 2775 cycles per K-tile against 2500-2600 (profiles/r04_b_gemm_pingpong_clock.txt, r04_l_*, r04_m_*).
 //
 // Epilogue: the v2 kernel's store path (per-wave 4-KiB LDS turn buffers -> whole 128-B lines); the tile's per-token and
 // per-channel values are prefetched by LDS-DMA into the wave's idle turn buffer two K-tiles ahead (all-fp32 parameter sets;
@@ -42,7 +42,6 @@
 // gate + residual epilogue needs 64 KiB for its residual prefetch ring: its kernels do not request the next tile's second
 // K-tile under the last K-tile, use that buffer for the ring and request it behind the store loop.
 #include "gemm_params.h"
-#include <stdlib.h>
 #include <type_traits>
 
 namespace wanq {
@@ -57,59 +56,10 @@ constexpr int PBUF = (PM + PN) * PK;  // one K-tile buffer: 64 KiB
 constexpr int PXB = PM * PK;          // offset of the W rows inside a buffer
 constexpr int PTURN = 2 * PBUF;       // eight 4-KiB turn buffers behind the ring
 constexpr int PLDS = PTURN + 8 * 4096;  // 160 KiB
-#if (defined(WANQ_PP_ABL_NODMA) || defined(WANQ_PP_ABL_NOREAD)) && !defined(WANQ_ALLOW_ABLATIONS)
-#error "WANQ_PP_ABL_* build deliberately wrong kernels (timing ablations): add -DWANQ_ALLOW_ABLATIONS, never in build.py's library"
-#endif
-#ifndef WANQ_PP_BURST
-#define WANQ_PP_BURST 32  // MFMAs per burst: 32 (two phases per K-tile, the shipped schedule) or 16 (four phases, the first form)
-#endif
 
 template <int OFF>
 __device__ __forceinline__ void dsr(v4i& d, uint32_t addr) {
-#ifdef WANQ_PP_ABL_NOREAD  // timing-only diagnostic build: fragments are never read (wrong results)
-  asm volatile("" : "=v"(d) : "v"(addr));
-#else
   asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF));
-#endif
-}
-
-template <int OUT>
-__device__ __forceinline__ uint2 pack16x4(const float (&y)[4]) {
-  uint2 v;
-  if (OUT == WANQ_F16) {
-    // the fp32 value first, then its cast (the reference's order, w8a8_gemm_cuda.cu:416-442): without the opaque copies hipcc may
-    // contract the last fma and the cast into v_fma_mixlo_f16 -- one rounding instead of two, a different half in rare cases, and
-    // which of the two a kernel gets depends on the code around it
-    float z[4] = {y[0], y[1], y[2], y[3]};
-    asm volatile("" : "+v"(z[0]), "+v"(z[1]), "+v"(z[2]), "+v"(z[3]));
-    __half2* h = reinterpret_cast<__half2*>(&v);
-    h[0] = __floats2half2_rn(z[0], z[1]);
-    h[1] = __floats2half2_rn(z[2], z[3]);
-  } else {
-    uint16_t b[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const __hip_bfloat16 t = __float2bfloat16(y[j]);
-      b[j] = *reinterpret_cast<const uint16_t*>(&t);
-    }
-    v = make_uint2((uint32_t)b[0] | ((uint32_t)b[1] << 16), (uint32_t)b[2] | ((uint32_t)b[3] << 16));
-  }
-  return v;
-}
-
-__device__ __forceinline__ void load4_ch(const void* p, int dt, int idx, float (&o)[4]) {
-  if (dt == WANQ_F32) {
-    const float4 v = *reinterpret_cast<const float4*>(static_cast<const float*>(p) + idx);
-    o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-  } else if (dt == WANQ_F16) {
-    const uint2 v = *reinterpret_cast<const uint2*>(static_cast<const __half*>(p) + idx);
-    const __half2* h = reinterpret_cast<const __half2*>(&v);
-    const float2 a = __half22float2(h[0]), b = __half22float2(h[1]);
-    o[0] = a.x; o[1] = a.y; o[2] = b.x; o[3] = b.y;
-  } else {  // WANQ_I16
-    const short4 v = *reinterpret_cast<const short4*>(static_cast<const short*>(p) + idx);
-    o[0] = (float)v.x; o[1] = (float)v.y; o[2] = (float)v.z; o[3] = (float)v.w;
-  }
 }
 
 // The tile's dequantisation values of one lane: its 16 channels (4 per channel block i) and its 8 tokens (one per token block j)
@@ -394,9 +344,6 @@ __device__ __forceinline__ void store32_res(const GemmParams& p, v4i (&acc)[4][8
 #undef PP_RES_DMA
 }
 
-#ifdef WANQ_PP_CLOCK  // diagnostic build only: shader clock and cycles of one workgroup's first K loop
-__device__ unsigned long long g_pp_clk[4];
-#endif
 template <int OUT, bool RES>  // RES: gate + residual epilogue (fp32 output only); an instantiation of its own for the register allocator
 __global__ __launch_bounds__(512, 2) void gemm_w8a8_pp_kernel(const GemmParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -449,21 +396,11 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_pp_kernel(const GemmParams p
   const int dstw = PXB + (g * 64 + c * 16) * PK;   // + 16384 for half b, + 1024 q
   int tileI, kI = 0;
   uint32_t kIoff = 0, bI = 0;
-#ifdef WANQ_PP_ABL_NODMA  // timing-only diagnostic build: no LDS-DMA behind the prologue (wrong results)
-#define PP_ISSUE(base, src, dst)                                                                                   \
-  do {                                                                                                             \
-    if (pp_prologue) {                                                                                             \
-      _Pragma("unroll") for (int q_ = 0; q_ < 2; ++q_)                                                             \
-        __builtin_amdgcn_global_load_lds((glb_void*)((base) + kIoff + src[q_]), (lds_void*)(smem + bI + (dst) + q_ * 1024), 16, 0, 0); \
-    }                                                                                                              \
-  } while (0)
-#else
 #define PP_ISSUE(base, src, dst)                                                                                   \
   do {                                                                                                             \
     _Pragma("unroll") for (int q_ = 0; q_ < 2; ++q_)                                                               \
       __builtin_amdgcn_global_load_lds((glb_void*)((base) + kIoff + src[q_]), (lds_void*)(smem + bI + (dst) + q_ * 1024), 16, 0, 0); \
   } while (0)
-#endif
 #define PP_ISSUE_XA() PP_ISSUE(p.a, sxa, dstx)
 #define PP_ISSUE_WA() PP_ISSUE(p.w, swa, dstw)
 #define PP_ISSUE_WB() PP_ISSUE(p.w, swb, dstw + 16384)
@@ -509,55 +446,21 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_pp_kernel(const GemmParams p
   tile_origin(tile, m0, n0);
   tileI = tile;
   set_sources(m0, n0, lane);
-  bool pp_prologue = true;
-  (void)pp_prologue;
-#if WANQ_PP_BURST == 32
   // prologue = what the schedule would have issued in front of the first load phase, in its order: W(0), X(0), W(1)
   PP_ISSUE_WA(); PP_ISSUE_WB(); PP_ISSUE_XA(); PP_ISSUE_XB_ADVANCE();
   PP_ISSUE_WA(); PP_ISSUE_WB();
   asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-#else
-  // prologue = the seven chunk issues the schedule would have made in front of the first load phase, in its order
-  PP_ISSUE_XA(); PP_ISSUE_WA(); PP_ISSUE_WB(); PP_ISSUE_XB_ADVANCE();
-  PP_ISSUE_XA(); PP_ISSUE_WA(); PP_ISSUE_WB();
-  asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-#endif
   __builtin_amdgcn_s_barrier();
   __builtin_amdgcn_sched_barrier(0);
-  pp_prologue = false;
-#ifdef WANQ_PP_ABL_NODMA
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
 
-  // Start-time stagger (experiment hook, off by default: launch_pp): workgroups start in `coh_n` cohorts, `coh_ticks` (10-ns units)
-  // apart, so that one cohort's epilogue (an HBM burst: 32 MiB of 16-bit stores or 128 MiB of residual read + write per tile
-  // round) falls into the others' K loops.  (The first K-tiles are already requested.)
-  if (p.coh_n > 1) {
-    const int coh = (blockIdx.x >> 3) % p.coh_n;  // neighbours inside an XCD take different cohorts
-    if (coh > 0) {
-      const unsigned long long until = wall_clock64() + (unsigned long long)coh * p.coh_ticks;
-      while (wall_clock64() < until) __builtin_amdgcn_s_sleep(8);
-    }
-  }
 #ifdef WANQ_PP_JITTER
   unsigned pp_jit = 0x9e3779b9u * (unsigned)(wave + 1) + blockIdx.x * 7919u;
 #endif
   uint32_t bC = 0;
-  // vector-memory wait at the end of a load phase: all but the pieces of the five youngest load phases (10), plus the store
-  // instructions of the epilogue while they are younger than the oldest of those phases (vm_left phases, vm_mode: 1 = 16 stores,
-  // 2 = 32 stores, 3 = behind the residual epilogue, whose own waits retired everything older than its last 8 stores)
+  // store instructions of a full tile's epilogue still in flight: vm_left > 0 until the next tile's first burst has counted them
+  // in its wait (vm_mode: 1 = 16 stores, 2 = 32 stores).  Behind the residual epilogue it stays 0: the first burst's plain vmcnt(4)
+  // retires its last stores (end of the tile loop)
   int vm_left = 0, vm_mode = 0;
-#define PP_WAITVM()                                                              \
-  do {                                                                           \
-    if (vm_left > 0) {                                                           \
-      --vm_left;                                                                 \
-      if (vm_mode == 1) asm volatile("s_waitcnt vmcnt(26)" ::: "memory");        \
-      else if (vm_mode == 2) asm volatile("s_waitcnt vmcnt(42)" ::: "memory");   \
-      else asm volatile("s_waitcnt vmcnt(18)" ::: "memory");                     \
-    } else {                                                                     \
-      asm volatile("s_waitcnt vmcnt(10)" ::: "memory");                          \
-    }                                                                            \
-  } while (0)
 #ifdef WANQ_PP_JITTER  // race screen (diagnostic build, correct results): every wave idles a pseudo-random 0-1500 cycles in front of every
   // barrier, so that no ordering holds merely because the waves run in lock-step (tools/ab_gemm_variants.py must stay bit-equal)
 #define PP_JIT()                                                                                   \
@@ -576,21 +479,8 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_pp_kernel(const GemmParams p
     __builtin_amdgcn_s_barrier();        \
     __builtin_amdgcn_sched_barrier(0);   \
   } while (0)
-  // one burst: acc[I0 .. I0+1][J0 .. J0+3] += W fragments (2 channel blocks) x X fragments (4 token blocks) over both k-steps
-#define PP_BURST(WF, I0, J0)                                                                                       \
-  do {                                                                                                             \
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                             \
-    __builtin_amdgcn_sched_barrier(0);                                                                             \
-    __builtin_amdgcn_s_setprio(1);                                                                                 \
-    _Pragma("unroll") for (int ks_ = 0; ks_ < 2; ++ks_)                                                            \
-      _Pragma("unroll") for (int ii_ = 0; ii_ < 2; ++ii_)                                                          \
-        _Pragma("unroll") for (int jj_ = 0; jj_ < 4; ++jj_)                                                        \
-          acc[(I0) + ii_][(J0) + jj_] =                                                                            \
-              __builtin_amdgcn_mfma_i32_16x16x64_i8(WF[ks_][ii_], xf[ks_][jj_], acc[(I0) + ii_][(J0) + jj_], 0, 0, 0); \
-    __builtin_amdgcn_s_setprio(0);                                                                                 \
-  } while (0)
-  // the 32-MFMA form: all four channel blocks (W halves a and b) x the four token blocks J0 .. J0+3; the reads were waited for in
-  // front of the barrier
+  // one burst: all four channel blocks (W halves a and b) x the four token blocks J0 .. J0+3; the reads were waited for in front
+  // of the barrier
 #define PP_BURST32(J0)                                                                                             \
   do {                                                                                                             \
     __builtin_amdgcn_sched_barrier(0);                                                                             \
@@ -629,24 +519,12 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_pp_kernel(const GemmParams p
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[i][j][r] = 0;
     if (g == 1) PP_BAR();  // group 1 runs one barrier interval behind group 0
-#ifdef WANQ_PP_CLOCK
-    const unsigned long long clk_c0 = clock64(), clk_w0 = wall_clock64();
-#endif
 
     for (int kt = 0; kt < nk; ++kt) {
       const bool hold = has_res && kt == nk - 1;  // residual epilogue ahead: the next tile's second K-tile is requested behind it
       const uint32_t xa0 = xrd[0] + bC, xa1 = xrd[1] + bC, wa0 = wrd[0] + bC, wa1 = wrd[1] + bC;
       v4i xf[2][4], wfa[2][2], wfb[2][2];
-#if WANQ_PP_BURST == 32
-      // ---- two phases per K-tile, 32-MFMA bursts (a 16-MFMA burst paid ~90 cycles of barrier / refill per 256: 2775 cycles per
-      // K-tile; profiles/r04_b_gemm_pingpong_clock.txt).  Slots relative to G0's first burst of K-tile t, G0 bursts in even slots:
-      //   slot -1 G0 LA: reads X0a, Wa, Wb (16)   issues X0a, X0b (t+1)        slot 0 G1 LA: X1a, Wa, Wb     issues X1a, X1b (t+1)
-      //   slot  1 G0 LB: reads X0b (8)            issues W rows of G0 (t+2)    slot 2 G1 LB: X1b             issues W rows of G1 (t+2)
-      // Bursts QA = Xa x (Wa, Wb), QB = Xb x (Wb, Wa).  Per wave the vector-memory queue is ... W(t+1) | X(t+1) | W(t+2) | X(t+2) ...
-      // (four pieces each): the wait at the END OF A BURST leaves the youngest group in flight and retires the one before it --
-      // W(t+1) behind QA(t), X(t+1) behind QB(t) -- 3.5 slots after its issue and one barrier before its first reader.  W is
-      // re-filled ONE slot after its last reader (G1's LA): load phases therefore finish their reads (lgkmcnt(0)) in front of
-      // their barrier, not behind it.
+      // ---- two phases per K-tile, 32-MFMA bursts: the schedule of the file header
       const bool sc_now = OUT != WANQ_I32 && fast_scales && kt == nk - 2;
       // phase A
       PP_JIT();
@@ -688,54 +566,8 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_pp_kernel(const GemmParams p
       else if (sc_now) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
       PP_BAR();
-#else
-      // phase 1
-      PP_READ_X(0);
-      PP_READ_W(wfa, 0);
-      if (OUT != WANQ_I32 && kt == nk - 2 && fast_scales) prefetch_scales(p, smem + PTURN + wave * 4096, n0 + c * 64, m0 + g * 128, lane, has_res);
-      PP_ISSUE_XB_ADVANCE();
-      PP_WAITVM();
-      PP_BAR();
-      PP_BURST(wfa, 0, 0);
-      PP_BAR();
-      // phase 2
-      PP_READ_W(wfb, 1);
-      if (!hold) {
-        PP_ISSUE_XA();
-        PP_WAITVM();
-      } else {
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      }
-      PP_BAR();
-      PP_BURST(wfb, 2, 0);
-      PP_BAR();
-      // phase 3
-      PP_READ_X(1);
-      if (!hold) {
-        PP_ISSUE_WA();
-        PP_WAITVM();
-      } else {
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-      }
-      PP_BAR();
-      PP_BURST(wfb, 2, 4);
-      PP_BAR();
-      // phase 4
-      if (!hold) {
-        PP_ISSUE_WB();
-        PP_WAITVM();
-      } else {
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-      }
-      PP_BAR();
-      PP_BURST(wfa, 0, 4);
-      PP_BAR();
-#endif
       bC ^= PBUF;
     }
-#ifdef WANQ_PP_CLOCK
-    if (blockIdx.x == 77 && tid == 0 && tile == blockIdx.x) { g_pp_clk[0] = clock64() - clk_c0; g_pp_clk[1] = wall_clock64() - clk_w0; }
-#endif
     if (g == 0) PP_BAR();  // both groups enter the epilogue together
 
     // ---- epilogue.  The lane-derived constants come from an OPAQUE copy of the lane id: derived from `lane` itself they are
@@ -767,17 +599,10 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_pp_kernel(const GemmParams p
       if (OUT16 && (p.epi & WANQ_EPI_GELU)) store_tile_g(sc, gt, std::true_type{});  // (GELU with a 32-bit output: v2 kernel)
       else store_tile_g(sc, gt, std::false_type{});
     };
-#ifdef WANQ_PP_CLOCK
-    const unsigned long long clk_e0 = clock64();
-    unsigned long long clk_e1 = clk_e0;
-#endif
     if (OUT != WANQ_I32 && fast_scales) {
       LaneScales sc;
       float gt[2][4];
       read_lane_scales(p, sc, gt, lds_base + PTURN + wave * 4096, e16, eq4, rd_c, has_res);
-#ifdef WANQ_PP_CLOCK
-      clk_e1 = clock64();
-#endif
       store_tile(sc, gt);
     } else {
       LaneScales sc;
@@ -793,9 +618,6 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_pp_kernel(const GemmParams p
       }
       store_tile(sc, gt);
     }
-#ifdef WANQ_PP_CLOCK
-    if (blockIdx.x == 77 && tid == 0 && tile == blockIdx.x) { g_pp_clk[2] = clk_e1 - clk_e0; g_pp_clk[3] = clock64() - clk_e0; }
-#endif
     if (next >= ntiles) break;
     {
       // The per-lane constants of the K loop (eight DMA source offsets, four fragment read addresses) are RECOMPUTED here from an
@@ -812,14 +634,8 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_pp_kernel(const GemmParams p
       // every wave is out of its residual ring before the held-back pieces (next tile, second K-tile) land in it
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       PP_BAR();
-#if WANQ_PP_BURST == 32
       PP_ISSUE_WA(); PP_ISSUE_WB();  // W(1) of the next tile; its first burst's wait (vmcnt(4): X(1) only) retires it and the last stores
       vm_left = 0;
-#else
-      PP_ISSUE_XA(); PP_ISSUE_WA(); PP_ISSUE_WB();
-      vm_mode = 3;
-      vm_left = 3;
-#endif
     } else if (full_tile) {
       vm_mode = stores_mode;
       vm_left = 5;
@@ -836,9 +652,7 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_pp_kernel(const GemmParams p
 #undef PP_ISSUE_WA
 #undef PP_ISSUE_WB
 #undef PP_ISSUE_XB_ADVANCE
-#undef PP_WAITVM
 #undef PP_BAR
-#undef PP_BURST
 #undef PP_BURST32
 #undef PP_READ_X
 #undef PP_READ_W
@@ -854,32 +668,8 @@ int launch_pp(GemmParams p, hipStream_t st) {
   p.mt = (p.M + PM - 1) / PM;
   p.nt = (p.N + PN - 1) / PN;
   const int tiles = p.mt * p.nt;
-  {
-    // Start-time stagger: an experiment hook only (WANQ_GEMM_STAGGER="cohorts:ns").  Measured on the four cfg-B block shapes
-    // (tools/gemm_stagger_scan.py, profiles/r04_f_gemm_stagger_scan.txt): alone, the short-K gate + residual GEMM gains 6 % with two
-    // cohorts 12 us apart (its epilogue is an HBM burst longer than its K loop), 16-bit outputs lose 1-10 %, K = 8960 loses 1-2 %;
-    // inside the denoising step the gain does not show (profiles/r04_j_bench_stagger_ab.txt): off by default.
-    static const bool rescan = getenv("WANQ_GEMM_STAGGER_SCAN") != nullptr;  // tools/gemm_stagger_scan.py changes the setting between launches
-    static const char* env0 = getenv("WANQ_GEMM_STAGGER");
-    const char* env = rescan ? getenv("WANQ_GEMM_STAGGER") : env0;
-    p.coh_n = 0;
-    p.coh_ticks = 0;
-    if (env) {
-      int n = 0, ns = 0;
-      if (sscanf(env, "%d:%d", &n, &ns) == 2) { p.coh_n = n; p.coh_ticks = ns / 10; }
-    }
-  }
   const int grid = tiles < 256 ? ((tiles + 7) & ~7) : 256;  // one workgroup per CU; % 8 == 0 for the XCD ranges
   hipLaunchKernelGGL((gemm_w8a8_pp_kernel<OUT, RES>), dim3((unsigned)grid), dim3(512), PLDS, st, p);
-#ifdef WANQ_PP_CLOCK
-  {
-    (void)hipStreamSynchronize(st);
-    unsigned long long h[4];
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_pp_clk), sizeof(h));
-    printf("[clock] pp gemm M=%d N=%d K=%d out=%d epi=%d: K loop %llu cycles = %.0f per K-tile, %.1f us -> %.0f MHz; epilogue: scales %llu, all %llu cycles\n",
-           p.M, p.N, p.K, OUT, p.epi, h[0], (double)h[0] / (p.K / PK), h[1] / 100.0, h[0] / (h[1] / 100.0), h[2], h[3]);
-  }
-#endif
   return check_launch("wanq_gemm_w8a8");
 }
 

@@ -253,16 +253,11 @@ __device__ __forceinline__ void hadamard_regs(float (&v)[KIN][EPL], int lane) { 
         }
   __builtin_amdgcn_sched_barrier(0);
   // ... then bits of c (lane bits 0 .. log2(LB)-1)
-#if (defined(WANQ_ROT_ABLATE_LANE) || defined(WANQ_ROT_ABLATE_MIX) || defined(WANQ_ROT_ABLATE_QUANT)) && !defined(WANQ_ALLOW_ABLATIONS)
-#error "WANQ_ROT_ABLATE_* build deliberately wrong kernels (timing ablations): add -DWANQ_ALLOW_ABLATIONS, never in build.py's library"
-#endif
-#ifndef WANQ_ROT_ABLATE_LANE  // (WANQ_ROT_ABLATE_*: timing probes only, tools/probes/rotate_ablate.py; never defined in the product build)
   lane_stage<1, KIN, EPL>(v, lane);
   lane_stage<2, KIN, EPL>(v, lane);
   lane_stage<4, KIN, EPL>(v, lane);
   lane_stage<8, KIN, EPL>(v, lane);
   if constexpr (LB >= 32) lane_stage<16, KIN, EPL>(v, lane);
-#endif
   __builtin_amdgcn_sched_barrier(0);
   // M_KIN across this lane's blocks
   if constexpr (is_pow2_c(KIN)) {
@@ -279,7 +274,6 @@ __device__ __forceinline__ void hadamard_regs(float (&v)[KIN][EPL], int lane) { 
           }
         }
   } else {
-#ifndef WANQ_ROT_ABLATE_MIX
     // Paley-I structure (column 0 all +1, row 0 = (+1, -1, ..., -1), core +1 on the diagonal and chi(a - b) off it): with
     // S = x_1 + ... + x_{K-1} and P_a = the sum of the x_b, b >= 1, b != a, with chi(a - b) = +1 ((K - 2) / 2 terms),
     //     y_0 = x_0 - S,     y_a = x_0 + x_a + (2 P_a - (S - x_a)) = (x_0 - S) + 2 (x_a + P_a)
@@ -305,7 +299,6 @@ __device__ __forceinline__ void hadamard_regs(float (&v)[KIN][EPL], int lane) { 
       for (int a = 0; a < KIN; ++a) v[a][j] = t[a];
       __builtin_amdgcn_sched_barrier(0);
     }
-#endif
   }
   // S_Q (Sylvester) across the lane groups of the row
   if constexpr (Q >= 2) lane_stage<LB, KIN, EPL>(v, lane);

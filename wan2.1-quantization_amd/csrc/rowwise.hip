@@ -9,7 +9,6 @@
 //   WPR = 1: one wave per row (cols <= 2048), 4 rows per 256-thread workgroup, no barriers, no LDS.
 //   WPR = 4: four waves per row (cols <= 16384), reductions finished through 64 B of LDS.
 #include "wanq_common.h"
-#include <stdlib.h>
 
 namespace wanq {
 
@@ -450,7 +449,6 @@ __global__ __launch_bounds__(256, 2) void quant_rows_wave_kernel(const void* x, 
     for (int j = 0; j < 8; j += 2) {
       float t0 = v[i][j], t1 = v[i][j + 1];
       if (GELU) {
-#ifndef WANQ_QW_SCALAR_GELU
         // gelu_tanh_fast_f32 on element PAIRS: the same operations, the plain ones as packed fp32 (bit-identical)
         typedef float v2f __attribute__((ext_vector_type(2)));
         const v2f x = {t0, t1}, c3 = {-0.10294324f, -0.10294324f}, c1 = {-2.3022082f, -2.3022082f}, one = {1.0f, 1.0f};
@@ -459,10 +457,6 @@ __global__ __launch_bounds__(256, 2) void quant_rows_wave_kernel(const void* x, 
         const v2f r = x * (v2f){__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
         t0 = r.x;
         t1 = r.y;
-#else
-        t0 = gelu_tanh_fast_f32(t0);
-        t1 = gelu_tanh_fast_f32(t1);
-#endif
       }
       t0 = ok ? t0 : 0.f;
       t1 = ok ? t1 : 0.f;
@@ -500,8 +494,7 @@ __global__ __launch_bounds__(256, 2) void quant_rows_wave_kernel(const void* x, 
 // cols in (8704, 9216] (the 1.3B FFN width 8960 = 17.5 chunks per lane): NCH = 18
 static bool launch_quant_rows_wave(const void* x, int x_dtype, int8_t* q, void* scale, void* sum, int vec_dtype, int64_t rows, int cols, int act,
                                    hipStream_t st) {
-  static const bool off = getenv("WANQ_QUANT_WAVE_OFF") != nullptr;
-  if (off || cols <= 8704 || cols > 9216 || (x_dtype != WANQ_BF16 && x_dtype != WANQ_F16)) return false;
+  if (cols <= 8704 || cols > 9216 || (x_dtype != WANQ_BF16 && x_dtype != WANQ_F16)) return false;
   const dim3 grid((unsigned)((rows + 3) / 4));
 #define WANQ_QW(T, G) hipLaunchKernelGGL((quant_rows_wave_kernel<T, 18, G>), grid, dim3(256), 0, st, x, q, scale, sum, vec_dtype, rows, cols)
   if (x_dtype == WANQ_BF16) { if (act) WANQ_QW(BF16, true); else WANQ_QW(BF16, false); }

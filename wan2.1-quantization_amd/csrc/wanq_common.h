@@ -245,7 +245,6 @@ __device__ __forceinline__ void quantN_pack_rne(const float (&x)[N], float s, fl
   static_assert(N % 4 == 0, "four codes per dword");
   float u[N];
   bool near = false;
-#ifndef WANQ_QUANT_SCALAR
   // on element PAIRS (v_pk_fma_f32 / v_pk_add_f32: the same IEEE operations per half, bit-identical codes, 2.5 instead of 4
   // vector instructions per element in front of the byte packing)
   typedef float v2f __attribute__((ext_vector_type(2)));
@@ -260,14 +259,6 @@ __device__ __forceinline__ void quantN_pack_rne(const float (&x)[N], float s, fl
     near |= fabsf(d2.x) >= 0.4999488f;
     near |= fabsf(d2.y) >= 0.4999488f;
   }
-#else
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    u[j] = fmaf(x[j], inv, WANQ_QMAGIC);
-    const float r = u[j] - WANQ_QMAGIC;
-    near |= fabsf(fmaf(x[j], inv, -r)) >= 0.4999488f;
-  }
-#endif
   if (near) {
 #pragma unroll
     for (int j = 0; j < N; ++j) u[j] = rintf(x[j] / s) + WANQ_QMAGIC;
@@ -289,7 +280,6 @@ __device__ __forceinline__ void quantN_pack_rne_pre(const float (&y)[N], float c
   static_assert(N % 4 == 0, "four codes per dword");
   float u[N];
   bool near = false;
-#ifndef WANQ_QUANT_SCALAR
   typedef float v2f __attribute__((ext_vector_type(2)));  // on element pairs, as in quantN_pack_rne
   const v2f cinv2 = {cinv, cinv}, magic2 = {WANQ_QMAGIC, WANQ_QMAGIC};
 #pragma unroll
@@ -302,14 +292,6 @@ __device__ __forceinline__ void quantN_pack_rne_pre(const float (&y)[N], float c
     near |= fabsf(d2.x) >= 0.4999488f;
     near |= fabsf(d2.y) >= 0.4999488f;
   }
-#else
-#pragma unroll
-  for (int j = 0; j < N; ++j) {
-    u[j] = fmaf(y[j], cinv, WANQ_QMAGIC);
-    const float r = u[j] - WANQ_QMAGIC;
-    near |= fabsf(fmaf(y[j], cinv, -r)) >= 0.4999488f;
-  }
-#endif
   if (near) {
 #pragma unroll
     for (int j = 0; j < N; ++j) u[j] = rintf((y[j] * c) / s) + WANQ_QMAGIC;
