@@ -114,6 +114,24 @@ int wanq_gemm_w8a8(const int8_t* a, const int8_t* w, void* out, int out_dtype, c
 int wanq_gemm_select_kernel(int which);
 
 /* ------------------------------------------------------------------------------------------------
+ * bf16 / fp16 GEMM on v_mfma_f32_16x16x32_{bf16,f16} with the epilogue of wanq_gemm_w8a8:
+ *   y   = sum_k a[m,k] * w[n,k]                     (fp32 accumulation; a, w both of `dtype`: WANQ_BF16 or WANQ_F16)
+ *   y   = y + bias[n]                               (bias may be NULL; bias_dtype F16 | BF16 | F32)
+ *   y   = gelu_tanh(y)                              if WANQ_EPI_GELU
+ *   y   = residual[m,n] + y * gate[n]               if WANQ_EPI_GATE_RES  (gate fp32[N], residual of out_dtype; out may alias it)
+ *   out = cast(y) to out_dtype (F16 | BF16 | F32): one rounding, all arithmetic above in fp32.
+ * Any M >= 1 (ragged last tile in-kernel, no host padding); N % 8 == 0; K % 32 == 0; a, w, out and residual 16-byte aligned,
+ * gate and bias aligned to 4 elements.  Anything else is refused (WANQ_E_SHAPE / WANQ_E_ARG, the message names the rule).
+ * Determinism: the fp32 summation order of element (m, n) depends on K only -- not on M, on the row's position in the launch or
+ * on the workgroup that ran it (one kernel form, no split-K), so a row gives the same bits in any launch, and repeated calls are
+ * bit-identical.
+ * Replaces the nn.Linear layers the reference's kernel-mode block keeps in floating point: the FFN with its separate GELU
+ * (ViDiT-Q/examples/Wan2.1/wan/quant_wanx_cuda.py:162-164) and the attention output projection (:360), whose
+ * gate + residual the reference applies in a separate pass. */
+int wanq_gemm_bf16(const void* a, const void* w, int dtype, void* out, int out_dtype, const void* bias, int bias_dtype,
+                   const float* gate, const void* residual, int epi_flags, int64_t M, int N, int K, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * PTQ calibration reduction: running per-channel absmax over tokens,
  *   colmax[c] = max(colmax[c], max_r |x[r,c]|)        (colmax fp32[cols], caller zero-initialises)
  * Replaces SaveActivationHook.__call__ default branch

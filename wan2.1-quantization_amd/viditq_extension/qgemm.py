@@ -218,3 +218,57 @@ def w4a8_of16_nobias_weight_asym_qserve(in_feats, kernel, wscales, ascales, w_sz
     zp = (-(w_szs.float() / wscales.float())).contiguous()  # asym epilogue: + a_ssum * zp * wscale
     w8a8_linear(in_feats, kernel, ascales, wscales.to(vec), None, a_ssums, zp.float(), out_dtype=out_feats.dtype, out=out_feats,
                 w4=True)
+
+
+# ---- 16-bit floating point ----------------------------------------------------------------------------------------
+def fp_linear(input, weight, bias=None, out_dtype=None, gelu=False, gate=None, residual=None, out=None):
+    """y = epilogue(input[M,K] @ weight[N,K]^T) on the bf16 / fp16 matrix cores (wanq_gemm_bf16, csrc/gemm_bf16.hip); input and
+    weight share a dtype (bf16 or fp16).  Epilogue in fp32: + bias, tanh-GELU (`gelu`), residual + y * gate (gate fp32 [N], residual
+    [M,N] of out_dtype, may alias `out`), one rounding to out_dtype (default: the input's dtype).  A row's bits do not depend on M
+    or on where the row sits in the launch.  Not counted by the int8 timer (`set_timer`)."""
+    _C.check_gpu("input", input)
+    _C.check_gpu("weight", weight)
+    _C.check_contig("input", input)
+    _C.check_contig("weight", weight)
+    _C.check_dtype("input", input, torch.bfloat16, torch.float16)
+    _C.check_dtype("weight", weight, input.dtype)
+    if input.dim() != 2 or weight.dim() != 2:
+        raise RuntimeError("Tensors input and weight must have dimension number (2)")
+    M, K = input.shape
+    N = weight.shape[0]
+    _C.check_shape("weight", weight, N, K)
+    out_dtype = out_dtype or input.dtype
+    if bias is not None:
+        _check_vec("bias", bias, N, (torch.bfloat16, torch.float16, torch.float32))
+    epi = _C.EPI_GELU if gelu else 0
+    if gate is not None or residual is not None:
+        if gate is None or residual is None:
+            raise RuntimeError("gate and residual must be given together")
+        _check_vec("gate", gate, N, (torch.float32,))
+        _C.check_gpu("residual", residual)
+        _C.check_contig("residual", residual)
+        _C.check_dtype("residual", residual, out_dtype)
+        _C.check_shape("residual", residual, M, N)
+        epi |= _C.EPI_GATE_RES
+    if out is None:
+        out = torch.empty((M, N), dtype=out_dtype, device=input.device)
+    else:
+        _C.check_gpu("out", out)
+        _C.check_contig("out", out)
+        _C.check_dtype("out", out, out_dtype)
+        _C.check_shape("out", out, M, N)
+    _C.check_same_device(input, weight, bias, gate, residual, out)
+    with torch.cuda.device(input.device):
+        _C.call("wanq_gemm_bf16", _C.ptr(input), _C.ptr(weight), _C.dt(input), _C.ptr(out), _C.dt(out_dtype), _C.ptr(bias),
+                _C.dt(bias) if bias is not None else _C.F32, _C.ptr(gate), _C.ptr(residual), epi, M, N, K, _C.stream())
+    return out
+
+
+def fp_linear_refusal(M, N, K):
+    """Why wanq_gemm_bf16 would refuse an [M, K] x [N, K] product (None = accepted): the shape rules of include/wanq_hip.h, checked on
+    the host so that a model can name a layer the kernel cannot take when it is built, not in its first forward."""
+    if N < 8 or N % 8:
+        return f"N={N} must be a positive multiple of 8"
+    if K < 32 or K % 32:
+        return f"K={K} must be a positive multiple of 32"
+    return None

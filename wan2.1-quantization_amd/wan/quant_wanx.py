@@ -109,13 +109,14 @@ class QuantWanModel(WanModel, QuantModel):
             torch.save(sd, save_path)
         return sd
 
-    def hardware_forward_refactor(self, load_path=None, seq_len=None, act_dtype=torch.bfloat16):
+    def hardware_forward_refactor(self, load_path=None, seq_len=None, act_dtype=torch.bfloat16, fp_gemm="torch"):
         """Switch forward() to kernel mode: every block becomes a WanAttentionBlockWithHipKernel (reference
         quant_wanx.py:188-228).  The blocks are built from the model's current layers (which fixes which Linears are
         quantized and which carry a rotation); with `load_path` the integer checkpoint is then LOADED into them, as the
         reference does with `int_weight.pt`: codes, scales, zero points, biases and activation pre-multipliers of every
         quantized Linear come from the file (either format of quantize_and_save_weight), a quantized Linear without its keys
-        or with a shape mismatch is an error, and the number of tensors taken is logged."""
+        or with a shape mismatch is an error, and the number of tensors taken is logged.  fp_gemm: the GEMM of the Linears kept
+        floating point, "torch" (hipBLASLt + separate GELU / gate + residual passes) or "hip" (csrc/gemm_bf16.hip, both fused)."""
         qk8, vb, amap = {}, {}, {}
         for key in ("attn", "cross_attn"):  # quant_config.attn.qk / cross_attn.qk (Q/base/quant_attn.py:19-29,130-143)
             sub = self.q_cfg.get(key, None) if self.q_cfg is not None else None
@@ -151,7 +152,7 @@ class QuantWanModel(WanModel, QuantModel):
         self.hip_blocks = nn.ModuleList([WanAttentionBlockWithHipKernel.from_float(
             b, None, False, act_dtype, attn_qk8=qk8.get("attn", False), cross_attn_qk8=qk8.get("cross_attn", False),
             attn_v_bits=vb.get("attn"), cross_attn_v_bits=vb.get("cross_attn"), attn_map=amap.get("attn"),
-            cross_attn_map=amap.get("cross_attn")) for b in self.blocks])
+            cross_attn_map=amap.get("cross_attn"), fp_gemm=fp_gemm, name=f"blocks.{i}") for i, b in enumerate(self.blocks)])
         if load_path:
             sd = torch.load(load_path, map_location="cpu", weights_only=True)
             taken = 0

@@ -129,19 +129,32 @@ class HipLinearW8A8(nn.Module):
                                  gelu=gelu, gate=gate, residual=residual, out=out)
 
 
+FP_GEMMS = ("torch", "hip")
+
+
 class HipLinearFp(nn.Module):
-    """A Linear the quant config leaves FP (remain_fp_regex): bf16 GEMM through torch (hipBLASLt), as the
-    reference's kernel-mode block keeps nn.Linear for those (quant_wanx_cuda.py:360,510)."""
+    """A Linear the quant config leaves FP (remain_fp_regex), as the reference's kernel-mode block keeps nn.Linear for those
+    (quant_wanx_cuda.py:360,510).  fp_gemm="torch": the bf16 GEMM through torch (hipBLASLt), GELU and gate + residual as separate
+    passes; "hip": qgemm.fp_linear (csrc/gemm_bf16.hip) with both in its epilogue, and rows whose bits do not depend on M."""
     quantized = False
     act_key = "fp"
 
-    def __init__(self, weight, bias, dtype=torch.bfloat16):
+    def __init__(self, weight, bias, dtype=torch.bfloat16, fp_gemm="torch", name="linear"):
         super().__init__()
+        if fp_gemm not in FP_GEMMS:
+            raise ValueError(f"fp_gemm={fp_gemm!r}: expected one of {FP_GEMMS}")
+        if fp_gemm == "hip":
+            why = qgemm.fp_linear_refusal(1, weight.shape[0], weight.shape[1])
+            if dtype not in (torch.bfloat16, torch.float16):
+                why = f"act_dtype {dtype} is not bf16 or fp16"
+            if why is not None:
+                raise ValueError(f"{name}: fp_gemm='hip' cannot take this layer ({tuple(weight.shape)}): {why}")
+        self.fp_gemm = fp_gemm
         self.register_buffer("weight", weight.detach().to(dtype).contiguous())
         self.register_buffer("bias", None if bias is None else bias.detach().to(dtype).contiguous())
 
 
-def _to_hip_linear(lin, n_bits, sym, act_dtype):
+def _to_hip_linear(lin, n_bits, sym, act_dtype, fp_gemm="torch", name="linear"):
     from qdiff.base.quant_layer import QuantizedLinear
 
     if isinstance(lin, QuantizedLinear):
@@ -149,7 +162,7 @@ def _to_hip_linear(lin, n_bits, sym, act_dtype):
             return HipLinearW8A8.from_quantized(lin)
         lin = lin.fp_module
     if n_bits is None:
-        return HipLinearFp(lin.weight.data, lin.bias.data if lin.bias is not None else None, act_dtype)
+        return HipLinearFp(lin.weight.data, lin.bias.data if lin.bias is not None else None, act_dtype, fp_gemm, name)
     return HipLinearW8A8.from_float(lin.weight.data, lin.bias.data if lin.bias is not None else None, n_bits, sym)
 
 
@@ -297,8 +310,12 @@ class _Attn(nn.Module):
 
 class WanAttentionBlockWithHipKernel(nn.Module):
     def __init__(self, dim, ffn_dim, num_heads, eps=1e-6, act_dtype=torch.bfloat16, attn_qk8=False, cross_attn_qk8=False,
-                 attn_v_bits=None, cross_attn_v_bits=None, attn_map=None, cross_attn_map=None):
+                 attn_v_bits=None, cross_attn_v_bits=None, attn_map=None, cross_attn_map=None, fp_gemm="torch"):
         super().__init__()
+        if fp_gemm not in FP_GEMMS:
+            raise ValueError(f"fp_gemm={fp_gemm!r}: expected one of {FP_GEMMS}")
+        # which GEMM runs the Linears kept in floating point (HipLinearFp); from_float hands it to each of them
+        self.fp_gemm = fp_gemm
         self.dim, self.ffn_dim, self.num_heads, self.head_dim, self.eps = dim, ffn_dim, num_heads, dim // num_heads, eps
         self.act_dtype = act_dtype
         # quant_config.attn.qk / cross_attn.qk (8-bit symmetric): q and k of that attention leave RMSNorm + RoPE as
@@ -317,20 +334,21 @@ class WanAttentionBlockWithHipKernel(nn.Module):
 
     @classmethod
     def from_float(cls, blk, n_bits=8, sym=False, act_dtype=torch.bfloat16, attn_qk8=False, cross_attn_qk8=False,
-                   attn_v_bits=None, cross_attn_v_bits=None, attn_map=None, cross_attn_map=None):
+                   attn_v_bits=None, cross_attn_v_bits=None, attn_map=None, cross_attn_map=None, fp_gemm="torch", name="block"):
         """Build from a WanAttentionBlock (wan/modules/model.py) whose Linears are either plain nn.Linear
         (quantized here with plain per-channel W8 when n_bits is given, kept FP when n_bits is None) or qdiff
-        QuantizedLinear variants (their codes / parameters / ViDiT transform are taken over as they are)."""
+        QuantizedLinear variants (their codes / parameters / ViDiT transform are taken over as they are).
+        fp_gemm: "torch" or "hip", the GEMM of the Linears kept FP (HipLinearFp); a layer "hip" cannot take is refused here, by name."""
         m = cls(blk.dim, blk.ffn_dim, blk.num_heads, blk.eps, act_dtype, attn_qk8, cross_attn_qk8, attn_v_bits,
-                cross_attn_v_bits, attn_map, cross_attn_map).to(blk.modulation.device)
-        for name in ("self_attn", "cross_attn"):
-            src, dst = getattr(blk, name), getattr(m, name)
+                cross_attn_v_bits, attn_map, cross_attn_map, fp_gemm).to(blk.modulation.device)
+        for name_ in ("self_attn", "cross_attn"):
+            src, dst = getattr(blk, name_), getattr(m, name_)
             for l in "qkvo":
-                setattr(dst, l, _to_hip_linear(getattr(src, l), n_bits, sym, act_dtype))
+                setattr(dst, l, _to_hip_linear(getattr(src, l), n_bits, sym, act_dtype, fp_gemm, f"{name}.{name_}.{l}"))
             dst.norm_q_weight.copy_(src.norm_q.weight.data.float())
             dst.norm_k_weight.copy_(src.norm_k.weight.data.float())
-        m.ffn0 = _to_hip_linear(blk.ffn[0], n_bits, sym, act_dtype)
-        m.ffn2 = _to_hip_linear(blk.ffn[2], n_bits, sym, act_dtype)
+        m.ffn0 = _to_hip_linear(blk.ffn[0], n_bits, sym, act_dtype, fp_gemm, f"{name}.ffn.0")
+        m.ffn2 = _to_hip_linear(blk.ffn[2], n_bits, sym, act_dtype, fp_gemm, f"{name}.ffn.2")
         m.modulation.copy_(blk.modulation.data.float())
         if isinstance(blk.norm3, nn.LayerNorm) and blk.norm3.weight is not None:
             m.norm3_weight.copy_(blk.norm3.weight.data.float())
@@ -354,6 +372,12 @@ class WanAttentionBlockWithHipKernel(nn.Module):
             if residual is not None:
                 return lin(q, s, ssum, torch.float32, gate=gate, residual=residual, out=residual)
             return lin(q, s, ssum, out_dtype, gelu=gelu)
+        if lin.fp_gemm == "hip":  # GELU and gate + residual in the GEMM's epilogue; reads lin.weight as it is now (--dit_fsdp views)
+            x = src.fp()
+            if residual is not None:
+                return qgemm.fp_linear(x, lin.weight, lin.bias, torch.float32, gate=gate.float().contiguous(), residual=residual,
+                                       out=residual)
+            return qgemm.fp_linear(x, lin.weight, lin.bias, x.dtype, gelu=gelu)
         y = torch.nn.functional.linear(src.fp(), lin.weight, lin.bias)
         if gelu:
             y = torch.nn.functional.gelu(y, approximate="tanh")
