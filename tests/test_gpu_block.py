@@ -338,7 +338,7 @@ def test_kernel_mode_block_with_asymmetric_or_narrow_activations_vs_simulation_o
 def test_config5_viditq_block_14b_shapes_rotated_4bit_ffn_vs_oracle_and_quality():
     """quant_configs/w4a8_mixed_viditq.yaml on one 14B-shape block (dim 5120, ffn 13824, 40 heads): FFN weights 4 bit (packed), the
     rest 8, ViDiT-Q mask + rotation on self-attention q / k / v AND on ffn.0 (5120 = 40 x 128) / ffn.2 (13824 = 108 x 128: the width
-    the reference's get_hadK asserts on; its own K = 108 branch here, csrc/rotate108.hip).  Masks from the activations the FP block
+    the reference's get_hadK asserts on; its own K = 108 branch here, csrc/rotate_paley.hip).  Masks from the activations the FP block
     really sees.  (a) parity: kernel-mode block vs the simulation oracle with the same masks / signs / bit-widths; (b) quality: the
     rotated 4-bit FFN against the plain 4-bit FFN of w4a8_mixed.yaml, both measured against the FP block."""
     import os

@@ -24,7 +24,7 @@ def test_rmsnorm_rope_and_attention_beside_the_attention_map_kernels_are_bit_sta
     rope = rope / rope.norm(dim=-1, keepdim=True)
 
     # the q / k / v transform (LayerNorm + modulation + ViDiT scale / rotate + quantise, rotate.hip) and the 8960-wide transform of
-    # ffn.2 (rotate140.hip) are the other kernels with packed fp32 ops of the op_sel form that failed (tools/isa_lint.py keeps
+    # ffn.2 (rotate_paley.hip) are the other kernels with packed fp32 ops of the op_sel form that failed (tools/isa_lint.py keeps
     # them away from load destinations with loads in flight; this keeps them in the hardware regression too: ADVICE r4)
     import viditq_extension.fused as fused
     from qdiff.quarot import quarot_utils as qu

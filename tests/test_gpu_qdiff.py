@@ -165,7 +165,7 @@ def test_viditq_linear_vs_reference_golden(golden):
 
 
 def test_rotate_8960_dtypes_and_outputs():
-    """n = 8960 = 140 x 64 (csrc/rotate140.hip: Paley-140 mix on the matrix cores with a three-way bf16 split of the fp32
+    """n = 8960 = 140 x 64 (csrc/rotate_paley.hip: Paley-140 mix on the matrix cores with a three-way bf16 split of the fp32
     values): bf16 / fp16 input as the GELU output has it, fp output in every dtype, scale / sum vectors in fp16 too."""
     import viditq_extension.fused as fused
     from qdiff.quarot import quarot_utils as qu
@@ -618,7 +618,7 @@ def test_viditq_linear_with_asymmetric_or_narrow_activations_vs_oracle(golden, a
 
 
 def test_rotate_13824_dtypes_outputs_and_viditq_layer():
-    """n = 13824 = 108 x 128, the 14B ffn.2 input (csrc/rotate108.hip; REPO-DEFINED: the reference asserts on this width):
+    """n = 13824 = 108 x 128, the 14B ffn.2 input (csrc/rotate_paley.hip; REPO-DEFINED: the reference asserts on this width):
     bf16 / fp16 / fp32 input, fp output in every dtype, codes / scales / sums against the oracle's H_108 (x) H_128 in float64, the
     eps row; then the width as a ViDiT layer (mask, double-quantised rotated weight, forward) against the oracle."""
     import viditq_extension.fused as fused

@@ -74,9 +74,9 @@ def test_hadamard_size_rules():
         qu.get_hadK(13824, strict=True)  # the reference to the letter asserts
     H, K = qu.get_hadK(13824)            # repo-defined: its own K = 108 branch
     assert K == 108 and torch.equal(H @ H.T, 108 * torch.eye(108, dtype=torch.float64))
-    k, h = qu.kernel_rotation_params(13824, "cpu")  # 108 x 128: its own kernel (csrc/rotate108.hip)
+    k, h = qu.kernel_rotation_params(13824, "cpu")  # 108 x 128: its own kernel (rotate108_kernel, csrc/rotate_paley.hip)
     assert k == 108 and h.shape == (108, 108)
-    k, h = qu.kernel_rotation_params(8960, "cpu")  # 140 x 64: its own kernel (csrc/rotate140.hip), Paley matrix of order 140
+    k, h = qu.kernel_rotation_params(8960, "cpu")  # 140 x 64: its own kernel (rotate140_kernel, csrc/rotate_paley.hip), Paley matrix of order 140
     assert k == 140 and h.shape == (140, 140) and torch.equal(h @ h.T, 140 * torch.eye(140))
     assert qu.kernel_rotation_params(140 * 32, "cpu") is None  # any other block < 128: no fused kernel
     k, h = qu.kernel_rotation_params(1536, "cpu")

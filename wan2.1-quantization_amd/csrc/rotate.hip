@@ -566,13 +566,10 @@ extern "C" int wanq_rotate_quant_rows(const void* x, int x_dtype, const float* p
     return premul_quant_rows(false, x, x_dtype, nullptr, nullptr, nullptr, 0, 1, 0.f, premul, out_fp, out_dtype, q, scale, sum,
                              vec_dtype, rows, cols, (hipStream_t)stream, what);
   if (int e = check_rows(what, rows)) return e;
-  if (had_k == 140) {  // 8960 = 140 x 64: the Paley-140 mix runs on the matrix cores (rotate140.hip)
-    WANQ_REQUIRE(cols == 8960, WANQ_E_SHAPE, "%s: had_k=140 is the transform of cols=8960 (got %d)", what, cols);
-    return rotate140_rows(x, x_dtype, premul, out_fp, out_dtype, q, scale, sum, vec_dtype, rows, (hipStream_t)stream, what);
-  }
-  if (had_k == 108) {  // 13824 = 108 x 128 (14B ffn.2): Paley-108 on the matrix cores (rotate108.hip); repo-defined, the reference asserts
-    WANQ_REQUIRE(cols == 13824, WANQ_E_SHAPE, "%s: had_k=108 is the transform of cols=13824 (got %d)", what, cols);
-    return rotate108_rows(x, x_dtype, premul, out_fp, out_dtype, q, scale, sum, vec_dtype, rows, (hipStream_t)stream, what);
+  if (had_k == 140 || had_k == 108) {  // 8960 = 140 x 64, 13824 = 108 x 128 (14B ffn.2; repo-defined, the reference asserts): the
+    const int n = had_k == 140 ? 8960 : 13824;  // Paley mix runs on the matrix cores (rotate_paley.hip)
+    WANQ_REQUIRE(cols == n, WANQ_E_SHAPE, "%s: had_k=%d is the transform of cols=%d (got %d)", what, had_k, n, cols);
+    return rotate_paley_rows(had_k, x, x_dtype, premul, out_fp, out_dtype, q, scale, sum, vec_dtype, rows, (hipStream_t)stream, what);
   }
   if (int e = check_rotation(what, had_k, cols)) return e;
   if (rows == 0) return WANQ_OK;
