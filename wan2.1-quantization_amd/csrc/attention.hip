@@ -104,7 +104,9 @@ __device__ __forceinline__ bf16x8 at_join(s16x4 lo, s16x4 hi) {
 // dependent v_add_f32 (128) and the s_nop hipcc puts between a v_exp and the add that consumes it (16 per tile).  Every row of
 // the 16x16 result is the row sum, so every lane holds its query's total (no cross-lane reduction in the epilogue), and l sums
 // exactly the bf16-rounded P that P.V uses.  The bf16 split-KV form has no 8 registers to spare for it (it spills) and keeps
-// per-lane v_add_f32 sums, reduced across the four lanes in the epilogue.
+// per-lane v_add_f32 sums, reduced across the four lanes in the epilogue -- of the same ROUNDED P: with sums of the unrounded
+// exponentials the rounding of a dominant key's P (up to 64 under the lazy reference, so not a power of two) does not cancel
+// between O and l, and a row with all its mass on one key comes out 2^-8 away from that key's v instead of equal to it.
 //
 // The wave index is a SCALAR (readfirstlane of threadIdx.x >> 6): hipcc cannot prove it uniform, and carried in a vector register
 // it made every LDS-DMA destination a v_readfirstlane + M0 write (8 per tile and DMA wave) and the dma_wave test an EXEC-mask
@@ -451,11 +453,12 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams
 #define A16_EXP(kb, nq, e)                                                     \
   {                                                                            \
     const float x_ = __builtin_amdgcn_exp2f(QK8 ? fmaf(sacc[kb][nq][e], c2[nq], -mc[nq]) : sacc[kb][nq][e]); \
-    if (!LSUM) {                                                               \
-      if (nq == 0) { ls0 += x_; asm volatile("" : "+v"(ls0)); }                \
-      else { ls1 += x_; asm volatile("" : "+v"(ls1)); }                        \
+    const __bf16 b_ = (__bf16)x_;                                              \
+    if (!LSUM) { /* the sum of the ROUNDED P, as the MFMA form has it */        \
+      if (nq == 0) { ls0 += (float)b_; asm volatile("" : "+v"(ls0)); }         \
+      else { ls1 += (float)b_; asm volatile("" : "+v"(ls1)); }                 \
     }                                                                          \
-    pf[(kb) >> 1][nq][4 * ((kb) & 1) + (e)] = (__bf16)x_;                      \
+    pf[(kb) >> 1][nq][4 * ((kb) & 1) + (e)] = b_;                              \
   }
 #define A16_EXP4(kb, nq) A16_EXP(kb, nq, 0) A16_EXP(kb, nq, 1) A16_EXP(kb, nq, 2) A16_EXP(kb, nq, 3)
 

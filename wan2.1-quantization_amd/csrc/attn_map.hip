@@ -12,7 +12,7 @@
 //   pass 0  row statistics (m_q, l_q)                       -> workspace [H][Lq] x 2
 //   pass 1  column maxima  c_k = max_q exp2(s - m_q) / l_q   -> workspace [H][Lk]   (atomic max on the bits of a float >= 0)
 //           then a small kernel turns c_k into (delta_k, 1 / delta_k)
-//   pass 2  O = sum_k P~[q,k] V[k]                           (P~ rounded to bf16 for the P.V MFMA, fp32 accumulation)
+//   pass 2  O = sum_k P~[q,k] V[k]                           (P~ as a bf16 pair hi + lo for the P.V MFMAs, fp32 accumulation)
 //
 // Round 3: the passes share the structure of the flash-attention kernel (attention.hip, 16x16 form) instead of reading their
 // operands straight from global memory: one workgroup = 8 waves x 32 queries of one head, 64-key tiles, K (and in pass 2 V)
@@ -357,7 +357,10 @@ __global__ __launch_bounds__(512, PASS == 2 ? 2 : 4) void attn_map_kernel(const 
     if (j + 2 < nt) dma_tile(j + 2, (j + 2) % 3);
     mf32x4 sacc[4][2];
     s_tile(j, st, sacc, skv);
-    mbf16x8 pf[2][2];
+    // P~ goes to the MFMA as a bf16 PAIR hi + lo (lo = the rounding residual of hi, itself rounded: 2^-16 of P~ is left): the map
+    // is NORMALISED, so unlike the flash kernel's P (1 for the row maximum) its typical value (1 / n for a flat row) is no bf16
+    // number, and a single rounding of it in front of the output's would move the whole row by up to 2^-8.
+    mbf16x8 pf[2][2], pl[2][2];
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
@@ -365,7 +368,10 @@ __global__ __launch_bounds__(512, PASS == 2 ? 2 : 4) void attn_map_kernel(const 
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float pr = __builtin_amdgcn_exp2f(QK8 ? fmaf(sacc[kb][nq][e], c2[nq], -mq[nq]) : sacc[kb][nq][e] - mq[nq]) * inv_l[nq];
-          pf[kb >> 1][nq][4 * (kb & 1) + e] = (__bf16)(__builtin_rintf(pr * di[kb][e]) * dk[kb][e]);
+          const float pq = __builtin_rintf(pr * di[kb][e]) * dk[kb][e];
+          const __bf16 hi = (__bf16)pq;
+          pf[kb >> 1][nq][4 * (kb & 1) + e] = hi;
+          pl[kb >> 1][nq][4 * (kb & 1) + e] = (__bf16)(pq - (float)hi);
         }
     const uint32_t vst = (uint32_t)(st * AM_STAGE);
 #pragma unroll
@@ -390,6 +396,8 @@ __global__ __launch_bounds__(512, PASS == 2 ? 2 : 4) void attn_map_kernel(const 
         const mbf16x8 vf = am_join(t0[db], t1[db]);
         o[db][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[ks][0], o[db][0], 0, 0, 0);
         o[db][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[ks][1], o[db][1], 0, 0, 0);
+        o[db][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pl[ks][0], o[db][0], 0, 0, 0);
+        o[db][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pl[ks][1], o[db][1], 0, 0, 0);
       }
     }
     wait_tile_ahead(j + 2 < nt);
