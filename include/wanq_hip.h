@@ -208,7 +208,9 @@ int wanq_rmsnorm_rope_scatter(const void* x, int x_dtype, const float* weight, c
 /* ------------------------------------------------------------------------------------------------
  * Flash-attention forward, non-causal:  o[q,h,:] = softmax_k(q[q,h,:].k[k,h,:] * scale) v[k,h,:] over the
  * first Lk keys.  Token-major tensors [tokens, heads*head_dim] with a token stride in ELEMENTS (so q/k/v may
- * be column slices of one packed buffer).  dtype: WANQ_BF16; head_dim: 128.  fp32 online softmax, bf16 MFMA.
+ * be column slices of one packed buffer).  dtype: WANQ_BF16 or WANQ_F16, the one type of q, k, v and o (any other code is
+ * refused with WANQ_E_ARG); head_dim: 128.  fp32 online softmax, S and P.V on v_mfma_f32_16x16x32_{bf16,f16}; the fp16 form keeps
+ * P 2^8 above the bf16 form's so that it stays in fp16's normal range down to 22 log2 units below the row maximum.
  * Replaces flash_attention(q, k, v, k_lens) (ViDiT-Q/examples/Wan2.1/wan/modules/attention.py:24-130, which
  * calls the external flash_attn library) for batch size 1. */
 int wanq_attention_fwd(const void* q, const void* k, const void* v, void* o, int dtype, int64_t Lq,
@@ -228,7 +230,7 @@ int wanq_attention_fwd_split(const void* q, const void* k, const void* v, void* 
                              int64_t v_stride, int64_t o_stride, float scale, int splits, void* workspace,
                              int64_t workspace_bytes, void* stream);
 
-/* Diagnostic: which form of the bf16 attention kernel wanq_attention_fwd launches.  The kernel exists with 8 waves per workgroup
+/* Diagnostic: which form of the attention kernel wanq_attention_fwd launches (bf16 and fp16 alike).  The kernel exists with 8 waves per workgroup
  * (256 queries, three ring stages, one workgroup per CU) and with 4 (128 queries, two stages, two workgroups per CU); key sequences
  * up to `nw4_keys` run the 4-wave form (start-up default 1024 or WANQ_ATTN_NW4_KEYS: cross-attention), longer ones the 8-wave form.
  * 0 = always 8 waves, a large value = always 4, -1 = back to the start-up value.  Process-wide; returns the previous setting.
@@ -239,7 +241,8 @@ int64_t wanq_attention_select_form(int64_t nw4_keys);
  *   o[q,h,:] = softmax_k( (q8[q,h,:] . k8[k,h,:]) * delta_q[h][q] * delta_k[h][k] * scale ) v[k,h,:]
  * q8 / k8: int8 [tokens, heads*128] with byte strides q8_stride / k8_stride; q_scale: fp32 [heads][qs_stride]; k_scale: fp32
  * two planes [heads][ks_stride] (delta_k, then -12582912*delta_k: the layout wanq_rmsnorm_rope_q8 writes), ks_stride >= Lk
- * rounded up to 64.  S = K8.Q8^T on v_mfma_i32_16x16x64_i8 (integer-exact), P.V in bf16 as above; v / o bf16.
+ * rounded up to 64.  S = K8.Q8^T on v_mfma_i32_16x16x64_i8 (integer-exact), P.V in `dtype` as above; v / o of `dtype`
+ * (WANQ_BF16 or WANQ_F16).
  * splits as in wanq_attention_fwd_split (1 = none; workspace from wanq_attention_split_workspace).
  * The reference wires this recipe for OpenSORA only (Q/base/quant_attn.py is imported, not used, by its Wan model). */
 int wanq_attention_qk8_fwd(const int8_t* q8, const float* q_scale, int64_t qs_stride, const int8_t* k8,
@@ -256,7 +259,8 @@ int wanq_attention_qk8_fwd(const int8_t* q8, const float* q_scale, int64_t qs_st
  * The reference materialises the N x N map (and asserts against flash attention); this entry point streams it in three passes
  * over the keys (row statistics, column maxima, quantised P.V), so it also runs at lengths where the map does not fit.  The map
  * is kept in fp32 (the reference rounds it to the model's 16-bit dtype first when it runs under autocast).
- * workspace: wanq_attention_map_workspace() bytes of device memory, 16-byte aligned.  q / k / v / o as in wanq_attention_fwd. */
+ * workspace: wanq_attention_map_workspace() bytes of device memory, 16-byte aligned.  q / k / v / o as in wanq_attention_fwd, but
+ * dtype WANQ_BF16 only (both map entry points): P reaches the MFMA as a bf16 hi + lo pair, numerics that have no fp16 form yet. */
 int64_t wanq_attention_map_workspace(int64_t Lq, int64_t Lk, int heads);
 int wanq_attention_map_quant_fwd(const void* q, const void* k, const void* v, void* o, int dtype, int64_t Lq, int64_t Lk,
                                  int heads, int head_dim, int64_t q_stride, int64_t k_stride, int64_t v_stride,

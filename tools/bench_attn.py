@@ -1,6 +1,12 @@
 #!/usr/bin/env python3
 """Attention kernel timing at cfg-B (L=32760, 12 heads, d=128): bf16 HIP kernel vs the int8 Q.K^T form (interleaved rounds in
-ONE process, median and minimum) vs torch SDPA, plus the quantisation error of the int8 form against the bf16 kernel."""
+ONE process, median and minimum) vs torch SDPA, plus the quantisation error of the int8 form against the bf16 kernel.
+
+    python tools/bench_attn.py [quick] [--dtype {bf16,fp16}]
+
+--dtype fp16 adds the fp16 forms of both kernels to the SAME interleaved rounds (the bf16 ones stay in as the baseline) and prints
+the fp16 / bf16 time ratios."""
+import argparse
 import math
 import os
 import sys
@@ -44,8 +50,12 @@ def ab(fns, rounds=7):
     return {n: (sorted(v)[len(v) // 2], min(v)) for n, v in ts.items()}
 
 
+ap = argparse.ArgumentParser()
+ap.add_argument("mode", nargs="?", choices=["quick"], help="quick: the cfg-B self-attention shape only")
+ap.add_argument("--dtype", choices=["bf16", "fp16"], default="bf16", help="fp16: time the fp16 forms against the bf16 ones, interleaved")
+args = ap.parse_args()
 shapes = [(32760, 32760, 12), (32760, 512, 12), (9450, 75600, 5)]
-if len(sys.argv) > 1 and sys.argv[1] == "quick":
+if args.mode == "quick":
     shapes = shapes[:1]
 for (Lq, Lk, H) in shapes:
     g = torch.Generator(device="cuda").manual_seed(0)
@@ -56,18 +66,29 @@ for (Lq, Lk, H) in shapes:
     q, k = ops.rmsnorm_rope_(xq.clone(), w, None, 128).to(torch.bfloat16), ops.rmsnorm_rope_(xk.clone(), w, None, 128).to(torch.bfloat16)
     q8, k8 = ops.rmsnorm_rope_q8(xq, w, None, 128, False), ops.rmsnorm_rope_q8(xk, w, None, 128, True)
     fl = 4.0 * Lq * Lk * 128 * H
-    r = ab({"bf16": lambda: ops.attention(q, k, v, H), "qk8": lambda: ops.attention_qk8(q8, k8, v, H)})
+    fns = {"bf16": lambda: ops.attention(q, k, v, H), "qk8": lambda: ops.attention_qk8(q8, k8, v, H)}
+    if args.dtype == "fp16":
+        qh, kh, vh = q.half(), k.half(), v.half()
+        fns["fp16"] = lambda: ops.attention(qh, kh, vh, H)
+        fns["qk8-fp16"] = lambda: ops.attention_qk8(q8, k8, vh, H)
+    r = ab(fns)
     for n, (med, mn) in r.items():
         print(f"{n:5s} attention Lq={Lq} Lk={Lk} H={H}: median {med*1e3:8.3f} ms  min {mn*1e3:8.3f} ms  {fl/med/1e12:7.1f} TFLOP/s "
               f"({fl/med/2.5e15*100:.1f}% of the bf16 MFMA peak)")
     print(f"      qk8 / bf16 time ratio {r['qk8'][0] / r['bf16'][0]:.3f}")
+    if args.dtype == "fp16":
+        print(f"      fp16 / bf16 time ratio {r['fp16'][0] / r['bf16'][0]:.3f} (median)  {r['fp16'][1] / r['bf16'][1]:.3f} (min)   "
+              f"qk8-fp16 / qk8 {r['qk8-fp16'][0] / r['qk8'][0]:.3f} (median)  {r['qk8-fp16'][1] / r['qk8'][1]:.3f} (min)")
+        oh = ops.attention(qh, kh, vh, H).float()
+        o16_ = ops.attention(q, k, v, H).float()
+        print(f"      fp16 vs bf16 kernel: rel L2 {((oh - o16_).norm() / o16_.norm()).item():.3e}")
     o16, o8 = ops.attention(q, k, v, H).float(), ops.attention_qk8(q8, k8, v, H).float()
     print(f"      int8 Q.K^T vs bf16 kernel: rel L2 {((o8 - o16).norm() / o16.norm()).item():.3e}  max abs {(o8 - o16).abs().max().item():.3e}")
     if Lq * Lk <= 32760 * 32760:
         t = time_once(lambda: attention_sdpa(q, k, v, H))
         print(f"sdpa  attention Lq={Lq} Lk={Lk} H={H}: {t*1e3:8.3f} ms {fl/t/1e12:7.1f} TFLOP/s")
 
-if len(sys.argv) > 1 and sys.argv[1] == "quick":
+if args.mode == "quick":
     sys.exit(0)
 # the per-rank shape under 4-way sequence parallelism (3 of 12 heads, all 32760 tokens): 384 workgroups on 256 CUs
 Lq = Lk = 32760

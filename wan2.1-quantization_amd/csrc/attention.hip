@@ -2,10 +2,11 @@
 //
 //   O[q, h, :] = softmax_k( Q[q,h,:] . K[k,h,:] / sqrt(d) ) V[k,h,:]
 //
-// One kernel template, attn_fwd16_kernel<SPLIT, QK8, NW>, for every form: bf16 or int8 Q.K^T (QK8), whole key range or one
-// share of it (SPLIT, merged by attn_combine_kernel), 8 or 4 waves per workgroup (NW, plain bf16 only).
+// One kernel template, attn_fwd16_kernel<SPLIT, QK8, NW, F16>, for every form: 16-bit or int8 Q.K^T (QK8), whole key range or one
+// share of it (SPLIT, merged by attn_combine_kernel), 8 or 4 waves per workgroup (NW, plain 16-bit form only), bf16 or fp16
+// elements (F16: the MFMA instruction, the conversions and the exponent headroom of P differ, see at_elem; the text below says bf16).
 //
-// Layout: Q/K/V/O are token-major [tokens, heads*128] bf16 (exactly what the q/k/v GEMMs write and what the
+// Layout: Q/K/V/O are token-major [tokens, heads*128] bf16 or fp16 (exactly what the q/k/v GEMMs write and what the
 // o-projection's quantiser reads), so no head transposes exist anywhere.
 //
 // Structure: every wave owns 32 queries of one head for the whole kernel and holds their Q fragments in registers.  Per
@@ -37,6 +38,7 @@
 namespace wanq {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -75,11 +77,26 @@ __device__ __forceinline__ int at_off(int row, int ch) {
   return row * 256 + ((ch ^ (((row & 3) << 2) | ((row >> 2) & 3))) << 4);
 }
 
-__device__ __forceinline__ bf16x8 at_join(s16x4 lo, s16x4 hi) {
+// The 16-bit element type of Q / K / V / P / O: bf16, or fp16 (F16).  The LDS images, the LDS-DMA and the transposed reads move
+// 16-bit elements whatever they mean; the type shows in the MFMA instruction, in the conversions (hipcc emits round-to-nearest-even
+// v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32 or v_cvt_f16_f32 for the casts below, never the round-toward-zero cvt_pkrtz) and in the exponent
+// headroom AT_F16_HEADROOM of P.
+template <bool F16> struct at_elem { typedef __bf16 e; typedef bf16x8 x8; typedef __bf16 x4 __attribute__((ext_vector_type(4))); };
+template <> struct at_elem<true> { typedef _Float16 e; typedef f16x8 x8; typedef _Float16 x4 __attribute__((ext_vector_type(4))); };
+
+template <typename X8> __device__ __forceinline__ X8 at_join(s16x4 lo, s16x4 hi) {
   typedef short s16x8 __attribute__((ext_vector_type(8)));
   const s16x8 vv = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, vv);
+  return __builtin_bit_cast(X8, vv);
 }
+
+__device__ __forceinline__ f32x4 at_mfma(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x4 at_mfma(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+
+// fp16 P: P' = exp2(s - reference + 8).  bf16 keeps its 8 bits down to 2^-126; fp16 leaves its normal range at 2^-14, so the
+// fp16 forms lift P by 2^8: the largest P of a row lies in [2^8, 2^14] (lazy reference) and a key keeps all 11 bits down to 22
+// log2 units below the row maximum.  The factor runs through the row sum too and cancels in O / l.
+constexpr float AT_F16_HEADROOM = 8.0f;
 
 #ifndef WANQ_ATTN_NW4_KEYS_DEFAULT  // key count up to which the plain bf16 kernel runs in its 4-wave form
 #define WANQ_ATTN_NW4_KEYS_DEFAULT 1024
@@ -115,12 +132,15 @@ __device__ __forceinline__ bf16x8 at_join(s16x4 lo, s16x4 hi) {
 // NW = waves per workgroup: 8 (256 queries, three ring stages, tiles requested two ahead), or 4 (128 queries per workgroup,
 // two ring stages = 64 KiB, so that TWO workgroups share a CU: SIMD partners then belong to different workgroups and are not
 // coupled by the per-tile barrier; one's prologue / epilogue runs under the other's tiles).
-template <bool SPLIT, bool QK8, int NW = 8>
+template <bool SPLIT, bool QK8, int NW = 8, bool F16 = false>
 __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams p) {
-  constexpr bool LSUM = !(SPLIT && !QK8);  // row sums on the matrix cores (the bf16 split-KV form has no 8 registers to spare: it spills)
+  typedef typename at_elem<F16>::e elem_t;
+  typedef typename at_elem<F16>::x8 elem8_t;
+  constexpr float HR = F16 ? AT_F16_HEADROOM : 0.f;  // exponent headroom of P (log2 units)
+  constexpr bool LSUM = !(SPLIT && !QK8);  // row sums on the matrix cores (the 16-bit split-KV form has no 8 registers to spare: it spills)
   constexpr int STAGE = QK8 ? AT_STAGE8 : AT_STAGE;
   constexpr int NST = NW == 8 ? 3 : 2, AHEAD = NST - 1;  // ring stages, prefetch distance in tiles
-  static_assert(NW == 8 || (NW == 4 && !SPLIT && !QK8), "the 4-wave form exists for the plain bf16 kernel only");
+  static_assert(NW == 8 || (NW == 4 && !SPLIT && !QK8), "the 4-wave form exists for the plain 16-bit kernel only");
   constexpr int VOFF = QK8 ? AT_K8 : AT_TILE;  // byte offset of the V tile inside a stage
   typedef int v4i __attribute__((ext_vector_type(4)));
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -147,7 +167,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams
 
   // ---- Q fragments: query q0 + 16 nq + n16, d = 32 s + 8 g4 + [0, 8), pre-scaled by softmax scale * log2(e)
   // QK8: int8 codes, d = 64 s + 16 g4 + [0, 16); the query's scale delta_q rides in the exp2 coefficient c2[nq]
-  bf16x8 qf[QK8 ? 1 : 2][QK8 ? 1 : 4];
+  elem8_t qf[QK8 ? 1 : 2][QK8 ? 1 : 4];
   v4i qf8[QK8 ? 2 : 1][QK8 ? 2 : 1];
   float c2[2] = {c, c};
 #pragma unroll
@@ -162,11 +182,11 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams
     } else {
       const uint16_t* qp = p.q + (int64_t)qr * p.q_stride + head * AT_D + 8 * g4;
 #pragma unroll
-      for (int s = 0; s < 4; ++s) qf[QK8 ? 0 : nq][QK8 ? 0 : s] = *reinterpret_cast<const bf16x8*>(qp + 32 * s);
+      for (int s = 0; s < 4; ++s) qf[QK8 ? 0 : nq][QK8 ? 0 : s] = *reinterpret_cast<const elem8_t*>(qp + 32 * s);
 #pragma unroll
       for (int s = 0; s < 4; ++s)
 #pragma unroll
-        for (int e = 0; e < 8; ++e) qf[QK8 ? 0 : nq][QK8 ? 0 : s][e] = (__bf16)((float)qf[QK8 ? 0 : nq][QK8 ? 0 : s][e] * c);
+        for (int e = 0; e < 8; ++e) qf[QK8 ? 0 : nq][QK8 ? 0 : s][e] = (elem_t)((float)qf[QK8 ? 0 : nq][QK8 ? 0 : s][e] * c);
     }
   }
 
@@ -267,9 +287,9 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams
       for (int r = 0; r < 4; ++r) o[i][nq][r] = 0.f;
   float m_run[2] = {QK8 ? -INFINITY : 0.f, QK8 ? -INFINITY : 0.f}, l_run[2] = {0.f, 0.f};
   f32x4 lacc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};  // LSUM: row sums as MFMA accumulators (all four elements equal)
-  bf16x8 ones;
+  elem8_t ones;
 #pragma unroll
-  for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
+  for (int e = 0; e < 8; ++e) ones[e] = (elem_t)1.0f;
   asm volatile("" : "+v"(ones));  // one register quad for the whole kernel, not rematerialised per use
   // bf16 form: -m_run (log2 domain) in all four registers: the initial accumulator of the S chains of query block nq, rewritten
   // only when the running maximum moves (the first tile and lazy-rescale events)
@@ -320,7 +340,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams
       // (hipcc merges the waits of the builtin form into three s_waitcnt lgkmcnt(0) per tile, each of which drains the
       // lookahead it was given; 2 and 6 in flight measured within 1 % of 4)
       constexpr int KA = 4;  // fragments in flight
-      bf16x8 kf[16];
+      elem8_t kf[16];
       const uint32_t kbase = lds_base + u * STAGE;
       const uint32_t ka0 = kbase + koff0, ka1 = kbase + koff1, ka2 = kbase + koff2, ka3 = kbase + koff3;
 #define A16_KR(i) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(kf[i]) : "v"(((i) & 3) == 0 ? ka0 : ((i) & 3) == 1 ? ka1 : ((i) & 3) == 2 ? ka2 : ka3), "n"(((i) >> 2) * 4096))
@@ -337,8 +357,8 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams
         else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(kf[i]));
         __builtin_amdgcn_sched_barrier(0);
         const int kb = i >> 2, s = i & 3;
-        sacc[kb][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[i], qf[0][QK8 ? 0 : s], s == 0 ? sinit[0] : sacc[kb][0], 0, 0, 0);
-        sacc[kb][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[i], qf[QK8 ? 0 : 1][QK8 ? 0 : s], s == 0 ? sinit[1] : sacc[kb][1], 0, 0, 0);
+        sacc[kb][0] = at_mfma(kf[i], qf[0][QK8 ? 0 : s], s == 0 ? sinit[0] : sacc[kb][0]);
+        sacc[kb][1] = at_mfma(kf[i], qf[QK8 ? 0 : 1][QK8 ? 0 : s], s == 0 ? sinit[1] : sacc[kb][1]);
       }
 #undef A16_KR
     } else {
@@ -413,12 +433,13 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams
             for (int r = 0; r < 4; ++r) o[i][nq][r] *= alpha;
         }
       }
-    } else if (first || __any(fmaxf(mx0, mx1) > 6.0f)) {
+    } else if (first || __any(fmaxf(mx0, mx1) > 6.0f + HR)) {
       // The accumulators hold s * scale * log2(e) - m_run already (Q carries the scale, the MFMA chains started from -m_run), so
       // the maxima are the growth of the row maximum over the reference and p = exp2(acc) with no further arithmetic.  The first
       // tile fixes the reference at its own maximum (whatever its sign); later the reference only grows, lazily: when some
       // query's maximum exceeds it by more than 2^6 (wave-uniform vote) -- P stays <= 64 instead of <= 1, the same 8 significant
-      // bits in bf16 -- and then O, l and this tile's scores are brought to the new reference.
+      // bits in bf16 -- and then O, l and this tile's scores are brought to the new reference.  fp16: the reference sits HR below
+      // that (the chains start from HR - m_run, at no instruction in the loop), so the accumulators are HR larger throughout.
       asm volatile("" ::: "memory");  // keep this a branch
       float mx[2] = {mx0, mx1};
 #pragma unroll
@@ -426,6 +447,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams
         float m = mx[nq];
         m = fmaxf(m, __shfl_xor(m, 16, 64));
         m = fmaxf(m, __shfl_xor(m, 32, 64));
+        if (F16) m -= HR;
         const float delta = first ? m : fmaxf(m, 0.f);
         if (!first) {
           const float alpha = __builtin_amdgcn_exp2f(-delta);
@@ -448,12 +470,13 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams
     }
     // P of key slice ks (32 keys) for query block nq: element j = 4 (kb & 1) + e of S block kb = 2 ks + (j >> 2)
     float ls0 = 0.f, ls1 = 0.f;
-    const float mc[2] = {QK8 ? m_run[0] * c2[0] : 0.f, QK8 ? m_run[1] * c2[1] : 0.f};
-    bf16x8 pf[2][2];
+    // (fp16: the headroom rides in the constant of the exponent's fma)
+    const float mc[2] = {QK8 ? (F16 ? fmaf(m_run[0], c2[0], -HR) : m_run[0] * c2[0]) : 0.f, QK8 ? (F16 ? fmaf(m_run[1], c2[1], -HR) : m_run[1] * c2[1]) : 0.f};
+    elem8_t pf[2][2];
 #define A16_EXP(kb, nq, e)                                                     \
   {                                                                            \
     const float x_ = __builtin_amdgcn_exp2f(QK8 ? fmaf(sacc[kb][nq][e], c2[nq], -mc[nq]) : sacc[kb][nq][e]); \
-    const __bf16 b_ = (__bf16)x_;                                              \
+    const elem_t b_ = (elem_t)x_;                                              \
     if (!LSUM) { /* the sum of the ROUNDED P, as the MFMA form has it */        \
       if (nq == 0) { ls0 += (float)b_; asm volatile("" : "+v"(ls0)); }         \
       else { ls1 += (float)b_; asm volatile("" : "+v"(ls1)); }                 \
@@ -476,9 +499,9 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams
   A16_TR(P##4, a2_, ks, 0); A16_TR(P##5, a2_, ks, 1); A16_TR(P##6, a3_, ks, 0); A16_TR(P##7, a3_, ks, 1)
 #define A16_WAIT8(P, n)                                                                                    \
   asm volatile("s_waitcnt lgkmcnt(" #n ")" : "+v"(P##0), "+v"(P##1), "+v"(P##2), "+v"(P##3), "+v"(P##4), "+v"(P##5), "+v"(P##6), "+v"(P##7))
-#define A16_PV(P, a, b, ks, db, nq) o[db][nq] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(at_join(P##a, P##b), pf[ks][nq], o[db][nq], 0, 0, 0)
+#define A16_PV(P, a, b, ks, db, nq) o[db][nq] = at_mfma(at_join<elem8_t>(P##a, P##b), pf[ks][nq], o[db][nq])
 #define A16_F() __builtin_amdgcn_sched_barrier(0)
-#define A16_LS(ks, nq) if (LSUM) lacc[nq] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pf[ks][nq], lacc[nq], 0, 0, 0)
+#define A16_LS(ks, nq) if (LSUM) lacc[nq] = at_mfma(ones, pf[ks][nq], lacc[nq])
     A16_TR8(ta, 0, va0, va1, va2, va3);
     A16_TR8(tb, 0, va4, va5, va6, va7);
     A16_EXP4(0, 0) A16_EXP4(1, 0) A16_EXP4(0, 1) A16_EXP4(1, 1)
@@ -562,18 +585,19 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams
       uint16_t* op = p.o + (int64_t)qr * p.o_stride + head * AT_D + 4 * g4;
 #pragma unroll
       for (int db = 0; db < 8; ++db) {
-        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-        bf16x4 b;
+        typename at_elem<F16>::x4 b;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) b[e] = (__bf16)(o[db][nq][e] * inv);
-        *reinterpret_cast<bf16x4*>(op + 16 * db) = b;
+        for (int e = 0; e < 4; ++e) b[e] = (elem_t)(o[db][nq][e] * inv);
+        *reinterpret_cast<typename at_elem<F16>::x4*>(op + 16 * db) = b;
       }
     }
   }
 }
 
 // Split-KV merge: out[q, h, :] = sum_z w_z O_z / sum_z w_z l_z,  w_z = 2^{(m_z - max_z m_z) c}.  One thread per 4 channels.
+template <bool F16>
 __global__ __launch_bounds__(256) void attn_combine_kernel(const AttnParams p, int splits) {
+  typedef typename at_elem<F16>::e elem_t;
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int per_q = p.H * (AT_D / 4);
   const int64_t q = t / per_q;
@@ -591,10 +615,9 @@ __global__ __launch_bounds__(256) void attn_combine_kernel(const AttnParams p, i
     l += w * ml[1];
   }
   const float inv = 1.0f / l;
-  typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-  bf16x4 b;
-  b[0] = (__bf16)(acc.x * inv); b[1] = (__bf16)(acc.y * inv); b[2] = (__bf16)(acc.z * inv); b[3] = (__bf16)(acc.w * inv);
-  *reinterpret_cast<bf16x4*>(p.o + q * p.o_stride + h * AT_D + 4 * d4) = b;
+  typename at_elem<F16>::x4 b;
+  b[0] = (elem_t)(acc.x * inv); b[1] = (elem_t)(acc.y * inv); b[2] = (elem_t)(acc.z * inv); b[3] = (elem_t)(acc.w * inv);
+  *reinterpret_cast<typename at_elem<F16>::x4*>(p.o + q * p.o_stride + h * AT_D + 4 * d4) = b;
 }
 
 }  // namespace wanq
@@ -621,6 +644,11 @@ static void allow_attn_dynamic_lds() {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd16_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * AT_STAGE);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd16_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * AT_STAGE8);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd16_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * AT_STAGE8);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd16_kernel<false, false, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * AT_STAGE);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd16_kernel<false, false, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * AT_STAGE);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd16_kernel<true, false, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * AT_STAGE);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd16_kernel<false, true, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * AT_STAGE8);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd16_kernel<true, true, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * AT_STAGE8);
     return true;
   }();
   (void)done;
@@ -631,7 +659,8 @@ static int attention_impl(const void* q, const void* k, const void* v, void* o, 
                           int splits, void* workspace, int64_t workspace_bytes, void* stream, const Qk8Args* q8 = nullptr) {
   const char* what = q8 ? "wanq_attention_qk8_fwd" : "wanq_attention_fwd";
   WANQ_REQUIRE((q8 || (q && k)) && v && o, WANQ_E_ARG, "%s: NULL pointer", what);
-  WANQ_REQUIRE(dtype == WANQ_BF16, WANQ_E_ARG, "%s: only bf16 is implemented (dtype code %d)", what, dtype);
+  WANQ_REQUIRE(dtype == WANQ_BF16 || dtype == WANQ_F16, WANQ_E_ARG, "%s: dtype must be WANQ_BF16 or WANQ_F16 (dtype code %d)", what, dtype);
+  const bool f16 = dtype == WANQ_F16;
   WANQ_REQUIRE(head_dim == AT_D, WANQ_E_SHAPE, "%s: head_dim=%d, only 128 is implemented", what, head_dim);
   WANQ_REQUIRE(heads >= 1 && heads <= 65535, WANQ_E_SHAPE, "%s: heads=%d out of range", what, heads);
   WANQ_REQUIRE(Lq >= 0 && Lk >= 1 && Lq < (1ll << 30) && Lk < (1ll << 30), WANQ_E_SHAPE, "%s: bad lengths", what);
@@ -668,14 +697,18 @@ static int attention_impl(const void* q, const void* k, const void* v, void* o, 
   allow_attn_dynamic_lds();
   if (splits <= 1) {
     if (q8) {
-      hipLaunchKernelGGL((attn_fwd16_kernel<false, true>), grid, dim3(512), 3 * AT_STAGE8, st, p);
+      if (f16) hipLaunchKernelGGL((attn_fwd16_kernel<false, true, 8, true>), grid, dim3(512), 3 * AT_STAGE8, st, p);
+      else hipLaunchKernelGGL((attn_fwd16_kernel<false, true>), grid, dim3(512), 3 * AT_STAGE8, st, p);
     } else {
       // 4-wave workgroups of 128 queries, two per CU (see attn_fwd16_kernel), up to WANQ_ATTN_NW4_KEYS keys (0 = never)
       static const int64_t nw4_env = [] { const char* e = getenv("WANQ_ATTN_NW4_KEYS"); return e ? atoll(e) : (int64_t)WANQ_ATTN_NW4_KEYS_DEFAULT; }();
       const int64_t nw4_sel = g_nw4_keys;  // wanq_attention_select_form: -1 = the start-up value
       if (Lk <= (nw4_sel >= 0 ? nw4_sel : nw4_env)) {
         const dim3 grid4((unsigned)((Lq + 4 * AT_QW - 1) / (4 * AT_QW)), (unsigned)heads);
-        hipLaunchKernelGGL((attn_fwd16_kernel<false, false, 4>), grid4, dim3(256), 2 * AT_STAGE, st, p);
+        if (f16) hipLaunchKernelGGL((attn_fwd16_kernel<false, false, 4, true>), grid4, dim3(256), 2 * AT_STAGE, st, p);
+        else hipLaunchKernelGGL((attn_fwd16_kernel<false, false, 4>), grid4, dim3(256), 2 * AT_STAGE, st, p);
+      } else if (f16) {
+        hipLaunchKernelGGL((attn_fwd16_kernel<false, false, 8, true>), grid, dim3(512), 3 * AT_STAGE, st, p);
       } else {
         hipLaunchKernelGGL((attn_fwd16_kernel<false, false>), grid, dim3(512), 3 * AT_STAGE, st, p);
       }
@@ -689,10 +722,13 @@ static int attention_impl(const void* q, const void* k, const void* v, void* o, 
   p.part_o = static_cast<float*>(workspace);
   p.part_ml = p.part_o + (int64_t)splits * Lq * heads * AT_D;
   grid.z = (unsigned)splits;
-  if (q8) hipLaunchKernelGGL((attn_fwd16_kernel<true, true>), grid, dim3(512), 3 * AT_STAGE8, st, p);
+  if (q8 && f16) hipLaunchKernelGGL((attn_fwd16_kernel<true, true, 8, true>), grid, dim3(512), 3 * AT_STAGE8, st, p);
+  else if (q8) hipLaunchKernelGGL((attn_fwd16_kernel<true, true>), grid, dim3(512), 3 * AT_STAGE8, st, p);
+  else if (f16) hipLaunchKernelGGL((attn_fwd16_kernel<true, false, 8, true>), grid, dim3(512), 3 * AT_STAGE, st, p);
   else hipLaunchKernelGGL((attn_fwd16_kernel<true, false>), grid, dim3(512), 3 * AT_STAGE, st, p);
   const int64_t threads = Lq * heads * (AT_D / 4);
-  hipLaunchKernelGGL(attn_combine_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, p, splits);
+  if (f16) hipLaunchKernelGGL(attn_combine_kernel<true>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, p, splits);
+  else hipLaunchKernelGGL(attn_combine_kernel<false>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, p, splits);
   return check_launch(what);
 }
 

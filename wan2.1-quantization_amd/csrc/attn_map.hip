@@ -461,7 +461,7 @@ extern "C" int64_t wanq_attention_map_workspace(int64_t Lq, int64_t Lk, int head
 static int attn_map_common(const char* what, AttnMapParams& p, const void* v, void* o, int dtype, int64_t Lq, int64_t Lk, int heads, int head_dim,
                            int64_t v_stride, int64_t o_stride, float scale, int n_bits, int sym, void* workspace, int64_t workspace_bytes) {
   WANQ_REQUIRE(v && o, WANQ_E_ARG, "%s: NULL pointer", what);
-  WANQ_REQUIRE(dtype == WANQ_BF16, WANQ_E_ARG, "%s: only bf16 is implemented (dtype code %d)", what, dtype);
+  WANQ_REQUIRE(dtype == WANQ_BF16, WANQ_E_ARG, "%s: only bf16 is implemented (dtype code %d); the attention-map forms have no fp16 form: P reaches the MFMA as a bf16 hi + lo pair", what, dtype);
   WANQ_REQUIRE(head_dim == 128, WANQ_E_SHAPE, "%s: head_dim=%d, only 128 is implemented", what, head_dim);
   WANQ_REQUIRE(heads >= 1 && heads <= 65535, WANQ_E_SHAPE, "%s: heads=%d out of range", what, heads);
   WANQ_REQUIRE(Lq >= 0 && Lk >= 1 && Lq < (1ll << 30) && Lk < (1ll << 30), WANQ_E_SHAPE, "%s: bad lengths", what);

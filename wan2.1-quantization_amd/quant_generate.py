@@ -39,7 +39,8 @@ def main(args):
         iw = os.path.join(args.output_dir, "checkpoint", "int_weight.pt")
         # the reference exports the integer checkpoint and loads it into the kernel-mode blocks (quant_generate.py:397-409);
         # ptq_wanx.py already wrote it next to quant_params.pth: load it when it is there
-        model.hardware_forward_refactor(iw if os.path.exists(iw) else None, fp_gemm=args.fp_gemm)
+        model.hardware_forward_refactor(iw if os.path.exists(iw) else None, fp_gemm=args.fp_gemm,
+                                        act_dtype=torch.float16 if args.act_dtype == "fp16" else torch.bfloat16)
         if args.dit_fsdp and world > 1:  # FULL_SHARD of the DiT blocks (wan/distributed/fsdp.py): integer weights over all ranks
             sh = model.shard_blocks(None)
             logging.info("dit_fsdp: %.1f MB of block weights per rank (of %.1f MB)", sh.bytes_per_rank() / 1e6,

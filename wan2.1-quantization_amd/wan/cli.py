@@ -57,6 +57,8 @@ def build_parser(description, quant=False):
         p.add_argument("--hardware", type=str2bool, default=True, help="kernel mode (if_hardware, quant_generate.py:372)")
         p.add_argument("--fp_gemm", type=str, default="torch", choices=["torch", "hip"],
                        help="kernel mode: GEMM of the Linears the quant config keeps floating point (hip = csrc/gemm_bf16.hip, fused epilogues)")
+        p.add_argument("--act_dtype", type=str, default="bf16", choices=["bf16", "fp16"],
+                       help="kernel mode: 16-bit type of the activations between kernels and of the attention (fp16 = the reference's)")
     return p
 
 

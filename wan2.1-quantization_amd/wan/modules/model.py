@@ -95,6 +95,12 @@ class WanLayerNorm(nn.LayerNorm):
         return super().forward(x.float()).type_as(x)
 
 
+def _attn_dtype(t):
+    """The attention's operand type: fp16 when the projections write fp16 (a .half() model, as the reference's flash_attention
+    keeps fp16 q / k / v: W/wan/modules/attention.py:52-60), bf16 otherwise."""
+    return torch.float16 if t.dtype == torch.float16 else torch.bfloat16
+
+
 class WanSelfAttention(nn.Module):
     def __init__(self, dim, num_heads, window_size=(-1, -1), qk_norm=True, eps=1e-6):
         super().__init__()
@@ -119,7 +125,7 @@ class WanSelfAttention(nn.Module):
             q = self.norm_q(self.q(x)).view(b, s, n, d)
             k = self.norm_k(self.k(x)).view(b, s, n, d)
             v = self.v(x).view(b, s, n, d)
-        outs = []
+        outs, adt = [], _attn_dtype(v)
         for i in range(b):
             off = sp.rank * s if par else 0
             if fuse:
@@ -131,11 +137,11 @@ class WanSelfAttention(nn.Module):
                 else:
                     ops.rmsnorm_rope_(qi, self.norm_q.weight.float(), None, d, eps=self.norm_q.eps)
                     ops.rmsnorm_rope_(ki, self.norm_k.weight.float(), None, d, eps=self.norm_k.eps)
-                qi, ki, vi = qi.to(torch.bfloat16), ki.to(torch.bfloat16), v[i].to(torch.bfloat16).contiguous()
+                qi, ki, vi = qi.to(adt), ki.to(adt), v[i].to(adt).contiguous()
             else:
-                qi = rope_apply(q[i], grid_sizes[i], freqs, off).to(torch.bfloat16).flatten(1)
-                ki = rope_apply(k[i], grid_sizes[i], freqs, off).to(torch.bfloat16).flatten(1)
-                vi = v[i].to(torch.bfloat16).flatten(1)
+                qi = rope_apply(q[i], grid_sizes[i], freqs, off).to(adt).flatten(1)
+                ki = rope_apply(k[i], grid_sizes[i], freqs, off).to(adt).flatten(1)
+                vi = v[i].to(adt).flatten(1)
             if par:
                 wq, wk, wv = (sp.scatter_heads(t_, async_op=True) for t_ in (qi, ki, vi))
                 oi = ops.attention(wq.wait(), wk.wait(), wv.wait(), n // sp.size, int(seq_lens[i]))
@@ -157,7 +163,8 @@ class WanT2VCrossAttention(WanSelfAttention):
             q = self.norm_q(self.q(x))
             k = self.norm_k(self.k(context))
         v = self.v(context)
-        outs = [ops.attention(q[i].to(torch.bfloat16), k[i].to(torch.bfloat16), v[i].to(torch.bfloat16), n,
+        adt = _attn_dtype(v)
+        outs = [ops.attention(q[i].to(adt), k[i].to(adt), v[i].to(adt), n,
                               None if context_lens is None else int(context_lens[i])) for i in range(b)]
         return self.o(torch.stack(outs))
 

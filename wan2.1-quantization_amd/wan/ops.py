@@ -62,6 +62,19 @@ def rmsnorm_rope_scatter(x, weight, rope, head_dim, out, head_map, rows_per_batc
     return out
 
 
+_ATTN_DTYPES = (torch.bfloat16, torch.float16)  # the 16-bit operand types of csrc/attention.hip
+
+
+def _check_attn_dtype(what, **tensors):
+    """The flash-attention operands are all bf16 or all fp16; a mixed set is refused by name."""
+    kinds = {n: t.dtype for n, t in tensors.items()}
+    first = next(iter(kinds.values()))
+    if first not in _ATTN_DTYPES or any(d != first for d in kinds.values()):
+        raise RuntimeError(f"{what}: " + ", ".join(f"{n} is {d}" for n, d in kinds.items()) +
+                           "; the operands must all be torch.bfloat16 or all be torch.float16")
+    return first
+
+
 class Q8Rows:
     """Per-(token, head) int8 form of a q or k tensor for the int8 Q.K^T attention: codes int8 [rows, C] and the fp32 scale
     planes [2, H, stride] (delta, -12582912 * delta) that wanq_rmsnorm_rope_q8 writes."""
@@ -87,8 +100,9 @@ class Q8Rows:
         return self
 
 
-def rmsnorm_rope_q8(x, weight, rope, head_dim, for_keys, eps=1e-6, want_fp=False):
-    """RMSNorm_C(x) * weight -> rotary -> per-(token, head) int8 quantise: returns Q8Rows (and the bf16 row when want_fp).
+def rmsnorm_rope_q8(x, weight, rope, head_dim, for_keys, eps=1e-6, want_fp=False, fp_dtype=None):
+    """RMSNorm_C(x) * weight -> rotary -> per-(token, head) int8 quantise: returns Q8Rows (and the 16-bit row when want_fp: of
+    fp_dtype, else of x's own type when that is bf16 / fp16, else bf16).
     for_keys: pad the scale planes' row stride to a multiple of 64 (the attention kernel fetches key scales per 64-key tile)."""
     _C.check_gpu("x", x)
     _C.check_contig("x", x)
@@ -104,10 +118,14 @@ def rmsnorm_rope_q8(x, weight, rope, head_dim, for_keys, eps=1e-6, want_fp=False
         _C.check_dtype("weight", weight, torch.float32)
         _C.check_shape("weight", weight, cols)
     q8 = Q8Rows(rows, cols, head_dim, x.device, 64 if for_keys else 1)
-    out = torch.empty(rows, cols, dtype=torch.bfloat16, device=x.device) if want_fp else None
+    if fp_dtype is None:
+        fp_dtype = x.dtype if x.dtype in _ATTN_DTYPES else torch.bfloat16
+    if fp_dtype not in _ATTN_DTYPES:
+        raise RuntimeError(f"rmsnorm_rope_q8: fp_dtype {fp_dtype} is not torch.bfloat16 or torch.float16")
+    out = torch.empty(rows, cols, dtype=fp_dtype, device=x.device) if want_fp else None
     with torch.cuda.device(x.device):
         _C.call("wanq_rmsnorm_rope_q8", _C.ptr(x), _C.dt(x), _C.ptr(weight), _C.ptr(rope), _C.ptr(out),
-                _C.BF16, _C.ptr(q8.codes), _C.ptr(q8.scales), q8.stride, rows, cols, head_dim, rows, positions, float(eps),
+                _C.F16 if fp_dtype == torch.float16 else _C.BF16, _C.ptr(q8.codes), _C.ptr(q8.scales), q8.stride, rows, cols, head_dim, rows, positions, float(eps),
                 _C.stream(), hbm=("rmsnorm_rope_q8", rows * cols * (x.element_size() + 1 + (2 if want_fp else 0)) +
                                   8 * rows * (cols // head_dim) + (min(rows, positions) * head_dim * 4 if rope is not None else 0)))
     return (q8, out) if want_fp else q8
@@ -115,16 +133,19 @@ def rmsnorm_rope_q8(x, weight, rope, head_dim, for_keys, eps=1e-6, want_fp=False
 
 def attention_qk8(q8, k8, v, num_heads, k_len=None, out=None, splits=None):
     """softmax((q8 . k8) * delta_q * delta_k / sqrt(d)) v with the score matrix on the int8 matrix cores
-    (csrc/attention.hip, QK8); q8 / k8: Q8Rows, v bf16 [Lk, C] -> bf16 [Lq, C]."""
+    (csrc/attention.hip, QK8); q8 / k8: Q8Rows, v bf16 or fp16 [Lk, C] -> [Lq, C] of v's type (P.V runs in that type)."""
     Lq, C = q8.codes.shape
     d = C // num_heads
     _C.check_gpu("v", v)
-    _C.check_dtype("v", v, torch.bfloat16)
+    if out is None:
+        _check_attn_dtype("attention_qk8", v=v)
+    else:
+        _check_attn_dtype("attention_qk8", v=v, out=out)
     if v.dim() != 2 or v.shape[1] != C or v.stride(1) != 1 or v.shape[0] != k8.codes.shape[0]:
         raise RuntimeError(f"Tensor v must be [{k8.codes.shape[0]}, {C}] with unit column stride")
     Lk = k8.codes.shape[0] if k_len is None else min(int(k_len), k8.codes.shape[0])
     if out is None:
-        out = torch.empty(Lq, C, dtype=torch.bfloat16, device=v.device)
+        out = torch.empty(Lq, C, dtype=v.dtype, device=v.device)
     if splits is None:
         splits = attention_splits(Lq, Lk, num_heads, v.device)
     ws, nbytes = None, 0
@@ -136,7 +157,7 @@ def attention_qk8(q8, k8, v, num_heads, k_len=None, out=None, splits=None):
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
         _C.call("wanq_attention_qk8_fwd", _C.ptr(q8.codes), _C.ptr(q8.scales), q8.stride, _C.ptr(k8.codes), _C.ptr(k8.scales),
-                k8.stride, _C.ptr(v), _C.ptr(out), _C.BF16, Lq, Lk, num_heads, d, q8.codes.stride(0), k8.codes.stride(0),
+                k8.stride, _C.ptr(v), _C.ptr(out), _C.dt(v), Lq, Lk, num_heads, d, q8.codes.stride(0), k8.codes.stride(0),
                 v.stride(0), out.stride(0), 1.0 / math.sqrt(d), max(1, int(splits)), _C.ptr(ws), nbytes, _C.stream())
         if _attn_timer is not None:
             ev1.record()
@@ -162,6 +183,8 @@ def attention_map_quant(q, k, v, num_heads, n_bits=8, sym=False, k_len=None, out
         return out
     Lq, C = q.shape
     d = C // num_heads
+    if torch.float16 in (q.dtype, k.dtype, v.dtype):
+        raise RuntimeError(_MAP_F16)
     for n, t in (("q", q), ("k", k), ("v", v)):
         _C.check_gpu(n, t)
         _C.check_dtype(n, t, torch.bfloat16)
@@ -181,6 +204,10 @@ def attention_map_quant(q, k, v, num_heads, n_bits=8, sym=False, k_len=None, out
     return out
 
 
+_MAP_F16 = ("attention_map_quant: fp16 operands are not implemented -- the attention-map kernels (csrc/attn_map.hip) hand P to the "
+            "matrix cores as a bf16 hi + lo pair and take bf16 q / k / v only")
+
+
 def _attention_map_quant_q8(q8, k8, v, num_heads, n_bits, sym, k_len, out, q_len):
     """attention_map_quant with q and k as Q8Rows (per-(token, head) int8 codes + scale planes): S runs on the int8 matrix cores
     in all three passes -- together with a fake-quantised v the reference's whole recipe (W/models/quant_opensora.py:431-476)."""
@@ -190,6 +217,8 @@ def _attention_map_quant_q8(q8, k8, v, num_heads, n_bits, sym, k_len, out, q_len
     Lq = rows if q_len is None else min(int(q_len), rows)
     d = C // num_heads
     _C.check_gpu("v", v)
+    if v.dtype == torch.float16:
+        raise RuntimeError(_MAP_F16)
     _C.check_dtype("v", v, torch.bfloat16)
     if v.dim() != 2 or v.shape[1] != C or v.stride(1) != 1 or v.shape[0] != k8.codes.shape[0]:
         raise RuntimeError(f"Tensor v must be [{k8.codes.shape[0]}, {C}] with unit column stride")
@@ -253,18 +282,21 @@ def attention_splits(Lq, Lk, num_heads, device, ncu=None):
 
 def attention(q, k, v, num_heads, k_len=None, out=None, splits=None):
     """softmax(q k^T / sqrt(d)) v for one sample on the HIP flash-attention kernel (csrc/attention.hip).
-    q [Lq, C], k/v [Lk, C] bf16, token-major (row stride may exceed C: column slices of a packed buffer are
-    fine) -> [Lq, C].  k_len masks key padding (flash_attention(..., k_lens), wan/modules/attention.py:78-80).
+    q [Lq, C], k/v [Lk, C] all bf16 or all fp16, token-major (row stride may exceed C: column slices of a packed buffer are
+    fine) -> [Lq, C] of that type.  k_len masks key padding (flash_attention(..., k_lens), wan/modules/attention.py:78-80).
     splits: None = attention_splits() decides; 1 = one workgroup per (query block, head); n = split-KV.
     fp32 operands (the kernel-mode block built with act_dtype=float32, a parity-test configuration) are rounded to bf16 here:
-    bf16 operands and a bf16 P are the kernel's contract, as they are flash_attn's in the reference."""
+    16-bit operands and a 16-bit P are the kernel's contract, as they are flash_attn's in the reference."""
     if q.dtype == torch.float32 and k.dtype == torch.float32 and v.dtype == torch.float32:
         q, k, v = q.to(torch.bfloat16), k.to(torch.bfloat16), v.to(torch.bfloat16)
     Lq, C = q.shape
     d = C // num_heads
+    if out is None:
+        _check_attn_dtype("attention", q=q, k=k, v=v)
+    else:
+        _check_attn_dtype("attention", q=q, k=k, v=v, out=out)
     for n, t in (("q", q), ("k", k), ("v", v)):
         _C.check_gpu(n, t)
-        _C.check_dtype(n, t, torch.bfloat16)
         if t.dim() != 2 or t.shape[1] != C or t.stride(1) != 1:
             raise RuntimeError(f"Tensor {n} must be [tokens, {C}] with unit column stride")
     if k.shape[0] != v.shape[0]:

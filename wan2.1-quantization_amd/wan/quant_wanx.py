@@ -136,6 +136,10 @@ class QuantWanModel(WanModel, QuantModel):
                     raise NotImplementedError(
                         f"{key}.attn_map.group = {am.get('group')!r}: the 'block' mode of the reference is tied to CogVideoX's 13x30x45 grid "
                         "and to per-head reorder tables (Q/base/quant_attn.py:176-236); 'row' is implemented (streamed, csrc/attn_map.hip)")
+                if act_dtype == torch.float16:
+                    raise NotImplementedError(
+                        f"{key}.attn_map with act_dtype=torch.float16: the attention-map kernels (csrc/attn_map.hip) hand P to the matrix "
+                        "cores as a bf16 hi + lo pair and take bf16 q / k / v only; build kernel mode with act_dtype=torch.bfloat16")
                 amap[key] = (int(am.get("n_bits", 8)), bool(am.get("sym", False)))
         # the fp32 ends of a pass (csrc/embed_head.hip: patch / time / text embeddings, head) read these parameters as fp32, as the
         # reference computes them (amp.autocast(dtype=torch.float32) around the time MLPs and the head, model.py:592-597,396-399):
