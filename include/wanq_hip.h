@@ -132,6 +132,29 @@ int wanq_gemm_bf16(const void* a, const void* w, int dtype, void* out, int out_d
                    const float* gate, const void* residual, int epi_flags, int64_t M, int N, int K, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Weight-only quantised GEMM (W8A16 / W4A16): 16-bit activations against integer weight codes, on the matrix cores and with the
+ * epilogue of wanq_gemm_bf16:
+ *   acc = sum_k a[m,k] * (c[n,k] + zp[n])           (a of `dtype`: WANQ_BF16 or WANQ_F16; fp32 accumulation)
+ *   y   = acc * sw[n] + bias[n]                     (one fp32 fma; sw fp32[N]; zp fp32[N] or NULL = 0; bias may be NULL)
+ *   y   = gelu_tanh(y)                              if WANQ_EPI_GELU
+ *   y   = residual[m,n] + y * gate[n]               if WANQ_EPI_GATE_RES
+ *   out = cast(y) to out_dtype (F16 | BF16 | F32): one rounding.
+ * w_bits = 8: c is int8 [N, K].  w_bits = 4: c is the unsigned nibbles of wanq_pack_w4's layout ([N, K/2] bytes) and zp follows
+ * the W4A8 convention, zero_point - 8.  The codes become 16-bit MFMA fragments in registers; no dequantised weight is written.
+ * Exactness: c + zp is an integer with |c + zp| <= 255 for every StaticQuantizer output (8-bit asymmetric: c in [-128, 127], zp in
+ * [-127, 128]; 4-bit: 0..15), exact in bf16 (8 significant bits) and in fp16, so the weight reaches the matrix cores without any
+ * rounding and each product a (c + zp) is exact in fp32; sw is applied once, in fp32.  zp must be integer valued.
+ * Any M >= 1; N % 8 == 0; K % 64 == 0; a, w, out, residual, sw and zp 16-byte aligned, gate and bias aligned to 4 elements.
+ * Anything else is refused (WANQ_E_SHAPE / WANQ_E_ARG, the message names the rule).
+ * Determinism: wanq_gemm_bf16's summation order -- with sw = 1 the output is bit-equal to wanq_gemm_bf16 on (c + zp) cast to `dtype`;
+ * a row gives the same bits in any launch.
+ * Replaces QuantizedLinear.forward with a weight quantiser and a_quantizer = None, F.linear(x, (c + zp) * delta, bias)
+ *   (ViDiT-Q/quant_utils/qdiff/base/quant_layer.py:68-72), which under autocast rounds (c + zp) * delta to bf16 first. */
+int wanq_gemm_wq16(const void* a, const void* w, int dtype, int w_bits, const float* sw, const float* zp, void* out,
+                   int out_dtype, const void* bias, int bias_dtype, const float* gate, const void* residual, int epi_flags,
+                   int64_t M, int N, int K, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * PTQ calibration reduction: running per-channel absmax over tokens,
  *   colmax[c] = max(colmax[c], max_r |x[r,c]|)        (colmax fp32[cols], caller zero-initialises)
  * Replaces SaveActivationHook.__call__ default branch

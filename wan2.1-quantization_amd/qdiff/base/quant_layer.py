@@ -11,6 +11,7 @@ but forward() does not use it.  It uses int8 codes of that same weight and runs
 The rotation is stored as its +-1 sign vector (`rotation_signs`); `rotation_matrix` materialises on demand."""
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from viditq_extension import qgemm
 
@@ -32,7 +33,7 @@ class QuantizedLinear(nn.Linear):
         self.rotation_signs = None
         self._premul = self._rot = None
         self.register_buffer("_codes", None, persistent=False)  # int8 [N,K], or uint8 [N,K/2] packed nibbles (4-bit weights)
-        self._zp_gemm = None
+        self._zp_gemm = self._wq16_vecs = None
         if quant_config.get("weight", None) is not None:
             wq = quant_config["weight"]
             self.w_quantizer = (MixedPrecisionStaticQuantizer if isinstance(wq["n_bits"], ListConfig) else StaticQuantizer)(wq)
@@ -74,7 +75,7 @@ class QuantizedLinear(nn.Linear):
             self._codes = qgemm.pack_w4(codes.contiguous(), bias=8)
         else:
             self._codes = codes
-        self._zp_gemm = None
+        self._zp_gemm = self._wq16_vecs = None
 
     def refresh(self):
         """Re-derive the quantized weight after the quantizer changed (bitwidth_refactor, load): the SAME derivation the
@@ -114,6 +115,8 @@ class QuantizedLinear(nn.Linear):
 
     def forward(self, x, *args, **kwargs):
         """x: [B, N_token, C] (or [tokens, C]) on the GPU."""
+        if self.quant_mode and self.w_quantizer is not None and self.a_quantizer is None and not (self.uses_mask or self.uses_rotation):
+            return self._forward_weight_only(x)
         if not self.quant_mode or self.w_quantizer is None or self.a_quantizer is None:
             return self.fp_module(x, *args, **kwargs)
         shape = x.shape
@@ -137,6 +140,36 @@ class QuantizedLinear(nn.Linear):
             t_a = (self.a_quantizer.zero_point.reshape(-1).float() * scale).to(y.dtype)
             y = torch.addcmul(y, t_a.unsqueeze(1), self.weight.data.float().sum(dim=1).to(y.dtype).unsqueeze(0))
         return y.view(*shape[:-1], self.out_features)
+
+    def weight_only_operands(self):
+        """(codes, scale fp32 [N], zp fp32 [N] or None, w4) of wanq_gemm_wq16 for this layer's quantised weight: int8 codes, or the
+        packed nibbles u = code + 8 with the 8 folded into the zero point (the W4A8 convention).  The two vectors are made once
+        and kept until the codes are set again (`int_weight`)."""
+        if self._wq16_vecs is None or self._wq16_vecs[0].device != self._codes.device:
+            wq, N = self.w_quantizer, self.out_features
+            w4 = self._codes.dtype == torch.uint8
+            sw = wq.delta.reshape(-1).float().expand(N).contiguous()
+            zp = None if wq.sym else wq.zero_point.reshape(-1).float().expand(N).contiguous()
+            if w4:
+                zp = ((zp if zp is not None else torch.zeros_like(sw)) - 8.0).contiguous()
+            self._wq16_vecs = (sw, zp, w4)
+        sw, zp, w4 = self._wq16_vecs
+        return self._codes, sw, zp, w4
+
+    def _forward_weight_only(self, x):
+        """A `weight:` section without an `act:` section: y = x @ W_hat^T + bias on the unquantised activations
+        (ViDiT-Q/quant_utils/qdiff/base/quant_layer.py:68-72 with a_quantizer None).  16-bit activations on the GPU go through
+        wanq_gemm_wq16 on the integer codes (exact weight operand, scale in the fp32 epilogue); anything else through the
+        reference's own expression, F.linear on the dequantised weight."""
+        if x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and self._codes is not None and self._codes.is_cuda:
+            x2 = x.reshape(-1, x.shape[-1])
+            if qgemm.wq16_linear_refusal(x2.shape[0], self.out_features, self.in_features) is None:
+                codes, sw, zp, w4 = self.weight_only_operands()
+                y = qgemm.wq16_linear(x2.contiguous(), codes, sw, zp, None if self.bias is None else self.bias.detach(), w4=w4)
+                return y.view(*x.shape[:-1], self.out_features)
+        w = self.weight if self.weight.dtype == x.dtype else self.weight.to(x.dtype)
+        b = self.bias if self.bias is None or self.bias.dtype == x.dtype else self.bias.to(x.dtype)
+        return F.linear(x, w, b)
 
     # ---- PTQ hooks shared by the variants ------------------------------------------------------------
     def get_channel_mask(self, act_mask):

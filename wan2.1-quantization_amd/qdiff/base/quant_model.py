@@ -48,13 +48,15 @@ def bitwidth_refactor_(submodule, name, parent_module, quant_config, full_name):
     (reference :76-105).  Unlike the reference the weight is re-quantised at the new width."""
     mp = quant_config.mixed_precision
     for kind, quantizer in (("weight", submodule.w_quantizer), ("act", submodule.a_quantizer)):
+        if mp.get(kind, None) is None:  # a weight-only config has no mixed_precision.act list
+            continue
         for idx, rgx in enumerate(mp[kind].layer_name_regex):
             if len(rgx) == 0 or not re.search(re.compile(rgx), full_name):
                 continue
             if idx == 0:
                 submodule.quant_mode = False
                 logger.info("[Mixed Precision] %s %s -> FP16", full_name, kind)
-            else:
+            elif quantizer is not None:  # None: the layer has no such quantiser (no `act:` section), nothing to set
                 quantizer.bitwidth_refactor(idx - 1)
                 if kind == "weight":
                     submodule.refresh()

@@ -272,3 +272,63 @@ def fp_linear_refusal(M, N, K):
     if K < 32 or K % 32:
         return f"K={K} must be a positive multiple of 32"
     return None
+
+
+# ---- weight-only quantisation: 16-bit activations x integer weight codes --------------------------------------------
+def wq16_linear(input, codes, scale_weight, zp=None, bias=None, out_dtype=None, gelu=False, gate=None, residual=None, out=None,
+                w4=False):
+    """y = epilogue(scale_weight[n] * input[M,K] @ (codes[N,K] + zp[n])^T) on the bf16 / fp16 matrix cores (wanq_gemm_wq16,
+    csrc/gemm_wq16.hip): `input` bf16 or fp16, `codes` int8 [N, K] or, with w4=True, uint8 [N, K/2] unsigned nibbles in the pack_w4
+    layout (zp = zero_point - 8 then); scale_weight and zp fp32 [N].  The codes become MFMA fragments in registers, exactly (c + zp
+    is an integer of at most 8 bits); epilogue as `fp_linear`.  Not counted by the int8 timer (`set_timer`).
+    `zp` must be integer valued, as StaticQuantizer's rounded zero point is: the kernel cuts the 16-bit operand from the fp32 sum
+    c + zp (bf16: truncation, fp16: round toward zero), so a fractional zp would be quantised silently, and differently for the two
+    activation types."""
+    _C.check_gpu("input", input)
+    _C.check_gpu("codes", codes)
+    _C.check_contig("input", input)
+    _C.check_contig("codes", codes)
+    _C.check_dtype("input", input, torch.bfloat16, torch.float16)
+    _C.check_dtype("codes", codes, torch.uint8 if w4 else torch.int8)
+    if input.dim() != 2 or codes.dim() != 2:
+        raise RuntimeError("Tensors input and codes must have dimension number (2)")
+    M, K = input.shape
+    N = codes.shape[0]
+    _C.check_shape("codes", codes, N, K // 2 if w4 else K)
+    _check_vec("scale_weight", scale_weight, N, (torch.float32,))
+    _check_vec("zp", zp, N, (torch.float32,))
+    out_dtype = out_dtype or input.dtype
+    if bias is not None:
+        _check_vec("bias", bias, N, (torch.bfloat16, torch.float16, torch.float32))
+    epi = _C.EPI_GELU if gelu else 0
+    if gate is not None or residual is not None:
+        if gate is None or residual is None:
+            raise RuntimeError("gate and residual must be given together")
+        _check_vec("gate", gate, N, (torch.float32,))
+        _C.check_gpu("residual", residual)
+        _C.check_contig("residual", residual)
+        _C.check_dtype("residual", residual, out_dtype)
+        _C.check_shape("residual", residual, M, N)
+        epi |= _C.EPI_GATE_RES
+    if out is None:
+        out = torch.empty((M, N), dtype=out_dtype, device=input.device)
+    else:
+        _C.check_gpu("out", out)
+        _C.check_contig("out", out)
+        _C.check_dtype("out", out, out_dtype)
+        _C.check_shape("out", out, M, N)
+    _C.check_same_device(input, codes, scale_weight, zp, bias, gate, residual, out)
+    with torch.cuda.device(input.device):
+        _C.call("wanq_gemm_wq16", _C.ptr(input), _C.ptr(codes), _C.dt(input), 4 if w4 else 8, _C.ptr(scale_weight), _C.ptr(zp),
+                _C.ptr(out), _C.dt(out_dtype), _C.ptr(bias), _C.dt(bias) if bias is not None else _C.F32, _C.ptr(gate),
+                _C.ptr(residual), epi, M, N, K, _C.stream())
+    return out
+
+
+def wq16_linear_refusal(M, N, K):
+    """Why wanq_gemm_wq16 would refuse an [M, K] x [N, K] product (None = accepted); see `fp_linear_refusal`."""
+    if N < 8 or N % 8:
+        return f"N={N} must be a positive multiple of 8"
+    if K < 64 or K % 64:
+        return f"K={K} must be a positive multiple of 64"
+    return None

@@ -159,15 +159,22 @@ class QuantWanModel(WanModel, QuantModel):
             cross_attn_map=amap.get("cross_attn"), fp_gemm=fp_gemm, name=f"blocks.{i}") for i, b in enumerate(self.blocks)])
         if load_path:
             sd = torch.load(load_path, map_location="cpu", weights_only=True)
-            taken = 0
+            taken = taken_wo = 0
             for i, hb in enumerate(self.hip_blocks):
                 for owner, attr, key in [(hb.self_attn, l, f"self_attn.{l}") for l in "qkvo"] + \
                                         [(hb.cross_attn, l, f"cross_attn.{l}") for l in "qkvo"] + \
                                         [(hb, "ffn0", "ffn.0"), (hb, "ffn2", "ffn.2")]:
                     lin = getattr(owner, attr)
-                    if not lin.quantized:
+                    weight_only = getattr(lin, "weight_only", False)  # HipLinearWq16: the same keys, no act_premul
+                    if not lin.quantized and not weight_only:
                         continue
                     base = f"blocks.{i}.{key}"
+                    # The two formats carry no marker.  What tells them apart is that reference_format=True writes fp16 scales and the
+                    # default format fp32 ones (quantize_and_save_weight): the test below relies on that.  A file with fp32 scales
+                    # around codes of the reference's half-precision equation would be taken as the default format.
+                    if weight_only and f"{base}.scale_weight" in sd and sd[f"{base}.scale_weight"].dtype == torch.float16:
+                        raise NotImplementedError(f"{load_path}: {base} is a weight-only layer and the file is in the reference's "
+                                                  "int_weight.pt format, which is W8A8 only (save with reference_format=False)")
                     for buf, k, required in (("weight", "weight", True), ("scale_weight", "scale_weight", True),
                                              ("zp_weight", "zp_weight", lin.zp_weight is not None),
                                              ("bias", "bias", lin.bias is not None),
@@ -188,8 +195,10 @@ class QuantWanModel(WanModel, QuantModel):
                             raise ValueError(f"{load_path}: {base}.{k} is {tuple(src.shape)} {src.dtype}, expected {tuple(dst.shape)} {dst.dtype}")
                         dst.copy_(src.to(dst.dtype))
                         taken += 1
+                        taken_wo += weight_only
                     lin.refresh_zp_gemm()
-            logger.info("loaded %d tensors of the integer checkpoint %s into the kernel-mode blocks", taken, load_path)
+            logger.info("loaded %d tensors of the integer checkpoint %s into the kernel-mode blocks (%d of them into weight-only layers)",
+                        taken, load_path, taken_wo)
         for i, hb in enumerate(self.hip_blocks):
             hb.block_index = i
         self.__dict__.pop("_mod_all", None)

@@ -154,12 +154,76 @@ class HipLinearFp(nn.Module):
         self.register_buffer("bias", None if bias is None else bias.detach().to(dtype).contiguous())
 
 
+class HipLinearWq16(nn.Module):
+    """A weight-only quantised Linear (a `weight:` section and no `act:` section: W8A16 / W4A16): HipLinearW8A8's integer codes,
+    per-channel fp32 (delta, zero_point) and fp32 bias -- 4-bit codes stay packed, `zp_gemm` = zero_point - 8 -- against the
+    block's 16-bit activations, through qgemm.wq16_linear (csrc/gemm_wq16.hip): the codes become MFMA fragments in registers,
+    exactly, and delta is applied in the fp32 epilogue.  No activation transform and no activation quantiser.
+    Counterpart of QuantizedLinear.forward with a_quantizer None (ViDiT-Q/quant_utils/qdiff/base/quant_layer.py:68-72)."""
+    quantized = False   # its input is not quantised: the block's int8 producers and their prefetch skip it
+    weight_only = True
+    act_key = "fp"
+    act_premul = None
+
+    def __init__(self, in_features, out_features, bias=True, sym=False, w_bits=8, name="linear"):
+        super().__init__()
+        assert w_bits in (4, 8), "integer storage exists for 8-bit and packed 4-bit weights"
+        why = qgemm.wq16_linear_refusal(1, out_features, in_features)
+        if why is not None:
+            raise ValueError(f"{name}: the weight-only GEMM cannot take this layer ({out_features}, {in_features}): {why}")
+        self.in_features, self.out_features, self.w_bits = in_features, out_features, w_bits
+        self.register_buffer("weight", torch.empty(out_features, in_features // 2 if w_bits == 4 else in_features,
+                                                   dtype=torch.uint8 if w_bits == 4 else torch.int8))
+        self.register_buffer("scale_weight", torch.empty(out_features, dtype=torch.float32))
+        self.register_buffer("zp_weight", None if sym else torch.empty(out_features, dtype=torch.float32))
+        self.register_buffer("zp_gemm", torch.empty(out_features, dtype=torch.float32) if w_bits == 4 else None)
+        self.register_buffer("bias", torch.empty(out_features, dtype=torch.float32) if bias else None)
+
+    def refresh_zp_gemm(self):
+        """After scale_weight / zp_weight were loaded from a checkpoint."""
+        if self.w_bits == 4:
+            self.zp_gemm.copy_((self.zp_weight if self.zp_weight is not None else torch.zeros_like(self.scale_weight)) - 8.0)
+
+    @classmethod
+    def from_quantized(cls, ql, name="linear"):
+        """From a plain qdiff QuantizedLinear without an activation quantiser: same integer codes, same parameters."""
+        if ql.uses_mask or ql.uses_rotation:
+            raise NotImplementedError(
+                f"{name}: a {type(ql).__name__} without an `act:` section has no kernel-mode form (its transform exists to "
+                "condition the activation quantiser, and the reference's forward calls that quantiser unconditionally); give the "
+                "config an `act:` section or leave the layer to the plain QuantizedLinear")
+        wq = ql.w_quantizer
+        if wq.n_bits not in (4, 8):
+            raise NotImplementedError(f"{name}: weight-only kernel mode stores 8-bit and packed 4-bit codes (n_bits={wq.n_bits})")
+        m = cls(ql.in_features, ql.out_features, ql.bias is not None, wq.sym, wq.n_bits, name).to(ql.fp_module.weight.device)
+        codes, sw, _, _ = ql.weight_only_operands()
+        if tuple(codes.shape) != tuple(m.weight.shape) or codes.dtype != m.weight.dtype:
+            raise ValueError(f"{name}: codes {tuple(codes.shape)} {codes.dtype} do not fit {tuple(m.weight.shape)} {m.weight.dtype}")
+        m.weight.copy_(codes)
+        m.scale_weight.copy_(sw)
+        if m.zp_weight is not None:
+            m.zp_weight.copy_(wq.zero_point.reshape(-1).float().expand(ql.out_features))
+        m.refresh_zp_gemm()
+        if ql.bias is not None:
+            m.bias.copy_(ql.bias.detach().float())
+        return m
+
+    def forward(self, x, out_dtype=None, gelu=False, gate=None, residual=None, out=None):
+        """Reads `weight` as it is now (--dit_fsdp re-points it at views of the gathered buffer)."""
+        return qgemm.wq16_linear(x, self.weight, self.scale_weight, self.zp_gemm if self.w_bits == 4 else self.zp_weight, self.bias,
+                                 out_dtype, gelu=gelu, gate=gate, residual=residual, out=out, w4=self.w_bits == 4)
+
+
 def _to_hip_linear(lin, n_bits, sym, act_dtype, fp_gemm="torch", name="linear"):
     from qdiff.base.quant_layer import QuantizedLinear
 
     if isinstance(lin, QuantizedLinear):
         if lin.quant_mode and lin.w_quantizer is not None and lin.a_quantizer is not None:
             return HipLinearW8A8.from_quantized(lin)
+        if lin.quant_mode and lin.w_quantizer is not None:
+            if act_dtype not in (torch.bfloat16, torch.float16):
+                raise ValueError(f"{name}: the weight-only GEMM takes bf16 or fp16 activations (act_dtype {act_dtype})")
+            return HipLinearWq16.from_quantized(lin, name)
         lin = lin.fp_module
     if n_bits is None:
         return HipLinearFp(lin.weight.data, lin.bias.data if lin.bias is not None else None, act_dtype, fp_gemm, name)
@@ -372,6 +436,11 @@ class WanAttentionBlockWithHipKernel(nn.Module):
             if residual is not None:
                 return lin(q, s, ssum, torch.float32, gate=gate, residual=residual, out=residual)
             return lin(q, s, ssum, out_dtype, gelu=gelu)
+        if getattr(lin, "weight_only", False):  # integer codes x 16-bit activations; GELU and gate + residual in the epilogue
+            x = src.fp()
+            if residual is not None:
+                return lin(x, torch.float32, gate=gate.float().contiguous(), residual=residual, out=residual)
+            return lin(x, x.dtype, gelu=gelu)
         if lin.fp_gemm == "hip":  # GELU and gate + residual in the GEMM's epilogue; reads lin.weight as it is now (--dit_fsdp views)
             x = src.fp()
             if residual is not None:
