@@ -240,6 +240,17 @@ int wanq_attention_fwd(const void* q, const void* k, const void* v, void* o, int
                        int64_t Lk, int heads, int head_dim, int64_t q_stride, int64_t k_stride,
                        int64_t v_stride, int64_t o_stride, float scale, void* stream);
 
+/* Sliding-window local attention: wanq_attention_fwd with every query restricted to a band of keys -- what the reference's
+ * WanSelfAttention asks of flash_attn with window_size=(left, right) (ViDiT-Q/examples/Wan2.1/wan/modules/model.py:110-169,
+ * attention.py:34,48,126).  With off = Lk - Lq, query i sees key j iff i + off - left <= j <= i + off + right and 0 <= j < Lk
+ * (flash_attn's bottom-right alignment); a negative side is unbounded; a query that sees no key gets a row of exact zeros.
+ * Arguments, refusals and the 8- / 4-wave choice (wanq_attention_select_form) as for wanq_attention_fwd, the choice made by the
+ * keys a 256-query block walks (left + right + 256, at most Lk) in place of Lk.  Both sides negative: exactly the launch of
+ * wanq_attention_fwd (bit-equal output).  A workgroup reads only the 64-key tiles its query block's band touches. */
+int wanq_attention_window_fwd(const void* q, const void* k, const void* v, void* o, int dtype, int64_t Lq, int64_t Lk,
+                              int heads, int head_dim, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                              int64_t o_stride, float scale, int64_t window_left, int64_t window_right, void* stream);
+
 /* The same with the keys split over `splits` workgroups per (query block, head) ("split-KV"): every share writes
  * unnormalised fp32 partials (O, reference maximum, row sum) into `workspace` and a second kernel merges them.  For launches
  * whose (query blocks x heads) grid leaves a large part of the last round of CUs idle -- 3 heads x 128 query blocks on 256

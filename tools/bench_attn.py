@@ -2,10 +2,14 @@
 """Attention kernel timing at cfg-B (L=32760, 12 heads, d=128): bf16 HIP kernel vs the int8 Q.K^T form (interleaved rounds in
 ONE process, median and minimum) vs torch SDPA, plus the quantisation error of the int8 form against the bf16 kernel.
 
-    python tools/bench_attn.py [quick] [--dtype {bf16,fp16}]
+    python tools/bench_attn.py [quick] [--dtype {bf16,fp16}] [--window LEFT RIGHT]...
 
 --dtype fp16 adds the fp16 forms of both kernels to the SAME interleaved rounds (the bf16 ones stay in as the baseline) and prints
-the fp16 / bf16 time ratios."""
+the fp16 / bf16 time ratios.
+
+--window LEFT RIGHT (repeatable) times sliding-window self-attention instead: at the cfg-B self-attention shape the dense launch and
+one banded launch per window run interleaved in the same rounds on the same operands, and every window prints its time, its ratio
+to the dense time beside it and the share of the key tiles a 256-query block walks (the ratio to expect, plus prologue)."""
 import argparse
 import math
 import os
@@ -53,7 +57,36 @@ def ab(fns, rounds=7):
 ap = argparse.ArgumentParser()
 ap.add_argument("mode", nargs="?", choices=["quick"], help="quick: the cfg-B self-attention shape only")
 ap.add_argument("--dtype", choices=["bf16", "fp16"], default="bf16", help="fp16: time the fp16 forms against the bf16 ones, interleaved")
+ap.add_argument("--window", nargs=2, type=int, action="append", metavar=("LEFT", "RIGHT"),
+                help="time ops.attention(window=(LEFT, RIGHT)) against the dense call, interleaved; repeatable")
 args = ap.parse_args()
+if args.window:
+    Lq = Lk = 32760
+    H = 12
+    g = torch.Generator(device="cuda").manual_seed(0)
+    w = torch.ones(H * 128, device="cuda")
+    dt = torch.float16 if args.dtype == "fp16" else torch.bfloat16
+    q, k = (ops.rmsnorm_rope_(torch.randn(Lq, H * 128, device="cuda", generator=g), w, None, 128).to(dt) for _ in range(2))
+    v = torch.randn(Lk, H * 128, device="cuda", generator=g).to(dt)
+    fns = {"dense": lambda: ops.attention(q, k, v, H, splits=1)}
+    for left, right in args.window:
+        fns[f"window({left},{right})"] = lambda left=left, right=right: ops.attention(q, k, v, H, window=(left, right))
+    r = ab(fns)
+    nt = -(-Lk // 64)
+    print(f"{args.dtype} self-attention Lq={Lq} Lk={Lk} H={H}, {nt} key tiles, dense and banded launches interleaved (median / min of 7 rounds x 3)")
+    for n, (med, mn) in r.items():
+        line = f"{n:22s} median {med*1e3:8.3f} ms  min {mn*1e3:8.3f} ms"
+        if n != "dense":
+            left, right = (int(x) for x in n[7:-1].split(","))
+            span = (left if left >= 0 else Lk) + (right if right >= 0 else Lk) + 256
+            tiles = min(nt, span // 64 + 2)  # tiles an interior 256-query block touches (an unaligned band adds one at each end)
+            fl = 4.0 * ops.window_pairs(Lq, Lk, (left, right)) * 128 * H
+            line += (f"  {fl/med/1e12:7.1f} TFLOP/s over visible pairs  time / dense {med / r['dense'][0]:.3f} (median) "
+                     f"{mn / r['dense'][1]:.3f} (min)  band tiles / all tiles <= {tiles / nt:.3f}")
+        else:
+            line += f"  {4.0 * Lq * Lk * 128 * H / med / 1e12:7.1f} TFLOP/s"
+        print(line)
+    sys.exit(0)
 shapes = [(32760, 32760, 12), (32760, 512, 12), (9450, 75600, 5)]
 if args.mode == "quick":
     shapes = shapes[:1]

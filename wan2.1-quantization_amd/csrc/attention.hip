@@ -1,10 +1,24 @@
-// Flash-attention forward for gfx950, head_dim 128, non-causal, key-length masking.
+// Flash-attention forward for gfx950, head_dim 128, non-causal, key-length masking, optional sliding window.
 //
 //   O[q, h, :] = softmax_k( Q[q,h,:] . K[k,h,:] / sqrt(d) ) V[k,h,:]
 //
-// One kernel template, attn_fwd16_kernel<SPLIT, QK8, NW, F16>, for every form: 16-bit or int8 Q.K^T (QK8), whole key range or one
-// share of it (SPLIT, merged by attn_combine_kernel), 8 or 4 waves per workgroup (NW, plain 16-bit form only), bf16 or fp16
-// elements (F16: the MFMA instruction, the conversions and the exponent headroom of P differ, see at_elem; the text below says bf16).
+// One kernel template, attn_fwd16_kernel<SPLIT, QK8, NW, F16, WIN>, for every form: 16-bit or int8 Q.K^T (QK8), whole key range or
+// one share of it (SPLIT, merged by attn_combine_kernel), 8 or 4 waves per workgroup (NW, plain 16-bit form only), bf16 or fp16
+// elements (F16: the MFMA instruction, the conversions and the exponent headroom of P differ, see at_elem; the text below says bf16),
+// all keys or a band of them per query (WIN, plain 16-bit form only).
+//
+// WIN (sliding-window local attention, wanq_attention_window_fwd; the `window_size=(left, right)` the reference's WanSelfAttention
+// hands to flash_attn, ViDiT-Q/examples/Wan2.1/wan/modules/model.py:110-169).  flash_attn is not part of the reference tree, so
+// the semantics are stated here, with Lk the number of valid keys (after k_len) and off = Lk - Lq:
+//   * query i sees key j iff  i + off - left <= j <= i + off + right  and  0 <= j < Lk  (flash_attn's bottom-right alignment);
+//   * a negative left or right means unbounded on that side;
+//   * a query that sees no key gets an output row of exact zeros;
+//   * the window runs over the flattened token sequence ((f, h, w) row-major in the model) and belongs to self-attention only:
+//     cross-attention never gets one, as in the reference.
+// A workgroup walks only the key tiles [jt0, jt1) that some query of its block sees (the mechanism of a split-KV share); a wave
+// masks element-wise the tiles its 32 queries see partly, leaves the ones they all see whole untouched and skips the math of the
+// ones none of them sees (it still issues its LDS-DMA pieces and meets every barrier).  A row's softmax reference is fixed by the
+// first tile in which the ROW sees a key, not by the workgroup's first tile (see the softmax block).
 //
 // Layout: Q/K/V/O are token-major [tokens, heads*128] bf16 or fp16 (exactly what the q/k/v GEMMs write and what the
 // o-projection's quantiser reads), so no head transposes exist anywhere.
@@ -51,7 +65,14 @@ struct AttnParams {
   int Lq, Lk, H;
   float c;  // softmax scale * log2(e)
   // split-KV (gridDim.z > 1): workgroup z covers key tiles [z*tiles_per_split, ...) and writes unnormalised partials
-  int tiles_per_split;
+  // sliding window (WIN; excludes split-KV, whose share size it shares a word with, and fills what was padding -- the layout
+  // the other instantiations read is unchanged): query i sees keys [i + win_lo, i + win_hi] (and < Lk); the host clamps both so
+  // that no 32-bit sum overflows
+  union {
+    int tiles_per_split;
+    int win_hi;
+  };
+  int win_lo;
   float* part_o;   // [splits, Lq, H*128] fp32: O^T accumulators relative to the split's reference maximum
   float* part_ml;  // [splits, Lq, H, 2]  fp32: (reference maximum m, row sum l)
   // int8 Q.K^T (QK8): per-(token, head) symmetric int8 codes [tokens, H*128] and fp32 scale planes [H][stride]
@@ -132,7 +153,11 @@ constexpr float AT_F16_HEADROOM = 8.0f;
 // NW = waves per workgroup: 8 (256 queries, three ring stages, tiles requested two ahead), or 4 (128 queries per workgroup,
 // two ring stages = 64 KiB, so that TWO workgroups share a CU: SIMD partners then belong to different workgroups and are not
 // coupled by the per-tile barrier; one's prologue / epilogue runs under the other's tiles).
-template <bool SPLIT, bool QK8, int NW = 8, bool F16 = false>
+//
+// WIN = sliding window: per workgroup the key tiles [jt0, jt1) that the band of its query block touches; per wave and tile one of
+// three wave-uniform cases -- outside the band of all 32 queries (no math), inside the band of all 32 (the dense tile, no mask), or
+// an edge (element-wise -inf mask, a branch like the ragged tile's).
+template <bool SPLIT, bool QK8, int NW = 8, bool F16 = false, bool WIN = false>
 __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams p) {
   typedef typename at_elem<F16>::e elem_t;
   typedef typename at_elem<F16>::x8 elem8_t;
@@ -141,6 +166,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams
   constexpr int STAGE = QK8 ? AT_STAGE8 : AT_STAGE;
   constexpr int NST = NW == 8 ? 3 : 2, AHEAD = NST - 1;  // ring stages, prefetch distance in tiles
   static_assert(NW == 8 || (NW == 4 && !SPLIT && !QK8), "the 4-wave form exists for the plain 16-bit kernel only");
+  static_assert(!WIN || (!SPLIT && !QK8), "the sliding window exists for the plain 16-bit kernel only");
   constexpr int VOFF = QK8 ? AT_K8 : AT_TILE;  // byte offset of the V tile inside a stage
   typedef int v4i __attribute__((ext_vector_type(4)));
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -161,8 +187,35 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams
   const int q0 = qblk * (AT_QW * NW) + wave * AT_QW;
   const int nt = (p.Lk + AT_KB - 1) / AT_KB;
   // key tiles of this workgroup: all of them, or one contiguous share under split-KV (the host makes every share non-empty)
-  const int jt0 = SPLIT ? (int)blockIdx.z * p.tiles_per_split : 0;
-  const int jt1 = SPLIT ? (jt0 + p.tiles_per_split < nt ? jt0 + p.tiles_per_split : nt) : nt;
+  // WIN: the tiles between the first key the block's first query sees and the last key its last query sees
+  int wjt0 = 0, wjt1 = nt;
+  if (WIN) {
+    const int qa = qblk * (AT_QW * NW), qb = (qa + AT_QW * NW < p.Lq ? qa + AT_QW * NW : p.Lq) - 1;
+    const int lo = qa + p.win_lo > 0 ? qa + p.win_lo : 0, hi = qb + p.win_hi < p.Lk - 1 ? qb + p.win_hi : p.Lk - 1;
+    if (lo > hi) {  // no query of this block sees a key: rows of zeros (workgroup-uniform, before any barrier)
+#pragma unroll
+      for (int nq = 0; nq < 2; ++nq) {
+        const int qr = q0 + 16 * nq + n16;
+        if (qr < p.Lq) {
+          uint16_t* op = p.o + (int64_t)qr * p.o_stride + head * AT_D + 4 * g4;
+#pragma unroll
+          for (int db = 0; db < 8; ++db) *reinterpret_cast<uint2*>(op + 16 * db) = make_uint2(0u, 0u);
+        }
+      }
+      return;
+    }
+    wjt0 = lo / AT_KB;
+    wjt1 = hi / AT_KB + 1;
+  }
+  const int jt0 = SPLIT ? (int)blockIdx.z * p.tiles_per_split : (WIN ? wjt0 : 0);
+  const int jt1 = SPLIT ? (jt0 + p.tiles_per_split < nt ? jt0 + p.tiles_per_split : nt) : (WIN ? wjt1 : nt);
+  // WIN: the wave's first and last query (clamped like the Q loads below, so rows past Lq repeat the last one) -- scalars
+  int wqa = 0, wqb = 0;
+  if (WIN) {
+    wqa = q0 < p.Lq - 1 ? q0 : p.Lq - 1;
+    wqb = q0 + AT_QW - 1 < p.Lq - 1 ? q0 + AT_QW - 1 : p.Lq - 1;
+  }
+  bool allseen = false;  // WIN: every row of the wave has had a visible key, i.e. has its reference (wave-uniform)
   const float c = p.c;
 
   // ---- Q fragments: query q0 + 16 nq + n16, d = 32 s + 8 g4 + [0, 8), pre-scaled by softmax scale * log2(e)
@@ -332,6 +385,8 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams
     // registers -- live across the whole loop and spills)
     asm volatile("" : "+v"(d_k0), "+v"(d_k1), "+v"(d_k2), "+v"(d_k3), "+v"(d_v0), "+v"(d_v1), "+v"(d_v2), "+v"(d_v3));
     if (j + AHEAD < jt1) A16_DMA(j + AHEAD, (u + AHEAD) % NST);
+    // WIN: a tile none of the wave's 32 queries sees costs it the DMA issue above and the barrier below, nothing else
+    if (!(WIN && (j * AT_KB + AT_KB - 1 < wqa + p.win_lo || j * AT_KB > wqb + p.win_hi))) {
 
     // ---------------- S^T blocks: fragment i = 4 kb + s read four ahead of its two MFMAs
     f32x4 sacc[4][2];
@@ -401,6 +456,22 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams
         for (int e = 0; e < 4; ++e)
           if (kbase + 16 * kb + e >= p.Lk) { sacc[kb][0][e] = -INFINITY; sacc[kb][1][e] = -INFINITY; }
     }
+    // WIN: unless all 32 queries see the whole tile, keys outside a query's band get -inf.  Lane (n16, g4), element e of block
+    // (kb, nq) is query 16 nq + n16 against key 64 j + 16 kb + 4 pi(g4) + e (layout above).
+    if (WIN && (j * AT_KB < wqb + p.win_lo || j * AT_KB + AT_KB - 1 > wqa + p.win_hi)) {
+      asm volatile("" ::: "memory");  // a branch, as above
+#pragma unroll
+      for (int nq = 0; nq < 2; ++nq) {
+        int qi = q0 + 16 * nq + n16;
+        qi = qi < p.Lq ? qi : p.Lq - 1;
+        const int klo = qi + p.win_lo - (j * AT_KB + 4 * pg), khi = qi + p.win_hi - (j * AT_KB + 4 * pg);
+#pragma unroll
+        for (int kb = 0; kb < 4; ++kb)
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            if (16 * kb + e < klo || 16 * kb + e > khi) sacc[kb][nq][e] = -INFINITY;
+      }
+    }
 
     // ---------------- online softmax: lane-local maxima, cross-lane only when the reference moves
     // lane-local maxima of the tile's scores for the lazy-rescale vote
@@ -433,24 +504,37 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams
             for (int r = 0; r < 4; ++r) o[i][nq][r] *= alpha;
         }
       }
-    } else if (first || __any(fmaxf(mx0, mx1) > 6.0f + HR)) {
+    } else if ((WIN ? !allseen : first) || __any(fmaxf(mx0, mx1) > 6.0f + HR)) {
       // The accumulators hold s * scale * log2(e) - m_run already (Q carries the scale, the MFMA chains started from -m_run), so
       // the maxima are the growth of the row maximum over the reference and p = exp2(acc) with no further arithmetic.  The first
       // tile fixes the reference at its own maximum (whatever its sign); later the reference only grows, lazily: when some
       // query's maximum exceeds it by more than 2^6 (wave-uniform vote) -- P stays <= 64 instead of <= 1, the same 8 significant
       // bits in bf16 -- and then O, l and this tile's scores are brought to the new reference.  fp16: the reference sits HR below
       // that (the chains start from HR - m_run, at no instruction in the loop), so the accumulators are HR larger throughout.
+      //
+      // WIN: the band starts at a different tile for every row, and the leading tiles of a later row are wholly masked: there
+      // m = -inf, and taken as the reference it would make every score of the row NaN.  So a row's reference is fixed by the first
+      // tile in which the ROW sees a key.  A row has its reference exactly when its sum l is positive (the key that fixed the
+      // reference, and after every rescale the key that caused it, has P = 2^HR), and the MFMA row sums keep l in every lane of
+      // the row, so that state costs no register.  A row without one: nothing visible in this tile -> delta = 0, its -inf scores
+      // stay -inf and add P = 0; something visible -> delta = m whatever its sign, and O = l = 0 are left alone (alpha = 1, never
+      // 0 * 2^-m).  A row with one treats a wholly masked tile as growth 0.  Until every row of the wave has its reference the
+      // block runs on every tile (a few tiles at the head of the wave's band); from then on the vote alone decides, as without
+      // a window.  A row that never sees a key keeps O = l = 0 and is written as zeros.
       asm volatile("" ::: "memory");  // keep this a branch
       float mx[2] = {mx0, mx1};
+      bool rows_seen = true;
 #pragma unroll
       for (int nq = 0; nq < 2; ++nq) {
         float m = mx[nq];
         m = fmaxf(m, __shfl_xor(m, 16, 64));
         m = fmaxf(m, __shfl_xor(m, 32, 64));
         if (F16) m -= HR;
-        const float delta = first ? m : fmaxf(m, 0.f);
-        if (!first) {
-          const float alpha = __builtin_amdgcn_exp2f(-delta);
+        const bool seen = WIN && lacc[nq][0] > 0.f, visible = m > -INFINITY;
+        if (WIN) rows_seen = rows_seen && (seen || visible);
+        const float delta = WIN ? (seen ? fmaxf(m, 0.f) : visible ? m : 0.f) : first ? m : fmaxf(m, 0.f);
+        if (WIN || !first) {
+          const float alpha = WIN && !seen ? 1.0f : __builtin_amdgcn_exp2f(-delta);
           l_run[nq] *= alpha;
 #pragma unroll
           for (int r = 0; r < 4; ++r) lacc[nq][r] *= alpha;
@@ -459,7 +543,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams
 #pragma unroll
             for (int r = 0; r < 4; ++r) o[i][nq][r] *= alpha;
         }
-        m_run[nq] = first ? delta : m_run[nq] + delta;
+        m_run[nq] = !WIN && first ? delta : m_run[nq] + delta;  // (WIN: 0 until the row has its reference)
 #pragma unroll
         for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
@@ -467,6 +551,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams
 #pragma unroll
         for (int r = 0; r < 4; ++r) sinit[nq][r] = -m_run[nq];
       }
+      if (WIN) allseen = __all(rows_seen);
     }
     // P of key slice ks (32 keys) for query block nq: element j = 4 (kb & 1) + e of S block kb = 2 ks + (j >> 2)
     float ls0 = 0.f, ls1 = 0.f;
@@ -539,6 +624,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams
 #undef A16_WAIT8
 #undef A16_PV
 #undef A16_F
+    }  // (WIN: the tile lies in the wave's band)
     // tile j+1 must have landed; the eight instructions of tile j+2 (if issued; waves 4-7 issue none) may stay in flight
     if (AHEAD == 2 && j + 2 < jt1) A16_WAIT_TILE_AHEAD();
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (two stages: the tile requested at the top of this one is the next)
@@ -579,7 +665,7 @@ __global__ __launch_bounds__(64 * NW, 2) void attn_fwd16_kernel(const AttnParams
       }
       continue;
     }
-    const float inv = 1.0f / l;
+    const float inv = WIN ? (l > 0.f ? 1.0f / l : 0.f) : 1.0f / l;  // WIN: a row that saw no key is a row of zeros
     const int qr = q0 + 16 * nq + n16;
     if (qr < p.Lq) {
       uint16_t* op = p.o + (int64_t)qr * p.o_stride + head * AT_D + 4 * g4;
@@ -649,6 +735,10 @@ static void allow_attn_dynamic_lds() {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd16_kernel<true, false, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * AT_STAGE);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd16_kernel<false, true, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * AT_STAGE8);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd16_kernel<true, true, 8, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * AT_STAGE8);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd16_kernel<false, false, 8, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * AT_STAGE);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd16_kernel<false, false, 4, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * AT_STAGE);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd16_kernel<false, false, 8, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 3 * AT_STAGE);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd16_kernel<false, false, 4, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * AT_STAGE);
     return true;
   }();
   (void)done;
@@ -656,8 +746,9 @@ static void allow_attn_dynamic_lds() {
 
 static int attention_impl(const void* q, const void* k, const void* v, void* o, int dtype, int64_t Lq, int64_t Lk, int heads,
                           int head_dim, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride, float scale,
-                          int splits, void* workspace, int64_t workspace_bytes, void* stream, const Qk8Args* q8 = nullptr) {
-  const char* what = q8 ? "wanq_attention_qk8_fwd" : "wanq_attention_fwd";
+                          int splits, void* workspace, int64_t workspace_bytes, void* stream, const Qk8Args* q8 = nullptr,
+                          const int64_t* window = nullptr) {
+  const char* what = q8 ? "wanq_attention_qk8_fwd" : window ? "wanq_attention_window_fwd" : "wanq_attention_fwd";
   WANQ_REQUIRE((q8 || (q && k)) && v && o, WANQ_E_ARG, "%s: NULL pointer", what);
   WANQ_REQUIRE(dtype == WANQ_BF16 || dtype == WANQ_F16, WANQ_E_ARG, "%s: dtype must be WANQ_BF16 or WANQ_F16 (dtype code %d)", what, dtype);
   const bool f16 = dtype == WANQ_F16;
@@ -703,8 +794,26 @@ static int attention_impl(const void* q, const void* k, const void* v, void* o, 
       // 4-wave workgroups of 128 queries, two per CU (see attn_fwd16_kernel), up to WANQ_ATTN_NW4_KEYS keys (0 = never)
       static const int64_t nw4_env = [] { const char* e = getenv("WANQ_ATTN_NW4_KEYS"); return e ? atoll(e) : (int64_t)WANQ_ATTN_NW4_KEYS_DEFAULT; }();
       const int64_t nw4_sel = g_nw4_keys;  // wanq_attention_select_form: -1 = the start-up value
-      if (Lk <= (nw4_sel >= 0 ? nw4_sel : nw4_env)) {
-        const dim3 grid4((unsigned)((Lq + 4 * AT_QW - 1) / (4 * AT_QW)), (unsigned)heads);
+      const int64_t nw4_keys = nw4_sel >= 0 ? nw4_sel : nw4_env;
+      const dim3 grid4((unsigned)((Lq + 4 * AT_QW - 1) / (4 * AT_QW)), (unsigned)heads);
+      if (window && (window[0] >= 0 || window[1] >= 0)) {
+        // Bounded on a side: the banded instantiations.  Query i sees keys [i + win_lo, i + win_hi]; an unbounded side and
+        // anything wider than the problem is cut to where it changes nothing, so that the kernel's 32-bit sums cannot overflow
+        // (Lq, Lk < 2^30).  The form is chosen as for the dense call, by the keys a 256-query block walks in place of Lk.
+        const int64_t off = Lk - Lq, span = Lq > Lk ? Lq : Lk;
+        const int64_t left = window[0] < 0 || window[0] > span ? span : window[0], right = window[1] < 0 || window[1] > span ? span : window[1];
+        p.win_lo = (int)(off - left > -Lq ? off - left : -Lq);
+        p.win_hi = (int)(off + right < Lk ? off + right : Lk);
+        const int64_t band = left + right + AT_QB < Lk ? left + right + AT_QB : Lk;
+        if (band <= nw4_keys) {
+          if (f16) hipLaunchKernelGGL((attn_fwd16_kernel<false, false, 4, true, true>), grid4, dim3(256), 2 * AT_STAGE, st, p);
+          else hipLaunchKernelGGL((attn_fwd16_kernel<false, false, 4, false, true>), grid4, dim3(256), 2 * AT_STAGE, st, p);
+        } else if (f16) {
+          hipLaunchKernelGGL((attn_fwd16_kernel<false, false, 8, true, true>), grid, dim3(512), 3 * AT_STAGE, st, p);
+        } else {
+          hipLaunchKernelGGL((attn_fwd16_kernel<false, false, 8, false, true>), grid, dim3(512), 3 * AT_STAGE, st, p);
+        }
+      } else if (Lk <= nw4_keys) {
         if (f16) hipLaunchKernelGGL((attn_fwd16_kernel<false, false, 4, true>), grid4, dim3(256), 2 * AT_STAGE, st, p);
         else hipLaunchKernelGGL((attn_fwd16_kernel<false, false, 4>), grid4, dim3(256), 2 * AT_STAGE, st, p);
       } else if (f16) {
@@ -747,6 +856,14 @@ extern "C" int wanq_attention_fwd(const void* q, const void* k, const void* v, v
                                   int64_t Lk, int heads, int head_dim, int64_t q_stride, int64_t k_stride,
                                   int64_t v_stride, int64_t o_stride, float scale, void* stream) {
   return attention_impl(q, k, v, o, dtype, Lq, Lk, heads, head_dim, q_stride, k_stride, v_stride, o_stride, scale, 1, nullptr, 0, stream);
+}
+
+extern "C" int wanq_attention_window_fwd(const void* q, const void* k, const void* v, void* o, int dtype, int64_t Lq, int64_t Lk,
+                                         int heads, int head_dim, int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                                         int64_t o_stride, float scale, int64_t window_left, int64_t window_right, void* stream) {
+  const int64_t window[2] = {window_left, window_right};
+  return attention_impl(q, k, v, o, dtype, Lq, Lk, heads, head_dim, q_stride, k_stride, v_stride, o_stride, scale, 1, nullptr, 0, stream,
+                        nullptr, window);
 }
 
 extern "C" int wanq_attention_fwd_split(const void* q, const void* k, const void* v, void* o, int dtype, int64_t Lq,

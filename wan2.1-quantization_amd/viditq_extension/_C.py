@@ -69,6 +69,7 @@ PROTOTYPES = {
     "wanq_pack_w4": [_vp, _vp, _i, _i64, _i, _vp],
     "wanq_unpack_w4": [_vp, _vp, _i, _i64, _i, _vp],
     "wanq_attention_fwd": [_vp, _vp, _vp, _vp, _i, _i64, _i64, _i, _i, _i64, _i64, _i64, _i64, _f, _vp],
+    "wanq_attention_window_fwd": [_vp, _vp, _vp, _vp, _i, _i64, _i64, _i, _i, _i64, _i64, _i64, _i64, _f, _i64, _i64, _vp],
     "wanq_attention_fwd_split": [_vp, _vp, _vp, _vp, _i, _i64, _i64, _i, _i, _i64, _i64, _i64, _i64, _f, _i, _vp, _i64, _vp],
     "wanq_attention_split_workspace": [_i64, _i, _i, _i],
     "wanq_attention_select_form": [_i64],

@@ -144,15 +144,18 @@ class WanSelfAttention(nn.Module):
                 vi = v[i].to(adt).flatten(1)
             if par:
                 wq, wk, wv = (sp.scatter_heads(t_, async_op=True) for t_ in (qi, ki, vi))
-                oi = ops.attention(wq.wait(), wk.wait(), wv.wait(), n // sp.size, int(seq_lens[i]))
+                # (after the exchange a rank holds all tokens of its heads, so the window's band is local)
+                oi = ops.attention(wq.wait(), wk.wait(), wv.wait(), n // sp.size, int(seq_lens[i]), **ops.window_kwargs(self.window_size))
                 outs.append(sp.gather_heads(oi))
             else:
-                outs.append(ops.attention(qi, ki, vi, n, int(seq_lens[i])))
+                outs.append(ops.attention(qi, ki, vi, n, int(seq_lens[i]), **ops.window_kwargs(self.window_size)))
         return self.o(torch.stack(outs))
 
 
 class WanT2VCrossAttention(WanSelfAttention):
     def forward(self, x, context, context_lens):
+        """(no window here: the block builds its cross-attention with window_size (-1, -1), the window belongs to self-attention
+        only, as in the reference, W/wan/modules/model.py:110-169 against :172-200)"""
         b, n = x.shape[0], self.num_heads
         if fused_fp(x) and self.qk_norm:
             q, k = self.q(x).contiguous(), self.k(context).contiguous()

@@ -280,11 +280,37 @@ def attention_splits(Lq, Lk, num_heads, device, ncu=None):
     return best
 
 
-def attention(q, k, v, num_heads, k_len=None, out=None, splits=None):
+def window_bounded(window):
+    """True when (left, right) restricts the keys of a query: a negative side is unbounded (flash_attn's convention)."""
+    return window is not None and (int(window[0]) >= 0 or int(window[1]) >= 0)
+
+
+def window_kwargs(window):
+    """attention()'s keyword for a model's window_size: passed only when the window is bounded, so that the dense call is the
+    call it was (callers that wrap or replace attention() see the keyword only where a window exists)."""
+    return {"window": (int(window[0]), int(window[1]))} if window_bounded(window) else {}
+
+
+def window_pairs(Lq, Lk, window):
+    """(query, key) pairs a sliding window leaves visible: query i sees key j iff i + off - left <= j <= i + off + right and
+    0 <= j < Lk, off = Lk - Lq (the rule of csrc/attention.hip's header)."""
+    if not window_bounded(window):
+        return Lq * Lk
+    left, right = (int(w) if int(w) >= 0 else Lq + Lk for w in window)
+    i = torch.arange(Lq, dtype=torch.int64)
+    lo, hi = (i + (Lk - Lq) - left).clamp_(min=0), (i + (Lk - Lq) + right).clamp_(max=Lk - 1)
+    return int((hi - lo + 1).clamp_(min=0).sum())
+
+
+def attention(q, k, v, num_heads, k_len=None, out=None, splits=None, window=(-1, -1)):
     """softmax(q k^T / sqrt(d)) v for one sample on the HIP flash-attention kernel (csrc/attention.hip).
     q [Lq, C], k/v [Lk, C] all bf16 or all fp16, token-major (row stride may exceed C: column slices of a packed buffer are
     fine) -> [Lq, C] of that type.  k_len masks key padding (flash_attention(..., k_lens), wan/modules/attention.py:78-80).
     splits: None = attention_splits() decides; 1 = one workgroup per (query block, head); n = split-KV.
+    window: (left, right), the model's window_size: sliding-window local attention over the token sequence, query i seeing the keys
+    i + (Lk - Lq) - left ... i + (Lk - Lq) + right of the first k_len (a negative side is unbounded; a query that sees no key gets a
+    row of zeros).  (-1, -1) is the dense call above; a bounded window runs the banded kernel, which has no split-KV form (its
+    workgroups already walk a share of the keys each): splits is then 1, and an explicit splits > 1 is refused.
     fp32 operands (the kernel-mode block built with act_dtype=float32, a parity-test configuration) are rounded to bf16 here:
     16-bit operands and a 16-bit P are the kernel's contract, as they are flash_attn's in the reference."""
     if q.dtype == torch.float32 and k.dtype == torch.float32 and v.dtype == torch.float32:
@@ -304,13 +330,21 @@ def attention(q, k, v, num_heads, k_len=None, out=None, splits=None):
     Lk = k.shape[0] if k_len is None else min(int(k_len), k.shape[0])
     if out is None:
         out = torch.empty(Lq, C, dtype=q.dtype, device=q.device)
-    if splits is None:
+    banded = window_bounded(window)
+    if banded and splits is not None and int(splits) > 1:
+        raise RuntimeError(f"attention: window={tuple(window)} with splits={splits}: the banded kernel has no split-KV form")
+    if banded:
+        splits = 1
+    elif splits is None:
         splits = attention_splits(Lq, Lk, num_heads, q.device)
     with torch.cuda.device(q.device):
         if _attn_timer is not None:
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record()
-        if splits <= 1:
+        if banded:
+            _C.call("wanq_attention_window_fwd", _C.ptr(q), _C.ptr(k), _C.ptr(v), _C.ptr(out), _C.dt(q), Lq, Lk, num_heads, d,
+                    q.stride(0), k.stride(0), v.stride(0), out.stride(0), 1.0 / math.sqrt(d), int(window[0]), int(window[1]), _C.stream())
+        elif splits <= 1:
             _C.call("wanq_attention_fwd", _C.ptr(q), _C.ptr(k), _C.ptr(v), _C.ptr(out), _C.dt(q), Lq, Lk, num_heads, d,
                     q.stride(0), k.stride(0), v.stride(0), out.stride(0), 1.0 / math.sqrt(d), _C.stream())
         else:
@@ -321,7 +355,7 @@ def attention(q, k, v, num_heads, k_len=None, out=None, splits=None):
                     _C.stream())
         if _attn_timer is not None:
             ev1.record()
-            _attn_timer.append((ev0, ev1, 4 * Lq * Lk * d * num_heads))
+            _attn_timer.append((ev0, ev1, 4 * window_pairs(Lq, Lk, window) * d * num_heads))  # the visible (query, key) pairs
     return out
 
 

@@ -389,6 +389,8 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         # (W/models/quant_opensora.py:438-440); P.V itself stays bf16 -- the reference's recipe has no integer P either
         self.attn_v_bits, self.cross_attn_v_bits = attn_v_bits, cross_attn_v_bits
         self.attn_map, self.cross_attn_map = attn_map, cross_attn_map  # (n_bits, sym) of the attention-map quantiser, or None
+        # the source block's self_attn.window_size (from_float): sliding-window self-attention on the plain 16-bit kernel
+        self.window_size = (-1, -1)
         self.self_attn, self.cross_attn = _Attn(dim), _Attn(dim)
         self.ffn0 = self.ffn2 = None
         self.register_buffer("modulation", torch.zeros(1, 6, dim))
@@ -403,8 +405,18 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         (quantized here with plain per-channel W8 when n_bits is given, kept FP when n_bits is None) or qdiff
         QuantizedLinear variants (their codes / parameters / ViDiT transform are taken over as they are).
         fp_gemm: "torch" or "hip", the GEMM of the Linears kept FP (HipLinearFp); a layer "hip" cannot take is refused here, by name."""
+        window = tuple(int(w) for w in getattr(blk.self_attn, "window_size", (-1, -1)))
+        if ops.window_bounded(window) and (attn_qk8 or attn_map is not None):
+            keys = [k for k, on in (("attn.qk", attn_qk8), ("attn.attn_map", attn_map is not None),
+                                    ("attn.v", attn_map is not None and attn_v_bits is not None)) if on]
+            raise NotImplementedError(
+                f"{name}.self_attn: window_size={window} with {' + '.join(keys)} configured: sliding-window attention exists for the "
+                "plain 16-bit kernel only (csrc/attention.hip, WIN); the int8 Q.K^T form and the attention-map quantiser have no banded "
+                "form, and running them dense would ignore the window.  Drop those keys from the quant config or build the model with "
+                "window_size=(-1, -1)")
         m = cls(blk.dim, blk.ffn_dim, blk.num_heads, blk.eps, act_dtype, attn_qk8, cross_attn_qk8, attn_v_bits,
                 cross_attn_v_bits, attn_map, cross_attn_map, fp_gemm).to(blk.modulation.device)
+        m.window_size = window
         for name_ in ("self_attn", "cross_attn"):
             src, dst = getattr(blk, name_), getattr(m, name_)
             for l in "qkvo":
@@ -577,7 +589,7 @@ class WanAttentionBlockWithHipKernel(nn.Module):
             if self.attn_map is not None:
                 o = ops.attention_map_quant(q, k, v, H, self.attn_map[0], self.attn_map[1], seq_len, q_len=seq_len)
             else:
-                o = ops.attention(q, k, v, H, seq_len)
+                o = ops.attention(q, k, v, H, seq_len, **ops.window_kwargs(self.window_size))
         else:
             # Ulysses, pipelined over head chunks: this rank's H/P heads are split in two; the exchange of chunk 1 (and the
             # way back of chunk 0) flies under the attention of the other chunk, so about half of the all-to-all time of a
@@ -606,7 +618,8 @@ class WanAttentionBlockWithHipKernel(nn.Module):
                 if self.attn_map is not None:
                     oc = ops.attention_map_quant(qc, kc, vc, (c1 - c0) // d, self.attn_map[0], self.attn_map[1], seq_len, q_len=seq_len)
                 else:
-                    oc = ops.attention(qc, kc, vc, (c1 - c0) // d, seq_len)
+                    # (the window's band is local too: all tokens of the chunk's heads are here)
+                    oc = ops.attention(qc, kc, vc, (c1 - c0) // d, seq_len, **ops.window_kwargs(self.window_size))
                 back.append(sp.gather_heads(oc, async_op=True, out=o, cols=(c0, c1)))
             for b in back:
                 b.wait()
