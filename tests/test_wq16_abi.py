@@ -28,6 +28,7 @@ def lib():
     lib = ctypes.CDLL(LIB)
     vp, i, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
     lib.wanq_gemm_wq16.argtypes = [vp, vp, i, i, vp, vp, vp, i, vp, i, vp, vp, i, i64, i, i, vp]
+    lib.wanq_gemm_bf16.argtypes = [vp, vp, i, vp, i, vp, i, vp, vp, i, i64, i, i, vp]
     lib.wanq_last_error.restype = ctypes.c_char_p
     return lib
 
@@ -46,6 +47,15 @@ def call(lib, ptr, **kw):
     a.update(kw)
     rc = lib.wanq_gemm_wq16(a["a"], a["w"], a["dtype"], a["w_bits"], a["sw"], a["zp"], a["out"], a["out_dtype"], a["bias"], a["bias_dtype"],
                             a["gate"], a["residual"], a["epi"], a["M"], a["N"], a["K"], None)
+    return rc, lib.wanq_last_error()
+
+
+def call_bf16(lib, ptr, **kw):
+    """wanq_gemm_bf16 on the same well-formed problem (no w_bits / sw / zp), with the named arguments replaced"""
+    a = dict(a=ptr, w=ptr, dtype=BF16, out=ptr, out_dtype=BF16, bias=None, bias_dtype=F32, gate=None, residual=None, epi=0, M=8, N=16, K=64)
+    a.update(kw)
+    rc = lib.wanq_gemm_bf16(a["a"], a["w"], a["dtype"], a["out"], a["out_dtype"], a["bias"], a["bias_dtype"], a["gate"], a["residual"],
+                            a["epi"], a["M"], a["N"], a["K"], None)
     return rc, lib.wanq_last_error()
 
 
@@ -107,6 +117,29 @@ def test_misaligned_operands_are_refused(lib, p, which):
     assert rc == 1 and b"aligned to 4 elements" in msg
 
 
+@pytest.mark.parametrize("rule", ["operand dtype", "out dtype", "bias dtype", "unknown flag", "gate without residual", "N=12",
+                                  "misaligned out"])
+def test_common_rules_refuse_alike_in_both_16bit_entries(lib, p, rule):
+    """One invalid argument set per rule the two entries share (csrc/gemm16_common.h): the same return code from wanq_gemm_bf16 and
+    wanq_gemm_wq16, and the same message once the entry's own name is taken out."""
+    bad = {"operand dtype": dict(dtype=F32), "out dtype": dict(out_dtype=3), "bias dtype": dict(bias=p[0], bias_dtype=4),
+           "unknown flag": dict(epi=4), "gate without residual": dict(out_dtype=F32, gate=p[0], epi=EPI_GATE_RES), "N=12": dict(N=12),
+           "misaligned out": dict(out=ctypes.c_void_p(p[0].value + 8))}[rule]
+    rc_f, msg_f = call_bf16(lib, p[0], **bad)
+    rc_q, msg_q = call(lib, p[0], **bad)
+    assert rc_f == rc_q and rc_f in (1, 2)
+    assert msg_f.startswith(b"wanq_gemm_bf16: ") and msg_q.startswith(b"wanq_gemm_wq16: ")
+    assert msg_f.replace(b"wanq_gemm_bf16", b"") == msg_q.replace(b"wanq_gemm_wq16", b"")
+
+
+def test_each_16bit_entry_names_its_own_k_multiple(lib, p):
+    rc, msg = call_bf16(lib, p[0], K=16)
+    assert rc == 2 and msg == b"wanq_gemm_bf16: K=16 must be a positive multiple of 32"
+    rc, msg = call(lib, p[0], K=32)
+    assert rc == 2 and msg == b"wanq_gemm_wq16: K=32 must be a positive multiple of 64"
+    assert call_bf16(lib, p[0], K=32, M=0)[0] == 0  # 32 is a whole K for the floating-point entry
+
+
 def test_m_zero_is_ok_and_launches_nothing(lib, p):
     rc, _ = call(lib, p[0], M=0)
     assert rc == 0
@@ -129,6 +162,32 @@ def test_wq16_linear_refusal_names_the_rule():
         assert qgemm.wq16_linear_refusal(1, N, K) is None
     assert "N=12" in qgemm.wq16_linear_refusal(1, 12, 64)
     assert "K=96" in qgemm.wq16_linear_refusal(1, 16, 96) and "multiple of 64" in qgemm.wq16_linear_refusal(1, 16, 96)
+
+
+def test_integer_weight_linears_keep_their_state_dict_keys():
+    """HipLinearW8A8 and HipLinearWq16 register the same buffers in the same order (checkpoints and the --dit_fsdp views go by these
+    keys); the lists are those of the classes before they shared a base."""
+    from wan.quant_wanx_hip import HipLinearW8A8, HipLinearWq16
+
+    expected = {  # (w_bits, sym, bias)
+        (4, False, False): ["weight", "scale_weight", "zp_weight", "zp_gemm"],
+        (4, False, True): ["weight", "scale_weight", "zp_weight", "zp_gemm", "bias"],
+        (4, True, False): ["weight", "scale_weight", "zp_gemm"],
+        (4, True, True): ["weight", "scale_weight", "zp_gemm", "bias"],
+        (8, False, False): ["weight", "scale_weight", "zp_weight"],
+        (8, False, True): ["weight", "scale_weight", "zp_weight", "bias"],
+        (8, True, False): ["weight", "scale_weight"],
+        (8, True, True): ["weight", "scale_weight", "bias"],
+    }
+    for cls in (HipLinearW8A8, HipLinearWq16):
+        for (w_bits, sym, bias), keys in expected.items():
+            m = cls(64, 16, bias, sym, w_bits)
+            sd = m.state_dict()
+            assert list(sd.keys()) == keys, (cls.__name__, w_bits, sym, bias)
+            assert sd["weight"].dtype == (torch.uint8 if w_bits == 4 else torch.int8)
+            assert tuple(sd["weight"].shape) == (16, 32 if w_bits == 4 else 64)
+            assert all(v.dtype == torch.float32 and tuple(v.shape) == (16,) for k, v in sd.items() if k != "weight")
+            assert (m.zp is m.zp_gemm) if w_bits == 4 else (m.zp is m.zp_weight)
 
 
 @pytest.mark.parametrize("name,bits", [("w8a16_all_linears.yaml", 8), ("w4a16_all_linears.yaml", 4)])

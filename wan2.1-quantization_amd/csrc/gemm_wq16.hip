@@ -11,14 +11,12 @@
 // that product to bf16 before F.linear (ViDiT-Q/quant_utils/qdiff/base/quant_layer.py:68-72): this path is the more exact one.
 // zp must be integer valued (every StaticQuantizer zero point is): the 16-bit operand is cut from the fp32 sum c + zp, not rounded.
 //
-// Structure.  gemm_bf16.hip's: one 128(M) x 128(N) tile per 256-thread workgroup (4 waves, 2 x 2, 64 x 64 each = 4 x 4 MFMA
-// tiles), K in tiles of 64, the same MFMA operand roles (weight fragment = A operand, token fragment = B) and the same epilogue.
-// The TOKEN half of a K-tile (128 rows of 128 B) goes global -> LDS by LDS-DMA (global_load_lds_dwordx4, 4 per wave) into one of
-// two 16-KiB buffers with gemm_bf16.hip's chunk swizzle.  The WEIGHT half never touches LDS and no dequantised copy is written
-// anywhere: each lane loads the codes of its own MFMA fragments straight from global memory -- channel (lane & 15) of each of
-// its four 16-channel blocks, the 8 codes at k = 32 kk + 8 (lane >> 4) of each of the two 32-deep steps: 8 bytes (W8,
-// global_load_dwordx2) or the one dword of wanq_pack_w4's 16-byte group that holds exactly those 8 nibbles (W4,
-// global_load_dword); 8 loads per lane per K-tile -- one K-tile ahead, into registers, and converts them next to the MFMAs:
+// Structure.  gemm_bf16.hip's tile, MFMA operand roles and epilogue (gemm16_common.h); the TOKEN half of a K-tile goes into one of
+// two 16-KiB buffers.  The WEIGHT half never touches LDS and no dequantised copy is written anywhere: each lane loads the codes of
+// its own MFMA fragments straight from global memory -- channel (lane & 15) of each of its four 16-channel blocks, the 8 codes at
+// k = 32 kk + 8 (lane >> 4) of each of the two 32-deep steps: 8 bytes (W8, global_load_dwordx2) or the one dword of wanq_pack_w4's
+// 16-byte group that holds exactly those 8 nibbles (W4, global_load_dword); 8 loads per lane per K-tile -- one K-tile ahead, into
+// registers, and converts them next to the MFMAs:
 //   wait for this wave's DMA and codes of tile t | barrier | issue the DMA of tile t+1 | convert the codes of tile t | load the
 //   codes of tile t+1 | 8 fragment reads of tile t | 32 MFMAs
 // The two waves that share a channel half load and convert the same codes (L1 / L2 hits).
@@ -30,25 +28,14 @@
 // i.e. 2.75 / 2.9 per code and 5.5 / 5.75 per MFMA, against ~16 cycles of matrix core per MFMA: the conversion does not hide
 // inside one wave's MFMA shadow; it overlaps with the MFMAs of the other workgroup on the SIMD (32 KiB of LDS, two per CU).
 //
-// Determinism.  gemm_bf16.hip's summation order: every output element is summed by one lane, over k in K-tile order and within a
-// tile in two 32-deep MFMA steps with the same k -> fragment-slot assignment, so with sw = 1 the output is bit-equal to
-// wanq_gemm_bf16 on the weight (c + zp) cast to the activation dtype.  No split-K, one kernel form; a row's bits do not depend on
-// M or on its place in the launch.  Rows past M are read from row M - 1 (computed, never stored); channels past N likewise.
-#include "gemm_params.h"
+// Determinism.  gemm_bf16.hip's summation order (gemm16_common.h), so with sw = 1 the output is bit-equal to wanq_gemm_bf16 on the
+// weight (c + zp) cast to the activation dtype.
+#include "gemm16_common.h"
 
 namespace wanq {
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-typedef _Float16 v8h __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void glb_void;
-
-constexpr int QM = 128, QN = 128, QK = 64;
-constexpr int QROW = QK * 2;        // bytes of one LDS row
-constexpr int QTILE = QM * QROW;    // one K-tile buffer: 16 KiB of token rows
+constexpr int QTILE = TM * TROW;  // one K-tile buffer: 16 KiB of token rows
 constexpr int QLDS = 2 * QTILE;
 
 struct WqGemmParams {
@@ -63,20 +50,6 @@ struct WqGemmParams {
   int bias_dtype, epi;
   int M, N, K, nt;
 };
-
-template <int OFF>
-__device__ __forceinline__ void dsr(v4i& d, uint32_t addr) {
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF));
-}
-
-template <bool F16IN>
-__device__ __forceinline__ v4f mfma(const v4i& a, const v4i& b, const v4f& c) {
-  if constexpr (F16IN) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(v8h, a), __builtin_bit_cast(v8h, b), c, 0, 0, 0);
-  } else {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, a), __builtin_bit_cast(v8bf, b), c, 0, 0, 0);
-  }
-}
 
 // two integer-valued floats (|x| <= 256) -> one dword of the 16-bit operand type, exactly
 template <bool F16IN>
@@ -97,70 +70,32 @@ __device__ __forceinline__ void cvt4(uint32_t u, float z, int& d0, int& d1) {
   d1 = pack2<F16IN>(f2, f3);
 }
 
-// four consecutive per-channel values of dtype F16 / BF16 / F32
-__device__ __forceinline__ void load4_any(const void* p, int dt, int idx, float (&o)[4]) {
-  if (dt == WANQ_BF16) {
-    const uint2 v = *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(p) + idx);
-    o[0] = __uint_as_float(v.x << 16); o[1] = __uint_as_float(v.x & 0xffff0000u);
-    o[2] = __uint_as_float(v.y << 16); o[3] = __uint_as_float(v.y & 0xffff0000u);
-  } else {
-    load4_ch(p, dt, idx, o);
-  }
-}
-
-template <int OUT>
-__device__ __forceinline__ void load4_out(const void* p, int64_t idx, float (&o)[4]) {
-  if constexpr (OUT == WANQ_F32) {
-    const float4 v = *reinterpret_cast<const float4*>(static_cast<const float*>(p) + idx);
-    o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
-  } else {
-    load4_any(static_cast<const uint16_t*>(p) + idx, OUT, 0, o);
-  }
-}
-
-template <int OUT>
-__device__ __forceinline__ void store4_out(void* p, int64_t idx, const float (&y)[4]) {
-  if constexpr (OUT == WANQ_F32) {
-    *reinterpret_cast<float4*>(static_cast<float*>(p) + idx) = make_float4(y[0], y[1], y[2], y[3]);
-  } else {
-    *reinterpret_cast<uint2*>(static_cast<uint16_t*>(p) + idx) = pack16x4<OUT>(y);
-  }
-}
-
 template <bool F16IN, bool W4, int OUT>
 __global__ void __launch_bounds__(256, 2) gemm_wq16_kernel(WqGemmParams p) {
   __shared__ __attribute__((aligned(1024))) char smem[QLDS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int tm = blockIdx.x / p.nt, tn = blockIdx.x - tm * p.nt;
-  const int m0 = tm * QM, n0 = tn * QN;
-  const int K = p.K, nk = K / QK;
+  const int m0 = tm * TM, n0 = tn * TN;
+  const int K = p.K, nk = K / TK;
 
-  // ---- LDS-DMA sources (token rows only): instruction q (0-3) of this wave fills LDS rows 8 g .. 8 g + 7, g = 4 q + wave; lane l
-  // writes row 8 g + (l >> 3), physical chunk l & 7 = logical chunk c ^ ((row >> 1) & 7)
-  const uint16_t* src[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int r = 8 * (4 * q + wave) + (lane >> 3);
-    const int c = (lane & 7) ^ ((r >> 1) & 7);
-    const int m = m0 + r < p.M ? m0 + r : p.M - 1;
-    src[q] = p.a + (int64_t)m * K + c * 8;
-  }
+  const uint16_t* src[4];  // LDS-DMA sources (token rows only)
+  token_dma_sources(p.a, m0, p.M, K, wave, lane, src);
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
   auto issue = [&](int t) {
     char* dst = smem + (t & 1) * QTILE + wave * 1024;
 #pragma unroll
     for (int q = 0; q < 4; ++q)
-      __builtin_amdgcn_global_load_lds((glb_void*)(src[q] + t * QK), (lds_void*)(dst + q * 4096), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((glb_void*)(src[q] + t * TK), (lds_void*)(dst + q * 4096), 16, 0, 0);
   };
 
   // ---- fragment geometry: lane l holds row (16-row block) + (l & 15), the 8 k of logical chunk 4 kk + (l >> 4)
-  const int fr = lane & 15, fq = lane >> 4, sw = (fr >> 1) & 7;
-  const uint32_t rd0 = lds0 + fr * QROW + ((fq ^ sw) << 4), rd1 = lds0 + fr * QROW + (((4 + fq) ^ sw) << 4);
+  const int fr = lane & 15, fq = lane >> 4;
+  const uint32_t rd0 = frag_addr(lds0, fr, fq, 0), rd1 = frag_addr(lds0, fr, fq, 1);
 
   // ---- weight codes of this lane: channel block j, step kk -> W8: 8 bytes at k = 64 t + 32 kk + 8 fq; W4: dword fq of the 16-byte
   // group of codes 64 t + 32 kk .. + 31 (low nibbles = codes 8 fq .. + 3, high nibbles = codes 8 fq + 4 .. + 7)
-  constexpr int CT = W4 ? QK / 2 : QK;  // bytes of codes per row and K-tile
+  constexpr int CT = W4 ? TK / 2 : TK;  // bytes of codes per row and K-tile
   const uint8_t* wp[4];
   float zadj[4];
 #pragma unroll
@@ -182,11 +117,8 @@ __global__ void __launch_bounds__(256, 2) gemm_wq16_kernel(WqGemmParams p) {
       }
   };
 
-  v4f acc[4][4];  // [token block i][channel block j]: channel (lane >> 4) * 4 + e, token lane & 15
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = v4f{0.f, 0.f, 0.f, 0.f};
+  v4f acc[4][4];
+  zero_acc(acc);
 
   issue(0);
   load_codes(0);
@@ -214,10 +146,10 @@ __global__ void __launch_bounds__(256, 2) gemm_wq16_kernel(WqGemmParams p) {
       }
     load_codes(t + 1 < nk ? t + 1 : t);  // last tile: re-read itself (never used)
     const uint32_t boff = (t & 1) * QTILE;
-    const uint32_t a0 = rd0 + boff + wm * 64 * QROW, a1 = rd1 + boff + wm * 64 * QROW;
+    const uint32_t a0 = rd0 + boff + wm * 64 * TROW, a1 = rd1 + boff + wm * 64 * TROW;
     v4i xa[2][4];
-    dsr<0>(xa[0][0], a0); dsr<16 * QROW>(xa[0][1], a0); dsr<32 * QROW>(xa[0][2], a0); dsr<48 * QROW>(xa[0][3], a0);
-    dsr<0>(xa[1][0], a1); dsr<16 * QROW>(xa[1][1], a1); dsr<32 * QROW>(xa[1][2], a1); dsr<48 * QROW>(xa[1][3], a1);
+    dsr<0>(xa[0][0], a0); dsr<16 * TROW>(xa[0][1], a0); dsr<32 * TROW>(xa[0][2], a0); dsr<48 * TROW>(xa[0][3], a0);
+    dsr<0>(xa[1][0], a1); dsr<16 * TROW>(xa[1][1], a1); dsr<32 * TROW>(xa[1][2], a1); dsr<48 * TROW>(xa[1][3], a1);
     // tied to the fragments: the MFMAs that read them cannot be scheduled above the wait (the compiler does not count the asm
     // reads in lgkmcnt), while the conversion of the codes stays free to interleave with the MFMAs
     asm volatile("s_waitcnt lgkmcnt(0)"
@@ -234,42 +166,12 @@ __global__ void __launch_bounds__(256, 2) gemm_wq16_kernel(WqGemmParams p) {
     __builtin_amdgcn_sched_barrier(0);
   }
 
-  // ---- epilogue, fp32: acc * sw + bias (one fma), GELU, residual + y * gate, one rounding
-  const bool gelu = p.epi & WANQ_EPI_GELU, gres = p.epi & WANQ_EPI_GATE_RES;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int n = n0 + wn * 64 + j * 16 + fq * 4;
-    if (n >= p.N) continue;
-    float s4[4], b4[4] = {0.f, 0.f, 0.f, 0.f}, g4[4] = {0.f, 0.f, 0.f, 0.f};
-    load4_ch(p.sw, WANQ_F32, n, s4);
-    if (p.bias) load4_any(p.bias, p.bias_dtype, n, b4);
-    if (gres) load4_ch(p.gate, WANQ_F32, n, g4);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int m = m0 + wm * 64 + i * 16 + fr;
-      if (m >= p.M) continue;
-      const int64_t o = (int64_t)m * p.N + n;
-      float y[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) y[e] = __fmaf_rn(acc[i][j][e], s4[e], b4[e]);
-      if (gelu) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) y[e] = gelu_tanh_fast_f32(y[e]);
-      }
-      if (gres) {
-        float r4[4];
-        load4_out<OUT>(p.residual, o, r4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) y[e] = r4[e] + y[e] * g4[e];
-      }
-      store4_out<OUT>(p.out, o, y);
-    }
-  }
+  epilogue16<OUT, true>(acc, m0, n0, wm, wn, fr, fq, p.M, p.N, p.sw, p.bias, p.bias_dtype, p.gate, p.residual, p.out, p.epi);
 }
 
 template <bool F16IN, bool W4, int OUT>
 int launch(const WqGemmParams& p, hipStream_t st) {
-  const int64_t tiles = (int64_t)((p.M + QM - 1) / QM) * p.nt;
+  const int64_t tiles = (int64_t)((p.M + TM - 1) / TM) * p.nt;
   hipLaunchKernelGGL((gemm_wq16_kernel<F16IN, W4, OUT>), dim3((unsigned)tiles), dim3(256), 0, st, p);
   return check_launch("wanq_gemm_wq16");
 }
@@ -283,8 +185,6 @@ int launch_out(const WqGemmParams& p, int out_dtype, hipStream_t st) {
   }
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 }  // namespace wanq
 
@@ -297,27 +197,18 @@ extern "C" int wanq_gemm_wq16(const void* a, const void* w, int dtype, int w_bit
   WANQ_REQUIRE(a && w && out && sw, WANQ_E_ARG, "%s: a, w, out and sw must be non-NULL", what);
   WANQ_REQUIRE(dtype == WANQ_BF16 || dtype == WANQ_F16, WANQ_E_ARG, "%s: operand dtype %d must be BF16 or F16", what, dtype);
   WANQ_REQUIRE(w_bits == 4 || w_bits == 8, WANQ_E_ARG, "%s: w_bits=%d must be 4 or 8", what, w_bits);
-  WANQ_REQUIRE(is_fp(out_dtype), WANQ_E_ARG, "%s: out dtype %d must be BF16, F16 or F32", what, out_dtype);
-  WANQ_REQUIRE(!bias || is_fp(bias_dtype), WANQ_E_ARG, "%s: bias dtype %d must be BF16, F16 or F32", what, bias_dtype);
-  WANQ_REQUIRE((epi_flags & ~(WANQ_EPI_GELU | WANQ_EPI_GATE_RES)) == 0, WANQ_E_ARG, "%s: unknown epilogue flag", what);
-  WANQ_REQUIRE(!(epi_flags & WANQ_EPI_GATE_RES) || (gate && residual), WANQ_E_ARG, "%s: WANQ_EPI_GATE_RES needs gate and residual",
-               what);
-  WANQ_REQUIRE(M >= 0 && M < (1ll << 31) - QM, WANQ_E_SHAPE, "%s: M=%lld out of range", what, (long long)M);
-  WANQ_REQUIRE(N >= 8 && N % 8 == 0, WANQ_E_SHAPE, "%s: N=%d must be a positive multiple of 8", what, N);
-  WANQ_REQUIRE(K >= 64 && K % 64 == 0, WANQ_E_SHAPE, "%s: K=%d must be a positive multiple of 64", what, K);
-  WANQ_REQUIRE(aligned(a, 16) && aligned(w, 16) && aligned(out, 16) && aligned(residual, 16), WANQ_E_ARG,
-               "%s: a, w, out and residual must be 16-byte aligned", what);
+  if (const int rc = check_gemm16_shapes(what, 64, a, w, out, out_dtype, bias, bias_dtype, gate, residual, epi_flags, M, N,
+                                         K))
+    return rc;
   WANQ_REQUIRE(aligned(sw, 16) && aligned(zp, 16), WANQ_E_ARG, "%s: sw and zp must be 16-byte aligned", what);
-  WANQ_REQUIRE(aligned(gate, 16) && (!bias || aligned(bias, bias_dtype == WANQ_F32 ? 16 : 8)), WANQ_E_ARG,
-               "%s: gate and bias must be aligned to 4 elements", what);
+  if (const int rc = check_gemm16_tail(what, bias, bias_dtype, gate, M, N)) return rc;
   if (M == 0) return WANQ_OK;
   WqGemmParams p{};
   p.a = static_cast<const uint16_t*>(a); p.w = static_cast<const uint8_t*>(w); p.out = out; p.sw = sw; p.zp = zp; p.bias = bias;
   p.gate = (epi_flags & WANQ_EPI_GATE_RES) ? gate : nullptr;
   p.residual = (epi_flags & WANQ_EPI_GATE_RES) ? residual : nullptr;
   p.bias_dtype = bias_dtype; p.epi = epi_flags;
-  p.M = (int)M; p.N = N; p.K = K; p.nt = (N + QN - 1) / QN;
-  WANQ_REQUIRE(((M + QM - 1) / QM) * p.nt < (1ll << 31), WANQ_E_SHAPE, "%s: too many tiles", what);
+  p.M = (int)M; p.N = N; p.K = K; p.nt = (N + TN - 1) / TN;
   hipStream_t st = (hipStream_t)stream;
   if (w_bits == 4) return dtype == WANQ_F16 ? launch_out<true, true>(p, out_dtype, st) : launch_out<false, true>(p, out_dtype, st);
   return dtype == WANQ_F16 ? launch_out<true, false>(p, out_dtype, st) : launch_out<false, false>(p, out_dtype, st);

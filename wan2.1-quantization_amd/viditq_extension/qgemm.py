@@ -43,6 +43,32 @@ def _check_vec(name, t, n, dtypes=_VEC):
     _C.check_shape(name, t, n)
 
 
+def _epi_flags(gelu, gate, residual, M, N, out_dtype):
+    """The epilogue flags of a launch, after the checks on gate (fp32 [N]) and residual ([M, N] of the out dtype): both or neither."""
+    epi = _C.EPI_GELU if gelu else 0
+    if gate is not None or residual is not None:
+        if gate is None or residual is None:
+            raise RuntimeError("gate and residual must be given together")
+        _check_vec("gate", gate, N, (torch.float32,))
+        _C.check_gpu("residual", residual)
+        _C.check_contig("residual", residual)
+        _C.check_dtype("residual", residual, out_dtype)
+        _C.check_shape("residual", residual, M, N)
+        epi |= _C.EPI_GATE_RES
+    return epi
+
+
+def _out_for(out, M, N, out_dtype, device):
+    """`out` checked against [M, N] of out_dtype, or a fresh tensor when None."""
+    if out is None:
+        return torch.empty((M, N), dtype=out_dtype, device=device)
+    _C.check_gpu("out", out)
+    _C.check_contig("out", out)
+    _C.check_dtype("out", out, out_dtype)
+    _C.check_shape("out", out, M, N)
+    return out
+
+
 # Packed 4-bit weights at large M: the int8 matrix cores are the bound, not the weight bytes, so the fastest W4A8 product on this
 # machine is the W8 ping-pong kernel on codes expanded ONCE per launch (wanq_unpack_w4: 1.5 N K bytes of traffic, 1-6 % of the
 # product's time from 32760 down to 9450 rows) instead of once per tile inside the kernel (wanq_gemm_w4a8's in-register expansion
@@ -84,23 +110,8 @@ def w8a8_linear(input, weight, scale_input, scale_weight, bias=None, input_sum=N
         raise RuntimeError("bias and scale_weight must share a dtype")
     if zp_weight is not None and input_sum is None:
         raise RuntimeError("asymmetric weights (zp_weight) need input_sum")
-    epi = _C.EPI_GELU if gelu else 0
-    if gate is not None or residual is not None:
-        if gate is None or residual is None:
-            raise RuntimeError("gate and residual must be given together")
-        _check_vec("gate", gate, N, (torch.float32,))
-        _C.check_gpu("residual", residual)
-        _C.check_contig("residual", residual)
-        _C.check_dtype("residual", residual, out_dtype)
-        _C.check_shape("residual", residual, M, N)
-        epi |= _C.EPI_GATE_RES
-    if out is None:
-        out = torch.empty((M, N), dtype=out_dtype, device=input.device)
-    else:
-        _C.check_gpu("out", out)
-        _C.check_contig("out", out)
-        _C.check_dtype("out", out, out_dtype)
-        _C.check_shape("out", out, M, N)
+    epi = _epi_flags(gelu, gate, residual, M, N, out_dtype)
+    out = _out_for(out, M, N, out_dtype, input.device)
     _C.check_same_device(input, weight, scale_input, scale_weight, bias, input_sum, zp_weight, gate, residual, out)
     with torch.cuda.device(input.device):
         if _timer is not None:
@@ -221,42 +232,35 @@ def w4a8_of16_nobias_weight_asym_qserve(in_feats, kernel, wscales, ascales, w_sz
 
 
 # ---- 16-bit floating point ----------------------------------------------------------------------------------------
+_BIAS16 = (torch.bfloat16, torch.float16, torch.float32)
+
+
+def _check_operands16(input, wname, weight, wdtype):
+    """The operand checks fp_linear and wq16_linear share: `input` bf16 / fp16 [M, K], `weight` (named `wname` in messages) a matrix
+    of `wdtype` (None: the input's dtype).  -> M, N, K"""
+    _C.check_gpu("input", input)
+    _C.check_gpu(wname, weight)
+    _C.check_contig("input", input)
+    _C.check_contig(wname, weight)
+    _C.check_dtype("input", input, torch.bfloat16, torch.float16)
+    _C.check_dtype(wname, weight, wdtype or input.dtype)
+    if input.dim() != 2 or weight.dim() != 2:
+        raise RuntimeError(f"Tensors input and {wname} must have dimension number (2)")
+    M, K = input.shape
+    return M, weight.shape[0], K
+
+
 def fp_linear(input, weight, bias=None, out_dtype=None, gelu=False, gate=None, residual=None, out=None):
     """y = epilogue(input[M,K] @ weight[N,K]^T) on the bf16 / fp16 matrix cores (wanq_gemm_bf16, csrc/gemm_bf16.hip); input and
     weight share a dtype (bf16 or fp16).  Epilogue in fp32: + bias, tanh-GELU (`gelu`), residual + y * gate (gate fp32 [N], residual
     [M,N] of out_dtype, may alias `out`), one rounding to out_dtype (default: the input's dtype).  A row's bits do not depend on M
     or on where the row sits in the launch.  Not counted by the int8 timer (`set_timer`)."""
-    _C.check_gpu("input", input)
-    _C.check_gpu("weight", weight)
-    _C.check_contig("input", input)
-    _C.check_contig("weight", weight)
-    _C.check_dtype("input", input, torch.bfloat16, torch.float16)
-    _C.check_dtype("weight", weight, input.dtype)
-    if input.dim() != 2 or weight.dim() != 2:
-        raise RuntimeError("Tensors input and weight must have dimension number (2)")
-    M, K = input.shape
-    N = weight.shape[0]
+    M, N, K = _check_operands16(input, "weight", weight, None)
     _C.check_shape("weight", weight, N, K)
     out_dtype = out_dtype or input.dtype
-    if bias is not None:
-        _check_vec("bias", bias, N, (torch.bfloat16, torch.float16, torch.float32))
-    epi = _C.EPI_GELU if gelu else 0
-    if gate is not None or residual is not None:
-        if gate is None or residual is None:
-            raise RuntimeError("gate and residual must be given together")
-        _check_vec("gate", gate, N, (torch.float32,))
-        _C.check_gpu("residual", residual)
-        _C.check_contig("residual", residual)
-        _C.check_dtype("residual", residual, out_dtype)
-        _C.check_shape("residual", residual, M, N)
-        epi |= _C.EPI_GATE_RES
-    if out is None:
-        out = torch.empty((M, N), dtype=out_dtype, device=input.device)
-    else:
-        _C.check_gpu("out", out)
-        _C.check_contig("out", out)
-        _C.check_dtype("out", out, out_dtype)
-        _C.check_shape("out", out, M, N)
+    _check_vec("bias", bias, N, _BIAS16)
+    epi = _epi_flags(gelu, gate, residual, M, N, out_dtype)
+    out = _out_for(out, M, N, out_dtype, input.device)
     _C.check_same_device(input, weight, bias, gate, residual, out)
     with torch.cuda.device(input.device):
         _C.call("wanq_gemm_bf16", _C.ptr(input), _C.ptr(weight), _C.dt(input), _C.ptr(out), _C.dt(out_dtype), _C.ptr(bias),
@@ -284,39 +288,14 @@ def wq16_linear(input, codes, scale_weight, zp=None, bias=None, out_dtype=None, 
     `zp` must be integer valued, as StaticQuantizer's rounded zero point is: the kernel cuts the 16-bit operand from the fp32 sum
     c + zp (bf16: truncation, fp16: round toward zero), so a fractional zp would be quantised silently, and differently for the two
     activation types."""
-    _C.check_gpu("input", input)
-    _C.check_gpu("codes", codes)
-    _C.check_contig("input", input)
-    _C.check_contig("codes", codes)
-    _C.check_dtype("input", input, torch.bfloat16, torch.float16)
-    _C.check_dtype("codes", codes, torch.uint8 if w4 else torch.int8)
-    if input.dim() != 2 or codes.dim() != 2:
-        raise RuntimeError("Tensors input and codes must have dimension number (2)")
-    M, K = input.shape
-    N = codes.shape[0]
+    M, N, K = _check_operands16(input, "codes", codes, torch.uint8 if w4 else torch.int8)
     _C.check_shape("codes", codes, N, K // 2 if w4 else K)
     _check_vec("scale_weight", scale_weight, N, (torch.float32,))
     _check_vec("zp", zp, N, (torch.float32,))
     out_dtype = out_dtype or input.dtype
-    if bias is not None:
-        _check_vec("bias", bias, N, (torch.bfloat16, torch.float16, torch.float32))
-    epi = _C.EPI_GELU if gelu else 0
-    if gate is not None or residual is not None:
-        if gate is None or residual is None:
-            raise RuntimeError("gate and residual must be given together")
-        _check_vec("gate", gate, N, (torch.float32,))
-        _C.check_gpu("residual", residual)
-        _C.check_contig("residual", residual)
-        _C.check_dtype("residual", residual, out_dtype)
-        _C.check_shape("residual", residual, M, N)
-        epi |= _C.EPI_GATE_RES
-    if out is None:
-        out = torch.empty((M, N), dtype=out_dtype, device=input.device)
-    else:
-        _C.check_gpu("out", out)
-        _C.check_contig("out", out)
-        _C.check_dtype("out", out, out_dtype)
-        _C.check_shape("out", out, M, N)
+    _check_vec("bias", bias, N, _BIAS16)
+    epi = _epi_flags(gelu, gate, residual, M, N, out_dtype)
+    out = _out_for(out, M, N, out_dtype, input.device)
     _C.check_same_device(input, codes, scale_weight, zp, bias, gate, residual, out)
     with torch.cuda.device(input.device):
         _C.call("wanq_gemm_wq16", _C.ptr(input), _C.ptr(codes), _C.dt(input), 4 if w4 else 8, _C.ptr(scale_weight), _C.ptr(zp),

@@ -21,7 +21,41 @@ from . import ops
 from .modules.model import WanModel
 
 
-class HipLinearW8A8(nn.Module):
+def _gelu_gate_residual(y, gelu, gate, residual):
+    """The unfused tail of a Linear: tanh-GELU, then residual <- residual + y * gate in place (the fp32 stream), as separate passes."""
+    if gelu:
+        y = torch.nn.functional.gelu(y, approximate="tanh")
+    if residual is not None:
+        fused.gate_residual_into_(residual, y, gate.view(1, -1))
+        return residual
+    return y
+
+
+class _HipLinearInt(nn.Module):
+    """The buffers HipLinearW8A8 and HipLinearWq16 both hold (described there), and the zero point their GEMMs take."""
+
+    def __init__(self, in_features, out_features, bias, sym, w_bits):
+        super().__init__()
+        assert w_bits in (4, 8), "integer storage exists for 8-bit and packed 4-bit weights"
+        self.in_features, self.out_features, self.w_bits = in_features, out_features, w_bits
+        self.register_buffer("weight", torch.empty(out_features, in_features // 2 if w_bits == 4 else in_features,
+                                                   dtype=torch.uint8 if w_bits == 4 else torch.int8))
+        self.register_buffer("scale_weight", torch.empty(out_features, dtype=torch.float32))
+        self.register_buffer("zp_weight", None if sym else torch.empty(out_features, dtype=torch.float32))
+        self.register_buffer("zp_gemm", torch.empty(out_features, dtype=torch.float32) if w_bits == 4 else None)
+        self.register_buffer("bias", torch.empty(out_features, dtype=torch.float32) if bias else None)
+
+    def refresh_zp_gemm(self):
+        """After scale_weight / zp_weight were loaded from a checkpoint."""
+        if self.w_bits == 4:
+            self.zp_gemm.copy_((self.zp_weight if self.zp_weight is not None else torch.zeros_like(self.scale_weight)) - 8.0)
+
+    @property
+    def zp(self):  # the zero point the GEMM takes (None: symmetric 8-bit codes)
+        return self.zp_gemm if self.w_bits == 4 else self.zp_weight
+
+
+class HipLinearW8A8(_HipLinearInt):
     """Integer weight + per-output-channel fp32 (delta, zero_point) + fp32 bias.
     weight_dequant = (code + zero_point) * delta  (StaticQuantizer.forward, qdiff/base/base_quantizer.py:56-59).
     w_bits 8: `weight` int8 [N, K].  w_bits 4: `weight` uint8 [N, K/2], the codes + 8 as nibbles in the library's packed layout
@@ -37,18 +71,8 @@ class HipLinearW8A8(nn.Module):
     act_quantizer = None
 
     def __init__(self, in_features, out_features, bias=True, sym=False, w_bits=8):
-        super().__init__()
-        assert w_bits in (4, 8), "integer storage exists for 8-bit and packed 4-bit weights"
-        self.in_features, self.out_features, self.w_bits = in_features, out_features, w_bits
-        if w_bits == 4:
-            assert in_features % 32 == 0, "packed 4-bit weights need in_features % 32 == 0"
-            self.register_buffer("weight", torch.empty(out_features, in_features // 2, dtype=torch.uint8))
-        else:
-            self.register_buffer("weight", torch.empty(out_features, in_features, dtype=torch.int8))
-        self.register_buffer("scale_weight", torch.empty(out_features, dtype=torch.float32))
-        self.register_buffer("zp_weight", None if sym else torch.empty(out_features, dtype=torch.float32))
-        self.register_buffer("zp_gemm", torch.empty(out_features, dtype=torch.float32) if w_bits == 4 else None)
-        self.register_buffer("bias", torch.empty(out_features, dtype=torch.float32) if bias else None)
+        super().__init__(in_features, out_features, bias, sym, w_bits)
+        assert w_bits == 8 or in_features % 32 == 0, "packed 4-bit weights need in_features % 32 == 0"
         self.register_buffer("act_premul", None)
         self.rot = None
 
@@ -82,10 +106,8 @@ class HipLinearW8A8(nn.Module):
         return r
 
     def refresh_zp_gemm(self):
-        """After scale_weight / zp_weight were loaded from a checkpoint."""
         self.__dict__.pop("_w_rowsum", None)
-        if self.w_bits == 4:
-            self.zp_gemm.copy_((self.zp_weight if self.zp_weight is not None else torch.zeros_like(self.scale_weight)) - 8.0)
+        super().refresh_zp_gemm()
 
     @classmethod
     def from_float(cls, weight, bias=None, n_bits=8, sym=False, delta=None, zero_point=None):
@@ -121,12 +143,9 @@ class HipLinearW8A8(nn.Module):
         return None if self.act_premul is None and self.rot is None else id(self)
 
     def forward(self, a_q, a_scale, a_sum, out_dtype=torch.bfloat16, gelu=False, gate=None, residual=None, out=None):
-        if self.w_bits == 4:
-            return qgemm.w8a8_linear(a_q, self.weight, a_scale, self.scale_weight, self.bias, a_sum, self.zp_gemm,
-                                     out_dtype=out_dtype, gelu=gelu, gate=gate, residual=residual, out=out, w4=True)
-        return qgemm.w8a8_linear(a_q, self.weight, a_scale, self.scale_weight, self.bias,
-                                 a_sum if self.zp_weight is not None else None, self.zp_weight, out_dtype=out_dtype,
-                                 gelu=gelu, gate=gate, residual=residual, out=out)
+        zp = self.zp
+        return qgemm.w8a8_linear(a_q, self.weight, a_scale, self.scale_weight, self.bias, a_sum if zp is not None else None, zp,
+                                 out_dtype=out_dtype, gelu=gelu, gate=gate, residual=residual, out=out, w4=self.w_bits == 4)
 
 
 FP_GEMMS = ("torch", "hip")
@@ -153,8 +172,16 @@ class HipLinearFp(nn.Module):
         self.register_buffer("weight", weight.detach().to(dtype).contiguous())
         self.register_buffer("bias", None if bias is None else bias.detach().to(dtype).contiguous())
 
+    def forward(self, x, out_dtype=None, gelu=False, gate=None, residual=None, out=None):
+        """HipLinearWq16.forward's call.  "hip": fused epilogue; reads `weight` as it is now (--dit_fsdp re-points it at views of the
+        gathered buffer).  "torch": the result has x's dtype and the update lands in `residual` (`out_dtype` is the fused form's)."""
+        if self.fp_gemm == "hip":
+            return qgemm.fp_linear(x, self.weight, self.bias, out_dtype, gelu=gelu, gate=gate, residual=residual, out=out)
+        assert out is None or out is residual, "fp_gemm='torch' writes into `residual` only"
+        return _gelu_gate_residual(torch.nn.functional.linear(x, self.weight, self.bias), gelu, gate, residual)
 
-class HipLinearWq16(nn.Module):
+
+class HipLinearWq16(_HipLinearInt):
     """A weight-only quantised Linear (a `weight:` section and no `act:` section: W8A16 / W4A16): HipLinearW8A8's integer codes,
     per-channel fp32 (delta, zero_point) and fp32 bias -- 4-bit codes stay packed, `zp_gemm` = zero_point - 8 -- against the
     block's 16-bit activations, through qgemm.wq16_linear (csrc/gemm_wq16.hip): the codes become MFMA fragments in registers,
@@ -166,23 +193,10 @@ class HipLinearWq16(nn.Module):
     act_premul = None
 
     def __init__(self, in_features, out_features, bias=True, sym=False, w_bits=8, name="linear"):
-        super().__init__()
-        assert w_bits in (4, 8), "integer storage exists for 8-bit and packed 4-bit weights"
+        super().__init__(in_features, out_features, bias, sym, w_bits)
         why = qgemm.wq16_linear_refusal(1, out_features, in_features)
         if why is not None:
             raise ValueError(f"{name}: the weight-only GEMM cannot take this layer ({out_features}, {in_features}): {why}")
-        self.in_features, self.out_features, self.w_bits = in_features, out_features, w_bits
-        self.register_buffer("weight", torch.empty(out_features, in_features // 2 if w_bits == 4 else in_features,
-                                                   dtype=torch.uint8 if w_bits == 4 else torch.int8))
-        self.register_buffer("scale_weight", torch.empty(out_features, dtype=torch.float32))
-        self.register_buffer("zp_weight", None if sym else torch.empty(out_features, dtype=torch.float32))
-        self.register_buffer("zp_gemm", torch.empty(out_features, dtype=torch.float32) if w_bits == 4 else None)
-        self.register_buffer("bias", torch.empty(out_features, dtype=torch.float32) if bias else None)
-
-    def refresh_zp_gemm(self):
-        """After scale_weight / zp_weight were loaded from a checkpoint."""
-        if self.w_bits == 4:
-            self.zp_gemm.copy_((self.zp_weight if self.zp_weight is not None else torch.zeros_like(self.scale_weight)) - 8.0)
 
     @classmethod
     def from_quantized(cls, ql, name="linear"):
@@ -210,8 +224,8 @@ class HipLinearWq16(nn.Module):
 
     def forward(self, x, out_dtype=None, gelu=False, gate=None, residual=None, out=None):
         """Reads `weight` as it is now (--dit_fsdp re-points it at views of the gathered buffer)."""
-        return qgemm.wq16_linear(x, self.weight, self.scale_weight, self.zp_gemm if self.w_bits == 4 else self.zp_weight, self.bias,
-                                 out_dtype, gelu=gelu, gate=gate, residual=residual, out=out, w4=self.w_bits == 4)
+        return qgemm.wq16_linear(x, self.weight, self.scale_weight, self.zp, self.bias, out_dtype, gelu=gelu, gate=gate,
+                                 residual=residual, out=out, w4=self.w_bits == 4)
 
 
 def _to_hip_linear(lin, n_bits, sym, act_dtype, fp_gemm="torch", name="linear"):
@@ -448,24 +462,12 @@ class WanAttentionBlockWithHipKernel(nn.Module):
             if residual is not None:
                 return lin(q, s, ssum, torch.float32, gate=gate, residual=residual, out=residual)
             return lin(q, s, ssum, out_dtype, gelu=gelu)
-        if getattr(lin, "weight_only", False):  # integer codes x 16-bit activations; GELU and gate + residual in the epilogue
-            x = src.fp()
-            if residual is not None:
-                return lin(x, torch.float32, gate=gate.float().contiguous(), residual=residual, out=residual)
-            return lin(x, x.dtype, gelu=gelu)
-        if lin.fp_gemm == "hip":  # GELU and gate + residual in the GEMM's epilogue; reads lin.weight as it is now (--dit_fsdp views)
-            x = src.fp()
-            if residual is not None:
-                return qgemm.fp_linear(x, lin.weight, lin.bias, torch.float32, gate=gate.float().contiguous(), residual=residual,
-                                       out=residual)
-            return qgemm.fp_linear(x, lin.weight, lin.bias, x.dtype, gelu=gelu)
-        y = torch.nn.functional.linear(src.fp(), lin.weight, lin.bias)
-        if gelu:
-            y = torch.nn.functional.gelu(y, approximate="tanh")
+        x = src.fp()  # floating input: HipLinearWq16 (integer codes x 16-bit activations) or HipLinearFp ("hip" or "torch")
         if residual is not None:
-            fused.gate_residual_into_(residual, y, gate.view(1, -1))
-            return residual
-        return y
+            if getattr(lin, "weight_only", False) or lin.fp_gemm == "hip":  # the fused epilogues take an fp32 gate
+                gate = gate.float().contiguous()
+            return lin(x, torch.float32, gate=gate, residual=residual, out=residual)
+        return lin(x, x.dtype, gelu=gelu)
 
     def _linear_any_act(self, lin, src, out_dtype, gelu, gate, residual):
         """A quantised Linear whose activation quantiser is not the fused producers' (asymmetric, below 8 bits, the mixed-precision
@@ -478,12 +480,8 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         y = lin(q, s, ssum, torch.float32)
         if not aq.sym:
             y = torch.addcmul(y, (aq.zero_point.reshape(-1).float() * s).unsqueeze(1), lin.w_rowsum().unsqueeze(0))
-        if gelu:
-            y = torch.nn.functional.gelu(y, approximate="tanh")
-        if residual is not None:
-            fused.gate_residual_into_(residual, y, gate.view(1, -1))
-            return residual
-        return y.to(out_dtype)
+        y = _gelu_gate_residual(y, gelu, gate, residual)
+        return y if residual is not None else y.to(out_dtype)
 
     @staticmethod
     def _vq(v, n_bits, k_len):
