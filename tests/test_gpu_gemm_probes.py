@@ -11,7 +11,8 @@ allocation holds a quiet-NaN bit pattern before EVERY launch, and after it both 
   E  CPU self-tests (not marked gpu): the dispatch rules restated and the shape table checked against them, exactness proved in
      float64 and float32 with both term orders, a plain fp32 numpy model that passes the checkers and mutants of it that fail.
 
-Dispatch (gemm_entry / launch_gemm in csrc/gemm_w8a8.hip, gemm_pp_eligible in csrc/gemm_w8a8_pp.hip), `dispatch()` below:
+Dispatch (gemm_entry / launch_gemm in csrc/gemm_w8a8.hip, gemm_pp_eligible in csrc/gemm_w8a8_pp.hip, both on persistent_shape_ok of
+csrc/gemm_i8_common.h), `dispatch()` below; `tile_origin()` below restates the walk of that header:
   pp   select 0, W8, M >= 512, K % 128 == 0, K >= 256, no gate + residual unless fp32 output, no GELU with fp32 output
   v2   select 0 / 2, M >= 512, K % 128 == 0              v1   everything else, or select 1
 Store loops: 16 (16-bit, no residual), f32res (fp32 + gate + residual, residual ring), f32 and i32 (the 32-bit loop), 16res (16-bit +

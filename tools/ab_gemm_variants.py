@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """A/B timing of int8-GEMM kernel VARIANTS in one process (interleaved rounds, median / min): every shared library given on the
-command line (built from different revisions of csrc/gemm_w8a8.hip, e.g. into lib/variants/) is loaded with ctypes and its
+command line (built from different revisions of csrc/gemm_w8a8.hip / csrc/gemm_w8a8_pp.hip, e.g. into lib/variants/) is loaded with ctypes and its
 wanq_gemm_w8a8 / wanq_gemm_w4a8 are called on the same tensors; outputs must be BIT-EQUAL to the first library's.
 Bit-equality here is NOT a race screen: the residual-prefetch epilogue passed it while a missing workgroup barrier let the next
 tile's LDS-DMA overwrite other waves' residual buffers (waves run in lock-step in this harness); the full model caught it, and
 tests/test_gpu_gemm.py::test_fp32_gate_residual_in_place_many_tiles (short K, in place, repeated) now pins it.
-usage: ab_gemm_variants.py libA.so libB.so ...   (build: hipcc -O3 --offload-arch=gfx950 -fPIC -std=c++17 -shared csrc/gemm_w8a8.hip csrc/runtime.hip)"""
+usage: ab_gemm_variants.py [--select N] libA.so libB.so ...
+  --select N   wanq_gemm_select_kernel(N) on every library: 0 the dispatcher's choice, 1 the 128 x 128 kernel, 2 no ping-pong kernel
+  (build: hipcc -O3 --offload-arch=gfx950 -fPIC -std=c++17 -shared csrc/gemm_w8a8.hip csrc/gemm_w8a8_pp.hip csrc/runtime.hip)"""
+import argparse
 import ctypes
-import sys
 
 import torch
 
@@ -15,9 +17,17 @@ F16, BF16, F32, I32 = 0, 1, 2, 3
 V = ctypes.c_void_p
 ARGS = [V, V, V, ctypes.c_int, V, V, ctypes.c_int, V, V, ctypes.c_int, V, ctypes.c_int, V, V, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
         ctypes.c_int, V]
+ap = argparse.ArgumentParser()
+ap.add_argument("--select", type=int, default=0)
+ap.add_argument("libs", nargs="+")
+opts = ap.parse_args()
 libs = []
-for path in sys.argv[1:]:
+for path in opts.libs:
     lib = ctypes.CDLL(path)
+    lib.wanq_gemm_select_kernel.argtypes = [ctypes.c_int]
+    lib.wanq_gemm_select_kernel.restype = ctypes.c_int
+    if lib.wanq_gemm_select_kernel(opts.select) < 0:
+        raise SystemExit(f"{path}: wanq_gemm_select_kernel({opts.select}) refused")
     for f in (lib.wanq_gemm_w8a8, lib.wanq_gemm_w4a8):
         f.argtypes = ARGS
         f.restype = ctypes.c_int
@@ -41,6 +51,10 @@ CASES = [  # (M, N, K, out dtype, epilogue flags, w4)
     (32760, 1536, 8960, BF16, 0, True), (32760, 8960, 1536, BF16, 1, True),
     (9450, 5120, 5120, BF16, 0, False), (9450, 13824, 5120, BF16, 1, False), (9450, 5120, 13824, F32, 2, False),
     (9450, 5120, 13824, BF16, 0, True), (1000, 1536, 1536, BF16, 0, False),
+    # what the persistent non-ping-pong kernel serves in production: packed weights below the unpack threshold, a 16-bit gate +
+    # residual, GELU with an fp32 output, one K-tile
+    (1000, 1536, 1536, BF16, 0, True), (2000, 1536, 1536, BF16, 0, True), (1000, 1536, 1536, F32, 2, True), (2000, 1536, 1536, F32, 2, True),
+    (32760, 1536, 1536, F16, 2, False), (32760, 8960, 1536, F32, 1, False), (2048, 1536, 128, BF16, 0, False),
 ]
 for (M, N, K, od, epi, w4) in CASES:
     g = torch.Generator(device=dev).manual_seed(M + N + K)
@@ -56,7 +70,8 @@ for (M, N, K, od, epi, w4) in CASES:
     zp = torch.randn(N, device=dev, generator=g).round()
     bias = torch.randn(N, device=dev, generator=g)
     gate = torch.randn(N, device=dev, generator=g)
-    tdt = {BF16: torch.bfloat16, F32: torch.float32, I32: torch.int32}[od]
+    tdt = {F16: torch.float16, BF16: torch.bfloat16, F32: torch.float32, I32: torch.int32}[od]
+    bits = torch.int16 if od in (F16, BF16) else torch.int32
     res = torch.randn(M, N, device=dev, generator=g).to(tdt) if epi & 2 else None
     outs = {}
 
@@ -90,6 +105,6 @@ for (M, N, K, od, epi, w4) in CASES:
         med = t[len(t) // 2]
         base = base or med
         a0, b0 = outs[n], outs[libs[0][0]]
-        same = torch.equal(a0.view(torch.int32 if od != BF16 else torch.int16), b0.view(torch.int32 if od != BF16 else torch.int16))
+        same = torch.equal(a0.view(bits), b0.view(bits))
         print(f"M={M} N={N} K={K} out={['f16','bf16','f32','i32'][od]} epi={epi} w4={int(w4)} {n:24s} median {med * 1e3:7.1f} us  min {t[0] * 1e3:7.1f} us "
               f"{ops / med / 1e9:7.1f} TOP/s  x{base / med:.3f}  bit-equal to first: {same}", flush=True)

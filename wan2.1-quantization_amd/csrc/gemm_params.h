@@ -1,5 +1,6 @@
-// What the int8 GEMM kernels share (gemm_w8a8.hip: v1 and persistent v2; gemm_w8a8_pp.hip: ping-pong v3): the launch
-// parameters and the epilogue helpers that convert four outputs and load four per-channel values.
+// What the int8 GEMM kernels share (gemm_w8a8.hip: v1 and persistent v2; gemm_w8a8_pp.hip: ping-pong v3), and the 16-bit GEMMs
+// with them: the launch parameters and the epilogue helpers that convert four outputs and load four per-channel values.  The
+// int8 kernels' tile walk and the persistent pair's tile rules are in gemm_i8_common.h.
 #pragma once
 #include "wanq_common.h"
 

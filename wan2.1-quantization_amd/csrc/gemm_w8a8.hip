@@ -13,11 +13,10 @@
 // them (one barrier per K tile).  LDS rows are 128 B with the 16-B chunk index XORed by (row>>1)&7:
 // ds_read_b128 fragment reads and ds_write_b128 staging writes are both bank-conflict free.
 // Workgroup ids are remapped so that each XCD's L2 sees a compact (8 m-tiles x n) panel.
-#include "gemm_params.h"
+#include "gemm_i8_common.h"
 
 namespace wanq {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 
 constexpr int BM = 128, BN = 128, BK = 128;
@@ -83,17 +82,9 @@ __global__ __launch_bounds__(256, 2) void gemm_w8a8_kernel(const GemmParams p) {
   const int wm = wave & 1, wn = wave >> 1;
   const int fr = lane & 31, fh = lane >> 5;
 
-  // ---- workgroup -> tile: XCD-contiguous ids (bijective remap), then groups of GROUP_M m-tiles
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xq = nwg >> 3, xr = nwg & 7, xcd = bid & 7;
-  const int wg = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (bid >> 3);
-  const int per_group = GROUP_M * p.nt;
-  const int group = wg / per_group;
-  const int first_m = group * GROUP_M;
-  const int gsz = (p.mt - first_m < GROUP_M) ? (p.mt - first_m) : GROUP_M;
-  const int in_g = wg - group * per_group;
-  const int m0 = (first_m + in_g % gsz) * BM;
-  const int n0 = (in_g / gsz) * BN;
+  // ---- workgroup -> tile: the walk of gemm_i8_common.h over the launched grid
+  int m0, n0;
+  tile_origin<BM>(blockIdx.x, gridDim.x, p.mt, p.nt, GROUP_M, m0, n0);
 
   const int K = p.K;
   const int nk = (K + BK - 1) / BK;
@@ -248,8 +239,7 @@ __global__ __launch_bounds__(256, 2) void gemm_w8a8_kernel(const GemmParams p) {
 //    stores), so the epilogue's stores drain to HBM underneath the next tile's main loop instead of stalling
 //    every CU at the same time.
 // Used when M >= 512 and K % 128 == 0; everything else takes the v1 kernel.
-constexpr int B2M = 256, B2N = 256, B2K = 128;
-constexpr int B2_STAGE = (B2M + B2N) * B2K;  // 64 KiB
+// The tile and its K-tile stage are PM, PN, PK and PBUF of gemm_i8_common.h.
 
 // W4 (packed 4-bit weights, wanq_pack_w4 layout): a K-tile of the weight panel is 256 rows x 64 B = 16 KiB instead of 32 (two
 // LDS-DMA instructions per wave instead of four: the weight half of the ingest stream halves); a lane reads the 8 packed bytes
@@ -268,12 +258,9 @@ constexpr int B2_STAGE = (B2M + B2N) * B2K;  // 64 KiB
 // A function of its own for its __restrict__ parameters: hipcc puts s_waitcnt vmcnt(0) in front of every LDS access that may
 // alias an LDS-DMA in flight, i.e. in front of the turn-buffer writes right behind the prefetch (seen in the ISA); with the three
 // LDS regions as distinct restrict pointers it knows they do not.
-typedef int gemm_v4i __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void b2_store_f32_res(const GemmParams& p, gemm_v4i (&acc)[4][8], const float (&sa_m)[8], const float (&asum_m)[8],
+__device__ __forceinline__ void b2_store_f32_res(const GemmParams& p, v4i (&acc)[4][8], const float (&sa_m)[8], const float (&asum_m)[8],
                                                  const float* __restrict__ chan, char* __restrict__ tb, char* __restrict__ rbuf, int cur_n0,
                                                  int tok_base, int wn, int e16, int eq4, int rd_row, int rd_c, int lane_e, bool full_tile) {
-  typedef __attribute__((address_space(3))) void lds_void;
-  typedef __attribute__((address_space(1))) const void glb_void;
   // rows past M / channels past N are clamped: fetched, never stored
 #define B2_RES_DMA(c)                                                                                          \
   _Pragma("unroll") for (int ps = 0; ps < 4; ++ps) {                                                           \
@@ -302,8 +289,7 @@ __device__ __forceinline__ void b2_store_f32_res(const GemmParams& p, gemm_v4i (
         const float swa[4] = {sw4.x, sw4.y, sw4.z, sw4.w}, zsa[4] = {zs4.x, zs4.y, zs4.z, zs4.w};
         const float ba[4] = {b4.x, b4.y, b4.z, b4.w};
         float y[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) y[e] = fmaf((float)acc[i][j][e] * sa_m[j], swa[e], fmaf(asum_m[j], zsa[e], ba[e]));
+        dequant4<false, false>(acc[i][j], sa_m[j], asum_m[j], swa, zsa, ba, y);
         if (p.epi & WANQ_EPI_GELU) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) y[e] = gelu_tanh_fast_f32(y[e]);
@@ -339,18 +325,16 @@ __device__ __forceinline__ void b2_store_f32_res(const GemmParams& p, gemm_v4i (
 // waited for on the spot, once per tile (seen in the ISA).  Inside this function the request carries the noalias scopes of
 // `chan` and `tb` and no wait is inserted: the stores queue up behind the LDS-DMA and the next tile's first barrier counts them.
 template <int OUT, bool W4>
-__device__ __forceinline__ void b2_store16_and_request(const GemmParams& p, gemm_v4i (&acc)[4][8], const float (&sa_m)[8], const float (&asum_m)[8],
+__device__ __forceinline__ void b2_store16_and_request(const GemmParams& p, v4i (&acc)[4][8], const float (&sa_m)[8], const float (&asum_m)[8],
                                                        const float* __restrict__ chan, char* __restrict__ tb, char* __restrict__ stage0, bool request,
                                                        const uint32_t (&srcx)[4], const uint32_t (&srcw)[4], int wave, int cur_n0, int tok_base, int wn,
                                                        int e16, int eq4, int rd_row, int rd_c, bool full_tile) {
-  typedef __attribute__((address_space(3))) void lds_void;
-  typedef __attribute__((address_space(1))) const void glb_void;
   if (request) {  // K-tile 0 of the next tile -> stage 0 (the pieces of B2_ISSUE(0, 0))
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
       __builtin_amdgcn_global_load_lds((glb_void*)(p.a + srcx[g]), (lds_void*)(stage0 + wave * 1024 + g * 8192), 16, 0, 0);
       if (!W4 || g < 2)
-        __builtin_amdgcn_global_load_lds((glb_void*)(p.w + srcw[g]), (lds_void*)(stage0 + B2M * B2K + wave * 1024 + g * 8192), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((glb_void*)(p.w + srcw[g]), (lds_void*)(stage0 + PM * PK + wave * 1024 + g * 8192), 16, 0, 0);
     }
   }
   // chunk = 32 tokens (token blocks 2J, 2J+1) x 64 channels in the output type.  The lane's 16 channels (4 per channel block i)
@@ -375,9 +359,7 @@ __device__ __forceinline__ void b2_store16_and_request(const GemmParams& p, gemm
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         float y[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e)  // acc*sA*sW + (sumA*(zp*sW) + bias)
-          y[e] = fmaf((float)acc[i][j][e] * sa_m[j], swa[i][e], fmaf(asum_m[j], zsa[i][e], ba[i][e]));
+        dequant4<false, false>(acc[i][j], sa_m[j], asum_m[j], swa[i], zsa[i], ba[i], y);
         if (p.epi & WANQ_EPI_GELU) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) y[e] = gelu_tanh_fast_f32(y[e]);
@@ -401,29 +383,13 @@ __device__ __forceinline__ void b2_store16_and_request(const GemmParams& p, gemm
 template <int OUT, bool W4>
 __global__ __launch_bounds__(512, 2) void gemm_w8a8_big_kernel(const GemmParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  typedef __attribute__((address_space(3))) void lds_void;
-  typedef __attribute__((address_space(1))) const void glb_void;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave & 1, wn = wave >> 1;
   const int fr = lane & 31, fh = lane >> 5;
   const int K = p.K;
-  const int nk = K / B2K;
+  const int nk = K / PK;
   const int ntiles = p.mt * p.nt;
-
-  // tile id -> (m0, n0): XCD-contiguous ids (bijective remap; gridDim.x % 8 == 0 so a workgroup's tiles all
-  // sit in its own XCD's range), then groups of GROUP_M m-tiles
-  auto tile_origin = [&](int t, int& m0, int& n0) {
-    const int xq = ntiles >> 3, xr = ntiles & 7, xcd = t & 7;
-    const int wg = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (t >> 3);
-    const int per_group = p.group_m * p.nt;
-    const int group = wg / per_group;
-    const int first_m = group * p.group_m;
-    const int gsz = (p.mt - first_m < p.group_m) ? (p.mt - first_m) : p.group_m;
-    const int in_g = wg - group * per_group;
-    m0 = (first_m + in_g % gsz) * B2M;
-    n0 = (in_g / gsz) * B2N;
-  };
 
   // LDS-DMA: instruction g of this wave fills rows 8*(wave+8g) .. +7 of a stage (1 KiB, lane-linear)
   const int drow = wave * 8 + (lane >> 3);  // + 64 g
@@ -449,12 +415,12 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_big_kernel(const GemmParams 
   // piece idx = 2 g + isW: instruction g of the activation tile / of the weight tile (W4: the packed panel has pieces g < 2 only)
 #define B2_PIECE(kt, stage, idx)                                                                              \
   do {                                                                                                        \
-    char* sx_ = smem + (stage) * B2_STAGE + wave * 1024 + ((idx) >> 1) * 8192;                                \
+    char* sx_ = smem + (stage) * PBUF + wave * 1024 + ((idx) >> 1) * 8192;                                \
     if (((idx) & 1) == 0)                                                                                     \
-      __builtin_amdgcn_global_load_lds((glb_void*)(p.a + (kt) * B2K + srcx[(idx) >> 1]), (lds_void*)sx_, 16, 0, 0); \
+      __builtin_amdgcn_global_load_lds((glb_void*)(p.a + (kt) * PK + srcx[(idx) >> 1]), (lds_void*)sx_, 16, 0, 0); \
     else if (!W4 || (idx) < 4)                                                                                \
-      __builtin_amdgcn_global_load_lds((glb_void*)(p.w + (kt) * (W4 ? B2K / 2 : B2K) + srcw[(idx) >> 1]),    \
-                                       (lds_void*)(sx_ + B2M * B2K), 16, 0, 0);                               \
+      __builtin_amdgcn_global_load_lds((glb_void*)(p.w + (kt) * (W4 ? PK / 2 : PK) + srcw[(idx) >> 1]),    \
+                                       (lds_void*)(sx_ + PM * PK), 16, 0, 0);                               \
   } while (0)
 #define B2_ISSUE(kt, stage)                                                   \
   do {                                                                        \
@@ -475,14 +441,14 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_big_kernel(const GemmParams 
     ck[ks] = ((4 * ks + q4) ^ fsw) << 4;
     cw4[ks] = (((2 * ks + (q4 >> 1)) ^ ((r16 >> 2) & 3)) << 4) + 8 * (q4 & 1);
   }
-  const int rowx = (wm * 128 + r16) * B2K;
-  const int roww = B2M * B2K + (wn * 64 + r16) * (W4 ? B2K / 2 : B2K);
+  const int rowx = (wm * 128 + r16) * PK;
+  const int roww = PM * PK + (wn * 64 + r16) * (W4 ? PK / 2 : PK);
 
   const bool dma_top = !W4 && nk >= 32;
   int tile = blockIdx.x;
   if (tile >= ntiles) return;
   int m0, n0;
-  tile_origin(tile, m0, n0);
+  tile_origin<PM>(tile, ntiles, p.mt, p.nt, p.group_m, m0, n0);
   set_sources(m0, n0);
   B2_ISSUE(0, 0);
   int pending_stores = 0;  // epilogue store instructions issued after the loads now in flight
@@ -510,7 +476,7 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_big_kernel(const GemmParams 
       const bool more = kt + 1 < nk;
       if (more && dma_top) B2_ISSUE(kt + 1, (kt + 1) & 1);
       const bool more_spread = more && !dma_top;
-      const char* st = smem + (kt & 1) * B2_STAGE;
+      const char* st = smem + (kt & 1) * PBUF;
       // A K-tile is sixteen groups of 4 MFMAs: group g = 8 ks + j multiplies the four weight fragments of k-step ks (64 deep)
       // with the activation fragment of token block j.  Activation fragments live in a ring of four registers quads, read
       // three groups (192 MFMA cycles) ahead of their use; the weight fragments of k-step 1 are read during k-step 0.
@@ -523,8 +489,8 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_big_kernel(const GemmParams 
       const v4i m4 = {0x0f0f0f0f, 0x0f0f0f0f, 0x0f0f0f0f, 0x0f0f0f0f};
 #define B2_LDW(ks)                                                                                          \
   _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                           \
-    if (!W4) wf[ks][i] = *reinterpret_cast<const v4i*>(st + roww + ck[ks] + i * 16 * B2K);                  \
-    else wraw[i] = *reinterpret_cast<const uint2*>(st + roww + cw4[ks] + i * 16 * (B2K / 2));              \
+    if (!W4) wf[ks][i] = *reinterpret_cast<const v4i*>(st + roww + ck[ks] + i * 16 * PK);                  \
+    else wraw[i] = *reinterpret_cast<const uint2*>(st + roww + cw4[ks] + i * 16 * (PK / 2));              \
   }
   // W4: 8 packed bytes -> the 16 codes of the operand (byte b of dword d: code 8 d + b low nibble, code 8 d + 4 + b high nibble);
   // placed a few groups AFTER the reads so that the conversion does not wait for them
@@ -535,7 +501,7 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_big_kernel(const GemmParams 
       wf[ks][i] = u_ & m4;                                                                                  \
     }                                                                                                       \
   }
-#define B2_LDX(g) xr[(g) & 3] = *reinterpret_cast<const v4i*>(st + rowx + ck[(g) >> 3] + ((g) & 7) * 16 * B2K);
+#define B2_LDX(g) xr[(g) & 3] = *reinterpret_cast<const v4i*>(st + rowx + ck[(g) >> 3] + ((g) & 7) * 16 * PK);
       uint2 wraw[4];
       B2_LDW(0)
       B2_LDX(0) B2_LDX(1) B2_LDX(2)
@@ -572,33 +538,9 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_big_kernel(const GemmParams 
     const bool has_res = (p.epi & WANQ_EPI_GATE_RES) != 0;
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    float* chan = reinterpret_cast<float*>(smem + B2_STAGE);  // [4][256]: sW, zp*sW, bias, gate
+    float* chan = reinterpret_cast<float*>(smem + PBUF);  // [4][256]: sW, zp*sW, bias, gate
     float sa_m[8], asum_m[8];
-    int mcl[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      sa_m[j] = 1.f;
-      asum_m[j] = 0.f;
-      const int mr = cur_m0 + wm * 128 + j * 16 + r16;
-      mcl[j] = mr < p.M ? mr : p.M - 1;
-    }
-    if (OUT != WANQ_I32) {  // one uniform branch per dtype so that the eight loads of a kind issue together
-      if (p.tok_dtype == WANQ_F32) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) sa_m[j] = static_cast<const float*>(p.sa)[mcl[j]];
-        if (p.zp) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) asum_m[j] = static_cast<const float*>(p.asum)[mcl[j]];
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) sa_m[j] = __half2float(static_cast<const __half*>(p.sa)[mcl[j]]);
-        if (p.zp) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) asum_m[j] = __half2float(static_cast<const __half*>(p.asum)[mcl[j]]);
-        }
-      }
-    }
+    load_token_scales<OUT>(p, sa_m, asum_m, cur_m0 + wm * 128, r16);
     if (OUT != WANQ_I32) {
       if (tid < 256) {
         const int nc = (cur_n0 + tid < p.N) ? cur_n0 + tid : p.N - 1;
@@ -614,12 +556,12 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_big_kernel(const GemmParams 
     }
     constexpr bool OUT16 = (OUT == WANQ_F16 || OUT == WANQ_BF16);
     if (next < ntiles) {
-      tile_origin(next, m0, n0);
+      tile_origin<PM>(next, ntiles, p.mt, p.nt, p.group_m, m0, n0);
       set_sources(m0, n0);
       // the 16-bit no-residual path requests the next tile's first K-tile inside its store function (b2_store16_and_request)
       if (!has_res && !OUT16) B2_ISSUE(0, 0);
     }
-    const bool full_tile = (cur_m0 + B2M <= p.M) && (cur_n0 + B2N <= p.N);
+    const bool full_tile = (cur_m0 + PM <= p.M) && (cur_n0 + PN <= p.N);
     // ---- store loop.  An accumulator has one token per lane and 4 channels per register quad, so storing it directly
     // writes 8-16 B per lane at a row stride: 32 partial lines per instruction (PMC: WRITE_SIZE 2.6-2.7x the output
     // bytes).  Each wave therefore turns its results through a private 4-KiB LDS buffer (32 tokens x 128 B, 16-B chunks
@@ -631,7 +573,7 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_big_kernel(const GemmParams 
     // of the stores issued so far)
     int lane_e = lane;
     asm volatile("" : "+v"(lane_e));
-    char* tb = smem + B2_STAGE + 4096 + wave * 4096;
+    char* tb = smem + PBUF + 4096 + wave * 4096;
     const int rd_row = lane_e >> 3, rd_c = lane_e & 7;  // read-back: row rd_row + 8*pass, 16-B chunk rd_c
     const int e16 = lane_e & 15, eq4 = lane_e >> 4;     // = r16, q4 (opaque copies)
     const int tok_base = cur_m0 + wm * 128;
@@ -666,9 +608,7 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_big_kernel(const GemmParams 
                 const float swa[4] = {sw4.x, sw4.y, sw4.z, sw4.w}, zsa[4] = {zs4.x, zs4.y, zs4.z, zs4.w};
                 const float ba[4] = {b4.x, b4.y, b4.z, b4.w};
                 float y[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                  y[e] = fmaf((float)acc[i][j][e] * sa_m[j], swa[e], fmaf(asum_m[j], zsa[e], ba[e]));
+                dequant4<false, false>(acc[i][j], sa_m[j], asum_m[j], swa, zsa, ba, y);
                 if (p.epi & WANQ_EPI_GELU) {
 #pragma unroll
                   for (int e = 0; e < 4; ++e) y[e] = gelu_tanh_fast_f32(y[e]);
@@ -730,16 +670,14 @@ static int launch_gemm(GemmParams p, hipStream_t st) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_w8a8_kernel<OUT, W4>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               2 * STAGE_BYTES);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_w8a8_big_kernel<OUT, W4>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 2 * B2_STAGE);
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 2 * PBUF);
     return true;
   }();
   (void)attr_set;
-  if (p.M >= 512 && p.K % B2K == 0 && g_kernel_sel != 1 && (int64_t)p.M * p.K < (1ll << 32) && (int64_t)p.N * p.K < (1ll << 32)) {
-    p.mt = (p.M + B2M - 1) / B2M;
-    p.nt = (p.N + B2N - 1) / B2N;
-    const int tiles = p.mt * p.nt;
-    const int grid = tiles < 256 ? ((tiles + 7) & ~7) : 256;  // one workgroup per CU; % 8 == 0 for the XCD ranges
-    hipLaunchKernelGGL((gemm_w8a8_big_kernel<OUT, W4>), dim3((unsigned)grid), dim3(512), 2 * B2_STAGE, st, p);
+  if (g_kernel_sel != 1 && persistent_shape_ok(p)) {
+    p.mt = (p.M + PM - 1) / PM;
+    p.nt = (p.N + PN - 1) / PN;
+    hipLaunchKernelGGL((gemm_w8a8_big_kernel<OUT, W4>), dim3((unsigned)persistent_grid(p.mt * p.nt)), dim3(512), 2 * PBUF, st, p);
   } else {
     hipLaunchKernelGGL((gemm_w8a8_kernel<OUT, W4>), dim3((unsigned)(p.mt * p.nt)), dim3(256), 2 * STAGE_BYTES, st, p);
   }

@@ -34,25 +34,20 @@
 // Why 32-MFMA bursts: the first form (four phases per K-tile, 16-MFMA bursts, one 8-KiB chunk per slot) paid ~90 cycles of
 // barrier / refill per 256: 2775 cycles per K-tile against 2500-2600 (profiles/r04_b_gemm_pingpong_clock.txt, r04_l_*, r04_m_*).
 //
-// Epilogue: the v2 kernel's store path (per-wave 4-KiB LDS turn buffers -> whole 128-B lines); the tile's per-token and
+// Epilogue: the store path of both persistent kernels (per-wave 4-KiB LDS turn buffers -> whole 128-B lines); the tile's per-token and
 // per-channel values are prefetched by LDS-DMA into the wave's idle turn buffer two K-tiles ahead (all-fp32 parameter sets;
 // otherwise loaded straight into registers) -- no LDS staging area, no workgroup barrier: the ring is full of the next tile's
 // K-tiles.  Store instructions share the vmcnt queue with the LDS-DMA pieces, so the first burst behind an epilogue waits with
 // the count raised by the stores a FULL tile issues (16 / 32); a ragged tile drains after its store loop instead.  The fp32 +
 // gate + residual epilogue needs 64 KiB for its residual prefetch ring: its kernels do not request the next tile's second
 // K-tile under the last K-tile, use that buffer for the ring and request it behind the store loop.
-#include "gemm_params.h"
+#include "gemm_i8_common.h"
 #include <type_traits>
 
 namespace wanq {
 namespace {
 
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void glb_void;
-
-constexpr int PM = 256, PN = 256, PK = 128;
-constexpr int PBUF = (PM + PN) * PK;  // one K-tile buffer: 64 KiB
+// the ring: two K-tile buffers of PBUF bytes (gemm_i8_common.h)
 constexpr int PXB = PM * PK;          // offset of the W rows inside a buffer
 constexpr int PTURN = 2 * PBUF;       // eight 4-KiB turn buffers behind the ring
 constexpr int PLDS = PTURN + 8 * 4096;  // 160 KiB
@@ -70,33 +65,8 @@ struct LaneScales {
 
 template <int OUT>
 __device__ __forceinline__ void load_lane_scales(const GemmParams& p, LaneScales& s, int n_base, int tok_base, int e16, int eq4) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    s.sa[j] = 1.f;
-    s.asum[j] = 0.f;
-  }
+  load_token_scales<OUT>(p, s.sa, s.asum, tok_base, e16);
   if (OUT == WANQ_I32) return;
-  int mcl[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int mr = tok_base + j * 16 + e16;
-    mcl[j] = mr < p.M ? mr : p.M - 1;
-  }
-  if (p.tok_dtype == WANQ_F32) {  // one uniform branch per dtype so that the eight loads of a kind issue together
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s.sa[j] = static_cast<const float*>(p.sa)[mcl[j]];
-    if (p.zp) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s.asum[j] = static_cast<const float*>(p.asum)[mcl[j]];
-    }
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) s.sa[j] = __half2float(static_cast<const __half*>(p.sa)[mcl[j]]);
-    if (p.zp) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s.asum[j] = __half2float(static_cast<const __half*>(p.asum)[mcl[j]]);
-    }
-  }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     int n = n_base + i * 16 + 4 * eq4;  // channels past N are clamped: computed, never stored
@@ -192,32 +162,12 @@ __device__ __forceinline__ void read_lane_scales(const GemmParams& p, LaneScales
 
 // (GELU is a template parameter of the store loops: tested per call site, the flag put a branch behind every four values --
 // 32 per tile -- and no two groups' conversion chains overlapped)
-// PK: the same expression on channel PAIRS (v_pk_mul_f32 / v_pk_fma_f32: IEEE per half, bit-identical to the scalar form, 2.25
-// instead of 4 vector instructions per value).  Used by the 16-bit and plain 32-bit store loops (bf16 q / k / v GEMM 1.050x, GELU
+// PK (dequant4, gemm_i8_common.h) is used by the 16-bit and plain 32-bit store loops (bf16 q / k / v GEMM 1.050x, GELU
 // ffn.0 1.048x, 14B shapes 1.02x alone); the gate + residual loop keeps the scalar form, which the packed one slowed to 0.953x at
 // K = 1536 (profiles/r04_zz_gemm_pk_epilogue_ab.txt).
 template <bool GELU, bool PK>
-__device__ __forceinline__ void dequant4(const v4i& a, const LaneScales& s, int i, int j, float (&y)[4]) {
-  if (PK) {
-    typedef float v2f __attribute__((ext_vector_type(2)));
-    const v2f sa2 = {s.sa[j], s.sa[j]}, as2 = {s.asum[j], s.asum[j]};
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const v2f af = {(float)a[2 * h], (float)a[2 * h + 1]};
-      const v2f sw2 = {s.sw[i][2 * h], s.sw[i][2 * h + 1]}, zs2 = {s.zs[i][2 * h], s.zs[i][2 * h + 1]}, b2 = {s.b[i][2 * h], s.b[i][2 * h + 1]};
-      const v2f r = __builtin_elementwise_fma(af * sa2, sw2, __builtin_elementwise_fma(as2, zs2, b2));
-      y[2 * h] = r.x;
-      y[2 * h + 1] = r.y;
-    }
-  } else {
-#pragma unroll
-    for (int e = 0; e < 4; ++e)  // acc*sA*sW + (sumA*(zp*sW) + bias): the v2 kernel's expression, bit for bit
-      y[e] = fmaf((float)a[e] * s.sa[j], s.sw[i][e], fmaf(s.asum[j], s.zs[i][e], s.b[i][e]));
-  }
-  if (GELU) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) y[e] = gelu_tanh_fast_f32(y[e]);
-  }
+__device__ __forceinline__ void dequant_ij(const v4i& a, const LaneScales& s, int i, int j, float (&y)[4]) {
+  dequant4<GELU, PK>(a, s.sa[j], s.asum[j], s.sw[i], s.zs[i], s.b[i], y);
 }
 
 // 16-bit store loop: chunk = 32 tokens (token blocks 2J, 2J+1) x 64 channels through the wave's turn buffer (32 rows x 128 B,
@@ -233,7 +183,7 @@ __device__ __forceinline__ void store16(const GemmParams& p, v4i (&acc)[4][8], c
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         float y[4];
-        dequant4<GELU, true>(acc[i][j], s, i, j, y);
+        dequant_ij<GELU, true>(acc[i][j], s, i, j, y);
         const int cb = (i * 16 + 4 * eq4) * 2;  // byte column inside the 128-B row
         *reinterpret_cast<uint2*>(tb + tr * 128 + ((((cb >> 4) ^ (tr & 7)) << 4) | (cb & 15))) = pack16x4<OUT>(y);
       }
@@ -273,7 +223,7 @@ __device__ __forceinline__ void store32(const GemmParams& p, v4i (&acc)[4][8], c
             *reinterpret_cast<int4*>(dst) = make_int4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
           } else {
             float y[4];
-            dequant4<GELU, true>(acc[i][j], s, i, j, y);
+            dequant_ij<GELU, true>(acc[i][j], s, i, j, y);
             *reinterpret_cast<float4*>(dst) = make_float4(y[0], y[1], y[2], y[3]);
           }
         }
@@ -296,7 +246,7 @@ __device__ __forceinline__ void store32(const GemmParams& p, v4i (&acc)[4][8], c
 }
 
 // fp32 + gate + residual store loop, residual lines prefetched ONE CHUNK AHEAD by LDS-DMA into rbuf (two 4-KiB halves per
-// wave, lane-linear; the v2 kernel's b2_store_f32_res).  Chunk c = 2 J + ih = 32 tokens x 32 channels.  Counted waits for a
+// wave, lane-linear; the twin of b2_store_f32_res in gemm_w8a8.hip: a change to the waits or guards of one belongs in both).  Chunk c = 2 J + ih = 32 tokens x 32 channels.  Counted waits for a
 // full tile (the four stores of chunk c-1 and the four pieces of chunk c+1 stay in flight), a drain for a ragged one.
 template <bool GELU>
 __device__ __forceinline__ void store32_res(const GemmParams& p, v4i (&acc)[4][8], const LaneScales& s, const float (&gt)[2][4],
@@ -322,7 +272,7 @@ __device__ __forceinline__ void store32_res(const GemmParams& p, v4i (&acc)[4][8
       for (int ii = 0; ii < 2; ++ii) {
         const int i = 2 * ih + ii;
         float y[4];
-        dequant4<GELU, false>(acc[i][j], s, i, j, y);
+        dequant_ij<GELU, false>(acc[i][j], s, i, j, y);
         *reinterpret_cast<float4*>(tb + tr * 128 + (((4 * ii + eq4) ^ (tr & 7)) << 4)) = make_float4(y[0], y[1], y[2], y[3]);
       }
     }
@@ -357,20 +307,7 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_pp_kernel(const GemmParams p
   const bool fast_scales = scales_all_f32(p) && p.K >= 4 * PK;  // (>= 4 K-tiles: the prefetch sits two K-tiles in front of the epilogue)
   const uint32_t lds_base = (uint32_t)(size_t)(__attribute__((address_space(3))) char*)smem;
 
-  // tile id -> (m0, n0): XCD-contiguous ids (bijective remap; gridDim.x % 8 == 0), then groups of group_m m-tiles (v2's walk)
-  auto tile_origin = [&](int t, int& m0, int& n0) {
-    const int xq = ntiles >> 3, xr = ntiles & 7, xcd = t & 7;
-    const int wg = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (t >> 3);
-    const int per_group = p.group_m * p.nt;
-    const int group = wg / per_group;
-    const int first_m = group * p.group_m;
-    const int gsz = (p.mt - first_m < p.group_m) ? (p.mt - first_m) : p.group_m;
-    const int in_g = wg - group * per_group;
-    m0 = (first_m + in_g % gsz) * PM;
-    n0 = (in_g / gsz) * PN;
-  };
-
-  // ---- issue side: byte offsets of this lane's 16 B inside the eight pieces a wave moves per K-tile (k = 0)
+    // ---- issue side: byte offsets of this lane's 16 B inside the eight pieces a wave moves per K-tile (k = 0)
   //   X half a / b, piece q: tile row 128 g + 64 s + 16 c + 8 q + (lane >> 3);   W half a / b of group g: physical row
   //   128 s + 64 g + 16 c + 8 q + (lane >> 3) = channel 64 (P' >> 5) + 32 s + (P' & 31) with P' = the row inside the half
   uint32_t sxa[2], sxb[2], swa[2], swb[2];
@@ -419,7 +356,7 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_pp_kernel(const GemmParams p
       if (tileI + (int)gridDim.x < ntiles) {          \
         tileI += gridDim.x;                           \
         int mi_, ni_;                                 \
-        tile_origin(tileI, mi_, ni_);                 \
+        tile_origin<PM>(tileI, ntiles, p.mt, p.nt, p.group_m, mi_, ni_);                 \
         set_sources(mi_, ni_, lane);                  \
       }                                               \
     }                                                 \
@@ -443,7 +380,7 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_pp_kernel(const GemmParams p
   int tile = blockIdx.x;
   if (tile >= ntiles) return;
   int m0, n0;
-  tile_origin(tile, m0, n0);
+  tile_origin<PM>(tile, ntiles, p.mt, p.nt, p.group_m, m0, n0);
   tileI = tile;
   set_sources(m0, n0, lane);
   // prologue = what the schedule would have issued in front of the first load phase, in its order: W(0), X(0), W(1)
@@ -571,7 +508,7 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_pp_kernel(const GemmParams p
     if (g == 0) PP_BAR();  // both groups enter the epilogue together
 
     // ---- epilogue.  The lane-derived constants come from an OPAQUE copy of the lane id: derived from `lane` itself they are
-    // loop-invariant and hipcc keeps them live across the main loop (v2 kernel: spills whose reloads wait vmcnt(0)).
+    // loop-invariant and hipcc keeps them live across the main loop (the spills' reloads wait vmcnt(0): the note at the store loop of gemm_w8a8.hip).
     const int next = tile + gridDim.x;
     int lane_e = lane;
     asm volatile("" : "+v"(lane_e));
@@ -596,7 +533,7 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_pp_kernel(const GemmParams p
       }
     };
     auto store_tile = [&](const LaneScales& sc, const float (&gt)[2][4]) {
-      if (OUT16 && (p.epi & WANQ_EPI_GELU)) store_tile_g(sc, gt, std::true_type{});  // (GELU with a 32-bit output: v2 kernel)
+      if (OUT16 && (p.epi & WANQ_EPI_GELU)) store_tile_g(sc, gt, std::true_type{});  // (GELU with a 32-bit output: gemm_w8a8_big_kernel)
       else store_tile_g(sc, gt, std::false_type{});
     };
     if (OUT != WANQ_I32 && fast_scales) {
@@ -626,7 +563,7 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_pp_kernel(const GemmParams p
       int lane_k = lane;
       asm volatile("" : "+v"(lane_k));
       int mi_, ni_;
-      tile_origin(tileI, mi_, ni_);
+      tile_origin<PM>(tileI, ntiles, p.mt, p.nt, p.group_m, mi_, ni_);
       set_sources(mi_, ni_, lane_k);
       set_read_addresses(lane_k);
     }
@@ -644,7 +581,7 @@ __global__ __launch_bounds__(512, 2) void gemm_w8a8_pp_kernel(const GemmParams p
       vm_left = 0;
     }
     tile = next;
-    tile_origin(tile, m0, n0);
+    tile_origin<PM>(tile, ntiles, p.mt, p.nt, p.group_m, m0, n0);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the issue stream's last (unread) pieces must not outlive the workgroup's LDS
 #undef PP_ISSUE
@@ -667,18 +604,15 @@ int launch_pp(GemmParams p, hipStream_t st) {
   (void)attr_set;
   p.mt = (p.M + PM - 1) / PM;
   p.nt = (p.N + PN - 1) / PN;
-  const int tiles = p.mt * p.nt;
-  const int grid = tiles < 256 ? ((tiles + 7) & ~7) : 256;  // one workgroup per CU; % 8 == 0 for the XCD ranges
-  hipLaunchKernelGGL((gemm_w8a8_pp_kernel<OUT, RES>), dim3((unsigned)grid), dim3(512), PLDS, st, p);
+  hipLaunchKernelGGL((gemm_w8a8_pp_kernel<OUT, RES>), dim3((unsigned)persistent_grid(p.mt * p.nt)), dim3(512), PLDS, st, p);
   return check_launch("wanq_gemm_w8a8");
 }
 
 }  // namespace
 
 bool gemm_pp_eligible(const GemmParams& p, int out_dtype, bool w4) {
-  if (w4) return false;
-  if (p.M < 512 || p.K % PK != 0 || p.K < 2 * PK) return false;
-  if ((int64_t)p.M * p.K >= (1ll << 32) || (int64_t)p.N * p.K >= (1ll << 32)) return false;
+  if (!persistent_shape_ok(p)) return false;
+  if (w4 || p.K < 2 * PK) return false;  // no packed-weight main loop; the issue stream runs two K-tiles ahead
   if ((p.epi & WANQ_EPI_GATE_RES) && out_dtype != WANQ_F32) return false;
   if ((p.epi & WANQ_EPI_GELU) && out_dtype == WANQ_F32) return false;
   return true;
