@@ -11,15 +11,15 @@ called through the C ABI, so mod_stride, gate_stride, rows_per_batch, positions,
   E  CPU self-tests (not marked gpu): the checkers take (outputs, case); a plain fp32 two-pass numpy model of each kernel
      passes them and eight mutants fail them.
 
-Width -> compiled form, by chunks = cols / 8 (launch_rowwise<true> in csrc/rowwise.hip, rmsnorm_rope_impl in csrc/attn_prep.hip):
+Width -> compiled form, by chunks = cols / 8 (row_ladder in csrc/row_frame.h: one ladder for launch_rowwise in csrc/rowwise.hip and
+rmsnorm_rope_impl in csrc/attn_prep.hip):
 
   chunks <=   64   128   192   256   512   768   1024  1280  1536  1792  2048
-  LayerNorm  (1,1) (1,2) (1,3) (1,4) (4,2) (4,3) (4,4) (4,5) (4,6) (4,7) (4,8)     (WPR, NCH)
-  RMSNorm    (1,1) (1,2) (1,3) (1,4) (4,2) (4,3) (4,4) (4,6) (4,6) (4,8) (4,8)
+  form       (1,1) (1,2) (1,3) (1,4) (4,2) (4,3) (4,4) (4,5) (4,6) (4,7) (4,8)     (WPR, NCH)
   cols  <=    512  1024  1536  2048  4096  6144  8192 10240 12288 14336 16384
 
   smallest / largest width of a form: 8 | 264 / 512, 520 / 1024, 1032 / 1536, 1544 / 2048, 2056 / 4096, 4104 / 6144, 6152 / 8192,
-  8200 / 10240, 10248 / 12288, 12296 / 14336, 14344 / 16384 (RMSNorm: 8200 / 12288 and 12296 / 16384 for its last two forms).
+  8200 / 10240, 10248 / 12288, 12296 / 14336, 14344 / 16384.
   At the smallest width of a form the last chunk slot of a lane is live on few lanes only (the ok[i] masking).
 
 had_k -> rotate_kernel<KIN, Q, EPL> (launch_rotate in csrc/rotate.hip), rows per wave = 64 / (128 / EPL * Q):
@@ -50,19 +50,20 @@ SENT8 = -77
 WANQ_OK, WANQ_E_ARG, WANQ_E_SHAPE = 0, 1, 2
 QMAGIC = np.float32(-12582912.0)
 
-LN_FORMS = [(64, 1, 1), (128, 1, 2), (192, 1, 3), (256, 1, 4), (512, 4, 2), (768, 4, 3), (1024, 4, 4), (1280, 4, 5), (1536, 4, 6),
-            (1792, 4, 7), (2048, 4, 8)]
-RMS_FORMS = [(64, 1, 1), (128, 1, 2), (192, 1, 3), (256, 1, 4), (512, 4, 2), (768, 4, 3), (1024, 4, 4), (1536, 4, 6), (2048, 4, 8)]
+FORMS = [(64, 1, 1), (128, 1, 2), (192, 1, 3), (256, 1, 4), (512, 4, 2), (768, 4, 3), (1024, 4, 4), (1280, 4, 5), (1536, 4, 6),
+         (1792, 4, 7), (2048, 4, 8)]
 LN_WIDTHS = [8, 264, 512, 520, 1024, 1032, 1536, 1544, 2048, 2056, 4096, 4104, 6144, 6152, 8192, 8200, 10240, 10248, 12288, 12296,
              14336, 14344, 16384, 5120, 8960, 13824]
-RMS_WIDTHS = [8, 512, 520, 1024, 1032, 1536, 1544, 2048, 2056, 4096, 4104, 6144, 6152, 8192, 8200, 12288, 12296, 16384]
-Q8_WIDTHS = [128, 512, 640, 1024, 1152, 1536, 1664, 2048, 2176, 4096, 4224, 6144, 6272, 8192, 8320, 12288, 12416, 16384]
+RMS_WIDTHS = [8, 512, 520, 1024, 1032, 1536, 1544, 2048, 2056, 4096, 4104, 6144, 6152, 8192, 8200, 10240, 10248, 12288, 12296, 14336, 14344,
+              16384]
+Q8_WIDTHS = [128, 512, 640, 1024, 1152, 1536, 1664, 2048, 2176, 4096, 4224, 6144, 6272, 8192, 8320, 10240, 10368, 12288, 12416, 14336, 14464,
+             16384]
 ROT_HADK = [1, 2, 4, 8, 16, 32, 12, 40]
 
 
-def form_of(cols, forms):
+def form_of(cols):
     """(WPR, NCH) of the instantiation that the dispatch picks for this width."""
-    for limit, wpr, nch in forms:
+    for limit, wpr, nch in FORMS:
         if cols // 8 <= limit:
             return wpr, nch
     raise ValueError(cols)
@@ -221,7 +222,7 @@ def ln_model(case, mutant=None):
     gamma, mshift, mscale = mod(case.gamma), mod(case.mshift), mod(case.mscale)
     xs = x
     if mutant == "drop_last_partial_chunk":  # the chunk slot NCH - 1 is left out of the mean where it is partial
-        wpr, nch = form_of(cols, LN_FORMS)
+        wpr, nch = form_of(cols)
         start = (nch - 1) * 64 * wpr * 8
         if start < cols < nch * 64 * wpr * 8:
             xs = x[:, :start]
@@ -822,7 +823,7 @@ class LnRandomCase:
 
     def _bound(self):
         x, n = self.x, self.cols
-        k = sum_depth(*form_of(n, LN_FORMS))
+        k = sum_depth(*form_of(n))
         mean = x.mean(axis=1)
         d = x - mean[:, None]
         rstd = 1.0 / np.sqrt((d * d).mean(axis=1) + float(np.float32(self.eps)))
@@ -916,7 +917,7 @@ class RmsRandomCase:
 
     def _bound(self):
         x, n = self.x, self.cols
-        k = sum_depth(*form_of(n, RMS_FORMS)) + 1  # + the square
+        k = sum_depth(*form_of(n)) + 1  # + the square
         rinv = 1.0 / np.sqrt((x * x).mean(axis=1) + float(np.float32(self.eps)))
         rho = (k + 2) * U / 2 + 2 * U  # sum, division, + eps under the square root; the square root; the reciprocal
         nrm = x * rinv[:, None] * self.weight
@@ -1065,14 +1066,14 @@ CPU_LN_WIDTHS = [8, 264, 512, 1032, 2056, 5120, 8200, 13824, 14344, 16384]
 
 
 def test_width_tables_reach_every_form():
-    """The smallest and the largest width of each (WPR, NCH) form of both dispatch tables, and all eight had_k."""
-    for forms, widths in ((LN_FORMS, LN_WIDTHS), (RMS_FORMS, RMS_WIDTHS), (RMS_FORMS, Q8_WIDTHS)):
+    """The smallest and the largest width of each (WPR, NCH) form of the dispatch ladder, for every width table, and all eight had_k."""
+    for widths in (LN_WIDTHS, RMS_WIDTHS, Q8_WIDTHS):
         lo = 0
-        for limit, wpr, nch in forms:
+        for limit, wpr, nch in FORMS:
             mine = [w for w in widths if lo < w // 8 <= limit]
             step = 128 if widths is Q8_WIDTHS else 8
             assert limit * 8 in mine and min(mine) <= (lo * 8 // step + 1) * step, (wpr, nch, mine)
-            assert all(form_of(w, forms) == (wpr, nch) for w in mine)
+            assert all(form_of(w) == (wpr, nch) for w in mine)
             lo = limit
     assert {5120, 8960, 13824} <= set(LN_WIDTHS) and 8 in LN_WIDTHS and 8 in RMS_WIDTHS
     assert sorted(k * 128 for k in ROT_HADK) == [128, 256, 512, 1024, 1536, 2048, 4096, 5120]

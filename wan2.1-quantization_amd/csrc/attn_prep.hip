@@ -5,7 +5,7 @@
 // rope table: fp32 [positions, head_dim/2, 2] = (cos, sin) per token position and complex pair; the host
 // builds it once per (F,H,W) grid in float64 (as the reference does its whole rotation) and rounds to fp32.
 // Rows at or beyond `positions` (sequence padding) are normalised but not rotated, as in the reference.
-#include "wanq_common.h"
+#include "row_frame.h"
 
 namespace wanq {
 
@@ -30,51 +30,27 @@ struct PrepParams {
   const int64_t* head_map;
 };
 
-__device__ __forceinline__ void prep_load8(const void* base, int dt, int64_t elem, float (&v)[8]) {
-  if (dt == WANQ_F16) Io<F16>::load8(base, elem, v);
-  else if (dt == WANQ_BF16) Io<BF16>::load8(base, elem, v);
-  else Io<F32>::load8(base, elem, v);
-}
-__device__ __forceinline__ void prep_store8(void* base, int dt, int64_t elem, const float (&v)[8]) {
-  if (dt == WANQ_F16) Io<F16>::store8(base, elem, v);
-  else if (dt == WANQ_BF16) Io<BF16>::store8(base, elem, v);
-  else Io<F32>::store8(base, elem, v);
-}
-
 // Q8: also emit the per-(token, head) int8 form (a template flag so that the plain kernel keeps its register count)
 template <int WPR, int NCH, bool Q8, bool SC = false>
 __global__ __launch_bounds__(256) void rmsnorm_rope_kernel(const PrepParams p) {
   __shared__ float slots[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t row = (WPR == 1) ? (int64_t)blockIdx.x * 4 + wave : (int64_t)blockIdx.x;
-  if (WPR == 1 && row >= p.rows) return;
-  const int sub = (WPR == 1) ? 0 : wave;
+  RowFrame<WPR, NCH> f;
+  if (f.surplus(p.rows)) return;
+  const int lane = f.lane;
+  const int64_t row = f.row;
   const int C = p.cols;
   const int64_t rbase = row * (int64_t)C;
   float v[NCH][8];
   bool ok[NCH];
+  f.load(p.x, p.x_dtype, rbase, C, v, ok);
   float ss = 0.f;
-  // one dtype branch per row (a branch per chunk serialises the row's loads: see rowwise.hip load_row)
-#define PREP_LOAD_ROW(T)                                                       \
-  _Pragma("unroll") for (int i = 0; i < NCH; ++i) {                            \
-    const int c0 = (sub * 64 + lane + i * 64 * WPR) * 8;                       \
-    ok[i] = c0 < C;                                                            \
-    if (ok[i]) Io<T>::load8(p.x, rbase + c0, v[i]);                            \
-  }
-  if (p.x_dtype == WANQ_F32) { PREP_LOAD_ROW(F32) } else if (p.x_dtype == WANQ_BF16) { PREP_LOAD_ROW(BF16) } else { PREP_LOAD_ROW(F16) }
-#undef PREP_LOAD_ROW
 #pragma unroll
   for (int i = 0; i < NCH; ++i)
     if (ok[i]) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) ss += v[i][j] * v[i][j];
     }
-  ss = wave_sum(ss);
-  if (WPR > 1) {
-    if (lane == 0) slots[wave] = ss;
-    __syncthreads();
-    ss = slots[0] + slots[1] + slots[2] + slots[3];
-  }
+  ss = RowReduce<WPR>{slots, f.wave}.template reduce<OpSum>(ss, 0);
   const float rinv = p.weight ? 1.0f / sqrtf(ss / (float)C + p.eps) : 1.0f;  // weight == NULL: rope only
   const int64_t pos = row % p.rows_per_batch;
   const bool rot = p.rope && pos < p.positions;
@@ -82,7 +58,7 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kernel(const PrepParams p) {
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
     if (!ok[i]) continue;
-    const int c0 = (sub * 64 + lane + i * 64 * WPR) * 8;
+    const int c0 = f.col(i);
     if (p.weight) {
       float w[8];
       Io<F32>::load8(p.weight, c0, w);
@@ -111,9 +87,9 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kernel(const PrepParams p) {
     }
     if (SC) {
       const int hd = c0 / p.head_dim;
-      prep_store8(p.out, p.out_dtype, p.head_map[2 * hd] + row * p.head_map[2 * hd + 1] + (c0 - hd * p.head_dim), v[i]);
+      store8_rt(p.out, p.out_dtype, p.head_map[2 * hd] + row * p.head_map[2 * hd + 1] + (c0 - hd * p.head_dim), v[i]);
     } else if (p.out) {
-      prep_store8(p.out, p.out_dtype, rbase + c0, v[i]);
+      store8_rt(p.out, p.out_dtype, rbase + c0, v[i]);
     }
     if (Q8) {  // head_dim == 128: a head is the 16 chunks of 16 consecutive lanes
       float m = 0.f;
@@ -121,8 +97,7 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kernel(const PrepParams p) {
       for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(v[i][j]));
       // lane ^ o inside the head's 16 lanes (DPP: wanq_common.h)
       m = fmaxf(m, lane_xor_dpp<1>(m)); m = fmaxf(m, lane_xor_dpp<2>(m)); m = fmaxf(m, lane_xor_dpp<4>(m)); m = fmaxf(m, lane_xor_dpp<8>(m));
-      float scale = m / 127.0f;
-      if (scale < 1e-6f) scale = 1e-6f;  // qdiff eps rule (base_quantizer.py:122-127)
+      const float scale = dyn_scale(m, 127.0f, 1e-6f);
       uint32_t pk[2];
       quantN_pack_rne<8>(v[i], scale, 1.0f / scale, pk);
       *reinterpret_cast<uint2*>(p.q8 + rbase + c0) = make_uint2(pk[0], pk[1]);
@@ -147,31 +122,20 @@ static int rmsnorm_rope_impl(const void* x, int x_dtype, const float* weight, co
                "wanq_rmsnorm_rope_q8: needs qscale, head_dim == 128, cols %% 128 == 0 and scale_stride >= rows");
   WANQ_REQUIRE(is_fp(x_dtype) && (!out || is_fp(out_dtype)), WANQ_E_ARG, "wanq_rmsnorm_rope: bad dtype code");
   WANQ_REQUIRE(weight || rope, WANQ_E_ARG, "wanq_rmsnorm_rope: nothing to do (weight and rope both NULL)");
-  WANQ_REQUIRE(cols >= 8 && cols % 8 == 0 && cols <= 16384, WANQ_E_SHAPE, "wanq_rmsnorm_rope: cols=%d must be a multiple of 8 in [8,16384]", cols);
+  if (int e = check_rows_cols("wanq_rmsnorm_rope", rows, cols)) return e;
   WANQ_REQUIRE(!rope || (head_dim >= 8 && head_dim % 8 == 0 && cols % head_dim == 0), WANQ_E_SHAPE,
                "wanq_rmsnorm_rope: head_dim=%d must be a multiple of 8 dividing cols=%d", head_dim, cols);
-  WANQ_REQUIRE(rows >= 0 && rows < (1ll << 31) && rows_per_batch >= 1, WANQ_E_SHAPE, "wanq_rmsnorm_rope: bad rows");
+  WANQ_REQUIRE(rows_per_batch >= 1, WANQ_E_SHAPE, "wanq_rmsnorm_rope: bad rows");
   if (rows == 0) return WANQ_OK;
   PrepParams p{x, out, weight, rope, x_dtype, out_dtype, rows, rows_per_batch, positions, cols, head_dim > 0 ? head_dim : 8, eps,
                q8, qscale, scale_stride, head_map};
   hipStream_t st = (hipStream_t)stream;
-  const int chunks = cols / 8;
-#define WANQ_PR(WPR, NCH)                                                                                                  \
-  do {                                                                                                                     \
-    if (q8) hipLaunchKernelGGL((rmsnorm_rope_kernel<WPR, NCH, true>), dim3((unsigned)((WPR) == 1 ? (rows + 3) / 4 : rows)), dim3(256), 0, st, p); \
-    else if (head_map) hipLaunchKernelGGL((rmsnorm_rope_kernel<WPR, NCH, false, true>), dim3((unsigned)((WPR) == 1 ? (rows + 3) / 4 : rows)), dim3(256), 0, st, p); \
-    else hipLaunchKernelGGL((rmsnorm_rope_kernel<WPR, NCH, false>), dim3((unsigned)((WPR) == 1 ? (rows + 3) / 4 : rows)), dim3(256), 0, st, p);   \
-  } while (0)
-  if (chunks <= 64) WANQ_PR(1, 1);
-  else if (chunks <= 128) WANQ_PR(1, 2);
-  else if (chunks <= 192) WANQ_PR(1, 3);
-  else if (chunks <= 256) WANQ_PR(1, 4);
-  else if (chunks <= 512) WANQ_PR(4, 2);
-  else if (chunks <= 768) WANQ_PR(4, 3);
-  else if (chunks <= 1024) WANQ_PR(4, 4);
-  else if (chunks <= 1536) WANQ_PR(4, 6);
-  else WANQ_PR(4, 8);
-#undef WANQ_PR
+  row_ladder(cols, rows, [&](auto wpr, auto nch, dim3 grid) {
+    constexpr int WPR = decltype(wpr)::value, NCH = decltype(nch)::value;
+    if (q8) hipLaunchKernelGGL((rmsnorm_rope_kernel<WPR, NCH, true>), grid, dim3(256), 0, st, p);
+    else if (head_map) hipLaunchKernelGGL((rmsnorm_rope_kernel<WPR, NCH, false, true>), grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL((rmsnorm_rope_kernel<WPR, NCH, false>), grid, dim3(256), 0, st, p);
+  });
   return check_launch("wanq_rmsnorm_rope");
 }
 

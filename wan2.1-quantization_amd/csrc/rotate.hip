@@ -17,7 +17,7 @@
 // This replaces the round-1 form that staged the row in an LDS buffer written by one lane and read back by other lanes of
 // the same wave: that hand-off was the one place to which a run-to-run deviation under two processes per GPU had been
 // traced; with the row in registers there is no such hand-off left.
-#include "wanq_common.h"
+#include "row_frame.h"
 
 namespace wanq {
 
@@ -482,8 +482,7 @@ __global__ __launch_bounds__(256, rot_waves_per_simd(KIN* EPL * ((MULTI && KIN *
 #pragma unroll
       for (int j = 0; j < EPL; ++j) m = fmaxf(m, fabsf(v[r][j]));
     const float amax = group_max<LPR>(m) * cdiv;  // == the maximum of the scaled values (rounding is monotone)
-    float scale = amax / 127.0f;
-    if (scale < 1e-6f) scale = 1e-6f;  // qdiff eps rule (base_quantizer.py:122-127)
+    const float scale = dyn_scale(amax, 127.0f, 1e-6f);
     const float cinv = cdiv * (1.0f / scale);
     int isum = 0;
 #pragma unroll
@@ -492,10 +491,10 @@ __global__ __launch_bounds__(256, rot_waves_per_simd(KIN* EPL * ((MULTI && KIN *
       quantN_pack_rne_pre<EPL>(v[r], cdiv, scale, cinv, pk);  // (dynamic scale: |v * cdiv / scale| <= 127.5)
       int8_t* dst = q8 + rbase + col0 + 128 * r;
       const uint32_t lo = pk[0];
-      isum = __builtin_amdgcn_sdot4((int)lo, 0x01010101, isum, false);  // sum of the four signed bytes
+      isum = byte_sum(lo, isum);
       if constexpr (EPL == 8) {
         const uint32_t hi = pk[EPL / 4 - 1];
-        isum = __builtin_amdgcn_sdot4((int)hi, 0x01010101, isum, false);
+        isum = byte_sum(hi, isum);
         if (live) *reinterpret_cast<uint2*>(dst) = make_uint2(lo, hi);
       } else {
         if (live) *reinterpret_cast<uint32_t*>(dst) = lo;
@@ -544,11 +543,6 @@ static int check_rotation(const char* what, int had_k, int cols) {
   const bool pow2 = (had_k & (had_k - 1)) == 0;
   WANQ_REQUIRE((pow2 && had_k <= 32) || had_k == 12 || had_k == 40, WANQ_E_SHAPE,
                "%s: cols=%d has no fused Hadamard transform here (supported: 2^p in [128, 4096], 1536, 5120; 8960 without LayerNorm)", what, cols);
-  return WANQ_OK;
-}
-
-static int check_rows(const char* what, int64_t rows) {
-  WANQ_REQUIRE(rows >= 0 && rows < (1ll << 31), WANQ_E_SHAPE, "%s: rows=%lld out of range", what, (long long)rows);
   return WANQ_OK;
 }
 

@@ -24,7 +24,7 @@
 //   140: a wave owns one 32-column half and 3 or 2 of the 5 row tiles of Y (140 -> 160), the 3 : 2 split alternating with the
 //        workgroup's parity so that the two waves a SIMD hosts add up to 5;
 //   108: wave w owns row tile w (of the 108 -> 128 rows of Y) for both 32-column sub-tiles of the half.
-#include "wanq_common.h"
+#include "row_frame.h"
 
 namespace wanq {
 
@@ -387,8 +387,7 @@ __device__ __forceinline__ void rotate_paley_body(const RotPaleyParams& p, char*
       else store_row<D, F32>(p.out_fp, rbase, bgrp, c8, v);
     }
     if (p.q) {
-      float scale = amax / 127.0f;
-      if (scale < 1e-6f) scale = 1e-6f;  // qdiff eps rule (base_quantizer.py:122-127)
+      const float scale = dyn_scale(amax, 127.0f, 1e-6f);
       const float inv = 1.0f / scale;
       int isum = 0;
 #pragma unroll
@@ -397,8 +396,7 @@ __device__ __forceinline__ void rotate_paley_body(const RotPaleyParams& p, char*
         if (b < K) {
           uint32_t pk[2];
           quantN_pack_rne<8>(v[ps], scale, inv, pk);
-          isum = __builtin_amdgcn_sdot4((int)pk[0], 0x01010101, isum, false);
-          isum = __builtin_amdgcn_sdot4((int)pk[1], 0x01010101, isum, false);
+          isum = byte_sum(pk[1], byte_sum(pk[0], isum));
           *reinterpret_cast<uint2*>(p.q + rbase + b * M + c8) = make_uint2(pk[0], pk[1]);
         }
       }

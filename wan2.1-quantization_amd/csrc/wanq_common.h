@@ -77,15 +77,15 @@ __device__ __forceinline__ uint2 pair32(int v) {
 
 // Wave reductions in the order 32, 16, 8, 4, 2, 1 (the operand pairs, and with them every rounding, are those of the
 // __shfl_xor butterflies these replace: bit-identical results)
-struct OpSum { template <typename T> static __device__ __forceinline__ T f(T a, T b) { return a + b; } };
-struct OpMax { static __device__ __forceinline__ float f(float a, float b) { return fmaxf(a, b); } };
-struct OpMin { static __device__ __forceinline__ float f(float a, float b) { return fminf(a, b); } };
-template <typename OP>
-__device__ __forceinline__ float wave_reduce(float v) {
-  uint2 r = pair32(__float_as_int(v));
-  v = OP::f(__uint_as_float(r.x), __uint_as_float(r.y));
-  r = pair16(__float_as_int(v));
-  v = OP::f(__uint_as_float(r.x), __uint_as_float(r.y));
+struct OpSum { static constexpr int id = 0; template <typename T> static __device__ __forceinline__ T f(T a, T b) { return a + b; } };
+struct OpMax { static constexpr float id = -__builtin_inff(); static __device__ __forceinline__ float f(float a, float b) { return fmaxf(a, b); } };
+struct OpMin { static constexpr float id = __builtin_inff(); static __device__ __forceinline__ float f(float a, float b) { return fminf(a, b); } };
+template <typename OP, typename T>
+__device__ __forceinline__ T wave_reduce(T v) {  // T: float, or int with OpSum
+  uint2 r = pair32(__builtin_bit_cast(int, v));
+  v = OP::f(__builtin_bit_cast(T, r.x), __builtin_bit_cast(T, r.y));
+  r = pair16(__builtin_bit_cast(int, v));
+  v = OP::f(__builtin_bit_cast(T, r.x), __builtin_bit_cast(T, r.y));
   v = OP::f(v, lane_xor_dpp<8>(v));
   v = OP::f(v, lane_xor_dpp<4>(v));
   v = OP::f(v, lane_xor_dpp<2>(v));
@@ -93,33 +93,19 @@ __device__ __forceinline__ float wave_reduce(float v) {
   return v;
 }
 __device__ __forceinline__ float wave_max(float v) { return wave_reduce<OpMax>(v); }
-__device__ __forceinline__ float wave_min(float v) { return wave_reduce<OpMin>(v); }
 __device__ __forceinline__ float wave_sum(float v) { return wave_reduce<OpSum>(v); }
-__device__ __forceinline__ int wave_sum(int v) {
-  uint2 r = pair32(v);
-  v = (int)r.x + (int)r.y;
-  r = pair16(v);
-  v = (int)r.x + (int)r.y;
-  v += lane_xor_dpp<8>(v);
-  v += lane_xor_dpp<4>(v);
-  v += lane_xor_dpp<2>(v);
-  v += lane_xor_dpp<1>(v);
-  return v;
-}
+__device__ __forceinline__ int wave_sum(int v) { return wave_reduce<OpSum>(v); }
 
 // ---------------------------------------------------------------- device: typed 8-element access
 struct F16 {};
 struct BF16 {};
 struct F32 {};
 
-__device__ __forceinline__ float bf16_bits_to_f32(uint32_t b) { return __uint_as_float(b << 16); }
-
 template <typename T>
 struct Io;
 
 template <>
 struct Io<F16> {
-  static constexpr int kBytes = 2;
   __device__ static __forceinline__ void load8(const void* base, int64_t elem, float (&v)[8]) {
     const uint4 r = *reinterpret_cast<const uint4*>(static_cast<const char*>(base) + elem * 2);
     const __half2* h = reinterpret_cast<const __half2*>(&r);
@@ -141,7 +127,6 @@ struct Io<F16> {
 
 template <>
 struct Io<BF16> {
-  static constexpr int kBytes = 2;
   __device__ static __forceinline__ void load8(const void* base, int64_t elem, float (&v)[8]) {
     const uint4 r = *reinterpret_cast<const uint4*>(static_cast<const char*>(base) + elem * 2);
     const uint32_t w[4] = {r.x, r.y, r.z, r.w};
@@ -166,7 +151,6 @@ struct Io<BF16> {
 
 template <>
 struct Io<F32> {
-  static constexpr int kBytes = 4;
   __device__ static __forceinline__ void load8(const void* base, int64_t elem, float (&v)[8]) {
     const float4* p = reinterpret_cast<const float4*>(static_cast<const char*>(base) + elem * 4);
     const float4 a = p[0], b = p[1];
@@ -189,15 +173,10 @@ __device__ __forceinline__ void vec_store(void* p, int dt, int64_t i, float v) {
   else static_cast<__half*>(p)[i] = __float2half_rn(v);
 }
 
-__device__ __forceinline__ float gelu_tanh_f32(float x) {
-  // 0.5 x (1 + tanh(0.79788456 (x + 0.044715 x^3)))   (reference fused.cu:22-26, in fp32)
-  const float inner = 0.79788456f * (x + 0.044715f * x * x * x);
-  return 0.5f * x * (1.0f + tanhf(inner));
-}
-
-// Same function through the identity 0.5 (1 + tanh u) = 1 / (1 + e^{-2u}): two transcendental instructions (v_exp_f32,
+// tanh-GELU 0.5 x (1 + tanh(0.79788456 (x + 0.044715 x^3)))   (reference fused.cu:22-26, in fp32)
+// through the identity 0.5 (1 + tanh u) = 1 / (1 + e^{-2u}): two transcendental instructions (v_exp_f32,
 // v_rcp_f32, 1 ulp each) and five plain ones instead of libm's branchy tanhf (~35).  Relative error < 3e-6 against the
-// form above, i.e. invisible after the fp16/bf16 rounding of a GEMM output; saturates correctly (e^{+inf} -> x/inf = -0,
+// literal form, i.e. invisible after the fp16/bf16 rounding of a GEMM output; saturates correctly (e^{+inf} -> x/inf = -0,
 // e^{-inf} -> x).  Used in the GEMM epilogue, where 293 M evaluations per FFN cost more than a tenth of the kernel.
 __device__ __forceinline__ float gelu_tanh_fast_f32(float x) {
   // -2 u log2(e) = x (c1 + c3 x^2),  c1 = -2*0.79788456*log2(e),  c3 = c1*0.044715
@@ -236,39 +215,8 @@ __device__ __forceinline__ void quant8_div_rne(const float (&x)[8], float s, flo
 //       the flagged chunk (about 1e-4 of the elements) takes the true division, as above.
 // Bit-identical codes to quant8_div_rne on that domain (tests/test_gpu_rowwise.py: ties, near-ties, eps rows, golden vectors).
 constexpr float WANQ_QMAGIC = 12582912.0f;
-template <int N>
-__device__ __forceinline__ void quantN_pack_rne(const float (&x)[N], float s, float inv, uint32_t (&packed)[N / 4]) {
-  static_assert(N % 4 == 0, "four codes per dword");
-  float u[N];
-  bool near = false;
-  // on element PAIRS (v_pk_fma_f32 / v_pk_add_f32: the same IEEE operations per half, bit-identical codes, 2.5 instead of 4
-  // vector instructions per element in front of the byte packing)
-  typedef float v2f __attribute__((ext_vector_type(2)));
-  const v2f inv2 = {inv, inv}, magic2 = {WANQ_QMAGIC, WANQ_QMAGIC};
-#pragma unroll
-  for (int j = 0; j < N; j += 2) {
-    const v2f x2 = {x[j], x[j + 1]};
-    const v2f u2 = __builtin_elementwise_fma(x2, inv2, magic2);
-    const v2f d2 = __builtin_elementwise_fma(x2, inv2, -(u2 - magic2));
-    u[j] = u2.x;
-    u[j + 1] = u2.y;
-    near |= fabsf(d2.x) >= 0.4999488f;
-    near |= fabsf(d2.y) >= 0.4999488f;
-  }
-  if (near) {
-#pragma unroll
-    for (int j = 0; j < N; ++j) u[j] = rintf(x[j] / s) + WANQ_QMAGIC;
-  }
-#pragma unroll
-  for (int g = 0; g < N / 4; ++g) {
-    const uint32_t b0 = __float_as_uint(u[4 * g]), b1 = __float_as_uint(u[4 * g + 1]), b2 = __float_as_uint(u[4 * g + 2]), b3 = __float_as_uint(u[4 * g + 3]);
-    // bytes (b0.0, b1.0, 0, 0) | (0, 0, b2.0, b3.0)
-    packed[g] = __builtin_amdgcn_perm(b1, b0, 0x0c0c0400u) | __builtin_amdgcn_perm(b3, b2, 0x04000c0cu);
-  }
-}
-
-// quantN_pack_rne for x = fl(y * c) WITHOUT forming x: the codes of rne(fl(y * c) / s), c > 0 a per-launch constant (the
-// 1 / sqrt(n) of the Hadamard transform), from u = fma(y, fl(c * inv), M).  The exact y * fl(c * inv) lies within
+// The general form quantises x = fl(y * c) WITHOUT forming x: the codes of rne(fl(y * c) / s), c > 0 a per-launch constant (the
+// 1 / sqrt(n) of the Hadamard transform), from u = fma(y, cinv, M) with cinv = fl(c * inv).  The exact y * fl(c * inv) lies within
 // 127 * 3 * 2^-24 + 2^-18 = 2.7e-5 of fl(fl(y * c) / s), inside the same threshold; the flagged chunk evaluates the
 // reference's two operations literally.  (The row maximum commutes with the scaling: fl(max|y| * c) == max fl(|y| * c).)
 template <int N>
@@ -276,7 +224,9 @@ __device__ __forceinline__ void quantN_pack_rne_pre(const float (&y)[N], float c
   static_assert(N % 4 == 0, "four codes per dword");
   float u[N];
   bool near = false;
-  typedef float v2f __attribute__((ext_vector_type(2)));  // on element pairs, as in quantN_pack_rne
+  // on element PAIRS (v_pk_fma_f32 / v_pk_add_f32: the same IEEE operations per half, bit-identical codes, 2.5 instead of 4
+  // vector instructions per element in front of the byte packing)
+  typedef float v2f __attribute__((ext_vector_type(2)));
   const v2f cinv2 = {cinv, cinv}, magic2 = {WANQ_QMAGIC, WANQ_QMAGIC};
 #pragma unroll
   for (int j = 0; j < N; j += 2) {
@@ -295,8 +245,14 @@ __device__ __forceinline__ void quantN_pack_rne_pre(const float (&y)[N], float c
 #pragma unroll
   for (int g = 0; g < N / 4; ++g) {
     const uint32_t b0 = __float_as_uint(u[4 * g]), b1 = __float_as_uint(u[4 * g + 1]), b2 = __float_as_uint(u[4 * g + 2]), b3 = __float_as_uint(u[4 * g + 3]);
+    // bytes (b0.0, b1.0, 0, 0) | (0, 0, b2.0, b3.0)
     packed[g] = __builtin_amdgcn_perm(b1, b0, 0x0c0c0400u) | __builtin_amdgcn_perm(b3, b2, 0x04000c0cu);
   }
+}
+// The plain form is c == 1 at compile time: y * 1.0f is exact (and folded), so the flagged chunk is x / s as stated above.
+template <int N>
+__device__ __forceinline__ void quantN_pack_rne(const float (&x)[N], float s, float inv, uint32_t (&packed)[N / 4]) {
+  quantN_pack_rne_pre<N>(x, 1.0f, s, inv, packed);
 }
 
 // 4 ints in [-128,127] -> packed bytes: two saturating i32->i16 packs + one byte permute
@@ -304,13 +260,6 @@ __device__ __forceinline__ uint32_t pack4_i8_fast(int a, int b, int c, int d) {
   typedef short s16x2 __attribute__((ext_vector_type(2)));
   const s16x2 lo = __builtin_amdgcn_cvt_pk_i16(a, b), hi = __builtin_amdgcn_cvt_pk_i16(c, d);
   return __builtin_amdgcn_perm(__builtin_bit_cast(uint32_t, hi), __builtin_bit_cast(uint32_t, lo), 0x06040200u);
-}
-
-__device__ __forceinline__ int quant_div_rne(float x, float s, float inv) {
-  float t = x * inv;
-  float r = rintf(t);
-  if (fabsf(t - r) >= fmaf(-4e-7f, fabsf(t), 0.5f)) r = rintf(x / s);
-  return (int)__builtin_amdgcn_fmed3f(r, -128.f, 127.f);
 }
 
 __device__ __forceinline__ uint32_t pack4_i8(int a, int b, int c, int d) {

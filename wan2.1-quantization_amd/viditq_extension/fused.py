@@ -1,5 +1,5 @@
 """`viditq_extension.fused` -- same functions as the reference pybind module
-(ViDiT-Q/kernels/csrc/fused/pybind.cpp:5-99), executed by libwanq_hip (csrc/rowwise.hip).
+(ViDiT-Q/kernels/csrc/fused/pybind.cpp:5-99), executed by libwanq_hip (csrc/rowwise.hip; the once-per-model and calibration ops: csrc/quant_tools.hip).
 
 Differences from the reference, all widenings:
   * input / output may be fp16, bf16 or fp32 (reference: fp16 only); per-token vectors fp16 or fp32;
