@@ -154,6 +154,22 @@ int wanq_gemm_wq16(const void* a, const void* w, int dtype, int w_bits, const fl
                    int out_dtype, const void* bias, int bias_dtype, const float* gate, const void* residual, int epi_flags,
                    int64_t M, int N, int K, void* stream);
 
+/* Group-wise form of wanq_gemm_wq16 (the weight scales of AWQ / GPTQ-style W4A16): one scale and one zero point per output channel
+ * and per group of `group_size` input channels, sw and zp fp32 [K / group_size][N] (group-major; zp may be NULL = 0):
+ *   part_g = sum_{k in group g} a[m,k] * (c[n,k] + zp[g,n])     (fp32, on the matrix cores, wanq_gemm_wq16's order within a group)
+ *   acc    = fma(part_g, sw[g,n], acc)                          (g ascending from acc = 0: one fp32 fma per group)
+ *   y      = acc + bias[n];  GELU, gate + residual and the one rounding to out_dtype as above.
+ * a, w (int8 [N, K] or packed nibbles [N, K/2], zp = zero_point - 8), out, bias, gate, residual and epi_flags as for wanq_gemm_wq16.
+ * The weight operand c + zp reaches the matrix cores unrounded and the scale is applied in fp32 only; no dequantised weight is
+ * written.  zp must be integer valued.  With group_size == K and bias NULL the output is bit-equal to wanq_gemm_wq16's.
+ * group_size % 64 == 0, K % group_size == 0, N % 8 == 0, sw and zp 16-byte aligned; every other rule as for wanq_gemm_wq16.
+ * Anything else is refused (WANQ_E_SHAPE / WANQ_E_ARG, the message names the rule).  A row gives the same bits in any launch.
+ * Group-wise weight quantisation is the reference's StaticQuantizer applied to w.view(N K / g, g): its quantisers are written for
+ * [N_group, -1] input (ViDiT-Q/quant_utils/qdiff/base/base_quantizer.py:72). */
+int wanq_gemm_wq16_grouped(const void* a, const void* w, int dtype, int w_bits, const float* sw, const float* zp, int group_size,
+                           void* out, int out_dtype, const void* bias, int bias_dtype, const float* gate, const void* residual,
+                           int epi_flags, int64_t M, int N, int K, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * PTQ calibration reduction: running per-channel absmax over tokens,
  *   colmax[c] = max(colmax[c], max_r |x[r,c]|)        (colmax fp32[cols], caller zero-initialises)

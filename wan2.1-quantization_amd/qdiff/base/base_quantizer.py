@@ -47,20 +47,38 @@ def static_params(x, n_bits, sym):
 
 
 class StaticQuantizer(BaseQuantizer):
-    """Per-row (output channel) static quantizer for weights."""
+    """Per-row (output channel) static quantizer for weights.
+    `group_size` g (the `weight.group_size` key): one (delta, zero_point) per row and per group of g input channels -- this same
+    quantiser on w.view(N K / g, g), the [N_group, -1] input the reference's quantisers are written for (base_quantizer.py:72).
+    `delta` / `zero_point` are then [N, K / g]; codes and the dequantised weight keep w's shape."""
+
+    def __init__(self, quant_config):
+        super().__init__(quant_config)
+        self.group_size = quant_config.get("group_size", None)
+
+    def _group_rows(self, x):
+        """x [N, K] as the quantiser's rows: itself, or [N K / g, g]"""
+        x = x.contiguous()
+        g = getattr(self, "group_size", None)
+        if g is None:
+            return x
+        if x.dim() != 2 or x.shape[1] % g:
+            raise ValueError(f"{self.module_name or 'StaticQuantizer'}: weight.group_size={g} does not divide the row length of {tuple(x.shape)}")
+        return x.view(-1, g)
 
     def init_quant_params(self, x):
-        delta, zp = static_params(x, self.n_bits, self.sym)
+        delta, zp = static_params(self._group_rows(x), self.n_bits, self.sym)
         if not torch.all(delta > 1e-6):
             raise AssertionError("unexpected small delta exists")  # the reference drops into ipdb here (:94-97)
-        self.delta, self.zero_point = delta.unsqueeze(-1), zp.unsqueeze(-1)
+        self.delta, self.zero_point = delta.view(x.shape[0], -1), zp.view(x.shape[0], -1)  # [N, 1], or [N, K / g]
 
     def codes_and_dequant(self, x, want_codes=True, want_dequant=True):
         if self.init_done is not True:
             self.init_quant_params(x)
         n = self.n_levels
-        codes, deq = fused.weight_quant(x.contiguous(), self.delta.reshape(-1).float().contiguous(),
+        codes, deq = fused.weight_quant(self._group_rows(x), self.delta.reshape(-1).float().contiguous(),
                                         self.zero_point.reshape(-1).float().contiguous(), -n - 1, n, want_codes, want_dequant)
+        codes, deq = (None if t is None else t.view(x.shape) for t in (codes, deq))
         if codes is not None and self.n_bits < 8:
             # The reference's clamp is one level looser than the bit-width (SURVEY D9): a row whose extremes tie exactly at a
             # .5 boundary (lo = -hi, e.g. lattice-valued rotated weights) produces a 17th level.  Integer STORAGE has 2^b

@@ -25,9 +25,10 @@ class QuantizedLinear(nn.Linear):
     uses_mask = False
     uses_rotation = False
 
-    def __init__(self, in_features, out_features, bias, device, quant_config, fp_module):
+    def __init__(self, in_features, out_features, bias, device, quant_config, fp_module, module_name=None):
         super().__init__(in_features, out_features, bias, device)
         self.fp_module, self.q_cfg = fp_module, quant_config
+        self.group_size = self._checked_group_size(quant_config, module_name)
         self.w_quantizer = self.a_quantizer = None
         self.channel_mask = None
         self.rotation_signs = None
@@ -48,7 +49,29 @@ class QuantizedLinear(nn.Linear):
             self.a_quantizer = (MixedPrecisionDynamicQuantizer if isinstance(aq["n_bits"], ListConfig) else DynamicQuantizer)(aq)
         self.use_kernel = False
         self.quant_mode = True
-        self.module_name = None
+        self.module_name = module_name
+
+    def _checked_group_size(self, quant_config, module_name):
+        """`weight.group_size` of the config (None: one scale per output channel), or the refusal of what has no group-wise form,
+        before any weight is quantised: the message names the layer and the key."""
+        wq = quant_config.get("weight", None)
+        g = None if wq is None else wq.get("group_size", None)
+        if g is None:
+            return None
+        name = module_name or type(self).__name__
+        if isinstance(g, bool) or not isinstance(g, int) or g <= 0:
+            raise ValueError(f"{name}: weight.group_size={g!r} must be a positive integer")
+        if isinstance(wq["n_bits"], ListConfig):
+            raise NotImplementedError(f"{name}: weight.group_size with a bit-width list (MixedPrecisionStaticQuantizer) is not supported")
+        if quant_config.get("act", None) is not None:
+            raise NotImplementedError(f"{name}: weight.group_size together with an `act:` section is not supported: the int8 GEMMs "
+                                      "apply one weight scale per output channel (group-wise scales exist for weight-only configs)")
+        if self.uses_mask or self.uses_rotation:
+            raise NotImplementedError(f"{name}: weight.group_size with {type(self).__name__} is not supported: the SmoothQuant / "
+                                      "QuaRot / ViDiT layer classes quantise one scale per output channel")
+        if self.in_features % g:
+            raise ValueError(f"{name}: weight.group_size={g} does not divide in_features={self.in_features}")
+        return g
 
     # ---- weight side --------------------------------------------------------------------------------
     def _requantize(self, w):
@@ -143,13 +166,18 @@ class QuantizedLinear(nn.Linear):
 
     def weight_only_operands(self):
         """(codes, scale fp32 [N], zp fp32 [N] or None, w4) of wanq_gemm_wq16 for this layer's quantised weight: int8 codes, or the
-        packed nibbles u = code + 8 with the 8 folded into the zero point (the W4A8 convention).  The two vectors are made once
-        and kept until the codes are set again (`int_weight`)."""
+        packed nibbles u = code + 8 with the 8 folded into the zero point (the W4A8 convention).  With a `group_size` scale and zp
+        are the [K / g, N] operands of wanq_gemm_wq16_grouped (the quantiser's [N, K / g], transposed).  The two tensors are made
+        once and kept until the codes are set again (`int_weight`)."""
         if self._wq16_vecs is None or self._wq16_vecs[0].device != self._codes.device:
             wq, N = self.w_quantizer, self.out_features
             w4 = self._codes.dtype == torch.uint8
-            sw = wq.delta.reshape(-1).float().expand(N).contiguous()
-            zp = None if wq.sym else wq.zero_point.reshape(-1).float().expand(N).contiguous()
+            if self.group_size is not None:
+                sw = wq.delta.float().reshape(N, -1).t().contiguous()
+                zp = None if wq.sym else wq.zero_point.float().reshape(N, -1).t().contiguous()
+            else:
+                sw = wq.delta.reshape(-1).float().expand(N).contiguous()
+                zp = None if wq.sym else wq.zero_point.reshape(-1).float().expand(N).contiguous()
             if w4:
                 zp = ((zp if zp is not None else torch.zeros_like(sw)) - 8.0).contiguous()
             self._wq16_vecs = (sw, zp, w4)
@@ -159,13 +187,18 @@ class QuantizedLinear(nn.Linear):
     def _forward_weight_only(self, x):
         """A `weight:` section without an `act:` section: y = x @ W_hat^T + bias on the unquantised activations
         (ViDiT-Q/quant_utils/qdiff/base/quant_layer.py:68-72 with a_quantizer None).  16-bit activations on the GPU go through
-        wanq_gemm_wq16 on the integer codes (exact weight operand, scale in the fp32 epilogue); anything else through the
-        reference's own expression, F.linear on the dequantised weight."""
+        wanq_gemm_wq16 -- with a `group_size` wanq_gemm_wq16_grouped -- on the integer codes (exact weight operand, scale in fp32);
+        anything else, a group size the kernel does not take (not a multiple of 64) included, through the reference's own
+        expression, F.linear on the dequantised weight."""
         if x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and self._codes is not None and self._codes.is_cuda:
             x2 = x.reshape(-1, x.shape[-1])
-            if qgemm.wq16_linear_refusal(x2.shape[0], self.out_features, self.in_features) is None:
+            if qgemm.wq16_linear_refusal(x2.shape[0], self.out_features, self.in_features, self.group_size) is None:
                 codes, sw, zp, w4 = self.weight_only_operands()
-                y = qgemm.wq16_linear(x2.contiguous(), codes, sw, zp, None if self.bias is None else self.bias.detach(), w4=w4)
+                bias = None if self.bias is None else self.bias.detach()
+                if self.group_size is not None:
+                    y = qgemm.wq16_grouped_linear(x2.contiguous(), codes, sw, zp, self.group_size, bias, w4=w4)
+                else:
+                    y = qgemm.wq16_linear(x2.contiguous(), codes, sw, zp, bias, w4=w4)
                 return y.view(*x.shape[:-1], self.out_features)
         w = self.weight if self.weight.dtype == x.dtype else self.weight.to(x.dtype)
         b = self.bias if self.bias is None or self.bias.dtype == x.dtype else self.bias.to(x.dtype)

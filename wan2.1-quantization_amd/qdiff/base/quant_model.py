@@ -35,7 +35,7 @@ def quant_layer_refactor_(submodule, name, parent_module, quant_config, full_nam
         logger.info("remain %s as FP due to fp_regex", full_name)
         return
     q = layer_type(submodule.in_features, submodule.out_features, submodule.bias is not None, submodule.weight.device,
-                   quant_config, submodule)
+                   quant_config, submodule, module_name=full_name)
     q.module_name = full_name
     for qz in (q.w_quantizer, q.a_quantizer):
         if qz is not None:

@@ -6,8 +6,8 @@ class SQQuantizedLinear(QuantizedLinear):
     """SmoothQuant: channel mask only (smooth_quant/sq_quant_layer.py:6-68)."""
     uses_mask = True
 
-    def __init__(self, in_features, out_features, bias, device, quant_config, fp_module):
-        super().__init__(in_features, out_features, bias, device, quant_config, fp_module)
+    def __init__(self, in_features, out_features, bias, device, quant_config, fp_module, module_name=None):
+        super().__init__(in_features, out_features, bias, device, quant_config, fp_module, module_name)
         self.alpha = quant_config.smooth_quant.alpha
 
     def update_quantized_weight_scaled(self):

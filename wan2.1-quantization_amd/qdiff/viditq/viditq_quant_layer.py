@@ -6,8 +6,8 @@ class ViDiTQuantizedLinear(QuantizedLinear):
     uses_mask = True
     uses_rotation = True
 
-    def __init__(self, in_features, out_features, bias, device, quant_config, fp_module):
-        super().__init__(in_features, out_features, bias, device, quant_config, fp_module)
+    def __init__(self, in_features, out_features, bias, device, quant_config, fp_module, module_name=None):
+        super().__init__(in_features, out_features, bias, device, quant_config, fp_module, module_name)
         self.alpha = quant_config.viditq.alpha
 
     def update_quantized_weight_rotated_and_scaled(self):

@@ -304,10 +304,45 @@ def wq16_linear(input, codes, scale_weight, zp=None, bias=None, out_dtype=None, 
     return out
 
 
-def wq16_linear_refusal(M, N, K):
-    """Why wanq_gemm_wq16 would refuse an [M, K] x [N, K] product (None = accepted); see `fp_linear_refusal`."""
+def wq16_grouped_linear(input, codes, scale_weight, zp=None, group_size=None, bias=None, out_dtype=None, gelu=False, gate=None,
+                        residual=None, out=None, w4=False):
+    """`wq16_linear` with one scale and one zero point per output channel and per group of `group_size` input channels
+    (wanq_gemm_wq16_grouped): scale_weight and zp fp32 [K / group_size, N] (group-major).  Each group's partial sum is accumulated on
+    the matrix cores from the exact operand c + zp[g, n] and folded into the result by one fp32 fma with scale_weight[g, n], groups
+    ascending; then + bias and the epilogue of `fp_linear`.  group_size % 64 == 0 and K % group_size == 0."""
+    M, N, K = _check_operands16(input, "codes", codes, torch.uint8 if w4 else torch.int8)
+    _C.check_shape("codes", codes, N, K // 2 if w4 else K)
+    why = wq16_linear_refusal(M, N, K, group_size)
+    if why is not None:
+        raise RuntimeError(f"wq16_grouped_linear: {why}")
+    for name, t in (("scale_weight", scale_weight), ("zp", zp)):
+        if t is not None:
+            _C.check_gpu(name, t)
+            _C.check_contig(name, t)
+            _C.check_dtype(name, t, torch.float32)
+            _C.check_shape(name, t, K // group_size, N)
+    out_dtype = out_dtype or input.dtype
+    _check_vec("bias", bias, N, _BIAS16)
+    epi = _epi_flags(gelu, gate, residual, M, N, out_dtype)
+    out = _out_for(out, M, N, out_dtype, input.device)
+    _C.check_same_device(input, codes, scale_weight, zp, bias, gate, residual, out)
+    with torch.cuda.device(input.device):
+        _C.call("wanq_gemm_wq16_grouped", _C.ptr(input), _C.ptr(codes), _C.dt(input), 4 if w4 else 8, _C.ptr(scale_weight),
+                _C.ptr(zp), int(group_size), _C.ptr(out), _C.dt(out_dtype), _C.ptr(bias),
+                _C.dt(bias) if bias is not None else _C.F32, _C.ptr(gate), _C.ptr(residual), epi, M, N, K, _C.stream())
+    return out
+
+
+def wq16_linear_refusal(M, N, K, group_size=None):
+    """Why wanq_gemm_wq16 -- with a `group_size`, wanq_gemm_wq16_grouped -- would refuse an [M, K] x [N, K] product (None =
+    accepted); see `fp_linear_refusal`."""
     if N < 8 or N % 8:
         return f"N={N} must be a positive multiple of 8"
     if K < 64 or K % 64:
         return f"K={K} must be a positive multiple of 64"
+    if group_size is not None:
+        if not isinstance(group_size, int) or group_size < 64 or group_size % 64:
+            return f"group_size={group_size} must be a positive multiple of 64"
+        if K % group_size:
+            return f"K={K} must be a multiple of group_size={group_size}"
     return None

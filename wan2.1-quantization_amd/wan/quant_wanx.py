@@ -74,6 +74,9 @@ class QuantWanModel(WanModel, QuantModel):
                 wq = mod.w_quantizer
                 premul, _ = mod._act_transform()
                 if reference_format:
+                    if getattr(mod, "group_size", None) is not None:
+                        raise NotImplementedError(f"{name}: the reference's int_weight.pt format has one scale per output channel "
+                                                  "(weight.group_size is set; save with reference_format=False)")
                     if wq.n_bits != 8:
                         raise NotImplementedError(f"{name}: the reference's int_weight.pt format is W8 only (n_bits={wq.n_bits})")
                     s16 = wq.delta.reshape(-1).to(f16).contiguous()
@@ -86,10 +89,13 @@ class QuantWanModel(WanModel, QuantModel):
                         sd[name + ".bias"] = mod.bias.detach().to(f16).clone()
                 else:
                     # 8-bit: int8 [N, K]; 4-bit: uint8 [N, K/2], the packed nibbles exactly as the GEMM reads them
+                    # (weight.group_size: the parameters as the group-wise GEMM reads them, [K / g, N])
+                    grouped = getattr(mod, "group_size", None) is not None
                     sd[name + ".weight"] = mod._codes.clone()
-                    sd[name + ".scale_weight"] = wq.delta.reshape(-1).float().clone()
+                    sd[name + ".scale_weight"] = (wq.delta.float().t().contiguous() if grouped else wq.delta.reshape(-1).float().clone())
                     if not wq.sym:
-                        sd[name + ".zp_weight"] = wq.zero_point.reshape(-1).float().clone()
+                        sd[name + ".zp_weight"] = (wq.zero_point.float().t().contiguous() if grouped
+                                                   else wq.zero_point.reshape(-1).float().clone())
                     if mod.bias is not None:
                         sd[name + ".bias"] = mod.bias.detach().float().clone()
                 if premul is not None:

@@ -34,15 +34,17 @@ def _gelu_gate_residual(y, gelu, gate, residual):
 class _HipLinearInt(nn.Module):
     """The buffers HipLinearW8A8 and HipLinearWq16 both hold (described there), and the zero point their GEMMs take."""
 
-    def __init__(self, in_features, out_features, bias, sym, w_bits):
+    def __init__(self, in_features, out_features, bias, sym, w_bits, group_size=None):
+        """group_size (HipLinearWq16 only): scale_weight / zp_weight / zp_gemm are [K / group_size, N] instead of [N]."""
         super().__init__()
         assert w_bits in (4, 8), "integer storage exists for 8-bit and packed 4-bit weights"
-        self.in_features, self.out_features, self.w_bits = in_features, out_features, w_bits
+        self.in_features, self.out_features, self.w_bits, self.group_size = in_features, out_features, w_bits, group_size
+        vec = (out_features,) if group_size is None else (in_features // group_size, out_features)
         self.register_buffer("weight", torch.empty(out_features, in_features // 2 if w_bits == 4 else in_features,
                                                    dtype=torch.uint8 if w_bits == 4 else torch.int8))
-        self.register_buffer("scale_weight", torch.empty(out_features, dtype=torch.float32))
-        self.register_buffer("zp_weight", None if sym else torch.empty(out_features, dtype=torch.float32))
-        self.register_buffer("zp_gemm", torch.empty(out_features, dtype=torch.float32) if w_bits == 4 else None)
+        self.register_buffer("scale_weight", torch.empty(vec, dtype=torch.float32))
+        self.register_buffer("zp_weight", None if sym else torch.empty(vec, dtype=torch.float32))
+        self.register_buffer("zp_gemm", torch.empty(vec, dtype=torch.float32) if w_bits == 4 else None)
         self.register_buffer("bias", torch.empty(out_features, dtype=torch.float32) if bias else None)
 
     def refresh_zp_gemm(self):
@@ -186,15 +188,20 @@ class HipLinearWq16(_HipLinearInt):
     per-channel fp32 (delta, zero_point) and fp32 bias -- 4-bit codes stay packed, `zp_gemm` = zero_point - 8 -- against the
     block's 16-bit activations, through qgemm.wq16_linear (csrc/gemm_wq16.hip): the codes become MFMA fragments in registers,
     exactly, and delta is applied in the fp32 epilogue.  No activation transform and no activation quantiser.
+    With a `group_size` (the config's `weight.group_size`, a multiple of 64 that divides in_features) the three parameter buffers are
+    [K / group_size, N] and the product is qgemm.wq16_grouped_linear: one fp32 fma per group and element instead of one in all.
     Counterpart of QuantizedLinear.forward with a_quantizer None (ViDiT-Q/quant_utils/qdiff/base/quant_layer.py:68-72)."""
     quantized = False   # its input is not quantised: the block's int8 producers and their prefetch skip it
     weight_only = True
     act_key = "fp"
     act_premul = None
 
-    def __init__(self, in_features, out_features, bias=True, sym=False, w_bits=8, name="linear"):
-        super().__init__(in_features, out_features, bias, sym, w_bits)
-        why = qgemm.wq16_linear_refusal(1, out_features, in_features)
+    def __init__(self, in_features, out_features, bias=True, sym=False, w_bits=8, name="linear", group_size=None):
+        if group_size is not None and (group_size < 64 or group_size % 64):
+            raise NotImplementedError(f"{name}: weight.group_size={group_size} has no kernel-mode form: the group-wise weight-only GEMM "
+                                      "takes groups that are multiples of 64 input channels (simulation mode runs any group size)")
+        why = qgemm.wq16_linear_refusal(1, out_features, in_features, group_size)
+        super().__init__(in_features, out_features, bias, sym, w_bits, None if why is not None else group_size)
         if why is not None:
             raise ValueError(f"{name}: the weight-only GEMM cannot take this layer ({out_features}, {in_features}): {why}")
 
@@ -209,14 +216,16 @@ class HipLinearWq16(_HipLinearInt):
         wq = ql.w_quantizer
         if wq.n_bits not in (4, 8):
             raise NotImplementedError(f"{name}: weight-only kernel mode stores 8-bit and packed 4-bit codes (n_bits={wq.n_bits})")
-        m = cls(ql.in_features, ql.out_features, ql.bias is not None, wq.sym, wq.n_bits, name).to(ql.fp_module.weight.device)
+        m = cls(ql.in_features, ql.out_features, ql.bias is not None, wq.sym, wq.n_bits, name,
+                getattr(ql, "group_size", None)).to(ql.fp_module.weight.device)
         codes, sw, _, _ = ql.weight_only_operands()
         if tuple(codes.shape) != tuple(m.weight.shape) or codes.dtype != m.weight.dtype:
             raise ValueError(f"{name}: codes {tuple(codes.shape)} {codes.dtype} do not fit {tuple(m.weight.shape)} {m.weight.dtype}")
         m.weight.copy_(codes)
         m.scale_weight.copy_(sw)
         if m.zp_weight is not None:
-            m.zp_weight.copy_(wq.zero_point.reshape(-1).float().expand(ql.out_features))
+            m.zp_weight.copy_(wq.zero_point.float().reshape(ql.out_features, -1).t() if m.group_size is not None
+                              else wq.zero_point.reshape(-1).float().expand(ql.out_features))
         m.refresh_zp_gemm()
         if ql.bias is not None:
             m.bias.copy_(ql.bias.detach().float())
@@ -224,6 +233,9 @@ class HipLinearWq16(_HipLinearInt):
 
     def forward(self, x, out_dtype=None, gelu=False, gate=None, residual=None, out=None):
         """Reads `weight` as it is now (--dit_fsdp re-points it at views of the gathered buffer)."""
+        if self.group_size is not None:
+            return qgemm.wq16_grouped_linear(x, self.weight, self.scale_weight, self.zp, self.group_size, self.bias, out_dtype,
+                                             gelu=gelu, gate=gate, residual=residual, out=out, w4=self.w_bits == 4)
         return qgemm.wq16_linear(x, self.weight, self.scale_weight, self.zp, self.bias, out_dtype, gelu=gelu, gate=gate,
                                  residual=residual, out=out, w4=self.w_bits == 4)
 
