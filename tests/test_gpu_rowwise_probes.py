@@ -28,6 +28,7 @@ had_k -> rotate_kernel<KIN, Q, EPL> (launch_rotate in csrc/rotate.hip), rows per
   cols    128      256      512      1024     2048     4096     1536      5120
   form    (1,1,8)  (2,1,8)  (4,1,8)  (2,4,8)  (8,2,8)  (8,4,8)  (12,1,4)  (20,2,4)
   rows/w  4        4        4        1        2        1        2         1
+  had_k 140 (cols 8960) and 108 (cols 13824): rotate140_kernel / rotate108_kernel of csrc/rotate_paley.hip -> tests/test_gpu_paley_probes.py
 """
 import collections
 import math
