@@ -3,7 +3,9 @@
 Bound against the float64 definition (stated): |y - y64| <= 2^-14 * (|a| |w|^T)[m,n] elementwise for an fp32 output -- far above fp32
 accumulation error over K <= 13824, far below one dropped 32-deep K slice.  Through GELU the bound grows by GELU's Lipschitz constant
 (1.13) plus the epilogue's fast-GELU relative error (3e-6); through gate + residual it is scaled by |gate|.  A 16-bit output may
-differ by one more unit in the last place of its type."""
+differ by one more unit in the last place of its type.  These are bounds on random data at full-size shapes; what the kernel and its
+epilogue compute exactly (the rounding mode, the k -> fragment-slot map, stores outside the output) is pinned in
+tests/test_gpu_gemm16_probes.py."""
 import math
 import os
 import subprocess
