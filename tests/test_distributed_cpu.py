@@ -167,6 +167,43 @@ def test_head_chunks_and_split_kv_policy():
     assert ops.attention_splits(32760, 512, 12, cpu, ncu=256) == 1
 
 
+def test_block_attention_dispatch_table(monkeypatch):
+    """WanAttentionBlockWithHipKernel._attend is the block's one choice of attention kernel (no GPU: the three wan.ops entry
+    points are replaced by recorders): map quantiser -> attention_map_quant for tensors and Q8Rows alike, Q8Rows ->
+    attention_qk8, else attention, which sees `window=` only for a bounded window.  The key length is a positional argument
+    where the caller has one (self-attention) and absent where it has none (cross-attention); q_len goes to the map form only."""
+    from wan import ops
+    from wan.quant_wanx_hip import WanAttentionBlockWithHipKernel
+
+    blk = WanAttentionBlockWithHipKernel(256, 512, 2)
+    calls, result = [], torch.zeros(1)
+    for name in ("attention", "attention_qk8", "attention_map_quant"):
+        monkeypatch.setattr(ops, name, lambda *a, _name=name, **kw: (calls.append((_name, a, kw)), result)[1])
+
+    def q8rows():
+        r = ops.Q8Rows.__new__(ops.Q8Rows)
+        r.rows, r.cols, r.heads, r.stride, r.codes, r.scales = 5, 256, 2, 5, None, None
+        return r
+
+    v = torch.zeros(5, 256)
+    for int8 in (False, True):
+        q, k = (q8rows(), q8rows()) if int8 else (torch.zeros(5, 256), torch.zeros(5, 256))
+        for map_cfg in (None, (8, False)):
+            for window in ((-1, -1), (3, 5)):
+                for k_len in (4, None):
+                    calls.clear()
+                    assert blk._attend(q, k, v, 2, k_len, 3, map_cfg, window) is result
+                    (name, args, kw), = calls
+                    assert args[0] is q and args[1] is k and args[2] is v and args[3] == 2  # the operands and `heads`
+                    tail = () if k_len is None else (4,)
+                    if map_cfg is not None:
+                        assert (name, args[4:], kw) == ("attention_map_quant", (8, False) + tail, {"q_len": 3})
+                    elif int8:
+                        assert (name, args[4:], kw) == ("attention_qk8", tail, {})
+                    else:
+                        assert (name, args[4:], kw) == ("attention", tail, {"window": (3, 5)} if window == (3, 5) else {})
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # --dit_fsdp: block weights sharded over the ranks, all-gathered one block ahead (wan/distributed/fsdp.py)
 class _ToyLin:
@@ -283,7 +320,7 @@ def test_packed_send_images_equal_transpose_pack_world2():
 
 
 def _q8_exchange_worker(rank, world, port, q):
-    """The int8 Q.K^T exchange of wan/quant_wanx_hip.py::_self_attention_qk8_ulysses in index form: per-(token, head) codes
+    """The int8 Q.K^T exchange of wan/quant_wanx_hip.py::_self_attention_ulysses in index form: per-(token, head) codes
     and the two scale planes, quantised on the token shard, must arrive as exactly the head group's slice of what ONE rank
     holding all tokens would have produced (codes, both planes, the 64-row zero padding of the key planes)."""
     import traceback

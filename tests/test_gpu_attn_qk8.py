@@ -399,6 +399,57 @@ def test_attention_map_quant_ignores_padded_query_rows():
     assert not torch.equal(counted[:Lq], ref)
 
 
+@pytest.mark.parametrize("form", ["bf16", "q8rows"])
+def test_attention_map_quant_pads_alike_in_both_operand_forms(form, monkeypatch):
+    """The bf16 and the Q8Rows form of attention_map_quant treat sequence padding in the same way: with q_len the padded output
+    rows are exactly zero (whatever `out` held), the real rows are bit-equal to the call on the real rows alone, and q_len = 0
+    launches nothing.  96 rows, 70 real, 130 keys: a ragged 64-key tile and a ragged 32-query wave."""
+    from viditq_extension import _C
+    from wan import ops
+
+    d, H, rows, n, Lk = 128, 2, 96, 70, 130
+    g = torch.Generator().manual_seed(12)
+    q = (torch.randn(rows, H * d, generator=g) * 1.5).to(torch.bfloat16)
+    k = (torch.randn(Lk, H * d, generator=g) * 1.5).to(torch.bfloat16)
+    v = torch.randn(Lk, H * d, generator=g).to(torch.bfloat16).to(DEV)
+    q[n:] = (k[:rows - n].float() * 4.0).to(torch.bfloat16)  # padding rows that would dominate the column maxima if counted
+    w = torch.ones(H * d, device=DEV)
+
+    def operand(t, for_keys):
+        t = t.contiguous().to(DEV)
+        return ops.rmsnorm_rope_q8(t, w, None, d, for_keys) if form == "q8rows" else t
+
+    def stale():
+        return torch.full((rows, H * d), 7.0, dtype=torch.bfloat16, device=DEV)
+
+    q_all, q_real, keys = operand(q, False), operand(q[:n], False), operand(k, True)
+    ref = ops.attention_map_quant(q_real, keys, v, H, 8, False)
+    out = ops.attention_map_quant(q_all, keys, v, H, 8, False, q_len=n, out=stale())
+    assert tuple(ref.shape) == (n, H * d) and bool(ref.any())
+    assert torch.equal(out[:n], ref) and not bool(out[n:].any())
+    launches, call = [], _C.call
+    monkeypatch.setattr(_C, "call", lambda name, *a, **kw: (launches.append(name), call(name, *a, **kw))[1])
+    none = ops.attention_map_quant(q_all, keys, v, H, 8, False, q_len=0, out=stale())
+    assert launches == [] and tuple(none.shape) == (rows, H * d) and not bool(none.any())
+
+
+def test_rmsnorm_rope_q8_refuses_a_misshaped_rope_table():
+    """A rotary table whose second dimension is not head_dim / 2 is refused by rmsnorm_rope_q8 as rmsnorm_rope_ refuses it."""
+    from wan import ops
+
+    L, H, d = 9, 2, 128
+    x = torch.randn(L, H * d, generator=torch.Generator().manual_seed(2)).to(DEV)
+    w = torch.ones(H * d, device=DEV)
+    bad = torch.zeros(L, d // 2 + 1, 2, device=DEV)
+    with pytest.raises(RuntimeError, match="rope must have shape"):
+        ops.rmsnorm_rope_(x.clone(), w, bad, d)
+    with pytest.raises(RuntimeError, match="rope must have shape"):
+        ops.rmsnorm_rope_q8(x, w, bad, d, False)
+    good = torch.zeros(L, d // 2, 2, device=DEV)
+    good[..., 0] = 1.0
+    assert ops.rmsnorm_rope_q8(x, w, good, d, False).codes.shape == (L, H * d)
+
+
 def test_attention_map_quant_matches_reference_golden(golden=None):
     """The same entry point on the inputs of the reference-generated fixture (q, k, v as bf16): against the reference's own
     `attn_quantised @ v`."""

@@ -1,9 +1,21 @@
 """Functional wrappers over libwanq_hip for the DiT block (no module state)."""
+import contextlib
 import math
 
 import torch
 
 from viditq_extension import _C, fused, qgemm  # noqa: F401
+
+
+def _rope_positions(rope, head_dim):
+    """The positions a rotary table holds (0 without one), after checking that it is contiguous fp32 [positions, head_dim/2, 2]."""
+    if rope is None:
+        return 0
+    _C.check_dtype("rope", rope, torch.float32)
+    _C.check_contig("rope", rope)
+    if rope.dim() != 3 or rope.shape[1] != head_dim // 2 or rope.shape[2] != 2:
+        raise RuntimeError(f"rope must have shape (positions, {head_dim // 2}, 2)")
+    return rope.shape[0]
 
 
 def rmsnorm_rope_(x, weight, rope, head_dim, rows_per_batch=None, eps=1e-6, out=None):
@@ -15,13 +27,7 @@ def rmsnorm_rope_(x, weight, rope, head_dim, rows_per_batch=None, eps=1e-6, out=
     if weight is not None:
         _C.check_dtype("weight", weight, torch.float32)
         _C.check_shape("weight", weight, cols)
-    positions = 0
-    if rope is not None:
-        _C.check_dtype("rope", rope, torch.float32)
-        _C.check_contig("rope", rope)
-        if rope.dim() != 3 or rope.shape[1] != head_dim // 2 or rope.shape[2] != 2:
-            raise RuntimeError(f"rope must have shape (positions, {head_dim // 2}, 2)")
-        positions = rope.shape[0]
+    positions = _rope_positions(rope, head_dim)
     out = x if out is None else out
     with torch.cuda.device(x.device):
         _C.call("wanq_rmsnorm_rope", _C.ptr(x), _C.dt(x), _C.ptr(weight), _C.ptr(rope), _C.ptr(out), _C.dt(out), rows, cols,
@@ -48,13 +54,7 @@ def rmsnorm_rope_scatter(x, weight, rope, head_dim, out, head_map, rows_per_batc
     if weight is not None:
         _C.check_dtype("weight", weight, torch.float32)
         _C.check_shape("weight", weight, cols)
-    positions = 0
-    if rope is not None:
-        _C.check_dtype("rope", rope, torch.float32)
-        _C.check_contig("rope", rope)
-        if rope.dim() != 3 or rope.shape[1] != head_dim // 2 or rope.shape[2] != 2:
-            raise RuntimeError(f"rope must have shape (positions, {head_dim // 2}, 2)")
-        positions = rope.shape[0]
+    positions = _rope_positions(rope, head_dim)
     with torch.cuda.device(x.device):
         _C.call("wanq_rmsnorm_rope_scatter", _C.ptr(x), _C.dt(x), _C.ptr(weight), _C.ptr(rope), _C.ptr(out), _C.dt(out),
                 _C.ptr(head_map), rows, cols, head_dim, rows_per_batch or rows, positions, float(eps), _C.stream(),
@@ -73,6 +73,41 @@ def _check_attn_dtype(what, **tensors):
         raise RuntimeError(f"{what}: " + ", ".join(f"{n} is {d}" for n, d in kinds.items()) +
                            "; the operands must all be torch.bfloat16 or all be torch.float16")
     return first
+
+
+def _check_tokens(C, rows=None, **tensors):
+    """The attention operands are on the GPU and [tokens, C] (`rows` tokens where given) with unit column stride."""
+    for n, t in tensors.items():
+        _C.check_gpu(n, t)
+        if t.dim() != 2 or t.shape[1] != C or t.stride(1) != 1 or (rows is not None and t.shape[0] != rows):
+            raise RuntimeError(f"Tensor {n} must be [{'tokens' if rows is None else rows}, {C}] with unit column stride")
+
+
+def _real_rows(n, rows):
+    """k_len / q_len: the first n of `rows` tokens are real (None: all of them), the rest is padding."""
+    return rows if n is None else min(int(n), rows)
+
+
+_attn_timer = None
+
+
+def set_attention_timer(t):
+    """bench.py hook: a list collecting (start_event, end_event, flops) per attention launch."""
+    global _attn_timer
+    _attn_timer = t
+
+
+@contextlib.contextmanager
+def _attn_timed(flops):
+    """bench.py's attention timer (set_attention_timer): an event pair around the launch in the body; flops() is its work."""
+    if _attn_timer is None:
+        yield
+        return
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev0.record()
+    yield
+    ev1.record()
+    _attn_timer.append((ev0, ev1, flops()))
 
 
 class Q8Rows:
@@ -109,11 +144,7 @@ def rmsnorm_rope_q8(x, weight, rope, head_dim, for_keys, eps=1e-6, want_fp=False
     rows, cols = x.shape
     if head_dim != 128:
         raise RuntimeError("the int8 Q.K^T attention is implemented for head_dim 128")
-    positions = 0
-    if rope is not None:
-        _C.check_dtype("rope", rope, torch.float32)
-        _C.check_contig("rope", rope)
-        positions = rope.shape[0]
+    positions = _rope_positions(rope, head_dim)
     if weight is not None:
         _C.check_dtype("weight", weight, torch.float32)
         _C.check_shape("weight", weight, cols)
@@ -136,14 +167,12 @@ def attention_qk8(q8, k8, v, num_heads, k_len=None, out=None, splits=None):
     (csrc/attention.hip, QK8); q8 / k8: Q8Rows, v bf16 or fp16 [Lk, C] -> [Lq, C] of v's type (P.V runs in that type)."""
     Lq, C = q8.codes.shape
     d = C // num_heads
-    _C.check_gpu("v", v)
+    _check_tokens(C, k8.codes.shape[0], v=v)
     if out is None:
         _check_attn_dtype("attention_qk8", v=v)
     else:
         _check_attn_dtype("attention_qk8", v=v, out=out)
-    if v.dim() != 2 or v.shape[1] != C or v.stride(1) != 1 or v.shape[0] != k8.codes.shape[0]:
-        raise RuntimeError(f"Tensor v must be [{k8.codes.shape[0]}, {C}] with unit column stride")
-    Lk = k8.codes.shape[0] if k_len is None else min(int(k_len), k8.codes.shape[0])
+    Lk = _real_rows(k_len, k8.codes.shape[0])
     if out is None:
         out = torch.empty(Lq, C, dtype=v.dtype, device=v.device)
     if splits is None:
@@ -152,55 +181,10 @@ def attention_qk8(q8, k8, v, num_heads, k_len=None, out=None, splits=None):
     if splits > 1:
         nbytes = _C.lib.wanq_attention_split_workspace(Lq, num_heads, d, int(splits))
         ws = torch.empty(nbytes // 4, dtype=torch.float32, device=v.device)
-    with torch.cuda.device(v.device):
-        if _attn_timer is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
+    with torch.cuda.device(v.device), _attn_timed(lambda: 4 * Lq * Lk * d * num_heads):
         _C.call("wanq_attention_qk8_fwd", _C.ptr(q8.codes), _C.ptr(q8.scales), q8.stride, _C.ptr(k8.codes), _C.ptr(k8.scales),
                 k8.stride, _C.ptr(v), _C.ptr(out), _C.dt(v), Lq, Lk, num_heads, d, q8.codes.stride(0), k8.codes.stride(0),
                 v.stride(0), out.stride(0), 1.0 / math.sqrt(d), max(1, int(splits)), _C.ptr(ws), nbytes, _C.stream())
-        if _attn_timer is not None:
-            ev1.record()
-            _attn_timer.append((ev0, ev1, 4 * Lq * Lk * d * num_heads))
-    return out
-
-
-def attention_map_quant(q, k, v, num_heads, n_bits=8, sym=False, k_len=None, out=None, q_len=None):
-    """softmax(q k^T / sqrt(d)) with every KEY column of the map fake-quantised over all queries, then @ v -- the reference's
-    `attn.attn_map` recipe, group 'row' (Q/base/quant_attn.py:118-173), streamed in three passes (csrc/attn_map.hip).
-    q [Lq, C], k / v [Lk, C] bf16 -> [Lq, C].  q_len: number of REAL query rows (the rest is sequence padding): a column's
-    quantisation step is taken over the real queries only, as the reference's map holds no padding rows; padded output rows
-    are zero."""
-    if isinstance(q, Q8Rows):  # the reference's full recipe: int8 q / k (attn.qk) under the map quantiser
-        return _attention_map_quant_q8(q, k, v, num_heads, n_bits, sym, k_len, out, q_len)
-    if q_len is not None and int(q_len) < q.shape[0]:
-        n = int(q_len)
-        if out is None:
-            out = torch.empty(q.shape[0], q.shape[1], dtype=q.dtype, device=q.device)
-        out[n:].zero_()
-        if n > 0:
-            attention_map_quant(q[:n], k, v, num_heads, n_bits, sym, k_len, out[:n])
-        return out
-    Lq, C = q.shape
-    d = C // num_heads
-    if torch.float16 in (q.dtype, k.dtype, v.dtype):
-        raise RuntimeError(_MAP_F16)
-    for n, t in (("q", q), ("k", k), ("v", v)):
-        _C.check_gpu(n, t)
-        _C.check_dtype(n, t, torch.bfloat16)
-        if t.dim() != 2 or t.shape[1] != C or t.stride(1) != 1:
-            raise RuntimeError(f"Tensor {n} must be [tokens, {C}] with unit column stride")
-    if k.shape[0] != v.shape[0]:
-        raise RuntimeError("k and v must have the same number of tokens")
-    Lk = k.shape[0] if k_len is None else min(int(k_len), k.shape[0])
-    if out is None:
-        out = torch.empty(Lq, C, dtype=q.dtype, device=q.device)
-    nbytes = _C.lib.wanq_attention_map_workspace(Lq, Lk, num_heads)
-    ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=q.device)
-    with torch.cuda.device(q.device):
-        _C.call("wanq_attention_map_quant_fwd", _C.ptr(q), _C.ptr(k), _C.ptr(v), _C.ptr(out), _C.dt(q), Lq, Lk, num_heads, d,
-                q.stride(0), k.stride(0), v.stride(0), out.stride(0), 1.0 / math.sqrt(d), int(n_bits), 1 if sym else 0, _C.ptr(ws),
-                nbytes, _C.stream())
     return out
 
 
@@ -208,33 +192,42 @@ _MAP_F16 = ("attention_map_quant: fp16 operands are not implemented -- the atten
             "matrix cores as a bf16 hi + lo pair and take bf16 q / k / v only")
 
 
-def _attention_map_quant_q8(q8, k8, v, num_heads, n_bits, sym, k_len, out, q_len):
-    """attention_map_quant with q and k as Q8Rows (per-(token, head) int8 codes + scale planes): S runs on the int8 matrix cores
-    in all three passes -- together with a fake-quantised v the reference's whole recipe (W/models/quant_opensora.py:431-476)."""
-    if not isinstance(k8, Q8Rows):
+def attention_map_quant(q, k, v, num_heads, n_bits=8, sym=False, k_len=None, out=None, q_len=None):
+    """softmax(q k^T / sqrt(d)) with every KEY column of the map fake-quantised over all queries, then @ v -- the reference's
+    `attn.attn_map` recipe, group 'row' (Q/base/quant_attn.py:118-173), streamed in three passes (csrc/attn_map.hip).
+    q [Lq, C], k / v [Lk, C] bf16 -> [Lq, C].  q and k may instead both be Q8Rows (per-(token, head) int8 codes + scale planes):
+    S then runs on the int8 matrix cores in all three passes -- together with a fake-quantised v the reference's whole recipe
+    (W/models/quant_opensora.py:431-476).  q_len: number of REAL query rows (the rest is sequence padding): a column's
+    quantisation step is taken over the real queries only, as the reference's map holds no padding rows; padded output rows
+    are zero."""
+    q8 = isinstance(q, Q8Rows)
+    if q8 != isinstance(k, Q8Rows):
         raise RuntimeError("attention_map_quant: q and k must both be Q8Rows or both be bf16 tensors")
-    rows, C = q8.codes.shape
-    Lq = rows if q_len is None else min(int(q_len), rows)
+    bf16 = {"v": v} if q8 else {"q": q, "k": k, "v": v}
+    qt, kt = (q.codes, k.codes) if q8 else (q, k)
+    rows, C = qt.shape
     d = C // num_heads
-    _C.check_gpu("v", v)
-    if v.dtype == torch.float16:
+    if not q8:
+        _check_tokens(C, q=q, k=k)
+    _check_tokens(C, kt.shape[0], v=v)
+    if any(t.dtype == torch.float16 for t in bf16.values()):
         raise RuntimeError(_MAP_F16)
-    _C.check_dtype("v", v, torch.bfloat16)
-    if v.dim() != 2 or v.shape[1] != C or v.stride(1) != 1 or v.shape[0] != k8.codes.shape[0]:
-        raise RuntimeError(f"Tensor v must be [{k8.codes.shape[0]}, {C}] with unit column stride")
-    Lk = k8.codes.shape[0] if k_len is None else min(int(k_len), k8.codes.shape[0])
+    for n, t in bf16.items():
+        _C.check_dtype(n, t, torch.bfloat16)
+    Lq, Lk = _real_rows(q_len, rows), _real_rows(k_len, kt.shape[0])
     if out is None:
         out = torch.empty(rows, C, dtype=torch.bfloat16, device=v.device)
     if Lq < rows:
-        out[Lq:].zero_()  # padding rows of the sequence: not queries of the map (see attention_map_quant)
+        out[Lq:].zero_()  # padding rows of the sequence: not queries of the map
     if Lq == 0:
         return out
     nbytes = _C.lib.wanq_attention_map_workspace(Lq, Lk, num_heads)
     ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=v.device)
+    lead = (_C.ptr(q.codes), _C.ptr(q.scales), q.stride, _C.ptr(k.codes), _C.ptr(k.scales), k.stride) if q8 else (_C.ptr(q), _C.ptr(k))
     with torch.cuda.device(v.device):
-        _C.call("wanq_attention_map_quant_qk8_fwd", _C.ptr(q8.codes), _C.ptr(q8.scales), q8.stride, _C.ptr(k8.codes), _C.ptr(k8.scales),
-                k8.stride, _C.ptr(v), _C.ptr(out), _C.BF16, Lq, Lk, num_heads, d, q8.codes.stride(0), k8.codes.stride(0), v.stride(0),
-                out.stride(0), 1.0 / math.sqrt(d), int(n_bits), 1 if sym else 0, _C.ptr(ws), nbytes, _C.stream())
+        _C.call("wanq_attention_map_quant_qk8_fwd" if q8 else "wanq_attention_map_quant_fwd", *lead, _C.ptr(v), _C.ptr(out), _C.BF16,
+                Lq, Lk, num_heads, d, qt.stride(0), kt.stride(0), v.stride(0), out.stride(0), 1.0 / math.sqrt(d), int(n_bits),
+                1 if sym else 0, _C.ptr(ws), nbytes, _C.stream())
     return out
 
 
@@ -250,25 +243,21 @@ def rope_table(freqs, grid, device):
     return torch.view_as_real(fi).to(torch.float32).contiguous().to(device)
 
 
-_attn_timer = None
-
-
-def set_attention_timer(t):
-    """bench.py hook: a list collecting (start_event, end_event, flops) per attention launch."""
-    global _attn_timer
-    _attn_timer = t
-
-
 _N_CU = {}
+
+
+def cu_count(device):
+    """Compute units of `device`, cached; 256 (an MI355X) off the GPU, where the host policies below are tested."""
+    if device not in _N_CU:
+        _N_CU[device] = torch.cuda.get_device_properties(device).multi_processor_count if device.type == "cuda" else 256
+    return _N_CU[device]
 
 
 def attention_splits(Lq, Lk, num_heads, device, ncu=None):
     """Key splits for wanq_attention_fwd_split: > 1 only when (query blocks x heads) leaves much of the last round of CUs idle
     and the key sequence is long enough to share (e.g. 3 heads x 128 blocks on 256 CUs: 1.5 rounds cost 2 -> split 2)."""
     if ncu is None:
-        if device not in _N_CU:
-            _N_CU[device] = torch.cuda.get_device_properties(device).multi_processor_count
-        ncu = _N_CU[device]
+        ncu = cu_count(device)
     blocks, tiles = -(-Lq // 256) * num_heads, -(-Lk // 64)
     if tiles < 32:
         return 1
@@ -321,13 +310,9 @@ def attention(q, k, v, num_heads, k_len=None, out=None, splits=None, window=(-1,
         _check_attn_dtype("attention", q=q, k=k, v=v)
     else:
         _check_attn_dtype("attention", q=q, k=k, v=v, out=out)
-    for n, t in (("q", q), ("k", k), ("v", v)):
-        _C.check_gpu(n, t)
-        if t.dim() != 2 or t.shape[1] != C or t.stride(1) != 1:
-            raise RuntimeError(f"Tensor {n} must be [tokens, {C}] with unit column stride")
-    if k.shape[0] != v.shape[0]:
-        raise RuntimeError("k and v must have the same number of tokens")
-    Lk = k.shape[0] if k_len is None else min(int(k_len), k.shape[0])
+    _check_tokens(C, q=q, k=k)
+    _check_tokens(C, k.shape[0], v=v)
+    Lk = _real_rows(k_len, k.shape[0])
     if out is None:
         out = torch.empty(Lq, C, dtype=q.dtype, device=q.device)
     banded = window_bounded(window)
@@ -337,10 +322,8 @@ def attention(q, k, v, num_heads, k_len=None, out=None, splits=None, window=(-1,
         splits = 1
     elif splits is None:
         splits = attention_splits(Lq, Lk, num_heads, q.device)
-    with torch.cuda.device(q.device):
-        if _attn_timer is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
+    # (the timer's flops: the visible (query, key) pairs)
+    with torch.cuda.device(q.device), _attn_timed(lambda: 4 * window_pairs(Lq, Lk, window) * d * num_heads):
         if banded:
             _C.call("wanq_attention_window_fwd", _C.ptr(q), _C.ptr(k), _C.ptr(v), _C.ptr(out), _C.dt(q), Lq, Lk, num_heads, d,
                     q.stride(0), k.stride(0), v.stride(0), out.stride(0), 1.0 / math.sqrt(d), int(window[0]), int(window[1]), _C.stream())
@@ -353,9 +336,6 @@ def attention(q, k, v, num_heads, k_len=None, out=None, splits=None, window=(-1,
             _C.call("wanq_attention_fwd_split", _C.ptr(q), _C.ptr(k), _C.ptr(v), _C.ptr(out), _C.dt(q), Lq, Lk, num_heads, d,
                     q.stride(0), k.stride(0), v.stride(0), out.stride(0), 1.0 / math.sqrt(d), int(splits), _C.ptr(ws), nbytes,
                     _C.stream())
-        if _attn_timer is not None:
-            ev1.record()
-            _attn_timer.append((ev0, ev1, 4 * window_pairs(Lq, Lk, window) * d * num_heads))  # the visible (query, key) pairs
     return out
 
 

@@ -361,7 +361,6 @@ class _FpSrc:
         return self.t
 
 
-_N_CU = {}
 _FORCE_CHUNK_UNIT = None  # tests: pipeline the exchange even when a tiny model's heads do not fill a GPU round
 
 
@@ -370,10 +369,8 @@ def _head_chunks(heads, seq_len, device, max_chunks=4):
     head, one per CU at a time, so a chunk should fill whole rounds of the GPU: with L = 32760 (128 workgroups per head,
     256 CUs) chunks are multiples of 2 heads -- 6 heads -> (2, 2, 2), never (3, 3), which would run 4 half-empty rounds
     instead of 3 full ones.  Small chunks first and last: those are the exchanges nothing hides."""
-    if device not in _N_CU:
-        _N_CU[device] = torch.cuda.get_device_properties(device).multi_processor_count if device.type == "cuda" else 256
     per_head = -(-seq_len // 256)
-    unit = _FORCE_CHUNK_UNIT or max(1, _N_CU[device] // per_head)   # heads per full round of the GPU (>= 1)
+    unit = _FORCE_CHUNK_UNIT or max(1, ops.cu_count(device) // per_head)   # heads per full round of the GPU (>= 1)
     units, rem = divmod(heads, unit)
     n = min(max_chunks - (1 if rem else 0), units)
     if n <= 0:
@@ -511,56 +508,85 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         memo = ctx.derived
         if memo is not None and id(self) in memo:
             return memo[id(self)]
-        ca, d = self.cross_attn, self.head_dim
+        ca = self.cross_attn
         k = self._linear(ca.k, ctx)
         v = self._vq(self._linear(ca.v, ctx), self.cross_attn_v_bits, None)
-        if self.cross_attn_qk8:
-            k = ops.rmsnorm_rope_q8(k, ca.norm_k_weight, None, d, True, eps=self.eps)
-        else:
-            ops.rmsnorm_rope_(k, ca.norm_k_weight, None, d, eps=self.eps)
+        k = self._prep_qk(k, ca.norm_k_weight, None, self.cross_attn_qk8, True)
         if memo is not None:
             memo[id(self)] = (k, v)
         return k, v
 
-    def _self_attention_qk8_ulysses(self, q, h, rope, seq_len, sp):
-        """attn.qk under Ulysses.  The q / k quantiser works on (token, head) rows (Q/base/quant_attn.py:168-174 on the reshape of
-        W/models/quant_opensora.py:431-436), and a rank holds whole (token, head) rows on BOTH sides of the head exchange -- so
-        the rows are quantised where RMSNorm + RoPE produces them (same kernel, same codes as on one GPU) and the all-to-all moves
-        the int8 codes and the two fp32 scale planes: half the xGMI bytes of the bf16 exchange, bit-equal to the single-rank
-        result.  Pipelined over head chunks like the bf16 path (chunk 0 of q under the k GEMM, of k under the v GEMM, the rest
-        and the way back under the attention of the previous chunk)."""
-        sa, d, P = self.self_attn, self.head_dim, sp.size
+    def _prep_qk(self, x, weight, rope, int8, for_keys):
+        """q or k behind its projection: RMSNorm + RoPE in place, or -- int8: attn.qk / cross_attn.qk -- the Q8Rows of that row."""
+        if int8:
+            return ops.rmsnorm_rope_q8(x, weight, rope, self.head_dim, for_keys, eps=self.eps)
+        return ops.rmsnorm_rope_(x, weight, rope, self.head_dim, eps=self.eps)
+
+    def _attend(self, q, k, v, heads, k_len, q_len, map_cfg, window=(-1, -1)):
+        """The one place that picks the attention kernel: the attention-map quantiser (16-bit or Q8Rows q / k alike: with attn.qk
+        and attn.v the reference's whole recipe), the int8 Q.K^T kernel for Q8Rows, else the plain 16-bit kernel, banded where
+        `window` is bounded.  k_len None (cross-attention: the text context carries no padding): the call names no key length."""
+        k_len = () if k_len is None else (k_len,)
+        if map_cfg is not None:
+            return ops.attention_map_quant(q, k, v, heads, map_cfg[0], map_cfg[1], *k_len, q_len=q_len)
+        if isinstance(q, ops.Q8Rows):
+            return ops.attention_qk8(q, k, v, heads, *k_len)
+        return ops.attention(q, k, v, heads, *k_len, **ops.window_kwargs(window))
+
+    def _self_attention_ulysses(self, q, h, rope, seq_len, sp):
+        """Self-attention under Ulysses, pipelined over head chunks (_head_chunks): chunk 0 of q is exchanged under the k GEMM and
+        chunk 0 of k under the v GEMM; the exchange of every further chunk, and the way back of the previous one, flies under the
+        attention of another chunk, so about half of the all-to-all time of a block hides behind its 2-6 ms of attention.  The
+        collectives run in issue order on the group's own stream.  Only the wire format of q and k varies:
+          * 16 bits: RMSNorm + RoPE writes q and k straight into the send images of the chunks ([P, Lp, w] each): no pack pass;
+          * int8 (attn.qk): the q / k quantiser works on (token, head) rows (Q/base/quant_attn.py:168-174 on the reshape of
+            W/models/quant_opensora.py:431-436), and a rank holds whole (token, head) rows on BOTH sides of the head exchange -- so
+            the rows are quantised where RMSNorm + RoPE produces them (same kernel, same codes as on one GPU) and the all-to-all
+            moves the int8 codes and the two fp32 scale planes: half the xGMI bytes of the 16-bit exchange, bit-equal to the
+            single-rank result."""
+        sa, d = self.self_attn, self.head_dim
         lp, C = q.shape
-        H = C // d
-        chunks = [(a * d, b * d) for a, b in _head_chunks(H // P, lp * P, q.device)]
+        chunks = [(a * d, b * d) for a, b in _head_chunks(C // d // sp.size, lp * sp.size, q.device)]
+        if self.attn_qk8:
+            def pack(x, weight, for_keys):
+                x8 = ops.rmsnorm_rope_q8(x, weight, rope, d, for_keys, eps=self.eps)
+                # scale planes [2, H, stride] -> [lp, H * 2]: a head's (delta, constant) pair travels with its codes
+                return x8.codes, x8.scales[:, :, :lp].permute(2, 1, 0).reshape(lp, 2 * (C // d))
 
-        def token_major(s8):  # scale planes [2, H, stride] -> [lp, H * 2]: a head's (delta, constant) pair travels with its codes
-            return s8.scales[:, :, :lp].permute(2, 1, 0).reshape(lp, 2 * H)
+            def send(packed, i):
+                c0, c1 = chunks[i]
+                return (sp.scatter_heads(packed[0], async_op=True, cols=(c0, c1)),
+                        sp.scatter_heads(packed[1], async_op=True, cols=(2 * c0 // d, 2 * c1 // d)))
 
-        def send(s8, planes, ch):
-            return (sp.scatter_heads(s8.codes, async_op=True, cols=ch),
-                    sp.scatter_heads(planes, async_op=True, cols=(2 * ch[0] // d, 2 * ch[1] // d)))
+            def receive(pending, for_keys):
+                return ops.Q8Rows.from_exchange(pending[0].wait(), pending[1].wait(), d, for_keys)
+        else:
+            _, hmap, where = sp.packed_layout(lp, C, d, chunks, q.device)
 
-        q8 = ops.rmsnorm_rope_q8(q, sa.norm_q_weight, rope, d, False, eps=self.eps)
-        qp = token_major(q8)
-        pend = [[send(q8, qp, chunks[0])]]
-        k8 = ops.rmsnorm_rope_q8(self._linear(sa.k, h), sa.norm_k_weight, rope, d, True, eps=self.eps)
-        kp = token_major(k8)
-        pend[0].append(send(k8, kp, chunks[0]))
+            def pack(x, weight, for_keys):
+                return ops.rmsnorm_rope_scatter(x, weight, rope, d, torch.empty(lp * C, dtype=x.dtype, device=x.device), hmap, eps=self.eps)
+
+            def send(packed, i):
+                return sp.scatter_packed(packed, lp, *where[i], async_op=True)
+
+            def receive(pending, for_keys):
+                return pending.wait()
+
+        qs = pack(q, sa.norm_q_weight, False)
+        pend = [[send(qs, 0)]]                                    # chunk 0 of q flies under the k GEMM
+        ks = pack(self._linear(sa.k, h), sa.norm_k_weight, True)
+        pend[0].append(send(ks, 0))                               # ... of k under the v GEMM
         v = self._linear(sa.v, h)
         pend[0].append(sp.scatter_heads(v, async_op=True, cols=chunks[0]))
-        for ch in chunks[1:]:
-            pend.append([send(q8, qp, ch), send(k8, kp, ch), sp.scatter_heads(v, async_op=True, cols=ch)])
-        o = torch.empty(lp, C, dtype=self.act_dtype, device=q.device)
+        for i in range(1, len(chunks)):
+            pend.append([send(qs, i), send(ks, i), sp.scatter_heads(v, async_op=True, cols=chunks[i])])
+        o = torch.empty(lp, C, dtype=self.act_dtype, device=q.device) if self.attn_qk8 else torch.empty_like(q)
         back = []
         for (c0, c1), (wq, wk, wv) in zip(chunks, pend):
-            qc = ops.Q8Rows.from_exchange(wq[0].wait(), wq[1].wait(), d, False)
-            kc = ops.Q8Rows.from_exchange(wk[0].wait(), wk[1].wait(), d, True)
-            vc = self._vq(wv.wait(), self.attn_v_bits, seq_len)
-            if self.attn_map is not None:
-                oc = ops.attention_map_quant(qc, kc, vc, (c1 - c0) // d, self.attn_map[0], self.attn_map[1], seq_len, q_len=seq_len)
-            else:
-                oc = ops.attention_qk8(qc, kc, vc, (c1 - c0) // d, seq_len)
+            # after the exchange a rank holds ALL tokens of its heads: v's per-(head, channel) statistics, the attention-map
+            # quantiser's per-key-column statistics over all queries and the window's band are all local
+            qc, kc, vc = receive(wq, False), receive(wk, True), self._vq(wv.wait(), self.attn_v_bits, seq_len)
+            oc = self._attend(qc, kc, vc, (c1 - c0) // d, seq_len, seq_len, self.attn_map, self.window_size)
             back.append(sp.gather_heads(oc, async_op=True, out=o, cols=(c0, c1)))
         for b in back:
             b.wait()
@@ -572,7 +598,7 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         tokens of the WHOLE sequence.  ctx: _FpSrc of the bf16 text context [Lc, C] (shared by all blocks so that
         its plain int8 copy is made once per pass).  sp: wan.distributed.SeqParallel or None.  e: this block's
         `modulation + e0` when the caller has it already (the model adds all blocks' modulations in one launch per pass)."""
-        H, d = self.num_heads, self.head_dim
+        H = self.num_heads
         if e is None:
             e = self.modulation + e0  # [1, 6, C] fp32
         sa, ca = self.self_attn, self.cross_attn
@@ -581,58 +607,13 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         h = _LnSrc(self, x, None, e[:, 0], e[:, 1])
         h.prefetch([sa.q, sa.k, sa.v])  # one pass over x for the three ViDiT-transformed int8 inputs
         q = self._linear(sa.q, h)
-        if self.attn_qk8 and sp is not None and sp.size > 1:
-            o = self._self_attention_qk8_ulysses(q, h, rope, seq_len, sp)
-        elif self.attn_qk8:
-            q8 = ops.rmsnorm_rope_q8(q, sa.norm_q_weight, rope, d, False, eps=self.eps)
-            k8 = ops.rmsnorm_rope_q8(self._linear(sa.k, h), sa.norm_k_weight, rope, d, True, eps=self.eps)
-            v = self._vq(self._linear(sa.v, h), self.attn_v_bits, seq_len)
-            if self.attn_map is not None:  # q / k / v quantisers AND the map quantiser: the reference's whole recipe
-                o = ops.attention_map_quant(q8, k8, v, H, self.attn_map[0], self.attn_map[1], seq_len, q_len=seq_len)
-            else:
-                o = ops.attention_qk8(q8, k8, v, H, seq_len)
-        elif sp is None or sp.size == 1:
-            ops.rmsnorm_rope_(q, sa.norm_q_weight, rope, d, eps=self.eps)
-            k = self._linear(sa.k, h)
-            ops.rmsnorm_rope_(k, sa.norm_k_weight, rope, d, eps=self.eps)
-            v = self._vq(self._linear(sa.v, h), self.attn_v_bits, seq_len)
-            if self.attn_map is not None:
-                o = ops.attention_map_quant(q, k, v, H, self.attn_map[0], self.attn_map[1], seq_len, q_len=seq_len)
-            else:
-                o = ops.attention(q, k, v, H, seq_len, **ops.window_kwargs(self.window_size))
+        if sp is not None and sp.size > 1:
+            o = self._self_attention_ulysses(q, h, rope, seq_len, sp)
         else:
-            # Ulysses, pipelined over head chunks: this rank's H/P heads are split in two; the exchange of chunk 1 (and the
-            # way back of chunk 0) flies under the attention of the other chunk, so about half of the all-to-all time of a
-            # block hides behind its 2-6 ms of attention.  The collectives run in issue order on the group's own stream.
-            # RMSNorm+RoPE writes q and k straight into the send images of the chunks ([P, Lp, w] each): no pack pass.
-            lp, C = q.shape
-            chunks = [(a * d, b * d) for a, b in _head_chunks(H // sp.size, lp * sp.size, q.device)]
-            _, hmap, where = sp.packed_layout(lp, C, d, chunks, q.device)
-            qs = ops.rmsnorm_rope_scatter(q, sa.norm_q_weight, rope, d, torch.empty(lp * C, dtype=q.dtype, device=q.device), hmap, eps=self.eps)
-            pend = [[sp.scatter_packed(qs, lp, *where[0], async_op=True)]]        # chunk 0 of q flies under the k GEMM
-            k = self._linear(sa.k, h)
-            ks = ops.rmsnorm_rope_scatter(k, sa.norm_k_weight, rope, d, torch.empty(lp * C, dtype=k.dtype, device=k.device), hmap, eps=self.eps)
-            pend[0].append(sp.scatter_packed(ks, lp, *where[0], async_op=True))   # ... of k under the v GEMM
-            v = self._linear(sa.v, h)
-            pend[0].append(sp.scatter_heads(v, async_op=True, cols=chunks[0]))
-            for cw, wh in zip(chunks[1:], where[1:]):
-                pend.append([sp.scatter_packed(qs, lp, *wh, async_op=True), sp.scatter_packed(ks, lp, *wh, async_op=True),
-                             sp.scatter_heads(v, async_op=True, cols=cw)])
-            o = torch.empty_like(q)
-            back = []
-            for (c0, c1), (wq, wk, wv) in zip(chunks, pend):
-                # (v of this rank's heads, all tokens: the per-(head, channel) statistics are local after the exchange)
-                # (after the exchange a rank holds ALL tokens of its heads: the attention-map quantiser's per-key-column statistics
-                # over all queries are local, like v's per-(head, channel) statistics)
-                qc, kc, vc = wq.wait(), wk.wait(), self._vq(wv.wait(), self.attn_v_bits, seq_len)
-                if self.attn_map is not None:
-                    oc = ops.attention_map_quant(qc, kc, vc, (c1 - c0) // d, self.attn_map[0], self.attn_map[1], seq_len, q_len=seq_len)
-                else:
-                    # (the window's band is local too: all tokens of the chunk's heads are here)
-                    oc = ops.attention(qc, kc, vc, (c1 - c0) // d, seq_len, **ops.window_kwargs(self.window_size))
-                back.append(sp.gather_heads(oc, async_op=True, out=o, cols=(c0, c1)))
-            for b in back:
-                b.wait()
+            q = self._prep_qk(q, sa.norm_q_weight, rope, self.attn_qk8, False)
+            k = self._prep_qk(self._linear(sa.k, h), sa.norm_k_weight, rope, self.attn_qk8, True)
+            v = self._vq(self._linear(sa.v, h), self.attn_v_bits, seq_len)
+            o = self._attend(q, k, v, H, seq_len, seq_len, self.attn_map, self.window_size)
         self._linear(sa.o, _FpSrc(o), gate=e[0, 2].contiguous(), residual=x)
 
         # ---- cross attention: LN_affine -> q; k,v from the text context
@@ -646,18 +627,8 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         gather_q = self.cross_attn_map is not None and sp is not None and sp.size > 1
         if gather_q:
             q = sp.all_gather_rows(q)
-        if self.cross_attn_qk8:
-            q8 = ops.rmsnorm_rope_q8(q, ca.norm_q_weight, None, d, False, eps=self.eps)
-            if self.cross_attn_map is not None:
-                o = ops.attention_map_quant(q8, k, v, H, self.cross_attn_map[0], self.cross_attn_map[1], q_len=seq_len)
-            else:
-                o = ops.attention_qk8(q8, k, v, H)
-        else:
-            ops.rmsnorm_rope_(q, ca.norm_q_weight, None, d, eps=self.eps)
-            if self.cross_attn_map is not None:
-                o = ops.attention_map_quant(q, k, v, H, self.cross_attn_map[0], self.cross_attn_map[1], q_len=seq_len)
-            else:
-                o = ops.attention(q, k, v, H)
+        q = self._prep_qk(q, ca.norm_q_weight, None, self.cross_attn_qk8, False)
+        o = self._attend(q, k, v, H, None, seq_len, self.cross_attn_map)
         if gather_q:
             o = sp.shard_rows(o).contiguous()
         self._linear(ca.o, _FpSrc(o), gate=self.ones_gate, residual=x)
