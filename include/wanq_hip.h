@@ -384,6 +384,36 @@ int wanq_gemm_w4a8(const int8_t* a, const uint8_t* w_packed, void* out, int out_
                    const void* zp, int zp_dtype, const float* gate, const void* residual, int epi_flags,
                    int64_t M, int N, int K, void* stream);
 
+/* Group-wise W8A8 / W4A8 GEMM (the W4A8-g128 form of QServe-style checkpoints): int8 activations against integer weight codes with
+ * one scale and one zero point per output channel and per group of `group_size` input channels.
+ *   - sw and zp are fp32 [K / group_size][N], group-major: the layout wanq_gemm_wq16_grouped takes.  zp may be NULL, meaning 0.
+ *   - w_bits = 4: w is the packed unsigned nibbles u of wanq_pack_w4 ([N, K/2] bytes) and zp = zero_point - 8, the W4A8 convention.
+ *     The integer weight operand is u + zp[g,n]; the kernel forms it in registers while expanding the nibbles, before the MFMA.  For
+ *     every StaticQuantizer output u + zp = q + zero_point lies in [-15, 15] (asymmetric: q + zero_point = round(w / delta) lies in
+ *     [round(min- / delta), round(min- / delta) + 15] and min- / delta >= -15), so the operand is an exact int8 and no per-token,
+ *     per-group activation sums are needed for the zero point.  Precondition: zp integer valued, u + zp in [-128, 127].
+ *   - w_bits = 8: w is int8 [N, K] and zp must be NULL (symmetric weights); a non-NULL zp is refused with WANQ_E_ARG: c + zp does not
+ *     fit int8, and the rank-one correction would need per-group token sums, which no producer writes.
+ *   - part_g[m,n] = sum_{k in group g} a[m,k] * (u[n,k] + zp[g,n]): int32, exact, on v_mfma_i32_32x32x32_i8.  The conversion
+ *     (float)part_g is exact while |part_g| < 2^24: for group_size <= 1024 at 8 bits, and always at 4 bits for group_size <= 8192.
+ *     Beyond that it is round-to-nearest-even.
+ *   - acc = fmaf((float)part_g, sw[g,n], acc), g ascending from acc = 0.
+ *   - y = fmaf(acc, sa[m], bias[n]), bias 0 when NULL; sa is the per-token scale of wanq_quant_rows, dtype tok_dtype (F16 | F32);
+ *     bias of ch_dtype (F16 | F32).
+ *   - WANQ_EPI_GELU, WANQ_EPI_GATE_RES (y = fmaf(y, gate[n], residual[m,n])) and the single rounding to out_dtype (F16 | BF16 | F32)
+ *     as wanq_gemm_w8a8 specifies them, with the same gelu_tanh_fast_f32.  out may alias residual.
+ *   - Determinism: the bits of element (m, n) depend on K and group_size only -- not on M, on the row's place in the launch or on
+ *     the workgroup.  No split-K.
+ *   - Shapes: any M >= 1 (ragged last tile in-kernel, no host padding); N % 8 == 0; group_size % 128 == 0 and K % group_size == 0;
+ *     a, w, out, residual, sw and zp 16-byte aligned; gate and bias aligned to 4 elements; out_dtype == WANQ_I32 is refused (there
+ *     is no single integer accumulator to return).  Anything else is refused (WANQ_E_SHAPE / WANQ_E_ARG, the message names the rule).
+ * wanq_gemm_select_kernel does not apply: one kernel form.  The reference has per-channel int8 GEMMs only
+ *   (ViDiT-Q/kernels/csrc/qgemm/w4a8/w4a8_per_channel_gemm_cuda_qserve.cu); group-wise weights are its StaticQuantizer applied to
+ *   w.view(N K / g, g), as for wanq_gemm_wq16_grouped. */
+int wanq_gemm_w8a8_grouped(const int8_t* a, const void* w, int w_bits, const float* sw, const float* zp, int group_size,
+                           void* out, int out_dtype, const void* sa, int tok_dtype, const void* bias, int ch_dtype,
+                           const float* gate, const void* residual, int epi_flags, int64_t M, int N, int K, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Step-level elementwise work of the denoising loop in one kernel:  out[o] = sum_i coef[o][i] * in[i]  over fp32 tensors of
  * `numel` elements (n_out <= 4, n_in <= 8; `in` / `out` are HOST arrays of device pointers, 16-byte aligned, outputs may

@@ -28,7 +28,7 @@ class QuantizedLinear(nn.Linear):
     def __init__(self, in_features, out_features, bias, device, quant_config, fp_module, module_name=None):
         super().__init__(in_features, out_features, bias, device)
         self.fp_module, self.q_cfg = fp_module, quant_config
-        self.group_size = self._checked_group_size(quant_config, module_name)
+        self.group_size = self._checked_group_size(quant_config, module_name, fp_module.weight.device)
         self.w_quantizer = self.a_quantizer = None
         self.channel_mask = None
         self.rotation_signs = None
@@ -51,9 +51,11 @@ class QuantizedLinear(nn.Linear):
         self.quant_mode = True
         self.module_name = module_name
 
-    def _checked_group_size(self, quant_config, module_name):
+    def _checked_group_size(self, quant_config, module_name, device=None):
         """`weight.group_size` of the config (None: one scale per output channel), or the refusal of what has no group-wise form,
-        before any weight is quantised: the message names the layer and the key."""
+        before any weight is quantised: the message names the layer and the key.  `device`: where the layer's weight lives.  With an
+        `act:` section the layer runs on wanq_gemm_w8a8_grouped, which exists on the GPU only: a weight in host memory is refused
+        here, by name, instead of by the first kernel that meets it."""
         wq = quant_config.get("weight", None)
         g = None if wq is None else wq.get("group_size", None)
         if g is None:
@@ -63,9 +65,10 @@ class QuantizedLinear(nn.Linear):
             raise ValueError(f"{name}: weight.group_size={g!r} must be a positive integer")
         if isinstance(wq["n_bits"], ListConfig):
             raise NotImplementedError(f"{name}: weight.group_size with a bit-width list (MixedPrecisionStaticQuantizer) is not supported")
-        if quant_config.get("act", None) is not None:
-            raise NotImplementedError(f"{name}: weight.group_size together with an `act:` section is not supported: the int8 GEMMs "
-                                      "apply one weight scale per output channel (group-wise scales exist for weight-only configs)")
+        if quant_config.get("act", None) is not None and device is not None and torch.device(device).type == "cpu":
+            raise NotImplementedError(f"{name}: weight.group_size together with an `act:` section needs the layer's weight on the GPU "
+                                      f"(it is on {device}): only wanq_gemm_w8a8_grouped applies per-group scales to int8 activations "
+                                      "and it has no host form; every other int8 GEMM applies one weight scale per output channel")
         if self.uses_mask or self.uses_rotation:
             raise NotImplementedError(f"{name}: weight.group_size with {type(self).__name__} is not supported: the SmoothQuant / "
                                       "QuaRot / ViDiT layer classes quantise one scale per output channel")
@@ -142,6 +145,8 @@ class QuantizedLinear(nn.Linear):
             return self._forward_weight_only(x)
         if not self.quant_mode or self.w_quantizer is None or self.a_quantizer is None:
             return self.fp_module(x, *args, **kwargs)
+        if self.group_size is not None:
+            return self._forward_grouped(x)
         shape = x.shape
         x2 = x.reshape(-1, shape[-1])
         premul, rot = self._act_transform()
@@ -164,10 +169,35 @@ class QuantizedLinear(nn.Linear):
             y = torch.addcmul(y, t_a.unsqueeze(1), self.weight.data.float().sum(dim=1).to(y.dtype).unsqueeze(0))
         return y.view(*shape[:-1], self.out_features)
 
+    def _forward_grouped(self, x):
+        """A `weight.group_size` with an `act:` section: the activation is quantised per token as in `forward` and multiplied on the
+        int8 matrix cores by wanq_gemm_w8a8_grouped, on the layer's codes and the [K / g, N] operands of `weight_only_operands`
+        (the 4-bit `zp - 8` convention is the same).  What that entry refuses -- a group that is not a multiple of 128, 8-bit
+        asymmetric weights -- goes through the reference's own expression, F.linear(a_quantizer(x), W_hat, bias) on the
+        dequantised weight."""
+        shape = x.shape
+        x2 = x.reshape(-1, shape[-1])
+        wq = self.w_quantizer
+        out_dtype = x.dtype if x.dtype in (torch.float16, torch.bfloat16, torch.float32) else torch.float32
+        w4 = self._codes.dtype == torch.uint8
+        if qgemm.w8a8_grouped_linear_refusal(x2.shape[0], self.out_features, self.in_features, self.group_size, 4 if w4 else 8,
+                                             bool(wq.sym)) is not None:
+            b = None if self.bias is None else self.bias.detach().float()
+            y = F.linear(self.a_quantizer(x2).float(), self.weight.data.float(), b).to(out_dtype)
+            return y.view(*shape[:-1], self.out_features)
+        q, scale, _ = self.a_quantizer.quantize_int8(x2, want_sum=False)
+        codes, sw, zp, w4 = self.weight_only_operands()
+        y = qgemm.w8a8_grouped_linear(q, codes, scale, sw, zp, self.group_size,
+                                      None if self.bias is None else self.bias.detach().float().contiguous(), out_dtype=out_dtype, w4=w4)
+        if not self.a_quantizer.sym:  # the rank-one term of `forward`: row sums of the dequantised weight, group-agnostic
+            t_a = (self.a_quantizer.zero_point.reshape(-1).float() * scale).to(y.dtype)
+            y = torch.addcmul(y, t_a.unsqueeze(1), self.weight.data.float().sum(dim=1).to(y.dtype).unsqueeze(0))
+        return y.view(*shape[:-1], self.out_features)
+
     def weight_only_operands(self):
         """(codes, scale fp32 [N], zp fp32 [N] or None, w4) of wanq_gemm_wq16 for this layer's quantised weight: int8 codes, or the
         packed nibbles u = code + 8 with the 8 folded into the zero point (the W4A8 convention).  With a `group_size` scale and zp
-        are the [K / g, N] operands of wanq_gemm_wq16_grouped (the quantiser's [N, K / g], transposed).  The two tensors are made
+        are the [K / g, N] operands of wanq_gemm_wq16_grouped and wanq_gemm_w8a8_grouped (the quantiser's [N, K / g], transposed).  The two tensors are made
         once and kept until the codes are set again (`int_weight`)."""
         if self._wq16_vecs is None or self._wq16_vecs[0].device != self._codes.device:
             wq, N = self.w_quantizer, self.out_features

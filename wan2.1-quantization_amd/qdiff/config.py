@@ -2,8 +2,8 @@
 `list`, i.e. exactly what the reference's code relies on (`cfg.weight.n_bits`, `cfg.get('viditq')`,
 `isinstance(n_bits, ListConfig)`).  Schema: ViDiT-Q/examples/Wan2.1/quant_configs/config.yaml, plus one key of
 this repository: `weight.group_size: <int>` -- one (delta, zero_point) per output channel and per group of that many input
-channels, for weight-only configs (no `act:` section, no bit-width list, no transform section; it must divide in_features;
-QuantizedLinear refuses everything else by layer name when it is built)."""
+channels, with or without an `act:` section (no bit-width list, no transform section; it must divide in_features; with an `act:`
+section the layer's weight must be on the GPU; QuantizedLinear refuses everything else by layer name when it is built)."""
 import yaml
 
 

@@ -346,3 +346,66 @@ def wq16_linear_refusal(M, N, K, group_size=None):
         if K % group_size:
             return f"K={K} must be a multiple of group_size={group_size}"
     return None
+
+
+# ---- group-wise weight scales on the int8 matrix cores ---------------------------------------------------------------
+def w8a8_grouped_linear(input_i8, codes, scale_input, scale_weight, zp, group_size, bias=None, out_dtype=None, gelu=False, gate=None,
+                        residual=None, out=None, w4=False):
+    """y = epilogue(scale_input[m] * sum_g scale_weight[g, n] * input_i8[M, K_g] @ (codes[N, K_g] + zp[g, n])^T) on the int8 matrix
+    cores (wanq_gemm_w8a8_grouped, csrc/gemm_i8_grouped.hip): `codes` int8 [N, K] (symmetric weights: zp must be None) or, with
+    w4=True, uint8 [N, K/2] unsigned nibbles in the pack_w4 layout (zp = zero_point - 8, integer valued, codes + zp an int8);
+    scale_weight and zp fp32 [K / group_size, N] (group-major).  Each group's int32 partial sum is folded into the result by one fp32
+    fma with scale_weight[g, n], groups ascending; then y = fma(acc, scale_input[m], bias[n]) and the epilogue of `w8a8_linear`
+    (`gelu`; gate fp32 [N] + residual [M, N] of the out dtype, which may alias `out`), one rounding to out_dtype (default fp16).
+    group_size % 128 == 0 and K % group_size == 0.  Counted by the int8 timer (`set_timer`)."""
+    _check_i8("input", input_i8)
+    M, K = input_i8.shape
+    _C.check_gpu("codes", codes)
+    _C.check_contig("codes", codes)
+    _C.check_dtype("codes", codes, torch.uint8 if w4 else torch.int8)
+    if codes.dim() != 2:
+        raise RuntimeError("Tensor codes must have dimension number (2)")
+    N = codes.shape[0]
+    _C.check_shape("codes", codes, N, K // 2 if w4 else K)
+    why = w8a8_grouped_linear_refusal(M, N, K, group_size, 4 if w4 else 8, zp is None)
+    if why is not None:
+        raise RuntimeError(f"w8a8_grouped_linear: {why}")
+    for name, t in (("scale_weight", scale_weight), ("zp", zp)):
+        if t is not None:
+            _C.check_gpu(name, t)
+            _C.check_contig(name, t)
+            _C.check_dtype(name, t, torch.float32)
+            _C.check_shape(name, t, K // group_size, N)
+    _check_vec("scale_input", scale_input, M)
+    _check_vec("bias", bias, N)
+    out_dtype = out_dtype or torch.float16
+    epi = _epi_flags(gelu, gate, residual, M, N, out_dtype)
+    out = _out_for(out, M, N, out_dtype, input_i8.device)
+    _C.check_same_device(input_i8, codes, scale_input, scale_weight, zp, bias, gate, residual, out)
+    with torch.cuda.device(input_i8.device):
+        if _timer is not None:
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record()
+        _C.call("wanq_gemm_w8a8_grouped", _C.ptr(input_i8), _C.ptr(codes), 4 if w4 else 8, _C.ptr(scale_weight), _C.ptr(zp),
+                int(group_size), _C.ptr(out), _C.dt(out_dtype), _C.ptr(scale_input), _C.dt(scale_input), _C.ptr(bias),
+                _C.dt(bias) if bias is not None else _C.F32, _C.ptr(gate), _C.ptr(residual), epi, M, N, K, _C.stream())
+        if _timer is not None:
+            ev1.record()
+            _timer.append((ev0, ev1, 2 * M * N * K))
+    return out
+
+
+def w8a8_grouped_linear_refusal(M, N, K, group_size, w_bits, sym):
+    """Why wanq_gemm_w8a8_grouped would refuse an [M, K] x [N, K] product of `w_bits`-bit weights, symmetric (`sym`: no zero point) or
+    not (None = accepted); see `fp_linear_refusal`."""
+    if w_bits not in (4, 8):
+        return f"w_bits={w_bits} must be 4 or 8"
+    if w_bits == 8 and not sym:
+        return "w_bits=8 takes symmetric weights only, zp must be None (c + zp does not fit int8)"
+    if N < 8 or N % 8:
+        return f"N={N} must be a positive multiple of 8"
+    if not isinstance(group_size, int) or group_size < 128 or group_size % 128:
+        return f"group_size={group_size} must be a positive multiple of 128"
+    if K < group_size or K % group_size:
+        return f"K={K} must be a positive multiple of group_size={group_size}"
+    return None

@@ -35,7 +35,7 @@ class _HipLinearInt(nn.Module):
     """The buffers HipLinearW8A8 and HipLinearWq16 both hold (described there), and the zero point their GEMMs take."""
 
     def __init__(self, in_features, out_features, bias, sym, w_bits, group_size=None):
-        """group_size (HipLinearWq16 only): scale_weight / zp_weight / zp_gemm are [K / group_size, N] instead of [N]."""
+        """group_size (the config's `weight.group_size`): scale_weight / zp_weight / zp_gemm are [K / group_size, N] instead of [N]."""
         super().__init__()
         assert w_bits in (4, 8), "integer storage exists for 8-bit and packed 4-bit weights"
         self.in_features, self.out_features, self.w_bits, self.group_size = in_features, out_features, w_bits, group_size
@@ -68,12 +68,24 @@ class HipLinearW8A8(_HipLinearInt):
     `act_quantizer`: None for the activation quantiser the fused producers implement (8-bit symmetric per token, eps 1e-6: every Wan
     configuration and the reference's kernels, fused.cu:330-370); otherwise the layer's own qdiff quantiser object (asymmetric,
     below 8 bits, or the mixed-precision class), and the block takes the UNFUSED path for this layer: fp32 activation -> that
-    quantiser's HIP kernels -> int8 GEMM -> the zero point's rank-one term (WanAttentionBlockWithHipKernel._linear_any_act)."""
+    quantiser's HIP kernels -> int8 GEMM -> the zero point's rank-one term (WanAttentionBlockWithHipKernel._linear_any_act).
+    With a `group_size` (the config's `weight.group_size`, a multiple of 128 that divides in_features; W4A8-g128) the three parameter
+    buffers are [K / group_size, N] and the product is qgemm.w8a8_grouped_linear (csrc/gemm_i8_grouped.hip): the zero point rides
+    in the integer operand, one fp32 fma per group and element applies the scales, and every fused epilogue is the same.  8-bit
+    asymmetric weights and a non-default activation quantiser have no group-wise form and are refused, by layer name."""
     quantized = True
     act_quantizer = None
 
-    def __init__(self, in_features, out_features, bias=True, sym=False, w_bits=8):
-        super().__init__(in_features, out_features, bias, sym, w_bits)
+    def __init__(self, in_features, out_features, bias=True, sym=False, w_bits=8, group_size=None, name="linear"):
+        if group_size is not None:
+            why = qgemm.w8a8_grouped_linear_refusal(1, out_features, in_features, group_size, w_bits, sym)
+            if why is not None and w_bits == 8 and not sym:
+                raise NotImplementedError(f"{name}: weight.group_size={group_size} with 8-bit asymmetric weights (weight.sym: False) has "
+                                          f"no kernel-mode form: {why}; the zero point's correction would need per-group token sums")
+            if why is not None:
+                raise NotImplementedError(f"{name}: weight.group_size={group_size} has no kernel-mode form: {why} (simulation mode "
+                                          "runs any group size)")
+        super().__init__(in_features, out_features, bias, sym, w_bits, group_size)
         assert w_bits == 8 or in_features % 32 == 0, "packed 4-bit weights need in_features % 32 == 0"
         self.register_buffer("act_premul", None)
         self.rot = None
@@ -125,16 +137,31 @@ class HipLinearW8A8(_HipLinearInt):
         return m
 
     @classmethod
-    def from_quantized(cls, ql):
+    def from_quantized(cls, ql, name="linear"):
         """From a qdiff QuantizedLinear (any variant): same integer codes, same parameters, same transform."""
         wq = ql.w_quantizer
-        m = cls(ql.in_features, ql.out_features, ql.bias is not None, wq.sym, wq.n_bits).to(ql.fp_module.weight.device)
-        m._set_codes(ql.int_weight, wq.delta.reshape(-1).float(), None if wq.sym else wq.zero_point.reshape(-1).float())
+        group = getattr(ql, "group_size", None)
+        aq = ql.a_quantizer
+        if group is not None and (not aq.sym or aq.n_bits != 8 or aq._sym_floor != 1e-6):
+            raise NotImplementedError(f"{name}: weight.group_size={group} with this `act:` section has no kernel-mode form: the fused "
+                                      "producers quantise 8-bit symmetric per token, and the unfused path's weight row sums are "
+                                      "per channel")
+        m = cls(ql.in_features, ql.out_features, ql.bias is not None, wq.sym, wq.n_bits, group, name).to(ql.fp_module.weight.device)
+        if group is not None:  # the [K / g, N] operands the simulation-mode layer hands the same entry
+            codes, sw, _, _ = ql.weight_only_operands()
+            if tuple(codes.shape) != tuple(m.weight.shape) or codes.dtype != m.weight.dtype:
+                raise ValueError(f"{name}: codes {tuple(codes.shape)} {codes.dtype} do not fit {tuple(m.weight.shape)} {m.weight.dtype}")
+            m.weight.copy_(codes)
+            m.scale_weight.copy_(sw)
+            if m.zp_weight is not None:
+                m.zp_weight.copy_(wq.zero_point.float().reshape(ql.out_features, -1).t())
+            m.refresh_zp_gemm()
+        else:
+            m._set_codes(ql.int_weight, wq.delta.reshape(-1).float(), None if wq.sym else wq.zero_point.reshape(-1).float())
         if ql.bias is not None:
             m.bias.copy_(ql.bias.detach().float())
         premul, rot = ql._act_transform()
         m.act_premul, m.rot = premul, rot
-        aq = ql.a_quantizer
         if not aq.sym or aq.n_bits != 8 or aq._sym_floor != 1e-6:
             m.__dict__["act_quantizer"] = aq  # (not a submodule: the quantiser belongs to the qdiff layer)
         return m
@@ -146,6 +173,9 @@ class HipLinearW8A8(_HipLinearInt):
 
     def forward(self, a_q, a_scale, a_sum, out_dtype=torch.bfloat16, gelu=False, gate=None, residual=None, out=None):
         zp = self.zp
+        if self.group_size is not None:
+            return qgemm.w8a8_grouped_linear(a_q, self.weight, a_scale, self.scale_weight, zp, self.group_size, self.bias,
+                                             out_dtype=out_dtype, gelu=gelu, gate=gate, residual=residual, out=out, w4=self.w_bits == 4)
         return qgemm.w8a8_linear(a_q, self.weight, a_scale, self.scale_weight, self.bias, a_sum if zp is not None else None, zp,
                                  out_dtype=out_dtype, gelu=gelu, gate=gate, residual=residual, out=out, w4=self.w_bits == 4)
 
@@ -245,7 +275,7 @@ def _to_hip_linear(lin, n_bits, sym, act_dtype, fp_gemm="torch", name="linear"):
 
     if isinstance(lin, QuantizedLinear):
         if lin.quant_mode and lin.w_quantizer is not None and lin.a_quantizer is not None:
-            return HipLinearW8A8.from_quantized(lin)
+            return HipLinearW8A8.from_quantized(lin, name)
         if lin.quant_mode and lin.w_quantizer is not None:
             if act_dtype not in (torch.bfloat16, torch.float16):
                 raise ValueError(f"{name}: the weight-only GEMM takes bf16 or fp16 activations (act_dtype {act_dtype})")
