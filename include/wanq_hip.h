@@ -64,6 +64,22 @@ int wanq_quant_rows(const void* x, int x_dtype, int8_t* q, void* scale, void* su
 int wanq_quant_rows_levels(const void* x, int x_dtype, int8_t* q, void* scale, void* sum, int vec_dtype,
                            int64_t rows, int cols, int n_levels, float floor, void* stream);
 
+/* Per-row dynamic OCP fp8 (e4m3fn) quantisation: the activation quantiser (one row = one token) and, once at conversion time, the
+ * weight quantiser (a weight [N, K] goes through it as rows = N: one row = one output channel) of wanq_gemm_fp8.
+ *   scale_r = max(absmax_r / 448, 1e-6)                          (448: the largest e4m3fn value; the floor of wanq_quant_rows)
+ *   q[r,c]  = e4m3fn_rne(clamp(x[r,c] / scale_r, -448, 448))     (true fp32 division; ONE rounding, fp32 -> e4m3fn, to nearest even,
+ *                                                                 subnormal codes kept, made by v_cvt_pk_fp8_f32 behind the clamp)
+ * x: F16 | BF16 | F32 [rows, cols], cols % 8 == 0, cols <= 16384.  q: one byte per element, OCP e4m3fn bit patterns (S.EEEE.MMM, bias
+ * 7, no infinities, 0x7f / 0xff NaN) -- NOT the e4m3fnuz format of gfx942.  scale: fp32 [rows].  There is no `sum` output: symmetric
+ * weights need none.  act: 0 = identity, 1 = tanh-GELU applied to x first (the gelu_tanh_fast_f32 of wanq_quant_rows).
+ * A row of zeros gets scale 1e-6 and codes 0.  -0 and negative values that round to zero give the code 0x80.
+ * Non-finite inputs: fmax drops NaN, so a NaN element does not enter absmax_r and its own code is unspecified (the clamp's result
+ * for a NaN); a row holding +-inf gets scale inf, codes 0 for its finite elements and unspecified codes for the infinite ones
+ * (inf / inf).  Nothing is trapped; no test pins these.
+ * Bit-identical to the torch expression (x / s).clamp(-448, 448).to(torch.float8_e4m3fn) with s = (x.abs().amax(-1) / 448).clamp(1e-6).
+ * No reference counterpart: the reference's Linear formats are integer ones. */
+int wanq_quant_rows_fp8(const void* x, int x_dtype, uint8_t* q, float* scale, int64_t rows, int cols, int act, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * LayerNorm (no bias, optional gamma) -> optional adaLN modulate -> fp output OR int8 quant (+sum).
  *   y = (x - mean) * rstd * gamma;  y = y * (1 + mscale[b]) + mshift[b]   (b = row / rows_per_batch)
@@ -413,6 +429,27 @@ int wanq_gemm_w4a8(const int8_t* a, const uint8_t* w_packed, void* out, int out_
 int wanq_gemm_w8a8_grouped(const int8_t* a, const void* w, int w_bits, const float* sw, const float* zp, int group_size,
                            void* out, int out_dtype, const void* sa, int tok_dtype, const void* bias, int ch_dtype,
                            const float* gate, const void* residual, int epi_flags, int64_t M, int N, int K, void* stream);
+
+/* fp8 W8A8 GEMM: per-token dynamic e4m3 activations against per-channel e4m3 weights (both from wanq_quant_rows_fp8), on
+ * v_mfma_scale_f32_16x16x128_f8f6f4 (e4m3 operands, unit block scales: twice the rate of the unscaled fp8 instruction) with the epilogue of
+ * wanq_gemm_bf16:
+ *   acc[m,n] = sum_k a[m,k] * w[n,k]               (a, w: OCP e4m3fn bytes, row-major [M, K] and [N, K]; every product exact in fp32,
+ *                                                   fp32 accumulation on the matrix cores)
+ *   y   = fmaf(acc * sa[m], sw[n], bias[n])        (sa fp32 [M], sw fp32 [N]; bias F16 | BF16 | F32 or NULL = 0; this order, fp32)
+ *   y   = gelu_tanh(y)                             if WANQ_EPI_GELU
+ *   y   = residual[m,n] + y * gate[n]              if WANQ_EPI_GATE_RES  (gate fp32 [N], residual of out_dtype; out may alias it)
+ *   out = cast(y) to out_dtype (F16 | BF16 | F32): one rounding.
+ * Shapes: any M >= 1 (ragged last tile in-kernel, no host padding); N % 8 == 0; K % 64 == 0 -- the kernel's K step: one 16-byte
+ * fragment read per lane, half of the 128-deep MFMA (K % 128 == 64 is a ragged last K-tile, handled in-kernel: the missing half of
+ * both fragments is zeros).  a, w, out, residual and sw
+ * 16-byte aligned, gate and bias aligned to 4 elements, sa to 4 bytes.  Anything else is refused (WANQ_E_SHAPE / WANQ_E_ARG, the
+ * message names the rule).
+ * Determinism: one kernel form, no split-K; the fp32 summation order of element (m, n) depends on K only, so a row gives the same
+ * bits at any m and in a launch of any M, and repeated calls are bit-identical.  With integer-valued operands whose partial sums
+ * stay below 2^24 the accumulator is the exact integer product.
+ * No reference counterpart (its 8-bit Linears are int8: ViDiT-Q/kernels/csrc/qgemm/w8a8/w8a8_gemm_cuda.cu). */
+int wanq_gemm_fp8(const uint8_t* a, const uint8_t* w, const float* sa, const float* sw, void* out, int out_dtype, const void* bias,
+                  int bias_dtype, const float* gate, const void* residual, int epi_flags, int64_t M, int N, int K, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Step-level elementwise work of the denoising loop in one kernel:  out[o] = sum_i coef[o][i] * in[i]  over fp32 tensors of

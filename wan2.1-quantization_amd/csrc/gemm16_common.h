@@ -1,6 +1,7 @@
 // What the two 16-bit GEMM kernels share (gemm_bf16.hip: floating-point weights; gemm_wq16.hip: integer weight codes): the tile
 // geometry, the token half of a K-tile in LDS, the MFMA fragment addresses, the fp32 epilogue and the argument rules of the two
-// extern "C" entries.
+// extern "C" entries.  The fp8 GEMM (gemm_fp8.hip) is built on the same geometry, fragment addresses, epilogue and argument rules,
+// with a K-tile of 128 one-byte elements in the same 128-byte LDS rows.
 //
 // Structure.  One 128(M) x 128(N) output tile per 256-thread workgroup (4 waves, 2 x 2, 64 x 64 each = 4 x 4 MFMA tiles), K in
 // tiles of 64.  The token half of a K-tile (128 rows of 128 B) is copied global -> LDS by LDS-DMA (global_load_lds_dwordx4, 4 per
@@ -99,11 +100,13 @@ __device__ __forceinline__ void zero_acc(v4f (&acc)[4][4]) {
     for (int j = 0; j < 4; ++j) acc[i][j] = v4f{0.f, 0.f, 0.f, 0.f};
 }
 
-// epilogue, fp32: acc + bias, or with SCALED acc * sw + bias in one fma; GELU; residual + y * gate; one rounding to OUT
-template <int OUT, bool SCALED>
+// epilogue, fp32: acc + bias, or with SCALED acc * sw + bias in one fma, or with TOKEN (gemm_fp8.hip) (acc * sa[m]) * sw + bias, the
+// per-token factor first and then one fma; GELU; residual + y * gate; one rounding to OUT
+template <int OUT, bool SCALED, bool TOKEN = false>
 __device__ __forceinline__ void epilogue16(const v4f (&acc)[4][4], int m0, int n0, int wm, int wn, int fr, int fq, int M, int N,
                                            const float* sw, const void* bias, int bias_dtype, const float* gate,
-                                           const void* residual, void* out, int epi) {
+                                           const void* residual, void* out, int epi, const float* sa = nullptr) {
+  static_assert(!TOKEN || SCALED, "the per-token factor comes with the per-channel one");
   const bool gelu = epi & WANQ_EPI_GELU, gres = epi & WANQ_EPI_GATE_RES;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -119,9 +122,12 @@ __device__ __forceinline__ void epilogue16(const v4f (&acc)[4][4], int m0, int n
       if (m >= M) continue;
       const int64_t o = (int64_t)m * N + n;
       float y[4];
+      float sm = 1.f;
+      if constexpr (TOKEN) sm = sa[m];
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        if constexpr (SCALED) y[e] = __fmaf_rn(acc[i][j][e], s4[e], b4[e]);
+        if constexpr (TOKEN) y[e] = __fmaf_rn(acc[i][j][e] * sm, s4[e], b4[e]);
+        else if constexpr (SCALED) y[e] = __fmaf_rn(acc[i][j][e], s4[e], b4[e]);
         else y[e] = acc[i][j][e] + b4[e];
       }
       if (gelu) {

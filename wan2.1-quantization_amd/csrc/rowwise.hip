@@ -270,6 +270,62 @@ static bool launch_quant_rows_wave(const void* x, int x_dtype, int8_t* q, void* 
   return true;
 }
 
+// ------------------------------------------------------------------------------ per-row dynamic OCP e4m3 (fp8) quantiser
+// scale = max(absmax / 448, 1e-6), q = e4m3fn_rne(clamp(x / scale, -448, 448)): the row frame and ladder of the int8 quantiser, the
+// true fp32 division, and one rounding, made by the packed hardware conversion (v_cvt_pk_fp8_f32: OCP e4m3fn on gfx950, round to
+// nearest even, subnormal codes kept) behind the clamp, so the conversion never meets a value past the format's largest.  Codes
+// leave as whole 8-byte chunks per lane.  Activations per token and, once at conversion time, weights per output channel.
+struct Fp8RowParams {
+  const void* x;
+  int x_dtype;
+  uint8_t* q;
+  float* scale;
+  int64_t rows;
+  int cols;
+  int act;
+};
+
+constexpr float FP8_E4M3_MAX = 448.0f;
+
+template <int WPR, int NCH>
+__global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const Fp8RowParams p) {
+  __shared__ float red_slots[4];
+  RowFrame<WPR, NCH> f;
+  if (f.surplus(p.rows)) return;
+  const RowReduce<WPR> red{red_slots, f.wave};
+  const int C = p.cols;
+  const int64_t rbase = f.row * (int64_t)C;
+
+  float v[NCH][8];
+  bool ok[NCH];
+  f.load(p.x, p.x_dtype, rbase, C, v, ok);
+  if (p.act == 1) {
+#pragma unroll
+    for (int i = 0; i < NCH; ++i)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[i][j] = gelu_tanh_fast_f32(v[i][j]);  // (a slot past the row end stays 0)
+  }
+  float m = 0.f;
+#pragma unroll
+  for (int i = 0; i < NCH; ++i)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(v[i][j]));
+  const float scale = dyn_scale(red.template reduce<OpMax>(m, 0), FP8_E4M3_MAX, 1e-6f);
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+    if (!ok[i]) continue;
+    float t[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) t[j] = __builtin_amdgcn_fmed3f(v[i][j] / scale, -FP8_E4M3_MAX, FP8_E4M3_MAX);
+    int lo = __builtin_amdgcn_cvt_pk_fp8_f32(t[0], t[1], 0, false);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(t[2], t[3], lo, true);
+    int hi = __builtin_amdgcn_cvt_pk_fp8_f32(t[4], t[5], 0, false);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(t[6], t[7], hi, true);
+    *reinterpret_cast<uint2*>(p.q + rbase + f.col(i)) = make_uint2((uint32_t)lo, (uint32_t)hi);
+  }
+  if (f.lane == 0 && f.sub == 0) p.scale[f.row] = scale;
+}
+
 // x * premul (-> LayerNorm + modulate first when `ln`) -> fp output and / or int8 quantise: the transform entry points of
 // rotate.hip with had_k == 0 (channel scale without rotation: SmoothQuant, Q/smooth_quant/sq_quant_layer.py:52-60).
 int premul_quant_rows(bool ln, const void* x, int x_dtype, const void* gamma, const void* mshift, const void* mscale,
@@ -317,6 +373,20 @@ extern "C" int wanq_quant_rows_levels(const void* x, int x_dtype, int8_t* q, voi
   p.x = x; p.x_dtype = x_dtype; p.q = q; p.scale = scale; p.sum = sum; p.vec_dtype = vec_dtype;
   p.rows = rows; p.cols = cols; p.rows_per_batch = 1; p.levels = (float)n_levels; p.floor = floor;
   return launch_rowwise<false>(p, (hipStream_t)stream, "wanq_quant_rows_levels");
+}
+
+extern "C" int wanq_quant_rows_fp8(const void* x, int x_dtype, uint8_t* q, float* scale, int64_t rows, int cols, int act,
+                                   void* stream) {
+  WANQ_REQUIRE(x && q && scale, WANQ_E_ARG, "wanq_quant_rows_fp8: x, q and scale must be non-NULL");
+  WANQ_REQUIRE(is_fp(x_dtype), WANQ_E_ARG, "wanq_quant_rows_fp8: bad x dtype %d", x_dtype);
+  WANQ_REQUIRE(act == 0 || act == 1, WANQ_E_ARG, "wanq_quant_rows_fp8: act must be 0 or 1");
+  if (int e = check_rows_cols("wanq_quant_rows_fp8", rows, cols)) return e;
+  if (rows == 0) return WANQ_OK;
+  const Fp8RowParams p{x, x_dtype, q, scale, rows, cols, act};
+  row_ladder(cols, rows, [&](auto wpr, auto nch, dim3 grid) {
+    hipLaunchKernelGGL((quant_rows_fp8_kernel<decltype(wpr)::value, decltype(nch)::value>), grid, dim3(256), 0, (hipStream_t)stream, p);
+  });
+  return check_launch("wanq_quant_rows_fp8");
 }
 
 extern "C" int wanq_layernorm_rows(const void* x, int x_dtype, const void* gamma, const void* mshift,

@@ -176,3 +176,58 @@ class DynamicQuantizer(BaseQuantizer):
             return self._asym(x, False, True)[1]
         q, scale, _ = self.quantize_int8(x, want_sum=False)
         return q.float() * scale.unsqueeze(-1)
+
+
+# ---- OCP fp8 (e4m3fn): `format: fp8_e4m3` ---------------------------------------------------------------------------------
+FP8_FORMAT = "fp8_e4m3"
+FP8_MAX = 448.0
+_FP8_LUT = {}
+
+
+def fp8_decode(codes):
+    """fp32 values of uint8 e4m3fn bit patterns (exact; a 256-entry table on the codes' device)."""
+    lut = _FP8_LUT.get(codes.device)
+    if lut is None:
+        lut = _FP8_LUT[codes.device] = torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).float().to(codes.device)
+    return lut[codes.long()]
+
+
+def fp8_quant_rows(x, gelu=False):
+    """(codes uint8, scale fp32 [rows]) of the per-row dynamic e4m3 quantiser: scale = max(absmax / 448, 1e-6), codes =
+    e4m3fn_rne(clamp(x / scale, -448, 448)).  On the GPU wanq_quant_rows_fp8; in host memory the torch expression it is bit-equal to
+    (this torch build casts fp32 -> float8_e4m3fn on the CPU to nearest even and keeps subnormals)."""
+    if x.is_cuda:
+        return fused.quant_rows_fp8(x.contiguous(), gelu)
+    x = x.float()
+    if gelu:
+        x = torch.nn.functional.gelu(x, approximate="tanh")
+    am = x.abs().amax(dim=-1, keepdim=True)
+    s = (am / _full(am, FP8_MAX)).clamp_min(1e-6)
+    codes = (x / s).clamp(-FP8_MAX, FP8_MAX).to(torch.float8_e4m3fn).view(torch.uint8)
+    return codes, s.reshape(-1)
+
+
+class Fp8Quantizer(BaseQuantizer):
+    """`format: fp8_e4m3` of a `weight:` or `act:` section (n_bits 8, sym True): one fp32 scale per row -- per output channel for a
+    weight, per token for an activation -- and OCP e4m3fn codes.  `delta` [rows, 1] is the scale, `zero_point` zeros, as the integer
+    quantisers keep them (save / load_quant_param_dict).  The scale is a function of the tensor alone (absmax / 448, floored at
+    1e-6): nothing is fitted or calibrated, so it is derived again at every call, for a weight too."""
+
+    def __init__(self, quant_config):
+        super().__init__(quant_config)
+        self.format = FP8_FORMAT
+
+    def codes_and_scale(self, x, gelu=False):
+        codes, scale = fp8_quant_rows(x, gelu)
+        self.delta, self.zero_point = scale.unsqueeze(-1), torch.zeros(scale.shape[0], 1, device=scale.device)
+        return codes, scale
+
+    def codes_and_dequant(self, x, want_codes=True, want_dequant=True):
+        codes, scale = self.codes_and_scale(x)
+        return codes, (fp8_decode(codes) * scale.unsqueeze(-1)) if want_dequant else None
+
+    def quantize(self, x):
+        return fp8_decode(self.codes_and_scale(x)[0])
+
+    def forward(self, x):
+        return self.codes_and_dequant(x, False, True)[1]

@@ -17,7 +17,7 @@ from viditq_extension import qgemm
 
 from ..config import ListConfig
 from ..quarot import quarot_utils
-from .base_quantizer import DynamicQuantizer, StaticQuantizer
+from .base_quantizer import FP8_FORMAT, DynamicQuantizer, Fp8Quantizer, StaticQuantizer, fp8_decode
 from .mixed_precision_quantizer import MixedPrecisionDynamicQuantizer, MixedPrecisionStaticQuantizer
 
 
@@ -28,6 +28,7 @@ class QuantizedLinear(nn.Linear):
     def __init__(self, in_features, out_features, bias, device, quant_config, fp_module, module_name=None):
         super().__init__(in_features, out_features, bias, device)
         self.fp_module, self.q_cfg = fp_module, quant_config
+        self.fp8 = self._checked_format(quant_config, module_name)
         self.group_size = self._checked_group_size(quant_config, module_name, fp_module.weight.device)
         self.w_quantizer = self.a_quantizer = None
         self.channel_mask = None
@@ -37,7 +38,8 @@ class QuantizedLinear(nn.Linear):
         self._zp_gemm = self._wq16_vecs = None
         if quant_config.get("weight", None) is not None:
             wq = quant_config["weight"]
-            self.w_quantizer = (MixedPrecisionStaticQuantizer if isinstance(wq["n_bits"], ListConfig) else StaticQuantizer)(wq)
+            self.w_quantizer = (Fp8Quantizer if self.fp8 else
+                                MixedPrecisionStaticQuantizer if isinstance(wq["n_bits"], ListConfig) else StaticQuantizer)(wq)
             self._requantize(fp_module.weight.data)
             self.w_quantizer.init_done = True
         else:
@@ -46,10 +48,44 @@ class QuantizedLinear(nn.Linear):
         self.bias = fp_module.bias
         if quant_config.get("act", None) is not None:
             aq = quant_config["act"]
-            self.a_quantizer = (MixedPrecisionDynamicQuantizer if isinstance(aq["n_bits"], ListConfig) else DynamicQuantizer)(aq)
+            self.a_quantizer = (Fp8Quantizer if self.fp8 else
+                                MixedPrecisionDynamicQuantizer if isinstance(aq["n_bits"], ListConfig) else DynamicQuantizer)(aq)
         self.use_kernel = False
         self.quant_mode = True
         self.module_name = module_name
+
+    def _checked_format(self, quant_config, module_name):
+        """True when the config's `weight:` and `act:` sections both say `format: fp8_e4m3` (per-token dynamic e4m3 activations against
+        per-channel e4m3 weights, wanq_gemm_fp8), False when neither has the key; every other combination is refused here, before
+        any weight is quantised, and the message names the layer and the key."""
+        wq, aq = quant_config.get("weight", None), quant_config.get("act", None)
+        fw, fa = (None if wq is None else wq.get("format", None)), (None if aq is None else aq.get("format", None))
+        if fw is None and fa is None:
+            return False
+        name = module_name or type(self).__name__
+        for sec, f in (("weight", fw), ("act", fa)):
+            if f is not None and f != FP8_FORMAT:
+                raise ValueError(f"{name}: {sec}.format={f!r} is not a known format (the one format key is {FP8_FORMAT!r})")
+        if fw is None or fa is None:
+            raise NotImplementedError(f"{name}: format: {FP8_FORMAT} must be set in both the `weight:` and the `act:` section (it is "
+                                      f"missing from `{'weight' if fw is None else 'act'}:`): the fp8 GEMM takes e4m3 codes on both sides")
+        for sec, q in (("weight", wq), ("act", aq)):
+            if isinstance(q["n_bits"], ListConfig):
+                raise NotImplementedError(f"{name}: {sec}.format with a bit-width list (mixed precision) is not supported: e4m3 is one "
+                                          "8-bit format")
+            if q["n_bits"] != 8:
+                raise NotImplementedError(f"{name}: {sec}.format: {FP8_FORMAT} needs {sec}.n_bits: 8 (it is {q['n_bits']!r})")
+            if not q.get("sym", False):
+                raise NotImplementedError(f"{name}: {sec}.format: {FP8_FORMAT} needs {sec}.sym: True: a floating-point code has no "
+                                          "zero point")
+        if wq.get("group_size", None) is not None:
+            raise NotImplementedError(f"{name}: weight.format with weight.group_size is not supported: the fp8 GEMM applies one weight "
+                                      "scale per output channel")
+        if self.uses_mask or self.uses_rotation:
+            raise NotImplementedError(f"{name}: weight.format / act.format with {type(self).__name__} is not supported: the SmoothQuant "
+                                      "/ QuaRot / ViDiT layer classes condition an integer quantiser (leave the layer to the plain "
+                                      "QuantizedLinear)")
+        return True
 
     def _checked_group_size(self, quant_config, module_name, device=None):
         """`weight.group_size` of the config (None: one scale per output channel), or the refusal of what has no group-wise form,
@@ -91,7 +127,7 @@ class QuantizedLinear(nn.Linear):
     def int_weight(self):
         """int8 codes [N, K].  4-bit layers keep them PACKED in HBM (two per byte, qgemm.pack_w4 layout); this view unpacks."""
         c = self._codes
-        if c is not None and c.dtype == torch.uint8:
+        if c is not None and c.dtype == torch.uint8 and not self.fp8:  # (an fp8 layer's uint8 codes are e4m3 bytes, one per weight)
             return qgemm.unpack_w4(c, bias=8)
         return c
 
@@ -145,6 +181,8 @@ class QuantizedLinear(nn.Linear):
             return self._forward_weight_only(x)
         if not self.quant_mode or self.w_quantizer is None or self.a_quantizer is None:
             return self.fp_module(x, *args, **kwargs)
+        if self.fp8:
+            return self._forward_fp8(x)
         if self.group_size is not None:
             return self._forward_grouped(x)
         shape = x.shape
@@ -167,6 +205,23 @@ class QuantizedLinear(nn.Linear):
             # (zp_a s_a)[token] x rowsum(w_dq)[channel]  (Q/base/base_quantizer.py:130-162; no Wan configuration uses this branch)
             t_a = (self.a_quantizer.zero_point.reshape(-1).float() * scale).to(y.dtype)
             y = torch.addcmul(y, t_a.unsqueeze(1), self.weight.data.float().sum(dim=1).to(y.dtype).unsqueeze(0))
+        return y.view(*shape[:-1], self.out_features)
+
+    def _forward_fp8(self, x):
+        """`format: fp8_e4m3`: the activation is quantised per token to e4m3 (Fp8Quantizer) and multiplied by the layer's e4m3 weight
+        codes, one fp32 scale per token and per output channel.  On the GPU these are kernel mode's two entries,
+        fused.quant_rows_fp8 and qgemm.fp8_linear.  In host memory, and for a shape the GEMM refuses, the same numbers through torch:
+        F.linear of the dequantised activation and the dequantised weight, in fp32."""
+        shape = x.shape
+        x2 = x.reshape(-1, shape[-1])
+        out_dtype = x.dtype if x.dtype in (torch.float16, torch.bfloat16, torch.float32) else torch.float32
+        a_q, a_s = self.a_quantizer.codes_and_scale(x2)
+        if x2.is_cuda and qgemm.fp8_linear_refusal(x2.shape[0], self.out_features, self.in_features) is None:
+            y = qgemm.fp8_linear(a_q, self._codes, a_s, self.w_quantizer.delta.reshape(-1).float().contiguous(),
+                                 None if self.bias is None else self.bias.detach().float().contiguous(), out_dtype=out_dtype)
+        else:
+            b = None if self.bias is None else self.bias.detach().float()
+            y = F.linear(fp8_decode(a_q) * a_s.unsqueeze(-1), self.weight.data.float(), b).to(out_dtype)
         return y.view(*shape[:-1], self.out_features)
 
     def _forward_grouped(self, x):

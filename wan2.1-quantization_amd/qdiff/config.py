@@ -3,7 +3,11 @@
 `isinstance(n_bits, ListConfig)`).  Schema: ViDiT-Q/examples/Wan2.1/quant_configs/config.yaml, plus one key of
 this repository: `weight.group_size: <int>` -- one (delta, zero_point) per output channel and per group of that many input
 channels, with or without an `act:` section (no bit-width list, no transform section; it must divide in_features; with an `act:`
-section the layer's weight must be on the GPU; QuantizedLinear refuses everything else by layer name when it is built)."""
+section the layer's weight must be on the GPU; QuantizedLinear refuses everything else by layer name when it is built), and
+`format: fp8_e4m3` in BOTH the `weight:` and the `act:` section -- OCP e4m3fn codes with one fp32 scale per output channel and per
+token (absmax / 448) instead of int8 codes, on wanq_gemm_fp8; `n_bits: 8, sym: True` stay as written.  Refused by layer name when
+the layer is built: the key in only one section, with `group_size`, with `sym: False`, with `n_bits` other than 8 or a bit-width
+list, and on a SmoothQuant / QuaRot / ViDiT layer."""
 import yaml
 
 

@@ -50,6 +50,8 @@ PROTOTYPES = {
     "wanq_gemm_wq16": [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
     "wanq_gemm_wq16_grouped": [_vp, _vp, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
     "wanq_gemm_w8a8_grouped": [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
+    "wanq_quant_rows_fp8": [_vp, _i, _vp, _vp, _i64, _i, _i, _vp],
+    "wanq_gemm_fp8": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
     "wanq_lincomb":[_i, _i, _vp, _vp, _vp, _i64, _vp],
     "wanq_linear_f32": [_vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp],
     "wanq_time_sinusoid": [_vp, _i, _vp, _i, _i, _vp],

@@ -79,6 +79,18 @@ def gelu_quant_sum(input, sum_output, scaling):
     return _quant_rows(input, sum_output, scaling, 1, 0)
 
 
+def quant_rows_fp8(x, gelu=False):
+    """Per-row dynamic OCP e4m3 quantisation (wanq_quant_rows_fp8): -> (codes uint8 of x's shape, e4m3fn bit patterns; scale fp32
+    [rows]) with scale = max(absmax / 448, 1e-6) and codes = e4m3fn_rne(clamp(x / scale, -448, 448)); `gelu`: the tanh-GELU of the
+    int8 quantiser applied to x first.  Activations per token, and a weight [N, K] per output channel."""
+    rows, cols = _rows_cols("x", x)
+    codes = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    scale = torch.empty(rows, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _C.call("wanq_quant_rows_fp8", _C.ptr(x), _C.dt(x), _C.ptr(codes), _C.ptr(scale), rows, cols, 1 if gelu else 0, _C.stream())
+    return codes, scale
+
+
 def _layernorm(output, input, weight, shift_msa, scale_msa, sum_output, scaling, epsilon, quant):
     rows, cols = _rows_cols("input", input)
     _C.check_gpu("output", output)

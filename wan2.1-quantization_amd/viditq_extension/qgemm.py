@@ -409,3 +409,54 @@ def w8a8_grouped_linear_refusal(M, N, K, group_size, w_bits, sym):
     if K < group_size or K % group_size:
         return f"K={K} must be a positive multiple of group_size={group_size}"
     return None
+
+
+# ---- fp8 (OCP e4m3fn) activations x fp8 weights ------------------------------------------------------------------------
+FP8_K_STEP = 64  # wanq_gemm_fp8's K multiple: one 16-byte fragment read per lane, half of the 128-deep fp8 MFMA
+
+
+def fp8_linear(a_q, w_q, a_scale, w_scale, bias=None, out_dtype=None, gelu=False, gate=None, residual=None, out=None):
+    """y = epilogue(a_scale[m] * w_scale[n] * a_q[M, K] @ w_q[N, K]^T) on the fp8 matrix cores (wanq_gemm_fp8, csrc/gemm_fp8.hip):
+    a_q and w_q uint8, OCP e4m3fn bit patterns as `fused.quant_rows_fp8` writes them; a_scale fp32 [M], w_scale fp32 [N].  fp32
+    accumulation, then y = fma(acc * a_scale[m], w_scale[n], bias[n]) and the epilogue of `fp_linear` (`gelu`; gate fp32 [N] +
+    residual [M, N] of out_dtype, which may alias `out`), one rounding to out_dtype (default bf16).  K % 64 == 0, N % 8 == 0.  A
+    row's bits do not depend on M or on where the row sits in the launch.  Not counted by the int8 timer (`set_timer`)."""
+    for name, t in (("a_q", a_q), ("w_q", w_q)):
+        _C.check_gpu(name, t)
+        _C.check_contig(name, t)
+        _C.check_dtype(name, t, torch.uint8)
+        if t.dim() != 2:
+            raise RuntimeError(f"Tensor {name} must have dimension number (2)")
+    M, K = a_q.shape
+    N = w_q.shape[0]
+    _C.check_shape("w_q", w_q, N, K)
+    why = fp8_linear_refusal(M, N, K)
+    if why is not None:
+        raise RuntimeError(f"fp8_linear: {why}")
+    _check_vec("a_scale", a_scale, M, (torch.float32,))
+    _check_vec("w_scale", w_scale, N, (torch.float32,))
+    if a_scale is None or w_scale is None:
+        raise RuntimeError("fp8_linear: a_scale and w_scale must be given")
+    out_dtype = out_dtype or torch.bfloat16
+    _check_vec("bias", bias, N, _BIAS16)
+    epi = _epi_flags(gelu, gate, residual, M, N, out_dtype)
+    out = _out_for(out, M, N, out_dtype, a_q.device)
+    _C.check_same_device(a_q, w_q, a_scale, w_scale, bias, gate, residual, out)
+    with torch.cuda.device(a_q.device):
+        _C.call("wanq_gemm_fp8", _C.ptr(a_q), _C.ptr(w_q), _C.ptr(a_scale), _C.ptr(w_scale), _C.ptr(out), _C.dt(out_dtype),
+                _C.ptr(bias), _C.dt(bias) if bias is not None else _C.F32, _C.ptr(gate), _C.ptr(residual), epi, M, N, K, _C.stream())
+    return out
+
+
+def fp8_linear_refusal(M, N, K):
+    """Why wanq_gemm_fp8 would refuse an [M, K] x [N, K] product (None = accepted): the shape rules of include/wanq_hip.h in the
+    order the entry checks them; see `fp_linear_refusal`."""
+    if M < 0 or M >= (1 << 31) - 128:
+        return f"M={M} out of range"
+    if N < 8 or N % 8:
+        return f"N={N} must be a positive multiple of 8"
+    if K < FP8_K_STEP or K % FP8_K_STEP:
+        return f"K={K} must be a positive multiple of {FP8_K_STEP}"
+    if ((M + 127) // 128) * ((N + 127) // 128) >= (1 << 31):
+        return "too many tiles"
+    return None

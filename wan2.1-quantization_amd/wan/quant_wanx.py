@@ -74,6 +74,9 @@ class QuantWanModel(WanModel, QuantModel):
                 wq = mod.w_quantizer
                 premul, _ = mod._act_transform()
                 if reference_format:
+                    if getattr(mod, "fp8", False):
+                        raise NotImplementedError(f"{name}: the reference's int_weight.pt format holds int8 codes (the layer is "
+                                                  "format: fp8_e4m3; save with reference_format=False)")
                     if getattr(mod, "group_size", None) is not None:
                         raise NotImplementedError(f"{name}: the reference's int_weight.pt format has one scale per output channel "
                                                   "(weight.group_size is set; save with reference_format=False)")
@@ -88,7 +91,8 @@ class QuantWanModel(WanModel, QuantModel):
                     if mod.bias is not None:
                         sd[name + ".bias"] = mod.bias.detach().to(f16).clone()
                 else:
-                    # 8-bit: int8 [N, K]; 4-bit: uint8 [N, K/2], the packed nibbles exactly as the GEMM reads them
+                    # 8-bit: int8 [N, K]; 4-bit: uint8 [N, K/2], the packed nibbles exactly as the GEMM reads them; format: fp8_e4m3:
+                    # uint8 [N, K], the e4m3 bytes, with their per-channel scales
                     # (weight.group_size: the parameters as the group-wise GEMM reads them, [K / g, N])
                     grouped = getattr(mod, "group_size", None) is not None
                     sd[name + ".weight"] = mod._codes.clone()
@@ -172,7 +176,7 @@ class QuantWanModel(WanModel, QuantModel):
                                         [(hb, "ffn0", "ffn.0"), (hb, "ffn2", "ffn.2")]:
                     lin = getattr(owner, attr)
                     weight_only = getattr(lin, "weight_only", False)  # HipLinearWq16: the same keys, no act_premul
-                    if not lin.quantized and not weight_only:
+                    if not lin.quantized and not weight_only and not getattr(lin, "fp8", False):
                         continue
                     base = f"blocks.{i}.{key}"
                     # The two formats carry no marker.  What tells them apart is that reference_format=True writes fp16 scales and the

@@ -270,10 +270,56 @@ class HipLinearWq16(_HipLinearInt):
                                  residual=residual, out=out, w4=self.w_bits == 4)
 
 
+class HipLinearFp8(nn.Module):
+    """An fp8 W8A8 Linear (`format: fp8_e4m3` in the config's `weight:` and `act:` sections): `weight` uint8 [N, K], OCP e4m3fn codes
+    of the weight quantised per output channel by wanq_quant_rows_fp8; `scale_weight` fp32 [N], absmax / 448; `bias` fp32.  Its input
+    is the block's activation quantised per token by the same entry (_LnSrc.fp8 / _FpSrc.fp8: codes + fp32 scale, shared by every
+    fp8 consumer of a source), and the product is qgemm.fp8_linear (csrc/gemm_fp8.hip) with GELU and gate + residual in its
+    epilogue.  No zero point, no activation transform; the int8 producers and their prefetch skip it."""
+    quantized = False   # not an int8 consumer
+    fp8 = True
+    act_key = "fp8"
+    act_premul = None
+    zp_weight = None
+
+    def __init__(self, in_features, out_features, bias=True, name="linear"):
+        super().__init__()
+        why = qgemm.fp8_linear_refusal(1, out_features, in_features)
+        if why is not None:
+            raise NotImplementedError(f"{name}: format: fp8_e4m3 has no kernel-mode form for this layer ({out_features}, "
+                                      f"{in_features}): {why}")
+        self.in_features, self.out_features = in_features, out_features
+        self.register_buffer("weight", torch.empty(out_features, in_features, dtype=torch.uint8))
+        self.register_buffer("scale_weight", torch.empty(out_features, dtype=torch.float32))
+        self.register_buffer("bias", torch.empty(out_features, dtype=torch.float32) if bias else None)
+
+    def refresh_zp_gemm(self):
+        """(the checkpoint loader's hook: nothing is derived from the loaded buffers)"""
+
+    @classmethod
+    def from_quantized(cls, ql, name="linear"):
+        """From a plain qdiff QuantizedLinear built with `format: fp8_e4m3`: the same codes and scales."""
+        m = cls(ql.in_features, ql.out_features, ql.bias is not None, name).to(ql.fp_module.weight.device)
+        if tuple(ql._codes.shape) != tuple(m.weight.shape) or ql._codes.dtype != torch.uint8:
+            raise ValueError(f"{name}: codes {tuple(ql._codes.shape)} {ql._codes.dtype} do not fit {tuple(m.weight.shape)} uint8")
+        m.weight.copy_(ql._codes)
+        m.scale_weight.copy_(ql.w_quantizer.delta.reshape(-1).float())
+        if ql.bias is not None:
+            m.bias.copy_(ql.bias.detach().float())
+        return m
+
+    def forward(self, a_q, a_scale, out_dtype=torch.bfloat16, gelu=False, gate=None, residual=None, out=None):
+        """Reads `weight` as it is now (--dit_fsdp re-points it at views of the gathered buffer)."""
+        return qgemm.fp8_linear(a_q, self.weight, a_scale, self.scale_weight, self.bias, out_dtype, gelu=gelu, gate=gate,
+                                residual=residual, out=out)
+
+
 def _to_hip_linear(lin, n_bits, sym, act_dtype, fp_gemm="torch", name="linear"):
     from qdiff.base.quant_layer import QuantizedLinear
 
     if isinstance(lin, QuantizedLinear):
+        if lin.quant_mode and getattr(lin, "fp8", False):
+            return HipLinearFp8.from_quantized(lin, name)
         if lin.quant_mode and lin.w_quantizer is not None and lin.a_quantizer is not None:
             return HipLinearW8A8.from_quantized(lin, name)
         if lin.quant_mode and lin.w_quantizer is not None:
@@ -337,6 +383,13 @@ class _LnSrc:
         for i, lin in enumerate(todo):
             self.cache[lin.act_key] = (qs[i], vec[i, 0], vec[i, 1])
 
+    def fp8(self, lin):
+        """(e4m3 codes, fp32 scale) for the fp8 consumers (HipLinearFp8), one copy for all of them: quantised from the fp32 row, what
+        a simulation-mode quantiser sees.  (A fused LayerNorm + modulate + fp8 producer would save the fp32 round trip.)"""
+        if "fp8" not in self.cache:
+            self.cache["fp8"] = fused.quant_rows_fp8(self.fp32())
+        return self.cache["fp8"]
+
     def fp(self):
         if "fp" not in self.cache:
             out = torch.empty(self.x.shape, dtype=self.blk.act_dtype, device=self.x.device)
@@ -375,6 +428,13 @@ class _FpSrc:
                 q = fused.rotate_quant(self.t, lin.act_premul, lin.rot, qs[1], qs[0])
             self.cache[key] = (q, qs[0], qs[1])
         return self.cache[key]
+
+    def fp8(self, lin):
+        """(e4m3 codes, fp32 scale) of the 16-bit tensor for the fp8 consumers, one copy for all of them; `gelu`: the quantiser
+        applies the tanh-GELU itself (its act = 1), as gelu_quant_sum does for the int8 consumers."""
+        if "fp8" not in self.cache:
+            self.cache["fp8"] = fused.quant_rows_fp8(self.t, gelu=self.gelu)
+        return self.cache["fp8"]
 
     def fp32(self):
         if "fp32" not in self.cache:
@@ -494,6 +554,11 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         """y = lin(src) with the producer / epilogue fusion the layer's kind allows.  With `residual` (the fp32
         stream) the result is residual + y*gate written in place."""
         out_dtype = out_dtype or self.act_dtype
+        if getattr(lin, "fp8", False):
+            q, s = src.fp8(lin)
+            if residual is not None:
+                return lin(q, s, torch.float32, gate=gate.float().contiguous(), residual=residual, out=residual)
+            return lin(q, s, out_dtype, gelu=gelu)
         if lin.quantized and lin.act_quantizer is not None:
             return self._linear_any_act(lin, src, out_dtype, gelu, gate, residual)
         if lin.quantized:
@@ -668,7 +733,8 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         # the GELU in the GEMM epilogue, whose store loop is vector-bound; cfg-B, tools/probes/ffn_gelu_placement.py); with a
         # rotation in front of ffn.2, or a floating-point ffn.2, it stays in ffn.0's epilogue.
         h = _LnSrc(self, x, None, e[:, 3], e[:, 4])
-        late_gelu = self.ffn0.quantized and self.ffn2.quantized and self.ffn2.act_key is None
+        late_gelu = (self.ffn0.quantized and self.ffn2.quantized and self.ffn2.act_key is None) or \
+            (getattr(self.ffn0, "fp8", False) and getattr(self.ffn2, "fp8", False))  # fp8: the quantiser's act = 1
         hid = self._linear(self.ffn0, h, gelu=not late_gelu)
         self._linear(self.ffn2, _FpSrc(hid, gelu=late_gelu), gate=e[0, 5].contiguous(), residual=x)
         return x
