@@ -80,6 +80,28 @@ int wanq_quant_rows_levels(const void* x, int x_dtype, int8_t* q, void* scale, v
  * No reference counterpart: the reference's Linear formats are integer ones. */
 int wanq_quant_rows_fp8(const void* x, int x_dtype, uint8_t* q, float* scale, int64_t rows, int cols, int act, void* stream);
 
+/* OCP Microscaling (MX) block quantisation: one E8M0 power-of-two scale per block of 32 consecutive columns.  The activation
+ * quantiser (fmt e4m3) and, once at conversion time, the weight quantiser (a weight [N, K] goes through it as rows = N, either
+ * format) of wanq_gemm_mx.  For row r and block b (columns 32 b .. 32 b + 31):
+ *   amax = max |x| over the block;  E = the biased fp32 exponent field of amax, (bits >> 23) & 0xff (0 for amax = 0 and for fp32
+ *          subnormals)
+ *   s    = clamp(E - emax, 0, 254)          scale byte; the block scale is 2^(s - 127); emax = 8 (e4m3), 2 (e2m1); 255, the E8M0
+ *                                           NaN, is never written
+ *   c    = rne_fmt(clamp(ldexp(x, 127 - s), -max, max))     max = 448 (e4m3), 6 (e2m1); ONE rounding, to nearest even, subnormal
+ *                                           codes kept
+ * fmt: WANQ_MX_E4M3 -- q [rows, cols] bytes, the OCP e4m3fn bit patterns of wanq_quant_rows_fp8;  WANQ_MX_E2M1 -- q [rows, cols / 2]
+ * bytes, two 4-bit codes per byte, element k in byte k / 2 with even k in the low nibble; a code is the sign in bit 3 and the
+ * magnitude index into {0, 0.5, 1, 1.5, 2, 3, 4, 6} in bits 0-2.  scale_u8: uint8 [rows, cols / 32], row-major.
+ * x: F16 | BF16 | F32 [rows, cols], cols % 32 == 0, cols <= 16384.  act: 0 = identity, 1 = tanh-GELU applied to x first (the
+ * gelu_tanh_fast_f32 of wanq_quant_rows).  -0 and negative values that round to zero keep their sign bit.
+ * Non-finite inputs: fmax drops NaN, so a NaN element does not enter amax and its own code is unspecified; a block holding +-inf
+ * gets s = 255 - emax and unspecified codes for the infinite elements.  Nothing is trapped; no test pins these.
+ * Bit-identical to the host expression mx_quant_rows of qdiff/base/base_quantizer.py.
+ * No reference counterpart: the reference's Linear formats are integer ones. */
+enum { WANQ_MX_E4M3 = 0, WANQ_MX_E2M1 = 1 };
+int wanq_quant_rows_mx(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int fmt, int act,
+                       void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * LayerNorm (no bias, optional gamma) -> optional adaLN modulate -> fp output OR int8 quant (+sum).
  *   y = (x - mean) * rstd * gamma;  y = y * (1 + mscale[b]) + mshift[b]   (b = row / rows_per_batch)
@@ -450,6 +472,27 @@ int wanq_gemm_w8a8_grouped(const int8_t* a, const void* w, int w_bits, const flo
  * No reference counterpart (its 8-bit Linears are int8: ViDiT-Q/kernels/csrc/qgemm/w8a8/w8a8_gemm_cuda.cu). */
 int wanq_gemm_fp8(const uint8_t* a, const uint8_t* w, const float* sa, const float* sw, void* out, int out_dtype, const void* bias,
                   int bias_dtype, const float* gate, const void* residual, int epi_flags, int64_t M, int N, int K, void* stream);
+
+/* MX GEMM: MXFP8 (e4m3) activations against MXFP8 (e4m3) or MXFP4 (e2m1) weights, both from wanq_quant_rows_mx, on
+ * v_mfma_scale_f32_16x16x128_f8f6f4 with the E8M0 block scales applied by the matrix cores, and the epilogue of wanq_gemm_bf16:
+ *   acc[m,n] = sum_b 2^(sa[m,b] - 127) 2^(sw[n,b] - 127) sum_{k in block b} a[m,k] * w[n,k]      (fp32 accumulation on the matrix cores;
+ *                                                   every product is exact in fp32)
+ *   y   = acc + bias[n]                            (bias F16 | BF16 | F32 or NULL = 0; no fp32 row or channel scale: the hardware has
+ *                                                   applied every scale)
+ *   y   = gelu_tanh(y)                             if WANQ_EPI_GELU
+ *   y   = residual[m,n] + y * gate[n]              if WANQ_EPI_GATE_RES  (gate fp32 [N], residual of out_dtype; out may alias it)
+ *   out = cast(y) to out_dtype (F16 | BF16 | F32): one rounding.
+ * a: e4m3 bytes [M, K].  w_fmt WANQ_MX_E4M3: w e4m3 bytes [N, K];  WANQ_MX_E2M1: w packed nibbles [N, K / 2].  sa_u8 [M, K / 32],
+ * sw_u8 [N, K / 32]: E8M0 bytes, 4-byte aligned (a K-tile's four bytes of a row are read as one dword).
+ * Shapes: any M >= 1 (ragged last tile in-kernel); N % 8 == 0; K % 128 == 0 (one K-tile = one 128-deep MFMA = four blocks).  a, w, out
+ * and residual 16-byte aligned, gate and bias aligned to 4 elements.  Anything else is refused (WANQ_E_SHAPE / WANQ_E_ARG, the
+ * message names the rule).
+ * Determinism: one kernel form per weight format, no split-K; the summation order of element (m, n) depends on K only, so a row
+ * gives the same bits at any m and in a launch of any M, and repeated calls are bit-identical.
+ * No reference counterpart (its Linears are integer ones: ViDiT-Q/kernels/csrc/qgemm/w8a8/w8a8_gemm_cuda.cu). */
+int wanq_gemm_mx(const uint8_t* a, const uint8_t* w, const uint8_t* sa_u8, const uint8_t* sw_u8, int w_fmt, void* out, int out_dtype,
+                 const void* bias, int bias_dtype, const float* gate, const void* residual, int epi_flags, int64_t M, int N, int K,
+                 void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Step-level elementwise work of the denoising loop in one kernel:  out[o] = sum_i coef[o][i] * in[i]  over fp32 tensors of

@@ -1,0 +1,602 @@
+"""The OCP MX Linears on the GPU: the block quantiser (csrc/rowwise.hip, wanq_quant_rows_mx / fused.quant_rows_mx), the GEMM
+(csrc/gemm_mx.hip, wanq_gemm_mx / qgemm.mx_linear) and what is built on them: simulation mode of a QuantizedLinear with `format:
+mxfp8_e4m3` / `mxfp4_e2m1`, kernel mode's HipLinearMx, the integer checkpoint and the entry points, with
+quant_configs/w8a8_mxfp8_all_linears.yaml and w4a8_mxfp4_all_linears.yaml.
+
+Contract (include/wanq_hip.h): per row and block of 32 columns  s = clamp(E(amax) - emax, 0, 254),  c = rne(clamp(x 2^(127 - s)));
+    acc = sum_b 2^(sa[m,b] - 127) 2^(sw[n,b] - 127) sum_{k in b} a[m,k] w[n,k] (fp32);  y = acc + bias;  GELU;  residual + y * gate.
+The quantiser is compared bit for bit with the host expression (qdiff/base/base_quantizer.py: mx_quant_rows_host, pinned value by
+value in tests/test_mx_abi.py).  Probes 1-3 establish what the matrix instruction does with a fragment and with the scale operands --
+which k a fragment byte / nibble is, which (row, block) a lane's scale byte belongs to -- with one-hot operands and single raised scale
+bytes; every expected value is an exact small number.  The integer tests use integer-valued (and half-integer e2m1) operands and scale
+exponents in {-1, 0, 1}: every partial sum is a multiple of 2^-3 below 2^19, exact in fp32 in any order, so the output must EQUAL the
+float64 evaluation.
+
+Bound on random data: that of tests/test_gpu_fp8.py::bound_case with unit fp32 scales, S = sum_k |a w| over the DEQUANTISED operands
+(every product is exact in fp32, the only error is the accumulation): |y - y64| <= MX_ACC (1.01 K + 3) u S + ... (the epilogue terms
+unchanged).  MX_ACC = 1 is the plain bound of K - 1 fp32 additions; the block-scaled MFMA does not meet it.  Measured against the float64
+product on random codes and random scale bytes (fp32 output, no GELU; profiles/gemm_mx.txt, profiles/PARITY_NOTES.md "MX GEMM"):
+err / bound 11.94 / 6.99 at K = 256 (e4m3 / e2m1 weights), 1.29 / 0.56 at K = 1536, 0.07 / 0.03 at K = 8960 (this file's own operands:
+10.97 / 7.19, 1.18 / 0.60, 0.07 / 0.03) -- an error of about
+2^-12.5 of the LARGEST product of a 128-deep instruction, not one that grows with K: the instruction aligns its 128 scaled products to
+the largest before adding them and drops what falls below, and random codes with random scales span 2^30 inside one instruction.
+MX_ACC = 24 is twice the measured worst case, as the issue prescribes; it was not tuned to pass.  The layer and model tests, whose
+operands come from the quantiser (every block filled up to its top binade), keep the plain bound."""
+import ctypes
+import logging
+import os
+
+import pytest
+import torch
+
+from test_gpu_fp8 import OUTS, PROBE_ROWS, _tiny_model, bound_case, e4m3, gen_for, ones, rel_l2
+from test_gpu_wq16 import DEV, DT, EPI_GATE_RES, EPI_GELU, PKG, Window
+
+pytestmark = pytest.mark.gpu
+MX_ACC = 24.0   # twice the measured worst err / bound of the block-scaled accumulation (module docstring)
+FP8, FP4 = "mxfp8_e4m3", "mxfp4_e2m1"
+YAML = {FP8: os.path.join(PKG, "quant_configs", "w8a8_mxfp8_all_linears.yaml"),
+        FP4: os.path.join(PKG, "quant_configs", "w4a8_mxfp4_all_linears.yaml")}
+FMTS = pytest.mark.parametrize("w_fmt", [FP8, FP4], ids=["w8", "w4"])
+E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+# ---- references, in host memory ------------------------------------------------------------------------------------------------
+def host_quant(x32, fmt, gelu=False):
+    from qdiff.base.base_quantizer import mx_quant_rows_host
+
+    return mx_quant_rows_host(x32, fmt, gelu)
+
+
+def deq64(codes, scale, fmt):
+    """float64 dequantised operand, on the codes' device"""
+    from qdiff.base.base_quantizer import mx_decode
+
+    return mx_decode(codes, scale, fmt, torch.float64)
+
+
+def e2m1(t):
+    """exactly representable values [rows, cols] -> packed e2m1 codes [rows, cols / 2] on the GPU"""
+    from qdiff.base.base_quantizer import mx_pack_e2m1
+
+    t = t.detach().float().cpu()
+    lut = torch.tensor(E2M1)
+    mag = (t.abs()[..., None] == lut).float().argmax(-1)
+    assert torch.equal(lut[mag], t.abs()), "not exact in e2m1"
+    return mx_pack_e2m1((mag | (torch.signbit(t).long() << 3)).to(torch.uint8)).to(DEV).contiguous()
+
+
+def codes_of(t, fmt):
+    return e4m3(t) if fmt == FP8 else e2m1(t)
+
+
+def unit(rows, K):
+    return torch.full((rows, K // 32), 127, dtype=torch.uint8, device=DEV)
+
+
+# ---- 1. the quantiser, bit for bit ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("fmt", [FP8, FP4], ids=["e4m3", "e2m1"])
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16, torch.float32], ids=["f16", "bf16", "f32"])
+@pytest.mark.parametrize("cols", [32, 1536, 2080, 8960])
+def test_random_rows_match_the_host_expression_bit_for_bit(cols, dtype, fmt):
+    """widths in both branch classes of the ladder (one wave per row: 32, 1536; four: 2080, 8960), a ragged last chunk slot (2080,
+    8960); rows of very different size, blocks of very different maxima inside a row (each block its own power of ten), an outlier
+    column, a row of zeros, zero blocks inside non-zero rows, a row of fp32 subnormals (f32: scale byte 0); two workgroups of the
+    wave-per-row form"""
+    from viditq_extension import fused
+
+    rows, nb = 7, cols // 32
+    g = torch.Generator().manual_seed(cols + 3)
+    x = torch.randn(rows, cols, generator=g) * (10.0 ** torch.arange(-4, 3).float())[:, None]
+    x[1] *= (10.0 ** torch.randint(-3, 4, (nb,), generator=g).float()).repeat_interleave(32)
+    x[:, cols // 3] *= 25.0
+    x[2] = 0
+    x[3].view(nb, 32)[::3] = 0
+    x[5].view(nb, 32)[nb // 2] = 0
+    x[4] = torch.randn(cols, generator=g) * 1e-39
+    x = x.to(dtype)
+    want, s = host_quant(x.float(), fmt)
+    codes, scale = fused.quant_rows_mx(x.to(DEV), fmt)
+    assert codes.dtype == torch.uint8 and tuple(codes.shape) == (rows, cols // (2 if fmt == FP4 else 1))
+    assert scale.dtype == torch.uint8 and tuple(scale.shape) == (rows, nb)
+    assert torch.equal(scale.cpu(), s), (scale.cpu() != s).nonzero()[:8].tolist()
+    assert int(s[2].max()) == 0 and not bool(codes[2].any()) and int(s.max()) < 255
+    assert len(set(s[1].tolist())) > 1 or nb == 1
+    bad = (codes.cpu() != want).nonzero()
+    assert bad.numel() == 0, [(r, j, hex(codes[r, j].item()), hex(want[r, j].item())) for r, j in bad[:8].tolist()]
+
+
+@pytest.mark.parametrize("fmt", [FP8, FP4], ids=["e4m3", "e2m1"])
+def test_code_tables_midpoints_and_the_exponent_boundary_on_the_gpu(fmt):
+    """the value-by-value rows of tests/test_mx_abi.py through the GPU entry: every e4m3 code / e2m1 value, every midpoint and its fp32
+    neighbours in blocks pinned at scale 2^0, and block maxima at a power of two and one ulp either side, 0, an fp32 subnormal and
+    the largest exponent"""
+    from viditq_extension import fused
+
+    vmax = 448.0 if fmt == FP8 else 6.0
+    vals = []
+    if fmt == FP8:
+        val = torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).float()
+        for c in range(256):
+            if c & 0x7f == 0x7f:
+                continue
+            vals.append(val[c:c + 1])
+            if (c + 1) & 0x7f != 0x7f:
+                mid = ((val[c:c + 1].double() + val[c + 1:c + 2].double()) / 2).float()
+                vals += [mid, torch.nextafter(mid, torch.zeros(1)), torch.nextafter(mid, mid * 2)]
+    else:
+        for sign in (1.0, -1.0):
+            vals.append(sign * torch.tensor(E2M1))
+            for mid in (0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0, 6.5, 7.0):
+                t = torch.tensor([mid])
+                vals += [sign * t, sign * torch.nextafter(t, torch.zeros(1)), sign * torch.nextafter(t, t * 2)]
+    flat = torch.cat(vals)
+    flat = torch.cat([flat, torch.zeros(-len(flat) % 31)]).view(-1, 31)
+    row = torch.cat([torch.full((flat.shape[0], 1), vmax), flat], dim=1).reshape(1, -1)
+    one = torch.tensor(1.0)
+    pins = [torch.nextafter(one, one * 0).item(), 1.0, torch.nextafter(one, one * 2).item(), 0.0, 2.0 ** -130, 2.0 ** 127 * 1.5, 2.0 ** -126,
+            torch.nextafter(one * 2, one).item() * 2.0 ** 10]
+    edge = torch.zeros(len(pins), 32)
+    edge[:, 0] = torch.tensor(pins)
+    edge[:, 1] = -edge[:, 0] / 2
+    edge[:, 2] = edge[:, 0] * 0.3
+    row = torch.cat([row, edge.reshape(1, -1)], dim=1).contiguous()
+    want, s = host_quant(row, fmt)
+    codes, scale = fused.quant_rows_mx(row.to(DEV), fmt)
+    assert torch.equal(scale.cpu(), s)
+    bad = (codes.cpu() != want).nonzero()
+    assert bad.numel() == 0, [(j, hex(codes[0, j].item()), hex(want[0, j].item())) for _, j in bad[:8].tolist()]
+
+
+@pytest.mark.parametrize("fmt", [FP8, FP4], ids=["e4m3", "e2m1"])
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16, torch.float32], ids=["f16", "bf16", "f32"])
+@pytest.mark.parametrize("cols", [64, 2112])
+def test_gelu_form_quantises_this_librarys_own_gelu(cols, dtype, fmt):
+    """act = 1 against the host expression applied to gelu_tanh_fast_f32(x) as the library itself computes it (the fp32 output of the
+    16-bit GEMM's GELU epilogue on x times the identity), as tests/test_gpu_fp8.py holds the GELU fixed for the fp8 quantiser"""
+    from viditq_extension import fused, qgemm
+
+    rows = 6
+    g = torch.Generator().manual_seed(cols)
+    x16 = (torch.randn(rows, cols, generator=g) * 3).to(torch.bfloat16 if dtype == torch.float32 else dtype).to(DEV)
+    eye = torch.eye(64, dtype=x16.dtype, device=DEV)
+    gel = qgemm.fp_linear(x16.view(-1, 64).contiguous(), eye, None, torch.float32, gelu=True).view(rows, cols)
+    want, s = host_quant(gel.cpu(), fmt)
+    codes, scale = fused.quant_rows_mx(x16.to(dtype), fmt, gelu=True)
+    assert torch.equal(scale.cpu(), s) and torch.equal(codes.cpu(), want)
+
+
+def test_quantiser_wrapper_refusals():
+    from viditq_extension import fused
+
+    with pytest.raises(RuntimeError, match=r"cols=40 must be a multiple of 32"):
+        fused.quant_rows_mx(torch.zeros(2, 40, device=DEV))
+    with pytest.raises(RuntimeError, match=r"fmt='fp8_e4m3' must be one of"):
+        fused.quant_rows_mx(torch.zeros(2, 64, device=DEV), "fp8_e4m3")
+    with pytest.raises(RuntimeError):
+        fused.quant_rows_mx(torch.zeros(2, 16416, device=DEV))
+    with pytest.raises(RuntimeError):
+        fused.quant_rows_mx(torch.zeros(2, 64, device=DEV, dtype=torch.int32))
+
+
+# ---- 2. the GEMM ----------------------------------------------------------------------------------------------------------------
+def call_abi(a, w, sa, sw, w_fmt, out_dtype, bias=None, gelu=False, gate=None, residual=None, inplace=False):
+    """wanq_gemm_mx through the C ABI into a guarded window; -> the [M, N] output (guards checked)"""
+    from viditq_extension import _C
+
+    M, K = a.shape
+    N = w.shape[0]
+    assert tuple(w.shape) == (N, K // 2 if w_fmt == FP4 else K) and tuple(sa.shape) == (M, K // 32) and tuple(sw.shape) == (N, K // 32)
+    assert all(t.dtype == torch.uint8 and t.is_contiguous() for t in (a, w, sa, sw))
+    win = Window(M, N, out_dtype)
+    if residual is not None and inplace:
+        win.out.copy_(residual)
+        residual = win.out
+    epi = (EPI_GELU if gelu else 0) | (EPI_GATE_RES if gate is not None else 0)
+    rc = _C.lib.wanq_gemm_mx(a.data_ptr(), w.data_ptr(), sa.data_ptr(), sw.data_ptr(), _C.MX_FMT[w_fmt], win.out.data_ptr(), DT[out_dtype],
+                             None if bias is None else bias.data_ptr(), DT[bias.dtype] if bias is not None else 2,
+                             None if gate is None else gate.data_ptr(), None if residual is None else residual.data_ptr(), epi, M, N, K,
+                             ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == 0, _C.lib.wanq_last_error()
+    torch.cuda.synchronize()
+    assert win.guards_intact(), "a guard region next to the output was written"
+    return win.out
+
+
+def asym_weight(N, K, w_fmt):
+    """w[n, k] asymmetric in n and k, exact in the format"""
+    n, k = torch.meshgrid(torch.arange(N), torch.arange(K), indexing="ij")
+    if w_fmt == FP8:
+        return (1 + (3 * n + 5 * k) % 13).float()
+    return torch.tensor(E2M1)[1 + (3 * n + 5 * k) % 7]
+
+
+@FMTS
+def test_probe1_operand_map_one_nonzero_activation_against_asymmetric_weights(w_fmt):
+    """a = 2 at one (m, k), w[n, k] asymmetric: the output is 2 w[:, k] in row m and 0 elsewhere, exactly.  Every k of the first K-tile
+    (every byte of a lane's e4m3 fragment, every nibble of its e2m1 fragment, all four lane groups) and every k of a second one; rows
+    in all four 16-row blocks of a wave and on both sides of the 128-row tile edge; 136 channels"""
+    M, N, K = 130, 136, 256
+    wv = asym_weight(N, K, w_fmt)
+    w = codes_of(wv, w_fmt)
+    two = e4m3(torch.tensor([2.0]))
+    sa, sw = unit(M, K), unit(N, K)
+    for k0 in range(K):
+        m0 = PROBE_ROWS[k0 % len(PROBE_ROWS)]
+        a = torch.zeros(M, K, dtype=torch.uint8, device=DEV)
+        a[m0, k0] = two[0]
+        out = call_abi(a, w, sa, sw, w_fmt, torch.float32)
+        expect = torch.zeros(M, N)
+        expect[m0] = 2 * wv[:, k0]
+        assert torch.equal(out.cpu(), expect), (m0, k0)
+
+
+@FMTS
+def test_probe1_operand_map_every_row_and_k_in_one_launch(w_fmt):
+    """one nonzero per row, a[m, (37 m + 5) % K] = 1 + m % 3, over three K-tiles and three row tiles"""
+    M, N, K = 260, 136, 384
+    wv = asym_weight(N, K, w_fmt)
+    k_of = (torch.arange(M) * 37 + 5) % K
+    av = torch.zeros(M, K)
+    av[torch.arange(M), k_of] = (1 + torch.arange(M) % 3).float()
+    out = call_abi(e4m3(av), codes_of(wv, w_fmt), unit(M, K), unit(N, K), w_fmt, torch.float32)
+    assert torch.equal(out.cpu(), wv[:, k_of].T * (1 + torch.arange(M) % 3).float()[:, None])
+
+
+def test_probe2_nibble_order_even_k_is_the_low_nibble():
+    """an e2m1 weight whose even-k elements are 0.5 and odd-k elements 6 (n-dependent sign), against a one-hot activation per row: row m
+    reads w[:, k(m)], so an instruction that took the high nibble first would swap 0.5 and 6 everywhere"""
+    M, N, K = 256, 136, 256
+    n, k = torch.meshgrid(torch.arange(N), torch.arange(K), indexing="ij")
+    wv = torch.where(k % 2 == 0, torch.tensor(0.5), torch.tensor(6.0)) * (1 - 2 * ((n + k // 2) % 2)).float()
+    av = torch.zeros(M, K)
+    av[torch.arange(M), torch.arange(M)] = 1.0
+    w = e2m1(wv)
+    assert w[0, 0].item() == (1 | (7 << 4)) and w[1, 0].item() == ((1 | 8) | ((7 | 8) << 4))   # the stored layout: even k low
+    out = call_abi(e4m3(av), w, unit(M, K), unit(N, K), FP4, torch.float32)
+    assert torch.equal(out.cpu(), wv.T.contiguous())
+
+
+@FMTS
+@pytest.mark.parametrize("side", ["act", "weight"])
+def test_probe3_scale_map_one_raised_scale_byte_per_row(side, w_fmt):
+    """all elements 1.0, all scale bytes 2^0, except one (row, block) per row whose byte is 2^e.  With e = 3 exactly that output row
+    (activation side) or column (weight side) rises by 32 * 7; here every row carries its own raised block, (row + j) % 8 in launch
+    j, and its own exponent 1 + row % 3, so the eight launches cover every (row of the 128-row tile, block of both K-tiles) and a
+    byte applied to a neighbouring row shows as the wrong rise.  Second part: the weights of block b are 1 + b % 4 (activation side) or
+    the activations are (weight side), so a byte applied to the wrong BLOCK of the right row shows too"""
+    M, N, K = 130, 136, 256
+    nb = K // 32
+    rows = M if side == "act" else N
+    r = torch.arange(rows)
+    e = 1 + r % 3
+    blockw = (1 + torch.arange(nb) % 4).float()
+    for weighted in (False, True):
+        other = blockw.repeat_interleave(32) if weighted else torch.ones(K)
+        av = torch.ones(M, K) if side == "act" else other.expand(M, K)
+        wv = other.expand(N, K) if side == "act" else torch.ones(N, K)
+        a, w = e4m3(av.contiguous()), codes_of(wv.contiguous(), w_fmt)
+        for j in range(nb):
+            b = (r + j) % nb
+            s = torch.full((rows, nb), 127, dtype=torch.uint8)
+            s[r, b] = (127 + e).to(torch.uint8)
+            sa, sw = (s.to(DEV), unit(N, K)) if side == "act" else (unit(M, K), s.to(DEV))
+            out = call_abi(a, w, sa, sw, w_fmt, torch.float32).cpu()
+            base = 32 * (blockw.sum() if weighted else float(nb))
+            rise = 32 * (blockw[b] if weighted else 1.0) * (2.0 ** e - 1)
+            want = (base + rise)[:, None].expand(M, N) if side == "act" else (base + rise)[None, :].expand(M, N)
+            assert torch.equal(out, want), (weighted, j, (out != want).nonzero()[:6].tolist())
+    # the issue's own case: one single byte 2^3 in the whole launch
+    s = torch.full((rows, nb), 127, dtype=torch.uint8)
+    s[77, 5] = 130
+    sa, sw = (s.to(DEV), unit(N, K)) if side == "act" else (unit(M, K), s.to(DEV))
+    out = call_abi(e4m3(torch.ones(M, K)), codes_of(torch.ones(N, K), w_fmt), sa, sw, w_fmt, torch.float32).cpu()
+    want = torch.full((M, N), float(K))
+    if side == "act":
+        want[77] += 32 * 7
+    else:
+        want[:, 77] += 32 * 7
+    assert torch.equal(out, want)
+
+
+def int_operands(M, N, K, w_fmt, seed):
+    """integer activations in [-4, 4]; e4m3 weights integers in [-4, 4], e2m1 weights from {0, +-0.5, ..., +-4}; scale exponents in
+    {-1, 0, 1} per (row, block): |a w| 2^(ea + ew) <= 64 and a multiple of 2^-3, so every partial sum is exact in fp32 below 2^19"""
+    g = torch.Generator().manual_seed(seed)
+    av = torch.randint(-4, 5, (M, K), generator=g).float()
+    if w_fmt == FP8:
+        wv = torch.randint(-4, 5, (N, K), generator=g).float()
+    else:
+        wv = torch.tensor(E2M1)[torch.randint(0, 7, (N, K), generator=g)] * (torch.randint(0, 2, (N, K), generator=g) * 2 - 1).float()
+    sa = torch.randint(126, 129, (M, K // 32), generator=g).to(torch.uint8).to(DEV)
+    sw = torch.randint(126, 129, (N, K // 32), generator=g).to(torch.uint8).to(DEV)
+    a, w = e4m3(av), codes_of(wv, w_fmt)
+    acc = deq64(a, sa, FP8) @ deq64(w, sw, w_fmt).T
+    return a, w, sa, sw, acc
+
+
+@FMTS
+@pytest.mark.parametrize("M", [1, 130])
+@pytest.mark.parametrize("K", [128, 256, 384, 640])
+def test_integer_operands_equal_the_float64_product_in_every_output_type(K, M, w_fmt):
+    N = 136
+    a, w, sa, sw, acc = int_operands(M, N, K, w_fmt, K + M)
+    assert torch.equal(acc.float().double(), acc) and float(acc.abs().max()) < 65504
+    for out_dtype in OUTS:
+        assert torch.equal(call_abi(a, w, sa, sw, w_fmt, out_dtype), acc.float().to(out_dtype)), out_dtype
+
+
+@FMTS
+@pytest.mark.parametrize("out_dtype", OUTS, ids=["f32", "bf16", "f16"])
+def test_bias_gate_and_residual_exactly_in_every_output_type(out_dtype, w_fmt):
+    """|gate| in {1/2, 1, 2}, integer bias (fp32, fp16 and bf16 vectors) and residual: every step is exact in fp32, so the output is the
+    float64 value rounded once into the output type; out of place and in place"""
+    M, N, K = 130, 136, 256
+    a, w, sa, sw, acc = int_operands(M, N, K, w_fmt, 7)
+    g = gen_for(11)
+    bias = torch.randint(-8, 9, (N,), device=DEV, generator=g).float()
+    gate = (2.0 ** torch.randint(-1, 2, (N,), device=DEV, generator=g).float()) * (torch.randint(0, 2, (N,), device=DEV, generator=g) * 2 - 1)
+    res = torch.randint(-16, 17, (M, N), device=DEV, generator=g).to(out_dtype)
+    for b in (None, bias, bias.half(), bias.bfloat16()):
+        y = acc + (0.0 if b is None else b.double())
+        assert torch.equal(y.float().double(), y)
+        assert torch.equal(call_abi(a, w, sa, sw, w_fmt, out_dtype, b), y.float().to(out_dtype))
+        yr = res.double() + y * gate.double()
+        assert torch.equal(yr.float().double(), yr)
+        for inplace in (False, True):
+            r = res.clone()
+            out = call_abi(a, w, sa, sw, w_fmt, out_dtype, b, False, gate, r, inplace)
+            assert torch.equal(out, yr.float().to(out_dtype)), (b is None, inplace)
+            assert torch.equal(r, res)
+
+
+@FMTS
+@pytest.mark.parametrize("out_dtype", OUTS, ids=["f32", "bf16", "f16"])
+def test_gelu_epilogue_on_exact_pre_activations(out_dtype, w_fmt):
+    """the pre-activation is exact (sparse small integers, power-of-two scales), so the error is the GELU's alone: gelu_bound, then
+    gate + residual and the store (bound_case of tests/test_gpu_fp8.py with S = 0)"""
+    M, N, K = 130, 136, 128
+    g0 = torch.Generator().manual_seed(5)
+    av = torch.randint(-4, 5, (M, K), generator=g0).float() * (torch.rand(M, K, generator=g0) < 0.1)
+    wv = torch.randint(-2, 3, (N, K), generator=g0).float()
+    a, w = e4m3(av), codes_of(wv, w_fmt)
+    sa = torch.randint(125, 127, (M, K // 32), generator=g0).to(torch.uint8).to(DEV)
+    sw = torch.randint(125, 128, (N, K // 32), generator=g0).to(torch.uint8).to(DEV)
+    acc = deq64(a, sa, FP8) @ deq64(w, sw, w_fmt).T
+    assert torch.equal(acc.float().double(), acc)
+    g = gen_for(13)
+    bias = torch.randint(-2, 3, (N,), device=DEV, generator=g).float() / 4
+    gate = torch.rand(N, device=DEV, generator=g) * 2 - 1
+    res = torch.randn(M, N, device=DEV, generator=g).to(out_dtype)
+    zero = torch.zeros_like(acc)
+    for gres in (False, True):
+        out = call_abi(a, w, sa, sw, w_fmt, out_dtype, bias, True, gate if gres else None, res.clone() if gres else None)
+        y, tol = bound_case(zero, acc, ones(M), ones(N), bias, True, gate if gres else None, res, out_dtype, 0)
+        err = (out.double() - y).abs()
+        assert not (err > tol).any(), (gres, (err / tol).max().item())
+
+
+def random_operands(M, N, K, w_fmt, gen):
+    """random finite codes and random scale bytes.  The scale exponents are spread over +-3 around -7 (activations) and -8 (weights):
+    a product is at least 2^-18 (two smallest e4m3 subnormals) 2^-21 = 2^-39 and at most 448^2 2^-9, nothing overflows fp32 or falls
+    below its normal range, and the outputs stay inside fp16 -- all three checked on the host before the launch"""
+    a = torch.randint(0, 256, (M, K), device=DEV, generator=gen, dtype=torch.uint8)
+    a[(a & 0x7f) == 0x7f] = 0x3c
+    if w_fmt == FP8:
+        w = torch.randint(0, 256, (N, K), device=DEV, generator=gen, dtype=torch.uint8)
+        w[(w & 0x7f) == 0x7f] = 0xbc
+    else:
+        w = torch.randint(0, 256, (N, K // 2), device=DEV, generator=gen, dtype=torch.uint8)
+    sa = torch.randint(117, 124, (M, K // 32), device=DEV, generator=gen, dtype=torch.uint8)
+    sw = torch.randint(116, 123, (N, K // 32), device=DEV, generator=gen, dtype=torch.uint8)
+    return a, w, sa, sw
+
+
+@FMTS
+@pytest.mark.parametrize("M,N,K", [(130, 136, 256), (300, 264, 1536), (257, 128, 8960)])
+def test_random_codes_and_scale_bytes_within_the_derived_bound(M, N, K, w_fmt):
+    g = gen_for(M + N + K)
+    a, w, sa, sw = random_operands(M, N, K, w_fmt, g)
+    a64, w64 = deq64(a, sa, FP8), deq64(w, sw, w_fmt)
+    acc, S = a64 @ w64.T, a64.abs() @ w64.abs().T
+    amin, wmin = a64.abs()[a64 != 0].min().item(), w64.abs()[w64 != 0].min().item()
+    assert amin * wmin > 2.0 ** -100 and a64.abs().max().item() * w64.abs().max().item() * K < 2.0 ** 100   # nothing lost, no overflow
+    assert float(S.max()) < 3e4                                                                               # every output inside fp16
+    bias = torch.randn(N, device=DEV, generator=g) * 0.1
+    gate = torch.rand(N, device=DEV, generator=g) * 2 - 1
+    worst = {}
+    for out_dtype in OUTS:
+        res = torch.randn(M, N, device=DEV, generator=g).to(out_dtype)
+        for gelu, gres in ((False, False), (True, False), (False, True), (True, True)):
+            out = call_abi(a, w, sa, sw, w_fmt, out_dtype, bias, gelu, gate if gres else None, res.clone() if gres else None, inplace=gres)
+            y, tol = bound_case(MX_ACC * S, acc, ones(M), ones(N), bias, gelu, gate if gres else None, res, out_dtype, K)
+            err = (out.double() - y).abs()
+            worst[(str(out_dtype)[6:], gelu, gres)] = round((err / tol).max().item(), 4)
+    print(f"MX GEMM {w_fmt} ({M}, {N}, {K}): worst err / (MX_ACC = {MX_ACC:.0f} bound) {max(worst.values()):.4f} {worst}")
+    assert max(worst.values()) <= 1.0, worst
+
+
+@FMTS
+def test_repeated_calls_and_rows_in_launches_of_another_size_are_bit_equal(w_fmt):
+    M, N, K = 300, 136, 512
+    g = gen_for(9)
+    a, w, sa, sw = random_operands(M, N, K, w_fmt, g)
+    bias = torch.randn(N, device=DEV, generator=g)
+    full = call_abi(a, w, sa, sw, w_fmt, torch.bfloat16, bias, True)
+    assert torch.equal(full, call_abi(a, w, sa, sw, w_fmt, torch.bfloat16, bias, True))
+    for m, off in ((1, 0), (1, 128), (1, 299), (77, 100), (130, 170)):
+        part = call_abi(a[off:off + m].contiguous(), w, sa[off:off + m].contiguous(), sw, w_fmt, torch.bfloat16, bias, True)
+        assert torch.equal(part, full[off:off + m]), (m, off)
+    f32 = call_abi(a, w, sa, sw, w_fmt, torch.float32)
+    moved = torch.cat([a[200:201], a[:130]]).contiguous(), torch.cat([sa[200:201], sa[:130]]).contiguous()   # row 200 placed at m = 0
+    assert torch.equal(call_abi(moved[0], w, moved[1], sw, w_fmt, torch.float32)[0], f32[200])
+
+
+def test_python_wrapper_refusals_carry_the_rule():
+    from viditq_extension import qgemm
+
+    z = lambda *s: torch.zeros(*s, dtype=torch.uint8, device=DEV)  # noqa: E731
+    with pytest.raises(RuntimeError, match=r"mx_linear: K=192 must be a positive multiple of 128"):
+        qgemm.mx_linear(z(8, 192), z(16, 192), z(8, 6), z(16, 6))
+    with pytest.raises(RuntimeError, match=r"mx_linear: N=12 must be a positive multiple of 8"):
+        qgemm.mx_linear(z(8, 128), z(12, 128), z(8, 4), z(12, 4))
+    with pytest.raises(RuntimeError, match=r"w_q must have shape \(16, 64\)"):
+        qgemm.mx_linear(z(8, 128), z(16, 128), z(8, 4), z(16, 4), FP4)
+    with pytest.raises(RuntimeError, match=r"w_q must have dtype"):
+        qgemm.mx_linear(z(8, 128), z(16, 128).view(torch.int8), z(8, 4), z(16, 4))
+    with pytest.raises(RuntimeError, match=r"a_scale must have shape"):
+        qgemm.mx_linear(z(8, 128), z(16, 128), z(8, 3), z(16, 4))
+    with pytest.raises(RuntimeError, match=r"w_scale must have dtype"):
+        qgemm.mx_linear(z(8, 128), z(16, 128), z(8, 4), torch.ones(16, 4, device=DEV))
+    with pytest.raises(RuntimeError, match=r"gate and residual must be given together"):
+        qgemm.mx_linear(z(8, 128), z(16, 128), z(8, 4), z(16, 4), gate=ones(16))
+    with pytest.raises(RuntimeError, match=r"w_fmt='int4' must be one of"):
+        qgemm.mx_linear(z(8, 128), z(16, 128), z(8, 4), z(16, 4), "int4")
+    for fmt, wk in ((FP8, 128), (FP4, 64)):
+        out = qgemm.mx_linear(z(8, 128), z(16, wk), z(8, 4), z(16, 4), fmt, torch.arange(16, device=DEV).float())
+        assert out.dtype == torch.bfloat16 and torch.equal(out.float(), torch.arange(16, device=DEV).float().expand(8, 16))
+
+
+# ---- 3. layer level ---------------------------------------------------------------------------------------------------------------
+def _sim_layer(w_fmt, K=256, N=136):
+    from qdiff import config as qcfg
+    from qdiff.base.quant_layer import QuantizedLinear
+
+    gen = torch.Generator().manual_seed(5)
+    fp = torch.nn.Linear(K, N).to(DEV)
+    fp.weight.data.copy_(torch.randn(N, K, generator=gen) * K ** -0.5)
+    fp.bias.data.copy_(torch.randn(N, generator=gen) * 0.1)
+    ql = QuantizedLinear(K, N, True, DEV, qcfg.load(YAML[w_fmt]), fp, module_name="blocks.0.ffn.0")
+    x = torch.randn(1, 133, K, generator=gen).to(torch.bfloat16).to(DEV)
+    return ql, x
+
+
+@FMTS
+def test_simulation_and_kernel_mode_layers_run_the_same_entries_and_match_the_host_expression(w_fmt):
+    from viditq_extension import fused, qgemm
+    from wan.quant_wanx_hip import HipLinearMx
+
+    ql, x = _sim_layer(w_fmt)
+    K, N = 256, 136
+    wc, ws = host_quant(ql.fp_module.weight.data.cpu(), w_fmt)   # the weight went through the GPU entry: the bits of the host expression
+    assert ql.mx == w_fmt and torch.equal(ql._codes.cpu(), wc) and torch.equal(ql.w_quantizer.scale_u8.cpu(), ws)
+    out = ql(x)
+    assert out.dtype == torch.bfloat16 and tuple(out.shape) == (1, 133, N)
+    q, s = fused.quant_rows_mx(x[0])
+    bias = ql.bias.detach().float()
+    assert torch.equal(out[0], qgemm.mx_linear(q, ql._codes, s, ql.w_quantizer.scale_u8, w_fmt, bias, torch.bfloat16))
+    hl = HipLinearMx.from_quantized(ql, "blocks.0.ffn.0")
+    assert torch.equal(hl.weight, ql._codes) and torch.equal(hl.scale_weight, ql.w_quantizer.scale_u8)
+    assert torch.equal(hl(q, s, torch.bfloat16), out[0])
+    # the host expression F.linear(dq(a), dq(w), bias) in float64, under the module's bound
+    a64, w64 = deq64(q, s, FP8), deq64(ql._codes, ql.w_quantizer.scale_u8, w_fmt)
+    assert torch.equal(w64.float(), ql.weight.data)
+    y, tol = bound_case(a64.abs() @ w64.abs().T, a64 @ w64.T, ones(133), ones(N), bias, False, None, None, torch.bfloat16, K)
+    host = torch.nn.functional.linear(a64, w64, bias.double())
+    assert float((host - y).abs().max()) <= 1e-12 * float(y.abs().max())
+    err = (out[0].double() - y).abs()
+    print(f"MX layer {w_fmt} vs the host expression: worst err / bound {(err / tol).max().item():.3f}")
+    assert not (err > tol).any()
+
+
+@FMTS
+def test_a_shape_the_gemm_refuses_falls_back_to_the_torch_expression(w_fmt):
+    from qdiff.base.base_quantizer import mx_decode
+    from viditq_extension import fused
+
+    ql, x = _sim_layer(w_fmt, K=96, N=24)
+    xs = x[:, :, :96].contiguous()
+    q, s = fused.quant_rows_mx(xs[0])
+    want = torch.nn.functional.linear(mx_decode(q, s, FP8), ql.weight.data.float(), ql.bias.detach().float()).to(torch.bfloat16)
+    assert torch.equal(ql(xs)[0], want)
+
+
+# ---- 4. block and model level ---------------------------------------------------------------------------------------------------
+@FMTS
+def test_kernel_mode_model_matches_simulation_mode_and_the_checkpoint_round_trips(tmp_path, caplog, w_fmt):
+    """The tiny 2-block model of tests/test_gpu_fp8.py (dim 256, ffn 512, 2 heads of 128, 130 tokens) under each shipped config: kernel
+    mode against simulation mode on the GPU.  Both run wanq_quant_rows_mx and wanq_gemm_mx; what differs is the 16-bit tensors
+    between kernel mode's layers.  Margin: the one the fp8 block test applies to the same comparison -- rel Frobenius error below 1e-2
+    and below 0.5 x (quantised vs floating-point model) + 5e-3.  Then quantize_and_save_weight -> hardware_forward_refactor(load_path=...)
+    gives the output of the model built directly, bit for bit, with the codes and scale bytes as saved."""
+    from qdiff import config as qcfg
+    from wan.quant_wanx_hip import HipLinearMx
+
+    t = torch.tensor([700], device=DEV)
+    model, fp, seq_len, ctx, lat0 = _tiny_model(qcfg.load(YAML[w_fmt]))
+    assert seq_len == 130
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        ref_fp = fp([lat0], t, [ctx], seq_len)[0].float().clone()
+    sim = model([lat0], t, [ctx], seq_len)[0].float().clone()
+    model.hardware_forward_refactor()
+    lins = [m for m in model.hip_blocks.modules() if isinstance(m, HipLinearMx)]
+    assert len(lins) == 20 and all(m.weight.dtype == torch.uint8 and m.scale_weight.dtype == torch.uint8 and m.mx == w_fmt for m in lins)
+    hw = model([lat0], t, [ctx], seq_len)[0].float().clone()
+    assert torch.isfinite(sim).all() and torch.isfinite(hw).all()
+    err, noise = rel_l2(hw, sim), rel_l2(sim, ref_fp)
+    print(f"MX model {w_fmt}, kernel mode vs simulation mode: rel err {err:.3e}; simulation mode vs the floating-point model {noise:.3e}")
+    assert noise > 0 and err < 1e-2 and err < 0.5 * noise + 5e-3
+
+    path = str(tmp_path / "int_weight.pt")
+    sd = model.quantize_and_save_weight(path)
+    wk = 512 if w_fmt == FP8 else 256
+    assert sd["blocks.0.ffn.2.weight"].dtype == torch.uint8 and tuple(sd["blocks.0.ffn.2.weight"].shape) == (256, wk)
+    assert sd["blocks.0.ffn.2.scale_weight"].dtype == torch.uint8 and tuple(sd["blocks.0.ffn.2.scale_weight"].shape) == (256, 16)
+    assert "blocks.0.ffn.2.zp_weight" not in sd
+    fresh, *_ = _tiny_model(qcfg.load(YAML[w_fmt]))
+    with caplog.at_level(logging.INFO, logger="wan.quant_wanx"):
+        fresh.hardware_forward_refactor(load_path=path)
+    assert any("loaded 60 tensors" in r.getMessage() for r in caplog.records)
+    for a, b in zip(lins, [m for m in fresh.hip_blocks.modules() if isinstance(m, HipLinearMx)]):
+        assert torch.equal(a.weight, b.weight) and torch.equal(a.scale_weight, b.scale_weight)
+    assert torch.equal(fresh([lat0], t, [ctx], seq_len)[0].float(), hw)
+
+
+@FMTS
+def test_two_pass_streams_and_sharded_weights_are_bit_equal_to_the_plain_kernel_mode_model(w_fmt):
+    """the conditional and the unconditional pass on two streams (wan/utils/two_pass.py), and --dit_fsdp's re-pointing of `weight` and
+    `scale_weight` at views of the gathered buffer (one rank: the whole buffer), give the bits of the plain kernel-mode model"""
+    from qdiff import config as qcfg
+    from wan.quant_wanx_hip import HipLinearMx
+    from wan.utils.two_pass import TwoPassStreams
+
+    model, _, seq_len, ctx, lat0 = _tiny_model(qcfg.load(YAML[w_fmt]))
+    model.hardware_forward_refactor()
+    ctxs = [ctx, torch.zeros_like(ctx)]
+    t = torch.tensor([500], device=DEV)
+
+    def both(two):
+        out = two(lambda c: model([lat0], t, [c], seq_len)[0], lat0, ctxs)
+        torch.cuda.synchronize()
+        return [o.clone() for o in out]
+
+    one = both(TwoPassStreams(DEV, enabled=False))
+    two = TwoPassStreams(DEV, mode="2")
+    both(two)                      # (call 1 fills the caches both passes read, on one stream)
+    assert two.enabled and all(torch.isfinite(a).all() and torch.equal(a, b) for a, b in zip(one, both(two)))
+    model.shard_blocks(None)
+    lins = [m for m in model.hip_blocks.modules() if isinstance(m, HipLinearMx)]
+    assert all(m.weight.numel() == 0 and m.scale_weight.numel() == 0 for m in lins)   # both buffers live in the shards now
+    assert all(torch.equal(a, b) for a, b in zip(one, both(TwoPassStreams(DEV, enabled=False))))
+
+
+@FMTS
+def test_shipped_config_through_ptq_and_quant_generate(tmp_path, w_fmt):
+    """ptq_wanx -> quant_generate (kernel mode from the exported checkpoint, and simulation mode) on the truncated backbone at toy size,
+    as tests/test_gpu_fp8.py runs the fp8 config; no calibration file.  Kernel mode against simulation mode: that test's margin (3e-2)."""
+    from test_gpu_entrypoints import run
+
+    cfg = YAML[w_fmt]
+    run("ptq_wanx.py", "--quant_config", cfg, cwd=tmp_path)
+    iw = torch.load(tmp_path / "checkpoint" / "int_weight.pt", weights_only=True)
+    wk = 1536 if w_fmt == FP8 else 768
+    assert iw["blocks.0.self_attn.q.weight"].dtype == torch.uint8 and tuple(iw["blocks.1.ffn.0.weight"].shape) == (8960, wk)
+    assert iw["blocks.1.ffn.0.scale_weight"].dtype == torch.uint8 and tuple(iw["blocks.1.ffn.0.scale_weight"].shape) == (8960, 48)
+    assert "blocks.1.ffn.0.zp_weight" not in iw
+    run("quant_generate.py", "--quant_config", cfg, cwd=tmp_path)
+    hw = torch.load(tmp_path / "quant_latent_0.pt", weights_only=True).float()
+    run("quant_generate.py", "--quant_config", cfg, "--hardware", "false", "--save_file", str(tmp_path / "sim.pt"), cwd=tmp_path)
+    sim = torch.load(tmp_path / "sim.pt", weights_only=True).float()
+    rel = ((hw - sim).norm() / sim.norm()).item()
+    print(f"{os.path.basename(cfg)}: kernel mode vs simulation mode {rel:.3e}")
+    assert hw.shape == (16, 2, 60, 104) and torch.isfinite(hw).all() and torch.isfinite(sim).all() and rel < 0.03

@@ -326,6 +326,81 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const Fp8RowParams 
   if (f.lane == 0 && f.sub == 0) p.scale[f.row] = scale;
 }
 
+// ------------------------------------------------------------------------------ OCP MX block quantiser (e4m3 / e2m1 codes, E8M0 scales)
+// One power-of-two scale per block of 32 consecutive columns: s = clamp(E(amax) - emax, 0, 254), c = rne(clamp(ldexp(x, 127 - s))).
+// The row frame and ladder of the other quantisers.  A block is four consecutive 8-element chunks, and chunk slot i of a lane is
+// chunk (a multiple of 64) + lane, so a block sits in the four lanes of one aligned quad at one slot: its maximum is two DPP quad
+// exchanges per slot, never a reduction over the row (no LDS, no barrier, in the four-wave form too).  cols % 32 == 0, so a quad is
+// inside the row or past it as a whole.  The scaling is one exact v_ldexp_f32; e4m3 is rounded by the packed hardware conversion
+// behind the clamp as in the fp8 quantiser, e2m1 by seven comparisons against the midpoints (> where the tie goes down to the even
+// code, >= where it goes up).  e4m3 codes leave as 8-byte chunks, e2m1 codes as one dword of eight nibbles (even k low), the scale
+// byte from the quad's first lane.
+struct MxRowParams {
+  const void* x;
+  int x_dtype;
+  uint8_t* q;
+  uint8_t* scale;
+  int64_t rows;
+  int cols;
+  int act;
+};
+
+__device__ __forceinline__ uint32_t e2m1_code(float t) {
+  const float a = fminf(fabsf(t), 6.0f);
+  const uint32_t mag = (uint32_t)(a > 0.25f) + (uint32_t)(a >= 0.75f) + (uint32_t)(a > 1.25f) + (uint32_t)(a >= 1.75f) +
+                       (uint32_t)(a > 2.5f) + (uint32_t)(a >= 3.5f) + (uint32_t)(a > 5.0f);
+  return mag | ((__float_as_uint(t) >> 28) & 8u);
+}
+
+template <int WPR, int NCH, bool FP4>
+__global__ __launch_bounds__(256) void quant_rows_mx_kernel(const MxRowParams p) {
+  RowFrame<WPR, NCH> f;
+  if (f.surplus(p.rows)) return;
+  const int C = p.cols;
+  const int64_t rbase = f.row * (int64_t)C;
+  constexpr int EMAX = FP4 ? 2 : 8;
+
+  float v[NCH][8];
+  bool ok[NCH];
+  f.load(p.x, p.x_dtype, rbase, C, v, ok);
+  if (p.act == 1) {
+#pragma unroll
+    for (int i = 0; i < NCH; ++i)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[i][j] = gelu_tanh_fast_f32(v[i][j]);  // (a slot past the row end stays 0)
+  }
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+    float m = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(v[i][j]));
+    m = fmaxf(m, lane_xor_dpp<1>(m));
+    m = fmaxf(m, lane_xor_dpp<2>(m));
+    if (!ok[i]) continue;
+    int s = (int)((__float_as_uint(m) >> 23) & 0xffu) - EMAX;
+    s = s < 0 ? 0 : (s > 254 ? 254 : s);
+    float t[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) t[j] = ldexpf(v[i][j], 127 - s);
+    const int col = f.col(i);
+    if constexpr (FP4) {
+      uint32_t w = 0;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) w |= e2m1_code(t[j]) << (4 * j);
+      *reinterpret_cast<uint32_t*>(p.q + ((rbase + col) >> 1)) = w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) t[j] = __builtin_amdgcn_fmed3f(t[j], -FP8_E4M3_MAX, FP8_E4M3_MAX);
+      int lo = __builtin_amdgcn_cvt_pk_fp8_f32(t[0], t[1], 0, false);
+      lo = __builtin_amdgcn_cvt_pk_fp8_f32(t[2], t[3], lo, true);
+      int hi = __builtin_amdgcn_cvt_pk_fp8_f32(t[4], t[5], 0, false);
+      hi = __builtin_amdgcn_cvt_pk_fp8_f32(t[6], t[7], hi, true);
+      *reinterpret_cast<uint2*>(p.q + rbase + col) = make_uint2((uint32_t)lo, (uint32_t)hi);
+    }
+    if ((f.lane & 3) == 0) p.scale[((rbase + col) >> 5)] = (uint8_t)s;
+  }
+}
+
 // x * premul (-> LayerNorm + modulate first when `ln`) -> fp output and / or int8 quantise: the transform entry points of
 // rotate.hip with had_k == 0 (channel scale without rotation: SmoothQuant, Q/smooth_quant/sq_quant_layer.py:52-60).
 int premul_quant_rows(bool ln, const void* x, int x_dtype, const void* gamma, const void* mshift, const void* mscale,
@@ -387,6 +462,26 @@ extern "C" int wanq_quant_rows_fp8(const void* x, int x_dtype, uint8_t* q, float
     hipLaunchKernelGGL((quant_rows_fp8_kernel<decltype(wpr)::value, decltype(nch)::value>), grid, dim3(256), 0, (hipStream_t)stream, p);
   });
   return check_launch("wanq_quant_rows_fp8");
+}
+
+extern "C" int wanq_quant_rows_mx(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int fmt, int act,
+                                  void* stream) {
+  WANQ_REQUIRE(x && q && scale_u8, WANQ_E_ARG, "wanq_quant_rows_mx: x, q and scale_u8 must be non-NULL");
+  WANQ_REQUIRE(is_fp(x_dtype), WANQ_E_ARG, "wanq_quant_rows_mx: bad x dtype %d", x_dtype);
+  WANQ_REQUIRE(fmt == WANQ_MX_E4M3 || fmt == WANQ_MX_E2M1, WANQ_E_ARG, "wanq_quant_rows_mx: fmt=%d must be WANQ_MX_E4M3 or WANQ_MX_E2M1",
+               fmt);
+  WANQ_REQUIRE(act == 0 || act == 1, WANQ_E_ARG, "wanq_quant_rows_mx: act must be 0 or 1");
+  if (int e = check_rows_cols("wanq_quant_rows_mx", rows, cols)) return e;
+  WANQ_REQUIRE(cols % 32 == 0, WANQ_E_SHAPE, "wanq_quant_rows_mx: cols=%d must be a multiple of 32 (one scale per block of 32)", cols);
+  WANQ_REQUIRE((reinterpret_cast<uintptr_t>(q) & 15) == 0, WANQ_E_ARG, "wanq_quant_rows_mx: q must be 16-byte aligned");
+  if (rows == 0) return WANQ_OK;
+  const MxRowParams p{x, x_dtype, q, scale_u8, rows, cols, act};
+  row_ladder(cols, rows, [&](auto wpr, auto nch, dim3 grid) {
+    constexpr int W = decltype(wpr)::value, NC = decltype(nch)::value;
+    if (fmt == WANQ_MX_E2M1) hipLaunchKernelGGL((quant_rows_mx_kernel<W, NC, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((quant_rows_mx_kernel<W, NC, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
+  });
+  return check_launch("wanq_quant_rows_mx");
 }
 
 extern "C" int wanq_layernorm_rows(const void* x, int x_dtype, const void* gamma, const void* mshift,

@@ -231,3 +231,111 @@ class Fp8Quantizer(BaseQuantizer):
 
     def forward(self, x):
         return self.codes_and_dequant(x, False, True)[1]
+
+
+# ---- OCP Microscaling (MX): `format: mxfp8_e4m3` / `format: mxfp4_e2m1` -------------------------------------------------------
+# One E8M0 power-of-two scale per block of 32 consecutive input channels (include/wanq_hip.h, wanq_quant_rows_mx).  Repository-
+# defined; the reference has no counterpart.  What follows is the host expression of the format: what simulation mode runs in host
+# memory and what the GPU entry is bit-equal to.
+MXFP8_FORMAT, MXFP4_FORMAT = "mxfp8_e4m3", "mxfp4_e2m1"
+MX_FORMATS = (MXFP8_FORMAT, MXFP4_FORMAT)
+MX_BLOCK = 32
+_MX_SPEC = {MXFP8_FORMAT: (8, 448.0, 0), MXFP4_FORMAT: (2, 6.0, 1)}   # emax, largest magnitude, the `fmt` code of the C ABI
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def mx_fmt_code(fmt):
+    return _MX_SPEC[fmt][2]
+
+
+def _pow2_f64(e):
+    """2.0 ** e for an integer tensor e in [-1022, 1023], exactly, as float64 (the exponent field written directly)"""
+    return ((e.long() + 1023) << 52).view(torch.float64)
+
+
+def mx_pack_e2m1(codes):
+    """[rows, cols] 4-bit codes -> [rows, cols / 2] bytes: element k in byte k / 2, even k in the low nibble"""
+    return (codes[..., 0::2] | (codes[..., 1::2] << 4)).contiguous()
+
+
+def mx_unpack_e2m1(packed):
+    """[rows, cols / 2] bytes -> [rows, cols] 4-bit codes"""
+    return torch.stack((packed & 0xf, packed >> 4), dim=-1).reshape(*packed.shape[:-1], packed.shape[-1] * 2)
+
+
+def mx_quant_rows_host(x, fmt, gelu=False):
+    """(codes uint8, scale bytes uint8 [rows, cols / 32]) of the block quantiser, in torch on x's device.  Per block: amax, E = its
+    biased fp32 exponent field, s = clamp(E - emax, 0, 254), c = rne(clamp(x 2^(127 - s), -max, max)).  The scaling is done in
+    float64, where it is exact; the one rounding is the cast to e4m3fn (this torch build rounds to nearest even and keeps subnormals)
+    or, for e2m1, the comparison against the seven midpoints with ties to the even code."""
+    emax, vmax, _ = _MX_SPEC[fmt]
+    x = x.float()
+    if gelu:
+        x = torch.nn.functional.gelu(x, approximate="tanh")
+    rows, cols = x.shape
+    if cols % MX_BLOCK:
+        raise ValueError(f"mx_quant_rows: cols={cols} must be a multiple of {MX_BLOCK}")
+    xb = x.reshape(rows, cols // MX_BLOCK, MX_BLOCK)
+    amax = xb.abs().amax(dim=-1).contiguous()
+    s = (((amax.view(torch.int32) >> 23) & 0xff) - emax).clamp(0, 254)
+    t = (xb.double() * _pow2_f64(127 - s).unsqueeze(-1)).clamp(-vmax, vmax).reshape(rows, cols)
+    if fmt == MXFP8_FORMAT:
+        codes = t.float().to(torch.float8_e4m3fn).view(torch.uint8)
+    else:
+        a = t.abs()
+        mag = ((a > 0.25).to(torch.uint8) + (a >= 0.75) + (a > 1.25) + (a >= 1.75) + (a > 2.5) + (a >= 3.5) + (a > 5.0)).to(torch.uint8)
+        codes = mx_pack_e2m1(mag | (torch.signbit(t).to(torch.uint8) << 3))
+    return codes, s.to(torch.uint8)
+
+
+def mx_quant_rows(x, fmt, gelu=False):
+    """The block quantiser: on the GPU wanq_quant_rows_mx, in host memory the host expression it is bit-equal to."""
+    if x.is_cuda:
+        return fused.quant_rows_mx(x.contiguous(), fmt, gelu)
+    return mx_quant_rows_host(x, fmt, gelu)
+
+
+def mx_decode(codes, scale_u8, fmt, dtype=torch.float32):
+    """Dequantised values [rows, cols] of codes + scale bytes: value(code) 2^(s - 127), exact in float64 (and in fp32 wherever the
+    result is a normal fp32 number, as for anything the quantiser wrote)."""
+    if fmt == MXFP8_FORMAT:
+        v = fp8_decode(codes).double()
+    else:
+        c = mx_unpack_e2m1(codes).long()
+        lut = torch.tensor(E2M1_VALUES, dtype=torch.float64, device=codes.device)
+        v = lut[c & 7] * (1 - 2 * (c >> 3)).double()
+    rows, cols = v.shape
+    v = v.reshape(rows, cols // MX_BLOCK, MX_BLOCK) * _pow2_f64(scale_u8.long() - 127).unsqueeze(-1)
+    return v.reshape(rows, cols).to(dtype)
+
+
+class MxQuantizer(BaseQuantizer):
+    """`format: mxfp8_e4m3` / `mxfp4_e2m1` of a `weight:` or `act:` section (n_bits 8 / 4, sym True): one E8M0 scale byte per row and
+    block of 32 input channels, e4m3 bytes or packed e2m1 nibbles.  `scale_u8` [rows, cols / 32] holds the bytes as the GEMM reads
+    them; `delta` = 2^(scale_u8 - 127) and `zero_point` zeros keep the integer quantisers' names (save / load_quant_param_dict).
+    Nothing is fitted or calibrated: the scales are a function of the tensor alone and are derived again at every call."""
+
+    def __init__(self, quant_config):
+        super().__init__(quant_config)
+        self.format = quant_config["format"]
+        self.register_buffer("scale_u8", None, persistent=False)
+
+    def codes_and_scale(self, x, gelu=False):
+        codes, s = mx_quant_rows(x, self.format, gelu)
+        self.scale_u8 = s
+        self.delta = _pow2_f64(s.long() - 127).float()
+        self.zero_point = torch.zeros_like(self.delta)
+        return codes, s
+
+    def dequantize(self, codes, scale_u8):
+        return mx_decode(codes, scale_u8, self.format)
+
+    def codes_and_dequant(self, x, want_codes=True, want_dequant=True):
+        codes, s = self.codes_and_scale(x)
+        return codes, self.dequantize(codes, s) if want_dequant else None
+
+    def quantize(self, x):
+        return self.codes_and_scale(x)[0]
+
+    def forward(self, x):
+        return self.codes_and_dequant(x, False, True)[1]

@@ -17,7 +17,8 @@ from viditq_extension import qgemm
 
 from ..config import ListConfig
 from ..quarot import quarot_utils
-from .base_quantizer import FP8_FORMAT, DynamicQuantizer, Fp8Quantizer, StaticQuantizer, fp8_decode
+from .base_quantizer import (FP8_FORMAT, MX_BLOCK, MX_FORMATS, MXFP4_FORMAT, MXFP8_FORMAT, DynamicQuantizer, Fp8Quantizer, MxQuantizer,
+                             StaticQuantizer, fp8_decode, mx_decode)
 from .mixed_precision_quantizer import MixedPrecisionDynamicQuantizer, MixedPrecisionStaticQuantizer
 
 
@@ -28,8 +29,10 @@ class QuantizedLinear(nn.Linear):
     def __init__(self, in_features, out_features, bias, device, quant_config, fp_module, module_name=None):
         super().__init__(in_features, out_features, bias, device)
         self.fp_module, self.q_cfg = fp_module, quant_config
+        self.mx = None  # the weight's MX format name (`format: mxfp8_e4m3` / `mxfp4_e2m1`), set by _checked_format
         self.fp8 = self._checked_format(quant_config, module_name)
-        self.group_size = self._checked_group_size(quant_config, module_name, fp_module.weight.device)
+        # (an MX layer's `weight.group_size: 32` names the format's own block: there is no integer group-wise path behind it)
+        self.group_size = None if self.mx else self._checked_group_size(quant_config, module_name, fp_module.weight.device)
         self.w_quantizer = self.a_quantizer = None
         self.channel_mask = None
         self.rotation_signs = None
@@ -38,7 +41,7 @@ class QuantizedLinear(nn.Linear):
         self._zp_gemm = self._wq16_vecs = None
         if quant_config.get("weight", None) is not None:
             wq = quant_config["weight"]
-            self.w_quantizer = (Fp8Quantizer if self.fp8 else
+            self.w_quantizer = (MxQuantizer if self.mx else Fp8Quantizer if self.fp8 else
                                 MixedPrecisionStaticQuantizer if isinstance(wq["n_bits"], ListConfig) else StaticQuantizer)(wq)
             self._requantize(fp_module.weight.data)
             self.w_quantizer.init_done = True
@@ -48,7 +51,7 @@ class QuantizedLinear(nn.Linear):
         self.bias = fp_module.bias
         if quant_config.get("act", None) is not None:
             aq = quant_config["act"]
-            self.a_quantizer = (Fp8Quantizer if self.fp8 else
+            self.a_quantizer = (MxQuantizer if self.mx else Fp8Quantizer if self.fp8 else
                                 MixedPrecisionDynamicQuantizer if isinstance(aq["n_bits"], ListConfig) else DynamicQuantizer)(aq)
         self.use_kernel = False
         self.quant_mode = True
@@ -64,8 +67,13 @@ class QuantizedLinear(nn.Linear):
             return False
         name = module_name or type(self).__name__
         for sec, f in (("weight", fw), ("act", fa)):
-            if f is not None and f != FP8_FORMAT:
-                raise ValueError(f"{name}: {sec}.format={f!r} is not a known format (the one format key is {FP8_FORMAT!r})")
+            if f is not None and f != FP8_FORMAT and f not in MX_FORMATS:
+                raise ValueError(f"{name}: {sec}.format={f!r} is not a known format (the format keys are {FP8_FORMAT!r}, "
+                                 f"{MXFP8_FORMAT!r} and, for weights, {MXFP4_FORMAT!r})")
+        if fw in MX_FORMATS or fa in MX_FORMATS:
+            self._check_mx_format(name, wq, aq, fw, fa)
+            self.mx = fw
+            return False
         if fw is None or fa is None:
             raise NotImplementedError(f"{name}: format: {FP8_FORMAT} must be set in both the `weight:` and the `act:` section (it is "
                                       f"missing from `{'weight' if fw is None else 'act'}:`): the fp8 GEMM takes e4m3 codes on both sides")
@@ -86,6 +94,37 @@ class QuantizedLinear(nn.Linear):
                                       "/ QuaRot / ViDiT layer classes condition an integer quantiser (leave the layer to the plain "
                                       "QuantizedLinear)")
         return True
+
+    def _check_mx_format(self, name, wq, aq, fw, fa):
+        """The accepted OCP MX pairs are (weight mxfp8_e4m3, act mxfp8_e4m3) and (weight mxfp4_e2m1, act mxfp8_e4m3), with n_bits 8 / 4,
+        sym True and weight.group_size absent or 32 (the format's block); everything else is refused by layer name."""
+        if fa == MXFP4_FORMAT:
+            raise NotImplementedError(f"{name}: act.format: {MXFP4_FORMAT} is not supported: no fp4 activation quantiser path is built "
+                                      f"yet (the MX GEMM takes {MXFP8_FORMAT} activations)")
+        if fw not in MX_FORMATS or fa not in MX_FORMATS:
+            sec, other = ("weight", fw) if fw not in MX_FORMATS else ("act", fa)
+            raise NotImplementedError(f"{name}: an MX format on one side needs an MX format on the other ({sec}.format is "
+                                      f"{other!r}): the MX GEMM takes block-scaled codes on both sides, weight {MXFP8_FORMAT} or "
+                                      f"{MXFP4_FORMAT} against act {MXFP8_FORMAT}")
+        for sec, q, f in (("weight", wq, fw), ("act", aq, fa)):
+            bits = 4 if f == MXFP4_FORMAT else 8
+            if isinstance(q["n_bits"], ListConfig):
+                raise NotImplementedError(f"{name}: {sec}.format with a bit-width list (mixed precision) is not supported: {f} is one "
+                                          f"{bits}-bit format")
+            if q["n_bits"] != bits:
+                raise NotImplementedError(f"{name}: {sec}.format: {f} needs {sec}.n_bits: {bits} (it is {q['n_bits']!r})")
+            if not q.get("sym", False):
+                raise NotImplementedError(f"{name}: {sec}.format: {f} needs {sec}.sym: True: a floating-point code has no zero point")
+        g = wq.get("group_size", None)
+        if g is not None and (isinstance(g, bool) or g != MX_BLOCK):
+            raise NotImplementedError(f"{name}: weight.format: {fw} with weight.group_size={g!r} is not supported: an MX block is "
+                                      f"{MX_BLOCK} input channels (leave the key out, or say {MX_BLOCK})")
+        if self.uses_mask or self.uses_rotation:
+            raise NotImplementedError(f"{name}: weight.format / act.format with {type(self).__name__} is not supported: the SmoothQuant "
+                                      "/ QuaRot / ViDiT layer classes condition an integer quantiser (leave the layer to the plain "
+                                      "QuantizedLinear)")
+        if self.in_features % MX_BLOCK:
+            raise ValueError(f"{name}: weight.format: {fw} needs in_features={self.in_features} to be a multiple of {MX_BLOCK}")
 
     def _checked_group_size(self, quant_config, module_name, device=None):
         """`weight.group_size` of the config (None: one scale per output channel), or the refusal of what has no group-wise form,
@@ -121,13 +160,13 @@ class QuantizedLinear(nn.Linear):
 
     @property
     def packed_w4(self):
-        return self.w_quantizer is not None and self.w_quantizer.n_bits == 4 and self.in_features % 32 == 0
+        return self.w_quantizer is not None and self.w_quantizer.n_bits == 4 and self.in_features % 32 == 0 and not self.mx
 
     @property
     def int_weight(self):
         """int8 codes [N, K].  4-bit layers keep them PACKED in HBM (two per byte, qgemm.pack_w4 layout); this view unpacks."""
         c = self._codes
-        if c is not None and c.dtype == torch.uint8 and not self.fp8:  # (an fp8 layer's uint8 codes are e4m3 bytes, one per weight)
+        if c is not None and c.dtype == torch.uint8 and not self.fp8 and not self.mx:  # (fp8 / MX layers: e4m3 bytes, e2m1 nibbles)
             return qgemm.unpack_w4(c, bias=8)
         return c
 
@@ -183,6 +222,8 @@ class QuantizedLinear(nn.Linear):
             return self.fp_module(x, *args, **kwargs)
         if self.fp8:
             return self._forward_fp8(x)
+        if self.mx:
+            return self._forward_mx(x)
         if self.group_size is not None:
             return self._forward_grouped(x)
         shape = x.shape
@@ -222,6 +263,23 @@ class QuantizedLinear(nn.Linear):
         else:
             b = None if self.bias is None else self.bias.detach().float()
             y = F.linear(fp8_decode(a_q) * a_s.unsqueeze(-1), self.weight.data.float(), b).to(out_dtype)
+        return y.view(*shape[:-1], self.out_features)
+
+    def _forward_mx(self, x):
+        """`format: mxfp8_e4m3` activations against `mxfp8_e4m3` / `mxfp4_e2m1` weights: the activation is quantised per block of 32
+        channels (MxQuantizer) and multiplied by the layer's codes with both sides' E8M0 scales applied by the matrix cores.  On the
+        GPU these are kernel mode's two entries, fused.quant_rows_mx and qgemm.mx_linear.  In host memory, and for a shape the GEMM
+        refuses, the host expression: F.linear of the dequantised activation and the dequantised weight, in fp32."""
+        shape = x.shape
+        x2 = x.reshape(-1, shape[-1])
+        out_dtype = x.dtype if x.dtype in (torch.float16, torch.bfloat16, torch.float32) else torch.float32
+        a_q, a_s = self.a_quantizer.codes_and_scale(x2)
+        if x2.is_cuda and qgemm.mx_linear_refusal(x2.shape[0], self.out_features, self.in_features, self.mx) is None:
+            y = qgemm.mx_linear(a_q, self._codes, a_s, self.w_quantizer.scale_u8, self.mx,
+                                None if self.bias is None else self.bias.detach().float().contiguous(), out_dtype=out_dtype)
+        else:
+            b = None if self.bias is None else self.bias.detach().float()
+            y = F.linear(mx_decode(a_q, a_s, MXFP8_FORMAT), self.weight.data.float(), b).to(out_dtype)
         return y.view(*shape[:-1], self.out_features)
 
     def _forward_grouped(self, x):

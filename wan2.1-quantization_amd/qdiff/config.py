@@ -7,7 +7,12 @@ section the layer's weight must be on the GPU; QuantizedLinear refuses everythin
 `format: fp8_e4m3` in BOTH the `weight:` and the `act:` section -- OCP e4m3fn codes with one fp32 scale per output channel and per
 token (absmax / 448) instead of int8 codes, on wanq_gemm_fp8; `n_bits: 8, sym: True` stay as written.  Refused by layer name when
 the layer is built: the key in only one section, with `group_size`, with `sym: False`, with `n_bits` other than 8 or a bit-width
-list, and on a SmoothQuant / QuaRot / ViDiT layer."""
+list, and on a SmoothQuant / QuaRot / ViDiT layer.
+The OCP Microscaling formats use the same key: `format: mxfp8_e4m3` (`n_bits: 8`) in `act:` and in `weight:`, `format: mxfp4_e2m1`
+(`n_bits: 4`) in `weight:` only -- one E8M0 power-of-two scale per block of 32 input channels on both sides, applied by the matrix
+cores (wanq_quant_rows_mx, wanq_gemm_mx).  The accepted pairs are weight mxfp8_e4m3 or mxfp4_e2m1 against act mxfp8_e4m3, `sym: True`,
+`weight.group_size` absent or 32; `act.format: mxfp4_e2m1`, an MX format against `fp8_e4m3` or against no format, a bit-width list,
+another group size and the SmoothQuant / QuaRot / ViDiT layer classes are refused by layer name."""
 import yaml
 
 

@@ -38,6 +38,9 @@ ABI_VERSION = 6
 _vp, _i, _i64, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
 
 # name -> argtypes, exactly include/wanq_hip.h
+# `fmt` / `w_fmt` codes of wanq_quant_rows_mx / wanq_gemm_mx (WANQ_MX_E4M3, WANQ_MX_E2M1) by the config's format names
+MX_FMT = {"mxfp8_e4m3": 0, "mxfp4_e2m1": 1}
+
 PROTOTYPES = {
     "wanq_quant_rows": [_vp, _i, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp],
     "wanq_quant_rows_levels": [_vp, _i, _vp, _vp, _vp, _i, _i64, _i, _i, _f, _vp],
@@ -52,6 +55,8 @@ PROTOTYPES = {
     "wanq_gemm_w8a8_grouped": [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
     "wanq_quant_rows_fp8": [_vp, _i, _vp, _vp, _i64, _i, _i, _vp],
     "wanq_gemm_fp8": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
+    "wanq_quant_rows_mx": [_vp, _i, _vp, _vp, _i64, _i, _i, _i, _vp],
+    "wanq_gemm_mx": [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
     "wanq_lincomb":[_i, _i, _vp, _vp, _vp, _i64, _vp],
     "wanq_linear_f32": [_vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp],
     "wanq_time_sinusoid": [_vp, _i, _vp, _i, _i, _vp],

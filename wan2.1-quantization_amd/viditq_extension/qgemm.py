@@ -460,3 +460,62 @@ def fp8_linear_refusal(M, N, K):
     if ((M + 127) // 128) * ((N + 127) // 128) >= (1 << 31):
         return "too many tiles"
     return None
+
+
+# ---- OCP MX: MXFP8 (e4m3) activations x MXFP8 / MXFP4 weights, E8M0 block scales ---------------------------------------------------
+MX_K_STEP = 128  # wanq_gemm_mx's K multiple: one K-tile = one 128-deep MFMA = four blocks of 32
+
+
+def mx_linear(a_q, w_q, a_scale, w_scale, w_fmt="mxfp8_e4m3", bias=None, out_dtype=None, gelu=False, gate=None, residual=None,
+              out=None):
+    """y = epilogue(sum over blocks of 2^(a_scale - 127) 2^(w_scale - 127) a_q @ w_q^T) on the block-scaled matrix cores (wanq_gemm_mx,
+    csrc/gemm_mx.hip): a_q uint8 [M, K] e4m3 bytes; w_q uint8 [N, K] e4m3 bytes (w_fmt "mxfp8_e4m3") or [N, K / 2] packed e2m1 nibbles
+    ("mxfp4_e2m1"); a_scale uint8 [M, K / 32], w_scale uint8 [N, K / 32], E8M0 bytes, all as `fused.quant_rows_mx` writes them.  fp32
+    accumulation, y = acc + bias and the epilogue of `fp_linear` (`gelu`; gate fp32 [N] + residual [M, N] of out_dtype, which may alias
+    `out`), one rounding to out_dtype (default bf16).  K % 128 == 0, N % 8 == 0.  A row's bits do not depend on M or on where the row
+    sits in the launch.  Not counted by the int8 timer (`set_timer`)."""
+    if w_fmt not in _C.MX_FMT:
+        raise RuntimeError(f"mx_linear: w_fmt={w_fmt!r} must be one of {tuple(_C.MX_FMT)}")
+    fp4 = _C.MX_FMT[w_fmt] == 1
+    for name, t in (("a_q", a_q), ("w_q", w_q), ("a_scale", a_scale), ("w_scale", w_scale)):
+        if t is None:
+            raise RuntimeError(f"mx_linear: {name} must be given")
+        _C.check_gpu(name, t)
+        _C.check_contig(name, t)
+        _C.check_dtype(name, t, torch.uint8)
+        if t.dim() != 2:
+            raise RuntimeError(f"Tensor {name} must have dimension number (2)")
+    M, K = a_q.shape
+    N = w_q.shape[0]
+    why = mx_linear_refusal(M, N, K, w_fmt)
+    if why is not None:
+        raise RuntimeError(f"mx_linear: {why}")
+    _C.check_shape("w_q", w_q, N, K // 2 if fp4 else K)
+    _C.check_shape("a_scale", a_scale, M, K // 32)
+    _C.check_shape("w_scale", w_scale, N, K // 32)
+    out_dtype = out_dtype or torch.bfloat16
+    _check_vec("bias", bias, N, _BIAS16)
+    epi = _epi_flags(gelu, gate, residual, M, N, out_dtype)
+    out = _out_for(out, M, N, out_dtype, a_q.device)
+    _C.check_same_device(a_q, w_q, a_scale, w_scale, bias, gate, residual, out)
+    with torch.cuda.device(a_q.device):
+        _C.call("wanq_gemm_mx", _C.ptr(a_q), _C.ptr(w_q), _C.ptr(a_scale), _C.ptr(w_scale), _C.MX_FMT[w_fmt], _C.ptr(out),
+                _C.dt(out_dtype), _C.ptr(bias), _C.dt(bias) if bias is not None else _C.F32, _C.ptr(gate), _C.ptr(residual), epi, M, N, K,
+                _C.stream())
+    return out
+
+
+def mx_linear_refusal(M, N, K, w_fmt="mxfp8_e4m3"):
+    """Why wanq_gemm_mx would refuse an [M, K] x [N, K] product (None = accepted): the shape rules of include/wanq_hip.h in the order
+    the entry checks them; see `fp_linear_refusal`."""
+    if w_fmt not in _C.MX_FMT:
+        return f"w_fmt={w_fmt!r} must be one of {tuple(_C.MX_FMT)}"
+    if M < 0 or M >= (1 << 31) - 128:
+        return f"M={M} out of range"
+    if N < 8 or N % 8:
+        return f"N={N} must be a positive multiple of 8"
+    if K < MX_K_STEP or K % MX_K_STEP:
+        return f"K={K} must be a positive multiple of {MX_K_STEP}"
+    if ((M + 127) // 128) * ((N + 127) // 128) >= (1 << 31):
+        return "too many tiles"
+    return None

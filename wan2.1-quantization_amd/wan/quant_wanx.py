@@ -77,6 +77,9 @@ class QuantWanModel(WanModel, QuantModel):
                     if getattr(mod, "fp8", False):
                         raise NotImplementedError(f"{name}: the reference's int_weight.pt format holds int8 codes (the layer is "
                                                   "format: fp8_e4m3; save with reference_format=False)")
+                    if getattr(mod, "mx", None):
+                        raise NotImplementedError(f"{name}: the reference's int_weight.pt format holds int8 codes (the layer is "
+                                                  f"format: {mod.mx}; save with reference_format=False)")
                     if getattr(mod, "group_size", None) is not None:
                         raise NotImplementedError(f"{name}: the reference's int_weight.pt format has one scale per output channel "
                                                   "(weight.group_size is set; save with reference_format=False)")
@@ -93,10 +96,12 @@ class QuantWanModel(WanModel, QuantModel):
                 else:
                     # 8-bit: int8 [N, K]; 4-bit: uint8 [N, K/2], the packed nibbles exactly as the GEMM reads them; format: fp8_e4m3:
                     # uint8 [N, K], the e4m3 bytes, with their per-channel scales
-                    # (weight.group_size: the parameters as the group-wise GEMM reads them, [K / g, N])
+                    # (weight.group_size: the parameters as the group-wise GEMM reads them, [K / g, N]); format: mxfp8_e4m3 /
+                    # mxfp4_e2m1: uint8 [N, K] e4m3 bytes / uint8 [N, K/2] packed e2m1 nibbles, scale_weight uint8 [N, K/32] E8M0 bytes
                     grouped = getattr(mod, "group_size", None) is not None
                     sd[name + ".weight"] = mod._codes.clone()
-                    sd[name + ".scale_weight"] = (wq.delta.float().t().contiguous() if grouped else wq.delta.reshape(-1).float().clone())
+                    sd[name + ".scale_weight"] = (wq.scale_u8.clone() if getattr(mod, "mx", None) else
+                                                  wq.delta.float().t().contiguous() if grouped else wq.delta.reshape(-1).float().clone())
                     if not wq.sym:
                         sd[name + ".zp_weight"] = (wq.zero_point.float().t().contiguous() if grouped
                                                    else wq.zero_point.reshape(-1).float().clone())
@@ -176,7 +181,7 @@ class QuantWanModel(WanModel, QuantModel):
                                         [(hb, "ffn0", "ffn.0"), (hb, "ffn2", "ffn.2")]:
                     lin = getattr(owner, attr)
                     weight_only = getattr(lin, "weight_only", False)  # HipLinearWq16: the same keys, no act_premul
-                    if not lin.quantized and not weight_only and not getattr(lin, "fp8", False):
+                    if not lin.quantized and not weight_only and not getattr(lin, "fp8", False) and not getattr(lin, "mx", None):
                         continue
                     base = f"blocks.{i}.{key}"
                     # The two formats carry no marker.  What tells them apart is that reference_format=True writes fp16 scales and the
@@ -201,7 +206,7 @@ class QuantWanModel(WanModel, QuantModel):
                             if buf == "zp_weight" and not bool(src.float().abs().max() > 0):
                                 continue
                             raise KeyError(f"{load_path}: {base}.{k} present but the model's layer has no {buf}")
-                        if tuple(src.shape) != tuple(dst.shape) or (buf == "weight" and src.dtype != dst.dtype):
+                        if tuple(src.shape) != tuple(dst.shape) or ((buf == "weight" or dst.dtype == torch.uint8) and src.dtype != dst.dtype):
                             raise ValueError(f"{load_path}: {base}.{k} is {tuple(src.shape)} {src.dtype}, expected {tuple(dst.shape)} {dst.dtype}")
                         dst.copy_(src.to(dst.dtype))
                         taken += 1

@@ -314,10 +314,57 @@ class HipLinearFp8(nn.Module):
                                 residual=residual, out=out)
 
 
+class HipLinearMx(nn.Module):
+    """An OCP MX Linear (`format: mxfp8_e4m3` activations against `mxfp8_e4m3` / `mxfp4_e2m1` weights): `weight` uint8 [N, K] e4m3
+    bytes or [N, K / 2] packed e2m1 nibbles, `scale_weight` uint8 [N, K / 32] E8M0 bytes, both from wanq_quant_rows_mx; `bias` fp32.
+    Its input is the block's activation quantised per block of 32 channels by the same entry (_LnSrc.mxfp8 / _FpSrc.mxfp8: codes +
+    scale bytes, one copy shared by every MX consumer of a source), and the product is qgemm.mx_linear (csrc/gemm_mx.hip) with GELU
+    and gate + residual in its epilogue.  No zero point, no activation transform; the int8 producers and their prefetch skip it."""
+    quantized = False   # not an int8 consumer
+    fp8 = False
+    act_key = "mxfp8"
+    act_premul = None
+    zp_weight = None
+
+    def __init__(self, in_features, out_features, bias=True, w_fmt="mxfp8_e4m3", name="linear"):
+        super().__init__()
+        why = qgemm.mx_linear_refusal(1, out_features, in_features, w_fmt)
+        if why is not None:
+            raise NotImplementedError(f"{name}: format: {w_fmt} has no kernel-mode form for this layer ({out_features}, "
+                                      f"{in_features}): {why}")
+        self.in_features, self.out_features, self.mx = in_features, out_features, w_fmt
+        wk = in_features // 2 if w_fmt == "mxfp4_e2m1" else in_features
+        self.register_buffer("weight", torch.empty(out_features, wk, dtype=torch.uint8))
+        self.register_buffer("scale_weight", torch.empty(out_features, in_features // 32, dtype=torch.uint8))
+        self.register_buffer("bias", torch.empty(out_features, dtype=torch.float32) if bias else None)
+
+    def refresh_zp_gemm(self):
+        """(the checkpoint loader's hook: nothing is derived from the loaded buffers)"""
+
+    @classmethod
+    def from_quantized(cls, ql, name="linear"):
+        """From a plain qdiff QuantizedLinear built with an MX format: the same codes and scale bytes."""
+        m = cls(ql.in_features, ql.out_features, ql.bias is not None, ql.mx, name).to(ql.fp_module.weight.device)
+        if tuple(ql._codes.shape) != tuple(m.weight.shape) or ql._codes.dtype != torch.uint8:
+            raise ValueError(f"{name}: codes {tuple(ql._codes.shape)} {ql._codes.dtype} do not fit {tuple(m.weight.shape)} uint8")
+        m.weight.copy_(ql._codes)
+        m.scale_weight.copy_(ql.w_quantizer.scale_u8)
+        if ql.bias is not None:
+            m.bias.copy_(ql.bias.detach().float())
+        return m
+
+    def forward(self, a_q, a_scale, out_dtype=torch.bfloat16, gelu=False, gate=None, residual=None, out=None):
+        """Reads `weight` and `scale_weight` as they are now (--dit_fsdp re-points them at views of the gathered buffer)."""
+        return qgemm.mx_linear(a_q, self.weight, a_scale, self.scale_weight, self.mx, self.bias, out_dtype, gelu=gelu, gate=gate,
+                               residual=residual, out=out)
+
+
 def _to_hip_linear(lin, n_bits, sym, act_dtype, fp_gemm="torch", name="linear"):
     from qdiff.base.quant_layer import QuantizedLinear
 
     if isinstance(lin, QuantizedLinear):
+        if lin.quant_mode and getattr(lin, "mx", None):
+            return HipLinearMx.from_quantized(lin, name)
         if lin.quant_mode and getattr(lin, "fp8", False):
             return HipLinearFp8.from_quantized(lin, name)
         if lin.quant_mode and lin.w_quantizer is not None and lin.a_quantizer is not None:
@@ -390,6 +437,13 @@ class _LnSrc:
             self.cache["fp8"] = fused.quant_rows_fp8(self.fp32())
         return self.cache["fp8"]
 
+    def mxfp8(self, lin):
+        """(e4m3 codes, E8M0 scale bytes) for the MX consumers (HipLinearMx), one copy for all of them: quantised from the fp32 row,
+        what a simulation-mode quantiser sees.  (A fused LayerNorm + modulate + MX producer would save the fp32 round trip.)"""
+        if "mxfp8" not in self.cache:
+            self.cache["mxfp8"] = fused.quant_rows_mx(self.fp32())
+        return self.cache["mxfp8"]
+
     def fp(self):
         if "fp" not in self.cache:
             out = torch.empty(self.x.shape, dtype=self.blk.act_dtype, device=self.x.device)
@@ -435,6 +489,13 @@ class _FpSrc:
         if "fp8" not in self.cache:
             self.cache["fp8"] = fused.quant_rows_fp8(self.t, gelu=self.gelu)
         return self.cache["fp8"]
+
+    def mxfp8(self, lin):
+        """(e4m3 codes, E8M0 scale bytes) of the 16-bit tensor for the MX consumers, one copy for all of them; `gelu`: the quantiser
+        applies the tanh-GELU itself (its act = 1)."""
+        if "mxfp8" not in self.cache:
+            self.cache["mxfp8"] = fused.quant_rows_mx(self.t, gelu=self.gelu)
+        return self.cache["mxfp8"]
 
     def fp32(self):
         if "fp32" not in self.cache:
@@ -556,6 +617,11 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         out_dtype = out_dtype or self.act_dtype
         if getattr(lin, "fp8", False):
             q, s = src.fp8(lin)
+            if residual is not None:
+                return lin(q, s, torch.float32, gate=gate.float().contiguous(), residual=residual, out=residual)
+            return lin(q, s, out_dtype, gelu=gelu)
+        if getattr(lin, "mx", None):
+            q, s = src.mxfp8(lin)
             if residual is not None:
                 return lin(q, s, torch.float32, gate=gate.float().contiguous(), residual=residual, out=residual)
             return lin(q, s, out_dtype, gelu=gelu)
@@ -734,7 +800,8 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         # rotation in front of ffn.2, or a floating-point ffn.2, it stays in ffn.0's epilogue.
         h = _LnSrc(self, x, None, e[:, 3], e[:, 4])
         late_gelu = (self.ffn0.quantized and self.ffn2.quantized and self.ffn2.act_key is None) or \
-            (getattr(self.ffn0, "fp8", False) and getattr(self.ffn2, "fp8", False))  # fp8: the quantiser's act = 1
+            (getattr(self.ffn0, "fp8", False) and getattr(self.ffn2, "fp8", False)) or \
+            (bool(getattr(self.ffn0, "mx", None)) and bool(getattr(self.ffn2, "mx", None)))  # fp8 / MX: the quantiser's act = 1
         hid = self._linear(self.ffn0, h, gelu=not late_gelu)
         self._linear(self.ffn2, _FpSrc(hid, gelu=late_gelu), gate=e[0, 5].contiguous(), residual=x)
         return x
