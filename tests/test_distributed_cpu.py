@@ -207,6 +207,8 @@ def test_block_attention_dispatch_table(monkeypatch):
 # ---------------------------------------------------------------------------------------------------------------------
 # --dit_fsdp: block weights sharded over the ranks, all-gathered one block ahead (wan/distributed/fsdp.py)
 class _ToyLin:
+    sharded = ("weight",)  # (what ShardedBlocks asks a kernel-mode Linear)
+
     def __init__(self, w):
         self.weight = w
 

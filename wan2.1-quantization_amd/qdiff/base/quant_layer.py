@@ -22,6 +22,10 @@ from .base_quantizer import (FP8_FORMAT, MX_BLOCK, MX_FORMATS, MXFP4_FORMAT, MXF
 from .mixed_precision_quantizer import MixedPrecisionDynamicQuantizer, MixedPrecisionStaticQuantizer
 
 
+# format key -> (its n_bits, its name in "... is one N-bit format")
+_FORMAT_BITS = {FP8_FORMAT: (8, "e4m3"), MXFP8_FORMAT: (8, MXFP8_FORMAT), MXFP4_FORMAT: (4, MXFP4_FORMAT)}
+
+
 class QuantizedLinear(nn.Linear):
     uses_mask = False
     uses_rotation = False
@@ -67,7 +71,7 @@ class QuantizedLinear(nn.Linear):
             return False
         name = module_name or type(self).__name__
         for sec, f in (("weight", fw), ("act", fa)):
-            if f is not None and f != FP8_FORMAT and f not in MX_FORMATS:
+            if f is not None and f not in _FORMAT_BITS:
                 raise ValueError(f"{name}: {sec}.format={f!r} is not a known format (the format keys are {FP8_FORMAT!r}, "
                                  f"{MXFP8_FORMAT!r} and, for weights, {MXFP4_FORMAT!r})")
         if fw in MX_FORMATS or fa in MX_FORMATS:
@@ -77,23 +81,30 @@ class QuantizedLinear(nn.Linear):
         if fw is None or fa is None:
             raise NotImplementedError(f"{name}: format: {FP8_FORMAT} must be set in both the `weight:` and the `act:` section (it is "
                                       f"missing from `{'weight' if fw is None else 'act'}:`): the fp8 GEMM takes e4m3 codes on both sides")
-        for sec, q in (("weight", wq), ("act", aq)):
-            if isinstance(q["n_bits"], ListConfig):
-                raise NotImplementedError(f"{name}: {sec}.format with a bit-width list (mixed precision) is not supported: e4m3 is one "
-                                          "8-bit format")
-            if q["n_bits"] != 8:
-                raise NotImplementedError(f"{name}: {sec}.format: {FP8_FORMAT} needs {sec}.n_bits: 8 (it is {q['n_bits']!r})")
-            if not q.get("sym", False):
-                raise NotImplementedError(f"{name}: {sec}.format: {FP8_FORMAT} needs {sec}.sym: True: a floating-point code has no "
-                                          "zero point")
+        self._check_format_sections(name, (("weight", wq, fw), ("act", aq, fa)))
         if wq.get("group_size", None) is not None:
             raise NotImplementedError(f"{name}: weight.format with weight.group_size is not supported: the fp8 GEMM applies one weight "
                                       "scale per output channel")
+        self._refuse_format_on_a_transformed_layer(name)
+        return True
+
+    def _check_format_sections(self, name, sections):
+        """What every format asks of the section that names it: one bit width, the format's own (_FORMAT_BITS), and `sym: True`."""
+        for sec, q, f in sections:
+            bits, one = _FORMAT_BITS[f]
+            if isinstance(q["n_bits"], ListConfig):
+                raise NotImplementedError(f"{name}: {sec}.format with a bit-width list (mixed precision) is not supported: {one} is one "
+                                          f"{bits}-bit format")
+            if q["n_bits"] != bits:
+                raise NotImplementedError(f"{name}: {sec}.format: {f} needs {sec}.n_bits: {bits} (it is {q['n_bits']!r})")
+            if not q.get("sym", False):
+                raise NotImplementedError(f"{name}: {sec}.format: {f} needs {sec}.sym: True: a floating-point code has no zero point")
+
+    def _refuse_format_on_a_transformed_layer(self, name):
         if self.uses_mask or self.uses_rotation:
             raise NotImplementedError(f"{name}: weight.format / act.format with {type(self).__name__} is not supported: the SmoothQuant "
                                       "/ QuaRot / ViDiT layer classes condition an integer quantiser (leave the layer to the plain "
                                       "QuantizedLinear)")
-        return True
 
     def _check_mx_format(self, name, wq, aq, fw, fa):
         """The accepted OCP MX pairs are (weight mxfp8_e4m3, act mxfp8_e4m3) and (weight mxfp4_e2m1, act mxfp8_e4m3), with n_bits 8 / 4,
@@ -106,23 +117,12 @@ class QuantizedLinear(nn.Linear):
             raise NotImplementedError(f"{name}: an MX format on one side needs an MX format on the other ({sec}.format is "
                                       f"{other!r}): the MX GEMM takes block-scaled codes on both sides, weight {MXFP8_FORMAT} or "
                                       f"{MXFP4_FORMAT} against act {MXFP8_FORMAT}")
-        for sec, q, f in (("weight", wq, fw), ("act", aq, fa)):
-            bits = 4 if f == MXFP4_FORMAT else 8
-            if isinstance(q["n_bits"], ListConfig):
-                raise NotImplementedError(f"{name}: {sec}.format with a bit-width list (mixed precision) is not supported: {f} is one "
-                                          f"{bits}-bit format")
-            if q["n_bits"] != bits:
-                raise NotImplementedError(f"{name}: {sec}.format: {f} needs {sec}.n_bits: {bits} (it is {q['n_bits']!r})")
-            if not q.get("sym", False):
-                raise NotImplementedError(f"{name}: {sec}.format: {f} needs {sec}.sym: True: a floating-point code has no zero point")
+        self._check_format_sections(name, (("weight", wq, fw), ("act", aq, fa)))
         g = wq.get("group_size", None)
         if g is not None and (isinstance(g, bool) or g != MX_BLOCK):
             raise NotImplementedError(f"{name}: weight.format: {fw} with weight.group_size={g!r} is not supported: an MX block is "
                                       f"{MX_BLOCK} input channels (leave the key out, or say {MX_BLOCK})")
-        if self.uses_mask or self.uses_rotation:
-            raise NotImplementedError(f"{name}: weight.format / act.format with {type(self).__name__} is not supported: the SmoothQuant "
-                                      "/ QuaRot / ViDiT layer classes condition an integer quantiser (leave the layer to the plain "
-                                      "QuantizedLinear)")
+        self._refuse_format_on_a_transformed_layer(name)
         if self.in_features % MX_BLOCK:
             raise ValueError(f"{name}: weight.format: {fw} needs in_features={self.in_features} to be a multiple of {MX_BLOCK}")
 
@@ -214,98 +214,85 @@ class QuantizedLinear(nn.Linear):
             self._premul = pm.contiguous()
         return self._premul, self._rot
 
+    @property
+    def kind(self):
+        """What this layer is now, the one place that says so: "fp" (quantisation off, or no `weight:` section: the FP module),
+        "weight_only" (no `act:` section), else by its format "fp8", "mx", "int8_grouped" (a `weight.group_size`) or "int8".  `forward`
+        dispatches on it and kernel mode maps it to a layer class (wan/quant_wanx_hip.py::_to_hip_linear).  A SmoothQuant / QuaRot /
+        ViDiT layer without an `act:` section is "weight_only" too: `forward` runs its FP module, kernel mode refuses it by name."""
+        if not self.quant_mode or self.w_quantizer is None:
+            return "fp"
+        if self.a_quantizer is None:
+            return "weight_only"
+        return "fp8" if self.fp8 else "mx" if self.mx else "int8_grouped" if self.group_size is not None else "int8"
+
     def forward(self, x, *args, **kwargs):
         """x: [B, N_token, C] (or [tokens, C]) on the GPU."""
-        if self.quant_mode and self.w_quantizer is not None and self.a_quantizer is None and not (self.uses_mask or self.uses_rotation):
-            return self._forward_weight_only(x)
-        if not self.quant_mode or self.w_quantizer is None or self.a_quantizer is None:
+        kind = self.kind
+        if kind == "fp" or (kind == "weight_only" and (self.uses_mask or self.uses_rotation)):
             return self.fp_module(x, *args, **kwargs)
-        if self.fp8:
-            return self._forward_fp8(x)
-        if self.mx:
-            return self._forward_mx(x)
-        if self.group_size is not None:
-            return self._forward_grouped(x)
-        shape = x.shape
-        x2 = x.reshape(-1, shape[-1])
+        if kind == "weight_only":
+            return self._forward_weight_only(x)
+        out_dtype = x.dtype if x.dtype in (torch.float16, torch.bfloat16, torch.float32) else torch.float32
+        bias = None if self.bias is None else self.bias.detach().float().contiguous()
+        y = self._FORWARDS[kind](self, x.reshape(-1, x.shape[-1]), out_dtype, bias)
+        return y.view(*x.shape[:-1], self.out_features)
+
+    def _forward_int8(self, x2, out_dtype, bias):
         premul, rot = self._act_transform()
         q, scale, ssum = self.a_quantizer.quantize_int8(x2, premul, rot)
         wq = self.w_quantizer
         zp = None if wq.sym else wq.zero_point.reshape(-1).float().contiguous()
-        out_dtype = x.dtype if x.dtype in (torch.float16, torch.bfloat16, torch.float32) else torch.float32
         w4 = self._codes.dtype == torch.uint8
         if w4:  # nibbles are stored as code + 8: fold the 8 into the zero point of the epilogue
             if self._zp_gemm is None:
                 self._zp_gemm = ((zp if zp is not None else torch.zeros_like(wq.delta.reshape(-1).float())) - 8.0).contiguous()
             zp = self._zp_gemm
-        y = qgemm.w8a8_linear(q, self._codes, scale, wq.delta.reshape(-1).float().contiguous(),
-                              None if self.bias is None else self.bias.detach().float().contiguous(),
+        y = qgemm.w8a8_linear(q, self._codes, scale, wq.delta.reshape(-1).float().contiguous(), bias,
                               ssum if zp is not None else None, zp, out_dtype=out_dtype, w4=w4)
-        if not self.a_quantizer.sym:
-            # asymmetric activations x_dq = (q + zp_a) * s_a: the zero point's share of x_dq . w_dq^T is the rank-one term
-            # (zp_a s_a)[token] x rowsum(w_dq)[channel]  (Q/base/base_quantizer.py:130-162; no Wan configuration uses this branch)
-            t_a = (self.a_quantizer.zero_point.reshape(-1).float() * scale).to(y.dtype)
-            y = torch.addcmul(y, t_a.unsqueeze(1), self.weight.data.float().sum(dim=1).to(y.dtype).unsqueeze(0))
-        return y.view(*shape[:-1], self.out_features)
+        return self._add_act_zero_point_term(y, scale)
 
-    def _forward_fp8(self, x):
+    def _add_act_zero_point_term(self, y, scale):
+        """asymmetric activations x_dq = (q + zp_a) * s_a: the zero point's share of x_dq . w_dq^T is the rank-one term
+        (zp_a s_a)[token] x rowsum(w_dq)[channel], row sums of the dequantised weight, so group-agnostic
+        (Q/base/base_quantizer.py:130-162; no Wan configuration uses this branch)"""
+        if self.a_quantizer.sym:
+            return y
+        t_a = (self.a_quantizer.zero_point.reshape(-1).float() * scale).to(y.dtype)
+        return torch.addcmul(y, t_a.unsqueeze(1), self.weight.data.float().sum(dim=1).to(y.dtype).unsqueeze(0))
+
+    def _forward_format(self, x2, out_dtype, bias):
         """`format: fp8_e4m3`: the activation is quantised per token to e4m3 (Fp8Quantizer) and multiplied by the layer's e4m3 weight
-        codes, one fp32 scale per token and per output channel.  On the GPU these are kernel mode's two entries,
-        fused.quant_rows_fp8 and qgemm.fp8_linear.  In host memory, and for a shape the GEMM refuses, the same numbers through torch:
-        F.linear of the dequantised activation and the dequantised weight, in fp32."""
-        shape = x.shape
-        x2 = x.reshape(-1, shape[-1])
-        out_dtype = x.dtype if x.dtype in (torch.float16, torch.bfloat16, torch.float32) else torch.float32
+        codes, one fp32 scale per token and per output channel.  `format: mxfp8_e4m3` activations against `mxfp8_e4m3` / `mxfp4_e2m1`
+        weights: quantised per block of 32 channels (MxQuantizer), both sides' E8M0 scales applied by the matrix cores.  On the GPU
+        these are kernel mode's two entries per format, fused.quant_rows_fp8 + qgemm.fp8_linear and fused.quant_rows_mx +
+        qgemm.mx_linear.  In host memory, and for a shape the GEMM refuses, the same numbers through torch: F.linear of the
+        dequantised activation and the dequantised weight, in fp32."""
         a_q, a_s = self.a_quantizer.codes_and_scale(x2)
-        if x2.is_cuda and qgemm.fp8_linear_refusal(x2.shape[0], self.out_features, self.in_features) is None:
-            y = qgemm.fp8_linear(a_q, self._codes, a_s, self.w_quantizer.delta.reshape(-1).float().contiguous(),
-                                 None if self.bias is None else self.bias.detach().float().contiguous(), out_dtype=out_dtype)
-        else:
-            b = None if self.bias is None else self.bias.detach().float()
-            y = F.linear(fp8_decode(a_q) * a_s.unsqueeze(-1), self.weight.data.float(), b).to(out_dtype)
-        return y.view(*shape[:-1], self.out_features)
+        refusal, gemm, fmt = (qgemm.mx_linear_refusal, qgemm.mx_linear, (self.mx,)) if self.mx else \
+            (qgemm.fp8_linear_refusal, qgemm.fp8_linear, ())
+        if x2.is_cuda and refusal(x2.shape[0], self.out_features, self.in_features, *fmt) is None:
+            w_s = self.w_quantizer.scale_u8 if self.mx else self.w_quantizer.delta.reshape(-1).float().contiguous()
+            return gemm(a_q, self._codes, a_s, w_s, *fmt, bias, out_dtype=out_dtype)
+        a = mx_decode(a_q, a_s, MXFP8_FORMAT) if self.mx else fp8_decode(a_q) * a_s.unsqueeze(-1)
+        return F.linear(a, self.weight.data.float(), bias).to(out_dtype)
 
-    def _forward_mx(self, x):
-        """`format: mxfp8_e4m3` activations against `mxfp8_e4m3` / `mxfp4_e2m1` weights: the activation is quantised per block of 32
-        channels (MxQuantizer) and multiplied by the layer's codes with both sides' E8M0 scales applied by the matrix cores.  On the
-        GPU these are kernel mode's two entries, fused.quant_rows_mx and qgemm.mx_linear.  In host memory, and for a shape the GEMM
-        refuses, the host expression: F.linear of the dequantised activation and the dequantised weight, in fp32."""
-        shape = x.shape
-        x2 = x.reshape(-1, shape[-1])
-        out_dtype = x.dtype if x.dtype in (torch.float16, torch.bfloat16, torch.float32) else torch.float32
-        a_q, a_s = self.a_quantizer.codes_and_scale(x2)
-        if x2.is_cuda and qgemm.mx_linear_refusal(x2.shape[0], self.out_features, self.in_features, self.mx) is None:
-            y = qgemm.mx_linear(a_q, self._codes, a_s, self.w_quantizer.scale_u8, self.mx,
-                                None if self.bias is None else self.bias.detach().float().contiguous(), out_dtype=out_dtype)
-        else:
-            b = None if self.bias is None else self.bias.detach().float()
-            y = F.linear(mx_decode(a_q, a_s, MXFP8_FORMAT), self.weight.data.float(), b).to(out_dtype)
-        return y.view(*shape[:-1], self.out_features)
-
-    def _forward_grouped(self, x):
-        """A `weight.group_size` with an `act:` section: the activation is quantised per token as in `forward` and multiplied on the
-        int8 matrix cores by wanq_gemm_w8a8_grouped, on the layer's codes and the [K / g, N] operands of `weight_only_operands`
+    def _forward_grouped(self, x2, out_dtype, bias):
+        """A `weight.group_size` with an `act:` section: the activation is quantised per token as in `_forward_int8` and multiplied on
+        the int8 matrix cores by wanq_gemm_w8a8_grouped, on the layer's codes and the [K / g, N] operands of `weight_only_operands`
         (the 4-bit `zp - 8` convention is the same).  What that entry refuses -- a group that is not a multiple of 128, 8-bit
         asymmetric weights -- goes through the reference's own expression, F.linear(a_quantizer(x), W_hat, bias) on the
         dequantised weight."""
-        shape = x.shape
-        x2 = x.reshape(-1, shape[-1])
-        wq = self.w_quantizer
-        out_dtype = x.dtype if x.dtype in (torch.float16, torch.bfloat16, torch.float32) else torch.float32
         w4 = self._codes.dtype == torch.uint8
         if qgemm.w8a8_grouped_linear_refusal(x2.shape[0], self.out_features, self.in_features, self.group_size, 4 if w4 else 8,
-                                             bool(wq.sym)) is not None:
-            b = None if self.bias is None else self.bias.detach().float()
-            y = F.linear(self.a_quantizer(x2).float(), self.weight.data.float(), b).to(out_dtype)
-            return y.view(*shape[:-1], self.out_features)
+                                             bool(self.w_quantizer.sym)) is not None:
+            return F.linear(self.a_quantizer(x2).float(), self.weight.data.float(), bias).to(out_dtype)
         q, scale, _ = self.a_quantizer.quantize_int8(x2, want_sum=False)
         codes, sw, zp, w4 = self.weight_only_operands()
-        y = qgemm.w8a8_grouped_linear(q, codes, scale, sw, zp, self.group_size,
-                                      None if self.bias is None else self.bias.detach().float().contiguous(), out_dtype=out_dtype, w4=w4)
-        if not self.a_quantizer.sym:  # the rank-one term of `forward`: row sums of the dequantised weight, group-agnostic
-            t_a = (self.a_quantizer.zero_point.reshape(-1).float() * scale).to(y.dtype)
-            y = torch.addcmul(y, t_a.unsqueeze(1), self.weight.data.float().sum(dim=1).to(y.dtype).unsqueeze(0))
-        return y.view(*shape[:-1], self.out_features)
+        y = qgemm.w8a8_grouped_linear(q, codes, scale, sw, zp, self.group_size, bias, out_dtype=out_dtype, w4=w4)
+        return self._add_act_zero_point_term(y, scale)
+
+    _FORWARDS = {"int8": _forward_int8, "int8_grouped": _forward_grouped, "fp8": _forward_format, "mx": _forward_format}
 
     def weight_only_operands(self):
         """(codes, scale fp32 [N], zp fp32 [N] or None, w4) of wanq_gemm_wq16 for this layer's quantised weight: int8 codes, or the

@@ -6,6 +6,7 @@ C assert that aborts the process otherwise); per-token / per-channel vectors fp1
 int16 or fp32; output fp16 (reference), bf16 or fp32; launched on the CURRENT stream (reference: legacy
 default stream).
 """
+import contextlib
 import os
 
 import torch
@@ -24,14 +25,32 @@ def set_timer(t):
     _timer = t
 
 
-def _check_i8(name, t, rows=None, cols=None):
+@contextlib.contextmanager
+def _timed(ops):
+    """The int8 timer's bracket (`set_timer`) around what the body launches on the current stream: `ops` int8 operations."""
+    if _timer is None:
+        yield
+        return
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev0.record()
+    yield
+    ev1.record()
+    _timer.append((ev0, ev1, ops))
+
+
+def _check_mat(name, t, dtype, *shape):
+    """A matrix operand: on the GPU, contiguous, of `dtype`, of rank 2 and, when given, of `shape`."""
     _C.check_gpu(name, t)
     _C.check_contig(name, t)
-    _C.check_dtype(name, t, torch.int8)
+    _C.check_dtype(name, t, dtype)
     if t.dim() != 2:
         raise RuntimeError(f"Tensor {name} must have dimension number (2)")
-    if rows is not None:
-        _C.check_shape(name, t, rows, cols)
+    if shape:
+        _C.check_shape(name, t, *shape)
+
+
+def _check_i8(name, t, rows=None, cols=None):
+    _check_mat(name, t, torch.int8, *(() if rows is None else (rows, cols)))
 
 
 def _check_vec(name, t, n, dtypes=_VEC):
@@ -113,19 +132,13 @@ def w8a8_linear(input, weight, scale_input, scale_weight, bias=None, input_sum=N
     epi = _epi_flags(gelu, gate, residual, M, N, out_dtype)
     out = _out_for(out, M, N, out_dtype, input.device)
     _C.check_same_device(input, weight, scale_input, scale_weight, bias, input_sum, zp_weight, gate, residual, out)
-    with torch.cuda.device(input.device):
-        if _timer is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
+    with torch.cuda.device(input.device), _timed(2 * M * N * K):
         if w4 and _W4_UNPACK_ROWS and M >= _W4_UNPACK_ROWS and K % 128 == 0 and K >= 256:
             weight, w4 = unpack_w4(weight, bias=0, out=_w4_scratch_for(weight)), False  # inside the timed region: part of this product's cost
         _C.call("wanq_gemm_w4a8" if w4 else "wanq_gemm_w8a8", _C.ptr(input), _C.ptr(weight), _C.ptr(out), _C.dt(out_dtype), _C.ptr(scale_input),
                 _C.ptr(input_sum), _C.dt(scale_input), _C.ptr(scale_weight), _C.ptr(bias), _C.dt(scale_weight),
                 _C.ptr(zp_weight), _C.dt(zp_weight) if zp_weight is not None else _C.F32, _C.ptr(gate),
                 _C.ptr(residual), epi, M, N, K, _C.stream())
-        if _timer is not None:
-            ev1.record()
-            _timer.append((ev0, ev1, 2 * M * N * K))
     return out
 
 
@@ -250,6 +263,43 @@ def _check_operands16(input, wname, weight, wdtype):
     return M, weight.shape[0], K
 
 
+def _shape_refusal(M, N, K, k_step, bounded=False):
+    """The shape rules the entries share, in the order they check them: N a positive multiple of 8, K one of `k_step` (None: the
+    entry has a K rule of its own) and, for a `bounded` entry, M's range before and the tile count after."""
+    if bounded and (M < 0 or M >= (1 << 31) - 128):
+        return f"M={M} out of range"
+    if N < 8 or N % 8:
+        return f"N={N} must be a positive multiple of 8"
+    if k_step is not None and (K < k_step or K % k_step):
+        return f"K={K} must be a positive multiple of {k_step}"
+    if bounded and ((M + 127) // 128) * ((N + 127) // 128) >= (1 << 31):
+        return "too many tiles"
+    return None
+
+
+def _check_group_params(K, N, group_size, scale_weight, zp):
+    """scale_weight and zp of a group-wise entry: fp32 [K / group_size, N] (zp may be None)."""
+    for name, t in (("scale_weight", scale_weight), ("zp", zp)):
+        if t is not None:
+            _C.check_gpu(name, t)
+            _C.check_contig(name, t)
+            _C.check_dtype(name, t, torch.float32)
+            _C.check_shape(name, t, K // group_size, N)
+
+
+def _launch16(entry, lead, operands, bias, out_dtype, gelu, gate, residual, out, M, N, K):
+    """What the entries with the 16-bit GEMMs' epilogue share behind their operand checks: bias, epilogue flags, `out`, one device,
+    then `entry`(*lead, out, out dtype, bias, bias dtype, gate, residual, epi, M, N, K, stream).  -> out"""
+    _check_vec("bias", bias, N, _BIAS16)
+    epi = _epi_flags(gelu, gate, residual, M, N, out_dtype)
+    out = _out_for(out, M, N, out_dtype, operands[0].device)
+    _C.check_same_device(*operands, bias, gate, residual, out)
+    with torch.cuda.device(operands[0].device):
+        _C.call(entry, *lead, _C.ptr(out), _C.dt(out_dtype), _C.ptr(bias), _C.dt(bias) if bias is not None else _C.F32, _C.ptr(gate),
+                _C.ptr(residual), epi, M, N, K, _C.stream())
+    return out
+
+
 def fp_linear(input, weight, bias=None, out_dtype=None, gelu=False, gate=None, residual=None, out=None):
     """y = epilogue(input[M,K] @ weight[N,K]^T) on the bf16 / fp16 matrix cores (wanq_gemm_bf16, csrc/gemm_bf16.hip); input and
     weight share a dtype (bf16 or fp16).  Epilogue in fp32: + bias, tanh-GELU (`gelu`), residual + y * gate (gate fp32 [N], residual
@@ -257,25 +307,14 @@ def fp_linear(input, weight, bias=None, out_dtype=None, gelu=False, gate=None, r
     or on where the row sits in the launch.  Not counted by the int8 timer (`set_timer`)."""
     M, N, K = _check_operands16(input, "weight", weight, None)
     _C.check_shape("weight", weight, N, K)
-    out_dtype = out_dtype or input.dtype
-    _check_vec("bias", bias, N, _BIAS16)
-    epi = _epi_flags(gelu, gate, residual, M, N, out_dtype)
-    out = _out_for(out, M, N, out_dtype, input.device)
-    _C.check_same_device(input, weight, bias, gate, residual, out)
-    with torch.cuda.device(input.device):
-        _C.call("wanq_gemm_bf16", _C.ptr(input), _C.ptr(weight), _C.dt(input), _C.ptr(out), _C.dt(out_dtype), _C.ptr(bias),
-                _C.dt(bias) if bias is not None else _C.F32, _C.ptr(gate), _C.ptr(residual), epi, M, N, K, _C.stream())
-    return out
+    return _launch16("wanq_gemm_bf16", (_C.ptr(input), _C.ptr(weight), _C.dt(input)), (input, weight), bias,
+                     out_dtype or input.dtype, gelu, gate, residual, out, M, N, K)
 
 
 def fp_linear_refusal(M, N, K):
     """Why wanq_gemm_bf16 would refuse an [M, K] x [N, K] product (None = accepted): the shape rules of include/wanq_hip.h, checked on
     the host so that a model can name a layer the kernel cannot take when it is built, not in its first forward."""
-    if N < 8 or N % 8:
-        return f"N={N} must be a positive multiple of 8"
-    if K < 32 or K % 32:
-        return f"K={K} must be a positive multiple of 32"
-    return None
+    return _shape_refusal(M, N, K, 32)
 
 
 # ---- weight-only quantisation: 16-bit activations x integer weight codes --------------------------------------------
@@ -292,16 +331,8 @@ def wq16_linear(input, codes, scale_weight, zp=None, bias=None, out_dtype=None, 
     _C.check_shape("codes", codes, N, K // 2 if w4 else K)
     _check_vec("scale_weight", scale_weight, N, (torch.float32,))
     _check_vec("zp", zp, N, (torch.float32,))
-    out_dtype = out_dtype or input.dtype
-    _check_vec("bias", bias, N, _BIAS16)
-    epi = _epi_flags(gelu, gate, residual, M, N, out_dtype)
-    out = _out_for(out, M, N, out_dtype, input.device)
-    _C.check_same_device(input, codes, scale_weight, zp, bias, gate, residual, out)
-    with torch.cuda.device(input.device):
-        _C.call("wanq_gemm_wq16", _C.ptr(input), _C.ptr(codes), _C.dt(input), 4 if w4 else 8, _C.ptr(scale_weight), _C.ptr(zp),
-                _C.ptr(out), _C.dt(out_dtype), _C.ptr(bias), _C.dt(bias) if bias is not None else _C.F32, _C.ptr(gate),
-                _C.ptr(residual), epi, M, N, K, _C.stream())
-    return out
+    return _launch16("wanq_gemm_wq16", (_C.ptr(input), _C.ptr(codes), _C.dt(input), 4 if w4 else 8, _C.ptr(scale_weight), _C.ptr(zp)),
+                     (input, codes, scale_weight, zp), bias, out_dtype or input.dtype, gelu, gate, residual, out, M, N, K)
 
 
 def wq16_grouped_linear(input, codes, scale_weight, zp=None, group_size=None, bias=None, out_dtype=None, gelu=False, gate=None,
@@ -315,36 +346,22 @@ def wq16_grouped_linear(input, codes, scale_weight, zp=None, group_size=None, bi
     why = wq16_linear_refusal(M, N, K, group_size)
     if why is not None:
         raise RuntimeError(f"wq16_grouped_linear: {why}")
-    for name, t in (("scale_weight", scale_weight), ("zp", zp)):
-        if t is not None:
-            _C.check_gpu(name, t)
-            _C.check_contig(name, t)
-            _C.check_dtype(name, t, torch.float32)
-            _C.check_shape(name, t, K // group_size, N)
-    out_dtype = out_dtype or input.dtype
-    _check_vec("bias", bias, N, _BIAS16)
-    epi = _epi_flags(gelu, gate, residual, M, N, out_dtype)
-    out = _out_for(out, M, N, out_dtype, input.device)
-    _C.check_same_device(input, codes, scale_weight, zp, bias, gate, residual, out)
-    with torch.cuda.device(input.device):
-        _C.call("wanq_gemm_wq16_grouped", _C.ptr(input), _C.ptr(codes), _C.dt(input), 4 if w4 else 8, _C.ptr(scale_weight),
-                _C.ptr(zp), int(group_size), _C.ptr(out), _C.dt(out_dtype), _C.ptr(bias),
-                _C.dt(bias) if bias is not None else _C.F32, _C.ptr(gate), _C.ptr(residual), epi, M, N, K, _C.stream())
-    return out
+    _check_group_params(K, N, group_size, scale_weight, zp)
+    return _launch16("wanq_gemm_wq16_grouped", (_C.ptr(input), _C.ptr(codes), _C.dt(input), 4 if w4 else 8, _C.ptr(scale_weight),
+                                                _C.ptr(zp), int(group_size)),
+                     (input, codes, scale_weight, zp), bias, out_dtype or input.dtype, gelu, gate, residual, out, M, N, K)
 
 
 def wq16_linear_refusal(M, N, K, group_size=None):
     """Why wanq_gemm_wq16 -- with a `group_size`, wanq_gemm_wq16_grouped -- would refuse an [M, K] x [N, K] product (None =
     accepted); see `fp_linear_refusal`."""
-    if N < 8 or N % 8:
-        return f"N={N} must be a positive multiple of 8"
-    if K < 64 or K % 64:
-        return f"K={K} must be a positive multiple of 64"
-    if group_size is not None:
-        if not isinstance(group_size, int) or group_size < 64 or group_size % 64:
-            return f"group_size={group_size} must be a positive multiple of 64"
-        if K % group_size:
-            return f"K={K} must be a multiple of group_size={group_size}"
+    why = _shape_refusal(M, N, K, 64)
+    if why is not None or group_size is None:
+        return why
+    if not isinstance(group_size, int) or group_size < 64 or group_size % 64:
+        return f"group_size={group_size} must be a positive multiple of 64"
+    if K % group_size:
+        return f"K={K} must be a multiple of group_size={group_size}"
     return None
 
 
@@ -360,38 +377,23 @@ def w8a8_grouped_linear(input_i8, codes, scale_input, scale_weight, zp, group_si
     group_size % 128 == 0 and K % group_size == 0.  Counted by the int8 timer (`set_timer`)."""
     _check_i8("input", input_i8)
     M, K = input_i8.shape
-    _C.check_gpu("codes", codes)
-    _C.check_contig("codes", codes)
-    _C.check_dtype("codes", codes, torch.uint8 if w4 else torch.int8)
-    if codes.dim() != 2:
-        raise RuntimeError("Tensor codes must have dimension number (2)")
+    _check_mat("codes", codes, torch.uint8 if w4 else torch.int8)
     N = codes.shape[0]
     _C.check_shape("codes", codes, N, K // 2 if w4 else K)
     why = w8a8_grouped_linear_refusal(M, N, K, group_size, 4 if w4 else 8, zp is None)
     if why is not None:
         raise RuntimeError(f"w8a8_grouped_linear: {why}")
-    for name, t in (("scale_weight", scale_weight), ("zp", zp)):
-        if t is not None:
-            _C.check_gpu(name, t)
-            _C.check_contig(name, t)
-            _C.check_dtype(name, t, torch.float32)
-            _C.check_shape(name, t, K // group_size, N)
+    _check_group_params(K, N, group_size, scale_weight, zp)
     _check_vec("scale_input", scale_input, M)
     _check_vec("bias", bias, N)
     out_dtype = out_dtype or torch.float16
     epi = _epi_flags(gelu, gate, residual, M, N, out_dtype)
     out = _out_for(out, M, N, out_dtype, input_i8.device)
     _C.check_same_device(input_i8, codes, scale_input, scale_weight, zp, bias, gate, residual, out)
-    with torch.cuda.device(input_i8.device):
-        if _timer is not None:
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record()
+    with torch.cuda.device(input_i8.device), _timed(2 * M * N * K):
         _C.call("wanq_gemm_w8a8_grouped", _C.ptr(input_i8), _C.ptr(codes), 4 if w4 else 8, _C.ptr(scale_weight), _C.ptr(zp),
                 int(group_size), _C.ptr(out), _C.dt(out_dtype), _C.ptr(scale_input), _C.dt(scale_input), _C.ptr(bias),
                 _C.dt(bias) if bias is not None else _C.F32, _C.ptr(gate), _C.ptr(residual), epi, M, N, K, _C.stream())
-        if _timer is not None:
-            ev1.record()
-            _timer.append((ev0, ev1, 2 * M * N * K))
     return out
 
 
@@ -402,8 +404,9 @@ def w8a8_grouped_linear_refusal(M, N, K, group_size, w_bits, sym):
         return f"w_bits={w_bits} must be 4 or 8"
     if w_bits == 8 and not sym:
         return "w_bits=8 takes symmetric weights only, zp must be None (c + zp does not fit int8)"
-    if N < 8 or N % 8:
-        return f"N={N} must be a positive multiple of 8"
+    why = _shape_refusal(M, N, K, None)
+    if why is not None:
+        return why
     if not isinstance(group_size, int) or group_size < 128 or group_size % 128:
         return f"group_size={group_size} must be a positive multiple of 128"
     if K < group_size or K % group_size:
@@ -422,11 +425,7 @@ def fp8_linear(a_q, w_q, a_scale, w_scale, bias=None, out_dtype=None, gelu=False
     residual [M, N] of out_dtype, which may alias `out`), one rounding to out_dtype (default bf16).  K % 64 == 0, N % 8 == 0.  A
     row's bits do not depend on M or on where the row sits in the launch.  Not counted by the int8 timer (`set_timer`)."""
     for name, t in (("a_q", a_q), ("w_q", w_q)):
-        _C.check_gpu(name, t)
-        _C.check_contig(name, t)
-        _C.check_dtype(name, t, torch.uint8)
-        if t.dim() != 2:
-            raise RuntimeError(f"Tensor {name} must have dimension number (2)")
+        _check_mat(name, t, torch.uint8)
     M, K = a_q.shape
     N = w_q.shape[0]
     _C.check_shape("w_q", w_q, N, K)
@@ -437,29 +436,14 @@ def fp8_linear(a_q, w_q, a_scale, w_scale, bias=None, out_dtype=None, gelu=False
     _check_vec("w_scale", w_scale, N, (torch.float32,))
     if a_scale is None or w_scale is None:
         raise RuntimeError("fp8_linear: a_scale and w_scale must be given")
-    out_dtype = out_dtype or torch.bfloat16
-    _check_vec("bias", bias, N, _BIAS16)
-    epi = _epi_flags(gelu, gate, residual, M, N, out_dtype)
-    out = _out_for(out, M, N, out_dtype, a_q.device)
-    _C.check_same_device(a_q, w_q, a_scale, w_scale, bias, gate, residual, out)
-    with torch.cuda.device(a_q.device):
-        _C.call("wanq_gemm_fp8", _C.ptr(a_q), _C.ptr(w_q), _C.ptr(a_scale), _C.ptr(w_scale), _C.ptr(out), _C.dt(out_dtype),
-                _C.ptr(bias), _C.dt(bias) if bias is not None else _C.F32, _C.ptr(gate), _C.ptr(residual), epi, M, N, K, _C.stream())
-    return out
+    return _launch16("wanq_gemm_fp8", (_C.ptr(a_q), _C.ptr(w_q), _C.ptr(a_scale), _C.ptr(w_scale)), (a_q, w_q, a_scale, w_scale), bias,
+                     out_dtype or torch.bfloat16, gelu, gate, residual, out, M, N, K)
 
 
 def fp8_linear_refusal(M, N, K):
     """Why wanq_gemm_fp8 would refuse an [M, K] x [N, K] product (None = accepted): the shape rules of include/wanq_hip.h in the
     order the entry checks them; see `fp_linear_refusal`."""
-    if M < 0 or M >= (1 << 31) - 128:
-        return f"M={M} out of range"
-    if N < 8 or N % 8:
-        return f"N={N} must be a positive multiple of 8"
-    if K < FP8_K_STEP or K % FP8_K_STEP:
-        return f"K={K} must be a positive multiple of {FP8_K_STEP}"
-    if ((M + 127) // 128) * ((N + 127) // 128) >= (1 << 31):
-        return "too many tiles"
-    return None
+    return _shape_refusal(M, N, K, FP8_K_STEP, bounded=True)
 
 
 # ---- OCP MX: MXFP8 (e4m3) activations x MXFP8 / MXFP4 weights, E8M0 block scales ---------------------------------------------------
@@ -480,11 +464,7 @@ def mx_linear(a_q, w_q, a_scale, w_scale, w_fmt="mxfp8_e4m3", bias=None, out_dty
     for name, t in (("a_q", a_q), ("w_q", w_q), ("a_scale", a_scale), ("w_scale", w_scale)):
         if t is None:
             raise RuntimeError(f"mx_linear: {name} must be given")
-        _C.check_gpu(name, t)
-        _C.check_contig(name, t)
-        _C.check_dtype(name, t, torch.uint8)
-        if t.dim() != 2:
-            raise RuntimeError(f"Tensor {name} must have dimension number (2)")
+        _check_mat(name, t, torch.uint8)
     M, K = a_q.shape
     N = w_q.shape[0]
     why = mx_linear_refusal(M, N, K, w_fmt)
@@ -493,16 +473,8 @@ def mx_linear(a_q, w_q, a_scale, w_scale, w_fmt="mxfp8_e4m3", bias=None, out_dty
     _C.check_shape("w_q", w_q, N, K // 2 if fp4 else K)
     _C.check_shape("a_scale", a_scale, M, K // 32)
     _C.check_shape("w_scale", w_scale, N, K // 32)
-    out_dtype = out_dtype or torch.bfloat16
-    _check_vec("bias", bias, N, _BIAS16)
-    epi = _epi_flags(gelu, gate, residual, M, N, out_dtype)
-    out = _out_for(out, M, N, out_dtype, a_q.device)
-    _C.check_same_device(a_q, w_q, a_scale, w_scale, bias, gate, residual, out)
-    with torch.cuda.device(a_q.device):
-        _C.call("wanq_gemm_mx", _C.ptr(a_q), _C.ptr(w_q), _C.ptr(a_scale), _C.ptr(w_scale), _C.MX_FMT[w_fmt], _C.ptr(out),
-                _C.dt(out_dtype), _C.ptr(bias), _C.dt(bias) if bias is not None else _C.F32, _C.ptr(gate), _C.ptr(residual), epi, M, N, K,
-                _C.stream())
-    return out
+    return _launch16("wanq_gemm_mx", (_C.ptr(a_q), _C.ptr(w_q), _C.ptr(a_scale), _C.ptr(w_scale), _C.MX_FMT[w_fmt]),
+                     (a_q, w_q, a_scale, w_scale), bias, out_dtype or torch.bfloat16, gelu, gate, residual, out, M, N, K)
 
 
 def mx_linear_refusal(M, N, K, w_fmt="mxfp8_e4m3"):
@@ -510,12 +482,4 @@ def mx_linear_refusal(M, N, K, w_fmt="mxfp8_e4m3"):
     the entry checks them; see `fp_linear_refusal`."""
     if w_fmt not in _C.MX_FMT:
         return f"w_fmt={w_fmt!r} must be one of {tuple(_C.MX_FMT)}"
-    if M < 0 or M >= (1 << 31) - 128:
-        return f"M={M} out of range"
-    if N < 8 or N % 8:
-        return f"N={N} must be a positive multiple of 8"
-    if K < MX_K_STEP or K % MX_K_STEP:
-        return f"K={K} must be a positive multiple of {MX_K_STEP}"
-    if ((M + 127) // 128) * ((N + 127) // 128) >= (1 << 31):
-        return "too many tiles"
-    return None
+    return _shape_refusal(M, N, K, MX_K_STEP, bounded=True)

@@ -23,16 +23,10 @@ import torch.distributed as dist
 
 
 def _weight_slots(block):
-    """(owner module, attribute) of every sharded tensor of a kernel-mode block, in a fixed order: each Linear's `weight` and, for an
-    MX Linear (HipLinearMx), its `scale_weight` bytes, a thirty-second or a sixteenth of the weight's bytes."""
-    out = []
+    """(owner module, attribute) of every sharded tensor of a kernel-mode block, in a fixed order: what each Linear names in `sharded`
+    (its `weight` and, for an MX Linear, its `scale_weight` bytes)."""
     lins = [getattr(attn, l) for attn in (block.self_attn, block.cross_attn) for l in "qkvo"] + [block.ffn0, block.ffn2]
-    for lin in lins:
-        if getattr(lin, "weight", None) is not None:
-            out.append((lin, "weight"))
-            if getattr(lin, "mx", None):
-                out.append((lin, "scale_weight"))
-    return out
+    return [(lin, attr) for lin in lins for attr in lin.sharded]
 
 
 class ShardedBlocks:

@@ -74,13 +74,10 @@ class QuantWanModel(WanModel, QuantModel):
                 wq = mod.w_quantizer
                 premul, _ = mod._act_transform()
                 if reference_format:
-                    if getattr(mod, "fp8", False):
+                    if mod.fp8 or mod.mx:
                         raise NotImplementedError(f"{name}: the reference's int_weight.pt format holds int8 codes (the layer is "
-                                                  "format: fp8_e4m3; save with reference_format=False)")
-                    if getattr(mod, "mx", None):
-                        raise NotImplementedError(f"{name}: the reference's int_weight.pt format holds int8 codes (the layer is "
-                                                  f"format: {mod.mx}; save with reference_format=False)")
-                    if getattr(mod, "group_size", None) is not None:
+                                                  f"format: {mod.mx or 'fp8_e4m3'}; save with reference_format=False)")
+                    if mod.group_size is not None:
                         raise NotImplementedError(f"{name}: the reference's int_weight.pt format has one scale per output channel "
                                                   "(weight.group_size is set; save with reference_format=False)")
                     if wq.n_bits != 8:
@@ -98,9 +95,9 @@ class QuantWanModel(WanModel, QuantModel):
                     # uint8 [N, K], the e4m3 bytes, with their per-channel scales
                     # (weight.group_size: the parameters as the group-wise GEMM reads them, [K / g, N]); format: mxfp8_e4m3 /
                     # mxfp4_e2m1: uint8 [N, K] e4m3 bytes / uint8 [N, K/2] packed e2m1 nibbles, scale_weight uint8 [N, K/32] E8M0 bytes
-                    grouped = getattr(mod, "group_size", None) is not None
+                    grouped = mod.group_size is not None
                     sd[name + ".weight"] = mod._codes.clone()
-                    sd[name + ".scale_weight"] = (wq.scale_u8.clone() if getattr(mod, "mx", None) else
+                    sd[name + ".scale_weight"] = (wq.scale_u8.clone() if mod.mx else
                                                   wq.delta.float().t().contiguous() if grouped else wq.delta.reshape(-1).float().clone())
                     if not wq.sym:
                         sd[name + ".zp_weight"] = (wq.zero_point.float().t().contiguous() if grouped
@@ -180,9 +177,9 @@ class QuantWanModel(WanModel, QuantModel):
                                         [(hb.cross_attn, l, f"cross_attn.{l}") for l in "qkvo"] + \
                                         [(hb, "ffn0", "ffn.0"), (hb, "ffn2", "ffn.2")]:
                     lin = getattr(owner, attr)
-                    weight_only = getattr(lin, "weight_only", False)  # HipLinearWq16: the same keys, no act_premul
-                    if not lin.quantized and not weight_only and not getattr(lin, "fp8", False) and not getattr(lin, "mx", None):
+                    if not lin.checkpointed:
                         continue
+                    weight_only = lin.weight_only  # HipLinearWq16: the same keys, no act_premul
                     base = f"blocks.{i}.{key}"
                     # The two formats carry no marker.  What tells them apart is that reference_format=True writes fp16 scales and the
                     # default format fp32 ones (quantize_and_save_weight): the test below relies on that.  A file with fp32 scales

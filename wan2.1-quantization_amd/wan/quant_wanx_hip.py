@@ -31,7 +31,33 @@ def _gelu_gate_residual(y, gelu, gate, residual):
     return y
 
 
-class _HipLinearInt(nn.Module):
+class _HipLinear(nn.Module):
+    """What the block, the checkpoint loader and --dit_fsdp ask of a kernel-mode Linear of any kind, with the answers of a layer that
+    takes the block's 16-bit activations as they are; a subclass overrides what it is.  Called as lin(*lin.operands(src), out_dtype,
+    gelu=, gate=, residual=, out=)."""
+    quantized = False      # an int8 consumer: the block's int8 producers and their prefetch serve it
+    fp8 = False
+    mx = None              # HipLinearMx: the weight's MX format name
+    weight_only = False
+    act_form = "fp"        # what its input is made into: "fp" (16 bits, no quantiser), "int8", "fp8" or "mxfp8"
+    act_key = "fp"         # layers with the same key share one copy of their input
+    plain_rows = False     # its quantiser takes the source's row without a transform, so it can apply the FFN's GELU itself
+    rot = act_quantizer = None
+    # (`act_premul` and `zp_weight` are buffers in the kinds that hold one, and a class attribute here would shadow a buffer: the
+    # kinds that hold none say None themselves)
+    checkpointed = True    # the integer checkpoint holds this layer (quant_wanx.py)
+    sharded = ("weight",)  # the tensors --dit_fsdp shards (distributed/fsdp.py)
+    fuses_epilogue = True  # GELU and gate + residual run in its GEMM's epilogue
+
+    def refresh_zp_gemm(self):
+        """(the checkpoint loader's hook: nothing is derived from the loaded buffers)"""
+
+    def operands(self, src):
+        """The leading arguments of forward, made from a source (_LnSrc / _FpSrc) in the form this layer consumes."""
+        return (src.fp(),)
+
+
+class _HipLinearInt(_HipLinear):
     """The buffers HipLinearW8A8 and HipLinearWq16 both hold (described there), and the zero point their GEMMs take."""
 
     def __init__(self, in_features, out_features, bias, sym, w_bits, group_size=None):
@@ -74,7 +100,7 @@ class HipLinearW8A8(_HipLinearInt):
     in the integer operand, one fp32 fma per group and element applies the scales, and every fused epilogue is the same.  8-bit
     asymmetric weights and a non-default activation quantiser have no group-wise form and are refused, by layer name."""
     quantized = True
-    act_quantizer = None
+    act_form = "int8"
 
     def __init__(self, in_features, out_features, bias=True, sym=False, w_bits=8, group_size=None, name="linear"):
         if group_size is not None:
@@ -88,7 +114,6 @@ class HipLinearW8A8(_HipLinearInt):
         super().__init__(in_features, out_features, bias, sym, w_bits, group_size)
         assert w_bits == 8 or in_features % 32 == 0, "packed 4-bit weights need in_features % 32 == 0"
         self.register_buffer("act_premul", None)
-        self.rot = None
 
     @staticmethod
     def quant_params(w, n_bits=8, sym=False):
@@ -140,7 +165,7 @@ class HipLinearW8A8(_HipLinearInt):
     def from_quantized(cls, ql, name="linear"):
         """From a qdiff QuantizedLinear (any variant): same integer codes, same parameters, same transform."""
         wq = ql.w_quantizer
-        group = getattr(ql, "group_size", None)
+        group = ql.group_size
         aq = ql.a_quantizer
         if group is not None and (not aq.sym or aq.n_bits != 8 or aq._sym_floor != 1e-6):
             raise NotImplementedError(f"{name}: weight.group_size={group} with this `act:` section has no kernel-mode form: the fused "
@@ -171,6 +196,13 @@ class HipLinearW8A8(_HipLinearInt):
         """Layers with the same key can share one quantised copy of their input."""
         return None if self.act_premul is None and self.rot is None else id(self)
 
+    @property
+    def plain_rows(self):
+        return self.act_key is None
+
+    def operands(self, src):
+        return src.int8(self)
+
     def forward(self, a_q, a_scale, a_sum, out_dtype=torch.bfloat16, gelu=False, gate=None, residual=None, out=None):
         zp = self.zp
         if self.group_size is not None:
@@ -183,12 +215,12 @@ class HipLinearW8A8(_HipLinearInt):
 FP_GEMMS = ("torch", "hip")
 
 
-class HipLinearFp(nn.Module):
+class HipLinearFp(_HipLinear):
     """A Linear the quant config leaves FP (remain_fp_regex), as the reference's kernel-mode block keeps nn.Linear for those
     (quant_wanx_cuda.py:360,510).  fp_gemm="torch": the bf16 GEMM through torch (hipBLASLt), GELU and gate + residual as separate
     passes; "hip": qgemm.fp_linear (csrc/gemm_bf16.hip) with both in its epilogue, and rows whose bits do not depend on M."""
-    quantized = False
-    act_key = "fp"
+    checkpointed = False   # its weight stays in the model's own state dict
+    act_premul = zp_weight = None
 
     def __init__(self, weight, bias, dtype=torch.bfloat16, fp_gemm="torch", name="linear"):
         super().__init__()
@@ -204,10 +236,14 @@ class HipLinearFp(nn.Module):
         self.register_buffer("weight", weight.detach().to(dtype).contiguous())
         self.register_buffer("bias", None if bias is None else bias.detach().to(dtype).contiguous())
 
+    @property
+    def fuses_epilogue(self):
+        return self.fp_gemm == "hip"
+
     def forward(self, x, out_dtype=None, gelu=False, gate=None, residual=None, out=None):
         """HipLinearWq16.forward's call.  "hip": fused epilogue; reads `weight` as it is now (--dit_fsdp re-points it at views of the
         gathered buffer).  "torch": the result has x's dtype and the update lands in `residual` (`out_dtype` is the fused form's)."""
-        if self.fp_gemm == "hip":
+        if self.fuses_epilogue:
             return qgemm.fp_linear(x, self.weight, self.bias, out_dtype, gelu=gelu, gate=gate, residual=residual, out=out)
         assert out is None or out is residual, "fp_gemm='torch' writes into `residual` only"
         return _gelu_gate_residual(torch.nn.functional.linear(x, self.weight, self.bias), gelu, gate, residual)
@@ -221,9 +257,7 @@ class HipLinearWq16(_HipLinearInt):
     With a `group_size` (the config's `weight.group_size`, a multiple of 64 that divides in_features) the three parameter buffers are
     [K / group_size, N] and the product is qgemm.wq16_grouped_linear: one fp32 fma per group and element instead of one in all.
     Counterpart of QuantizedLinear.forward with a_quantizer None (ViDiT-Q/quant_utils/qdiff/base/quant_layer.py:68-72)."""
-    quantized = False   # its input is not quantised: the block's int8 producers and their prefetch skip it
-    weight_only = True
-    act_key = "fp"
+    weight_only = True   # (its input is not quantised: the block's int8 producers and their prefetch skip it)
     act_premul = None
 
     def __init__(self, in_features, out_features, bias=True, sym=False, w_bits=8, name="linear", group_size=None):
@@ -246,8 +280,7 @@ class HipLinearWq16(_HipLinearInt):
         wq = ql.w_quantizer
         if wq.n_bits not in (4, 8):
             raise NotImplementedError(f"{name}: weight-only kernel mode stores 8-bit and packed 4-bit codes (n_bits={wq.n_bits})")
-        m = cls(ql.in_features, ql.out_features, ql.bias is not None, wq.sym, wq.n_bits, name,
-                getattr(ql, "group_size", None)).to(ql.fp_module.weight.device)
+        m = cls(ql.in_features, ql.out_features, ql.bias is not None, wq.sym, wq.n_bits, name, ql.group_size).to(ql.fp_module.weight.device)
         codes, sw, _, _ = ql.weight_only_operands()
         if tuple(codes.shape) != tuple(m.weight.shape) or codes.dtype != m.weight.dtype:
             raise ValueError(f"{name}: codes {tuple(codes.shape)} {codes.dtype} do not fit {tuple(m.weight.shape)} {m.weight.dtype}")
@@ -270,43 +303,55 @@ class HipLinearWq16(_HipLinearInt):
                                  residual=residual, out=out, w4=self.w_bits == 4)
 
 
-class HipLinearFp8(nn.Module):
-    """An fp8 W8A8 Linear (`format: fp8_e4m3` in the config's `weight:` and `act:` sections): `weight` uint8 [N, K], OCP e4m3fn codes
-    of the weight quantised per output channel by wanq_quant_rows_fp8; `scale_weight` fp32 [N], absmax / 448; `bias` fp32.  Its input
-    is the block's activation quantised per token by the same entry (_LnSrc.fp8 / _FpSrc.fp8: codes + fp32 scale, shared by every
-    fp8 consumer of a source), and the product is qgemm.fp8_linear (csrc/gemm_fp8.hip) with GELU and gate + residual in its
-    epilogue.  No zero point, no activation transform; the int8 producers and their prefetch skip it."""
-    quantized = False   # not an int8 consumer
-    fp8 = True
-    act_key = "fp8"
-    act_premul = None
-    zp_weight = None
+class _HipLinearCodes(_HipLinear):
+    """What HipLinearFp8 and HipLinearMx share: uint8 `weight` codes and their `scale_weight` as the format's row quantiser wrote
+    them for the simulation-mode layer, an fp32 `bias`, and an input that the same quantiser makes from the source's plain row
+    (_LnSrc.rows / _FpSrc.rows, one copy for every consumer of that form).  No zero point, no activation transform; the int8
+    producers and their prefetch skip it.  A subclass says what its scales are, where they come from, and calls its GEMM."""
+    plain_rows = True
+    act_premul = zp_weight = None
 
-    def __init__(self, in_features, out_features, bias=True, name="linear"):
+    def __init__(self, in_features, out_features, bias, fmt, why, weight_cols, scale_shape, scale_dtype, name):
         super().__init__()
-        why = qgemm.fp8_linear_refusal(1, out_features, in_features)
         if why is not None:
-            raise NotImplementedError(f"{name}: format: fp8_e4m3 has no kernel-mode form for this layer ({out_features}, "
+            raise NotImplementedError(f"{name}: format: {fmt} has no kernel-mode form for this layer ({out_features}, "
                                       f"{in_features}): {why}")
         self.in_features, self.out_features = in_features, out_features
-        self.register_buffer("weight", torch.empty(out_features, in_features, dtype=torch.uint8))
-        self.register_buffer("scale_weight", torch.empty(out_features, dtype=torch.float32))
+        self.register_buffer("weight", torch.empty(out_features, weight_cols, dtype=torch.uint8))
+        self.register_buffer("scale_weight", torch.empty(scale_shape, dtype=scale_dtype))
         self.register_buffer("bias", torch.empty(out_features, dtype=torch.float32) if bias else None)
 
-    def refresh_zp_gemm(self):
-        """(the checkpoint loader's hook: nothing is derived from the loaded buffers)"""
+    def _take(self, ql, scale, name):
+        """The codes, `scale` and the bias of the qdiff layer `ql`."""
+        if tuple(ql._codes.shape) != tuple(self.weight.shape) or ql._codes.dtype != torch.uint8:
+            raise ValueError(f"{name}: codes {tuple(ql._codes.shape)} {ql._codes.dtype} do not fit {tuple(self.weight.shape)} uint8")
+        self.weight.copy_(ql._codes)
+        self.scale_weight.copy_(scale)
+        if ql.bias is not None:
+            self.bias.copy_(ql.bias.detach().float())
+        return self
+
+    def operands(self, src):
+        return src.rows(self.act_form)
+
+
+class HipLinearFp8(_HipLinearCodes):
+    """An fp8 W8A8 Linear (`format: fp8_e4m3` in the config's `weight:` and `act:` sections): `weight` uint8 [N, K], OCP e4m3fn codes
+    of the weight quantised per output channel by wanq_quant_rows_fp8; `scale_weight` fp32 [N], absmax / 448; `bias` fp32.  Its input
+    is the block's activation quantised per token by the same entry (codes + fp32 scale), and the product is qgemm.fp8_linear
+    (csrc/gemm_fp8.hip) with GELU and gate + residual in its epilogue."""
+    fp8 = True
+    act_form = act_key = "fp8"
+
+    def __init__(self, in_features, out_features, bias=True, name="linear"):
+        super().__init__(in_features, out_features, bias, "fp8_e4m3", qgemm.fp8_linear_refusal(1, out_features, in_features),
+                         in_features, (out_features,), torch.float32, name)
 
     @classmethod
     def from_quantized(cls, ql, name="linear"):
         """From a plain qdiff QuantizedLinear built with `format: fp8_e4m3`: the same codes and scales."""
         m = cls(ql.in_features, ql.out_features, ql.bias is not None, name).to(ql.fp_module.weight.device)
-        if tuple(ql._codes.shape) != tuple(m.weight.shape) or ql._codes.dtype != torch.uint8:
-            raise ValueError(f"{name}: codes {tuple(ql._codes.shape)} {ql._codes.dtype} do not fit {tuple(m.weight.shape)} uint8")
-        m.weight.copy_(ql._codes)
-        m.scale_weight.copy_(ql.w_quantizer.delta.reshape(-1).float())
-        if ql.bias is not None:
-            m.bias.copy_(ql.bias.detach().float())
-        return m
+        return m._take(ql, ql.w_quantizer.delta.reshape(-1).float(), name)
 
     def forward(self, a_q, a_scale, out_dtype=torch.bfloat16, gelu=False, gate=None, residual=None, out=None):
         """Reads `weight` as it is now (--dit_fsdp re-points it at views of the gathered buffer)."""
@@ -314,44 +359,24 @@ class HipLinearFp8(nn.Module):
                                 residual=residual, out=out)
 
 
-class HipLinearMx(nn.Module):
+class HipLinearMx(_HipLinearCodes):
     """An OCP MX Linear (`format: mxfp8_e4m3` activations against `mxfp8_e4m3` / `mxfp4_e2m1` weights): `weight` uint8 [N, K] e4m3
     bytes or [N, K / 2] packed e2m1 nibbles, `scale_weight` uint8 [N, K / 32] E8M0 bytes, both from wanq_quant_rows_mx; `bias` fp32.
-    Its input is the block's activation quantised per block of 32 channels by the same entry (_LnSrc.mxfp8 / _FpSrc.mxfp8: codes +
-    scale bytes, one copy shared by every MX consumer of a source), and the product is qgemm.mx_linear (csrc/gemm_mx.hip) with GELU
-    and gate + residual in its epilogue.  No zero point, no activation transform; the int8 producers and their prefetch skip it."""
-    quantized = False   # not an int8 consumer
-    fp8 = False
-    act_key = "mxfp8"
-    act_premul = None
-    zp_weight = None
+    Its input is the block's activation quantised per block of 32 channels by the same entry (codes + scale bytes), and the product is
+    qgemm.mx_linear (csrc/gemm_mx.hip) with GELU and gate + residual in its epilogue."""
+    act_form = act_key = "mxfp8"
+    sharded = ("weight", "scale_weight")   # the scale bytes are a thirty-second or a sixteenth of the weight's
 
     def __init__(self, in_features, out_features, bias=True, w_fmt="mxfp8_e4m3", name="linear"):
-        super().__init__()
-        why = qgemm.mx_linear_refusal(1, out_features, in_features, w_fmt)
-        if why is not None:
-            raise NotImplementedError(f"{name}: format: {w_fmt} has no kernel-mode form for this layer ({out_features}, "
-                                      f"{in_features}): {why}")
-        self.in_features, self.out_features, self.mx = in_features, out_features, w_fmt
-        wk = in_features // 2 if w_fmt == "mxfp4_e2m1" else in_features
-        self.register_buffer("weight", torch.empty(out_features, wk, dtype=torch.uint8))
-        self.register_buffer("scale_weight", torch.empty(out_features, in_features // 32, dtype=torch.uint8))
-        self.register_buffer("bias", torch.empty(out_features, dtype=torch.float32) if bias else None)
-
-    def refresh_zp_gemm(self):
-        """(the checkpoint loader's hook: nothing is derived from the loaded buffers)"""
+        super().__init__(in_features, out_features, bias, w_fmt, qgemm.mx_linear_refusal(1, out_features, in_features, w_fmt),
+                         in_features // 2 if w_fmt == "mxfp4_e2m1" else in_features, (out_features, in_features // 32), torch.uint8, name)
+        self.mx = w_fmt
 
     @classmethod
     def from_quantized(cls, ql, name="linear"):
         """From a plain qdiff QuantizedLinear built with an MX format: the same codes and scale bytes."""
         m = cls(ql.in_features, ql.out_features, ql.bias is not None, ql.mx, name).to(ql.fp_module.weight.device)
-        if tuple(ql._codes.shape) != tuple(m.weight.shape) or ql._codes.dtype != torch.uint8:
-            raise ValueError(f"{name}: codes {tuple(ql._codes.shape)} {ql._codes.dtype} do not fit {tuple(m.weight.shape)} uint8")
-        m.weight.copy_(ql._codes)
-        m.scale_weight.copy_(ql.w_quantizer.scale_u8)
-        if ql.bias is not None:
-            m.bias.copy_(ql.bias.detach().float())
-        return m
+        return m._take(ql, ql.w_quantizer.scale_u8, name)
 
     def forward(self, a_q, a_scale, out_dtype=torch.bfloat16, gelu=False, gate=None, residual=None, out=None):
         """Reads `weight` and `scale_weight` as they are now (--dit_fsdp re-points them at views of the gathered buffer)."""
@@ -359,27 +384,43 @@ class HipLinearMx(nn.Module):
                                residual=residual, out=out)
 
 
+# QuantizedLinear.kind -> the layer class that takes it over ("fp": the layer's FP module, below)
+_HIP_LINEAR_OF = {"int8": HipLinearW8A8, "int8_grouped": HipLinearW8A8, "weight_only": HipLinearWq16, "fp8": HipLinearFp8,
+                  "mx": HipLinearMx}
+
+
 def _to_hip_linear(lin, n_bits, sym, act_dtype, fp_gemm="torch", name="linear"):
     from qdiff.base.quant_layer import QuantizedLinear
 
     if isinstance(lin, QuantizedLinear):
-        if lin.quant_mode and getattr(lin, "mx", None):
-            return HipLinearMx.from_quantized(lin, name)
-        if lin.quant_mode and getattr(lin, "fp8", False):
-            return HipLinearFp8.from_quantized(lin, name)
-        if lin.quant_mode and lin.w_quantizer is not None and lin.a_quantizer is not None:
-            return HipLinearW8A8.from_quantized(lin, name)
-        if lin.quant_mode and lin.w_quantizer is not None:
-            if act_dtype not in (torch.bfloat16, torch.float16):
-                raise ValueError(f"{name}: the weight-only GEMM takes bf16 or fp16 activations (act_dtype {act_dtype})")
-            return HipLinearWq16.from_quantized(lin, name)
+        cls = _HIP_LINEAR_OF.get(lin.kind)
+        if cls is HipLinearWq16 and act_dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"{name}: the weight-only GEMM takes bf16 or fp16 activations (act_dtype {act_dtype})")
+        if cls is not None:
+            return cls.from_quantized(lin, name)
         lin = lin.fp_module
     if n_bits is None:
         return HipLinearFp(lin.weight.data, lin.bias.data if lin.bias is not None else None, act_dtype, fp_gemm, name)
     return HipLinearW8A8.from_float(lin.weight.data, lin.bias.data if lin.bias is not None else None, n_bits, sym)
 
 
-class _LnSrc:
+# activation form -> the fused row quantiser that makes it, (codes, scales) = f(rows, gelu=); a new form adds its entry here
+_ROW_QUANTISERS = {"fp8": "quant_rows_fp8", "mxfp8": "quant_rows_mx"}
+
+
+class _Src:
+    """What _LnSrc and _FpSrc share: the forms a row quantiser without a transform makes, one cached copy per form."""
+
+    def rows(self, form):
+        """(codes, scales) of this activation in `form` for every consumer of it (HipLinearFp8: e4m3 codes + fp32 scale;
+        HipLinearMx: e4m3 codes + E8M0 scale bytes), quantised from what `_plain_row` hands over."""
+        if form not in self.cache:
+            x, gelu = self._plain_row()
+            self.cache[form] = getattr(fused, _ROW_QUANTISERS[form])(x, gelu=gelu)
+        return self.cache[form]
+
+
+class _LnSrc(_Src):
     """Lazy activation = LayerNorm(x) (* gamma) * (1 + scale) + shift, materialised per consumer format."""
 
     def __init__(self, blk, x, gamma, shift, scale):
@@ -414,7 +455,7 @@ class _LnSrc:
         whenever the consumers do not all rotate with the same Hadamard parameters."""
         todo = []
         for lin in lins:
-            if not getattr(lin, "quantized", False) or lin.act_key is None or lin.act_key in self.cache or lin.rot is None or \
+            if not lin.quantized or lin.act_key is None or lin.act_key in self.cache or lin.rot is None or \
                     lin.act_quantizer is not None:
                 continue
             if lin.act_key not in [l.act_key for l in todo]:
@@ -430,19 +471,10 @@ class _LnSrc:
         for i, lin in enumerate(todo):
             self.cache[lin.act_key] = (qs[i], vec[i, 0], vec[i, 1])
 
-    def fp8(self, lin):
-        """(e4m3 codes, fp32 scale) for the fp8 consumers (HipLinearFp8), one copy for all of them: quantised from the fp32 row, what
-        a simulation-mode quantiser sees.  (A fused LayerNorm + modulate + fp8 producer would save the fp32 round trip.)"""
-        if "fp8" not in self.cache:
-            self.cache["fp8"] = fused.quant_rows_fp8(self.fp32())
-        return self.cache["fp8"]
-
-    def mxfp8(self, lin):
-        """(e4m3 codes, E8M0 scale bytes) for the MX consumers (HipLinearMx), one copy for all of them: quantised from the fp32 row,
-        what a simulation-mode quantiser sees.  (A fused LayerNorm + modulate + MX producer would save the fp32 round trip.)"""
-        if "mxfp8" not in self.cache:
-            self.cache["mxfp8"] = fused.quant_rows_mx(self.fp32())
-        return self.cache["mxfp8"]
+    def _plain_row(self):
+        """The fp32 row, what a simulation-mode quantiser sees.  (A fused LayerNorm + modulate + fp8 / MX producer would save the
+        fp32 round trip.)"""
+        return self.fp32(), False
 
     def fp(self):
         if "fp" not in self.cache:
@@ -460,7 +492,7 @@ class _LnSrc:
         return self.cache["fp32"]
 
 
-class _FpSrc:
+class _FpSrc(_Src):
     """An activation that already exists in bf16 (attention output, FFN hidden, text context).  `gelu`: the tensor is the FFN's
     PRE-activation and the quantiser applies the tanh-GELU itself (gelu_quant_sum -- the reference's own split,
     K/csrc/fused/fused.cu gelu_quant_sum behind a 16-bit GEMM output, W/models/quant_opensora_cuda.py:402); only offered to a
@@ -483,19 +515,10 @@ class _FpSrc:
             self.cache[key] = (q, qs[0], qs[1])
         return self.cache[key]
 
-    def fp8(self, lin):
-        """(e4m3 codes, fp32 scale) of the 16-bit tensor for the fp8 consumers, one copy for all of them; `gelu`: the quantiser
-        applies the tanh-GELU itself (its act = 1), as gelu_quant_sum does for the int8 consumers."""
-        if "fp8" not in self.cache:
-            self.cache["fp8"] = fused.quant_rows_fp8(self.t, gelu=self.gelu)
-        return self.cache["fp8"]
-
-    def mxfp8(self, lin):
-        """(e4m3 codes, E8M0 scale bytes) of the 16-bit tensor for the MX consumers, one copy for all of them; `gelu`: the quantiser
-        applies the tanh-GELU itself (its act = 1)."""
-        if "mxfp8" not in self.cache:
-            self.cache["mxfp8"] = fused.quant_rows_mx(self.t, gelu=self.gelu)
-        return self.cache["mxfp8"]
+    def _plain_row(self):
+        """The 16-bit tensor; `gelu`: the quantiser applies the tanh-GELU itself (its act = 1), as gelu_quant_sum does for the int8
+        consumers."""
+        return self.t, self.gelu
 
     def fp32(self):
         if "fp32" not in self.cache:
@@ -536,6 +559,12 @@ def _head_chunks(heads, seq_len, device, max_chunks=4):
         out.append((a, a + sz))
         a += sz
     return out if len(out) > 1 else [(0, heads)]
+
+
+def _late_gelu(ffn0, ffn2):
+    """ffn.2's quantiser applies the FFN's GELU (int8: gelu_quant_sum; fp8 / MX: the row quantiser's act = 1) instead of ffn.0's
+    epilogue: when it quantises the plain row, and that row is ffn.0's output in the form ffn.0 itself consumes."""
+    return ffn2.plain_rows and ffn0.act_form == ffn2.act_form
 
 
 class _Attn(nn.Module):
@@ -615,29 +644,12 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         """y = lin(src) with the producer / epilogue fusion the layer's kind allows.  With `residual` (the fp32
         stream) the result is residual + y*gate written in place."""
         out_dtype = out_dtype or self.act_dtype
-        if getattr(lin, "fp8", False):
-            q, s = src.fp8(lin)
-            if residual is not None:
-                return lin(q, s, torch.float32, gate=gate.float().contiguous(), residual=residual, out=residual)
-            return lin(q, s, out_dtype, gelu=gelu)
-        if getattr(lin, "mx", None):
-            q, s = src.mxfp8(lin)
-            if residual is not None:
-                return lin(q, s, torch.float32, gate=gate.float().contiguous(), residual=residual, out=residual)
-            return lin(q, s, out_dtype, gelu=gelu)
-        if lin.quantized and lin.act_quantizer is not None:
+        if lin.act_quantizer is not None:
             return self._linear_any_act(lin, src, out_dtype, gelu, gate, residual)
-        if lin.quantized:
-            q, s, ssum = src.int8(lin)
-            if residual is not None:
-                return lin(q, s, ssum, torch.float32, gate=gate, residual=residual, out=residual)
-            return lin(q, s, ssum, out_dtype, gelu=gelu)
-        x = src.fp()  # floating input: HipLinearWq16 (integer codes x 16-bit activations) or HipLinearFp ("hip" or "torch")
-        if residual is not None:
-            if getattr(lin, "weight_only", False) or lin.fp_gemm == "hip":  # the fused epilogues take an fp32 gate
-                gate = gate.float().contiguous()
-            return lin(x, torch.float32, gate=gate, residual=residual, out=residual)
-        return lin(x, x.dtype, gelu=gelu)
+        a = lin.operands(src)
+        if residual is not None:  # (the gate is a contiguous fp32 [C] at every call site: a modulation row, or `ones_gate`)
+            return lin(*a, torch.float32, gate=gate, residual=residual, out=residual)
+        return lin(*a, out_dtype, gelu=gelu)
 
     def _linear_any_act(self, lin, src, out_dtype, gelu, gate, residual):
         """A quantised Linear whose activation quantiser is not the fused producers' (asymmetric, below 8 bits, the mixed-precision
@@ -799,9 +811,7 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         # the GELU in the GEMM epilogue, whose store loop is vector-bound; cfg-B, tools/probes/ffn_gelu_placement.py); with a
         # rotation in front of ffn.2, or a floating-point ffn.2, it stays in ffn.0's epilogue.
         h = _LnSrc(self, x, None, e[:, 3], e[:, 4])
-        late_gelu = (self.ffn0.quantized and self.ffn2.quantized and self.ffn2.act_key is None) or \
-            (getattr(self.ffn0, "fp8", False) and getattr(self.ffn2, "fp8", False)) or \
-            (bool(getattr(self.ffn0, "mx", None)) and bool(getattr(self.ffn2, "mx", None)))  # fp8 / MX: the quantiser's act = 1
+        late_gelu = _late_gelu(self.ffn0, self.ffn2)
         hid = self._linear(self.ffn0, h, gelu=not late_gelu)
         self._linear(self.ffn2, _FpSrc(hid, gelu=late_gelu), gate=e[0, 5].contiguous(), residual=x)
         return x
