@@ -225,6 +225,7 @@ int wanq_fake_quant_cols(const void* x, int x_dtype, const float* colmax, void* 
 
 /* Fake-quantisation with a PRECOMPUTED delta of x's own shape, elementwise over n values (n % 8 == 0):
  *   d = max(delta, 1e-6);  plain (bits == NULL): d' = d / (2^b - 1), out = clamp(rne(x / d'), 0, 2^b - 1) * d'
+ *     (everything at or below zero, rne(x / d') = -0.0 included, gives +0.0: the clamp's lower bound is the result)
  *   bits != NULL (int32 per element): d' = d / (2^bits - 1), out = min(rne(x / d'), 2^bits - 1) * d', 0 bits -> 0.
  * Replaces DynamicQuantizer.forward_with_quant_params (quant_utils/qdiff/base/base_quantizer.py:164-206: the fake-quant step of
  *   the reference's block-wise attention-map quantisers, symmetric quantisers only).  Bit-identical for fp32 x.  In place allowed. */
