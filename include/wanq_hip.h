@@ -274,6 +274,29 @@ int wanq_rmsnorm_rope_q8(const void* x, int x_dtype, const float* weight, const 
                          int out_dtype, int8_t* q8, float* qscale, int64_t scale_stride, int64_t rows, int cols,
                          int head_dim, int64_t rows_per_batch, int64_t positions, float eps, void* stream);
 
+/* K smoothing for the int8 Q.K^T attention (SageAttention's remedy for a per-channel offset shared by all keys): subtracting one
+ * vector c[cols] from every key changes all scores of a query row by the same q.c, which softmax does not see, so the keys may be
+ * quantised as y - c with c = the mean of y over the tokens, and no attention kernel changes.  Two entries:
+ *
+ * wanq_rmsnorm_rope_colsum: colsum[c] = sum over all `rows` of y[r, c], y being the fp32 row wanq_rmsnorm_rope_q8 quantises (same
+ * arguments, same bits; weight and rope may both be NULL: y = x).  Deterministic, a function of (rows, cols) only: rows are cut
+ * into slabs of 64 rows (doubled until at most 1024 slabs remain), a slab is added in ascending row order per column, the slab
+ * partials go to `workspace` and a second kernel adds them in ascending slab order; no floating-point atomics.  rows == 0 writes
+ * zeros.  workspace: wanq_rmsnorm_rope_colsum_workspace(rows, cols) bytes of device memory, 16-byte aligned.  The centre of
+ * `rows` tokens is colsum / rows (the caller's division; under sequence parallelism the sums of the ranks are added first). */
+int64_t wanq_rmsnorm_rope_colsum_workspace(int64_t rows, int cols);
+int wanq_rmsnorm_rope_colsum(const void* x, int x_dtype, const float* weight, const float* rope, int64_t rows, int cols,
+                             int head_dim, int64_t rows_per_batch, int64_t positions, float eps, float* colsum,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+
+/* wanq_rmsnorm_rope_q8 with the codes taken of y - center (center: fp32 [cols], required; one fp32 subtraction per element):
+ * delta, clamp, rounding and both scale planes as above, on the centred row.  `out`, when given, still receives the uncentred y.
+ * center all zeros: bit-identical to wanq_rmsnorm_rope_q8. */
+int wanq_rmsnorm_rope_q8_centered(const void* x, int x_dtype, const float* weight, const float* rope, void* out,
+                                  int out_dtype, int8_t* q8, float* qscale, int64_t scale_stride, const float* center,
+                                  int64_t rows, int cols, int head_dim, int64_t rows_per_batch, int64_t positions, float eps,
+                                  void* stream);
+
 /* The same as wanq_rmsnorm_rope with the store scattered per head: head h (head_dim columns) of row r lands at
  * out + head_map[2h] + r * head_map[2h+1] (elements of out_dtype).  head_map: DEVICE int64 [cols/head_dim][2].
  * Writes the Ulysses head-scatter all-to-all send buffers ([P][rows][w] per head chunk) directly, in place of the

@@ -71,6 +71,9 @@ PROTOTYPES = {
     "wanq_fake_quant_with_delta": [_vp, _i, _vp, _vp, _vp, _i, _i, _i64, _vp],
     "wanq_rmsnorm_rope_scatter": [_vp, _i, _vp, _vp, _vp, _i, _vp, _i64, _i, _i, _i64, _i64, _f, _vp],
     "wanq_rmsnorm_rope_q8": [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i64, _i64, _i, _i, _i64, _i64, _f, _vp],
+    "wanq_rmsnorm_rope_q8_centered": [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i64, _vp, _i64, _i, _i, _i64, _i64, _f, _vp],
+    "wanq_rmsnorm_rope_colsum_workspace": [_i64, _i],
+    "wanq_rmsnorm_rope_colsum": [_vp, _i, _vp, _vp, _i64, _i, _i, _i64, _i64, _f, _vp, _vp, _i64, _vp],
     "wanq_attention_qk8_fwd": [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i, _i64, _i64, _i, _i, _i64, _i64, _i64, _i64, _f, _i, _vp, _i64, _vp],
     "wanq_rotate_quant_rows": [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i64, _i, _vp],
     "wanq_layernorm_rotate_quant_rows": [_vp, _i, _vp, _vp, _vp, _i, _i64, _i64, _f, _vp, _i, _vp, _vp, _vp, _i, _i64, _i, _vp],
@@ -95,6 +98,7 @@ lib.wanq_last_error.restype = ctypes.c_char_p
 lib.wanq_attention_split_workspace.restype = ctypes.c_int64
 lib.wanq_attention_select_form.restype = ctypes.c_int64
 lib.wanq_attention_map_workspace.restype = ctypes.c_int64
+lib.wanq_rmsnorm_rope_colsum_workspace.restype = ctypes.c_int64
 lib.wanq_abi_version.restype = ctypes.c_int
 if lib.wanq_abi_version() != ABI_VERSION:
     raise ImportError(f"libwanq_hip.so ABI {lib.wanq_abi_version()} != binding ABI {ABI_VERSION}; rebuild")

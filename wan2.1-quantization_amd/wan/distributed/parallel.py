@@ -93,6 +93,19 @@ class SeqParallel:
         post = lambda r: r.view(P * lp, w)  # noqa: E731  blocks arrive in rank order == sequence order
         return _Pending(work, recv, post) if async_op else post(recv)
 
+    def mean_rows(self, colsum, rows):
+        """K smoothing's centre under Ulysses: every rank holds the fp32 column sums [C] of its `rows` tokens of k; the sums of the
+        group are added (an all-reduce SUM, spelled as an all-gather and a sum in rank order, so that every rank gets the same
+        bits on every run) and divided by the group's row count.  Runs before the centred quantiser and before the head exchange.
+        Equal to the single-rank centre up to the rounding of a differently ordered sum, not bit for bit."""
+        if self.size == 1:
+            return colsum / torch.full_like(colsum, float(rows))  # (tensor by tensor: a true division, see wan.ops.center_of)
+        total = self.all_gather_rows(colsum.view(1, -1))  # [P, C] in rank order
+        acc = total[0].clone()
+        for r in range(1, self.size):
+            acc += total[r]
+        return acc / torch.full_like(acc, float(rows * self.size))
+
     # ---- send images written by the producer kernel (no pack pass) ---------------------------------------------------
     def packed_layout(self, lp, c, head_dim, chunks, device):
         """Where every head of a [Lp, C] tensor goes so that each head chunk's all-to-all send image [P, Lp, w] is contiguous:

@@ -135,10 +135,40 @@ class Q8Rows:
         return self
 
 
-def rmsnorm_rope_q8(x, weight, rope, head_dim, for_keys, eps=1e-6, want_fp=False, fp_dtype=None):
+def rmsnorm_rope_colsum(x, weight, rope, head_dim, eps=1e-6):
+    """Column sums over all rows of the fp32 y = rotary(RMSNorm_C(x) * weight) that rmsnorm_rope_q8 quantises -> fp32 [cols]
+    (wanq_rmsnorm_rope_colsum: fixed summation order, bit-reproducible, a function of the shape alone).  weight and rope may both
+    be None (y = x).  center_of() turns the sums into K smoothing's centre."""
+    _C.check_gpu("x", x)
+    _C.check_contig("x", x)
+    rows, cols = x.shape
+    positions = _rope_positions(rope, head_dim)
+    if weight is not None:
+        _C.check_dtype("weight", weight, torch.float32)
+        _C.check_shape("weight", weight, cols)
+    colsum = torch.empty(cols, dtype=torch.float32, device=x.device)
+    nbytes = _C.lib.wanq_rmsnorm_rope_colsum_workspace(rows, cols)
+    ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _C.call("wanq_rmsnorm_rope_colsum", _C.ptr(x), _C.dt(x), _C.ptr(weight), _C.ptr(rope), rows, cols, head_dim, max(rows, 1), positions,
+                float(eps), _C.ptr(colsum), _C.ptr(ws), nbytes, _C.stream(),
+                hbm=("rmsnorm_rope_colsum", rows * cols * x.element_size() + 2 * nbytes + 4 * cols +
+                     (min(rows, positions) * head_dim * 4 if rope is not None else 0)))
+    return colsum
+
+
+def center_of(colsum, rows):
+    """K smoothing's centre of `rows` tokens from their column sums: colsum / rows, a true fp32 division (one rounding).
+    (Tensor by tensor: torch divides a GPU tensor by a Python scalar as a product with the scalar's reciprocal, two roundings.)"""
+    return colsum / torch.full_like(colsum, float(rows))
+
+
+def rmsnorm_rope_q8(x, weight, rope, head_dim, for_keys, eps=1e-6, want_fp=False, fp_dtype=None, center=None):
     """RMSNorm_C(x) * weight -> rotary -> per-(token, head) int8 quantise: returns Q8Rows (and the 16-bit row when want_fp: of
     fp_dtype, else of x's own type when that is bf16 / fp16, else bf16).
-    for_keys: pad the scale planes' row stride to a multiple of 64 (the attention kernel fetches key scales per 64-key tile)."""
+    for_keys: pad the scale planes' row stride to a multiple of 64 (the attention kernel fetches key scales per 64-key tile).
+    center: fp32 [cols] subtracted from the row in front of the quantiser only (K smoothing: center_of(rmsnorm_rope_colsum(...)));
+    the 16-bit row of want_fp stays uncentred."""
     _C.check_gpu("x", x)
     _C.check_contig("x", x)
     rows, cols = x.shape
@@ -154,11 +184,21 @@ def rmsnorm_rope_q8(x, weight, rope, head_dim, for_keys, eps=1e-6, want_fp=False
     if fp_dtype not in _ATTN_DTYPES:
         raise RuntimeError(f"rmsnorm_rope_q8: fp_dtype {fp_dtype} is not torch.bfloat16 or torch.float16")
     out = torch.empty(rows, cols, dtype=fp_dtype, device=x.device) if want_fp else None
+    if center is not None:
+        _C.check_gpu("center", center)
+        _C.check_dtype("center", center, torch.float32)
+        _C.check_contig("center", center)
+        _C.check_shape("center", center, cols)
+    lead = (_C.ptr(x), _C.dt(x), _C.ptr(weight), _C.ptr(rope), _C.ptr(out), _C.F16 if fp_dtype == torch.float16 else _C.BF16,
+            _C.ptr(q8.codes), _C.ptr(q8.scales), q8.stride)
+    tail = (rows, cols, head_dim, rows, positions, float(eps), _C.stream())
+    nbytes = (rows * cols * (x.element_size() + 1 + (2 if want_fp else 0)) + 8 * rows * (cols // head_dim) +
+              (min(rows, positions) * head_dim * 4 if rope is not None else 0))
     with torch.cuda.device(x.device):
-        _C.call("wanq_rmsnorm_rope_q8", _C.ptr(x), _C.dt(x), _C.ptr(weight), _C.ptr(rope), _C.ptr(out),
-                _C.F16 if fp_dtype == torch.float16 else _C.BF16, _C.ptr(q8.codes), _C.ptr(q8.scales), q8.stride, rows, cols, head_dim, rows, positions, float(eps),
-                _C.stream(), hbm=("rmsnorm_rope_q8", rows * cols * (x.element_size() + 1 + (2 if want_fp else 0)) +
-                                  8 * rows * (cols // head_dim) + (min(rows, positions) * head_dim * 4 if rope is not None else 0)))
+        if center is None:
+            _C.call("wanq_rmsnorm_rope_q8", *lead, *tail, hbm=("rmsnorm_rope_q8", nbytes))
+        else:  # (x is read a second time here: the first read was rmsnorm_rope_colsum's, counted there)
+            _C.call("wanq_rmsnorm_rope_q8_centered", *lead, _C.ptr(center), *tail, hbm=("rmsnorm_rope_q8_centered", nbytes + 4 * cols))
     return (q8, out) if want_fp else q8
 
 

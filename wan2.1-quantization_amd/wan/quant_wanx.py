@@ -129,7 +129,7 @@ class QuantWanModel(WanModel, QuantModel):
         quantized Linear come from the file (either format of quantize_and_save_weight), a quantized Linear without its keys
         or with a shape mismatch is an error, and the number of tensors taken is logged.  fp_gemm: the GEMM of the Linears kept
         floating point, "torch" (hipBLASLt + separate GELU / gate + residual passes) or "hip" (csrc/gemm_bf16.hip, both fused)."""
-        qk8, vb, amap = {}, {}, {}
+        qk8, vb, amap, smooth = {}, {}, {}, {}
         for key in ("attn", "cross_attn"):  # quant_config.attn.qk / cross_attn.qk (Q/base/quant_attn.py:19-29,130-143)
             sub = self.q_cfg.get(key, None) if self.q_cfg is not None else None
             qk = sub.get("qk", None) if sub is not None else None
@@ -137,6 +137,11 @@ class QuantWanModel(WanModel, QuantModel):
                 if qk.get("n_bits", 8) != 8 or not qk.get("sym", True):
                     raise NotImplementedError(f"{key}.qk: the int8 Q.K^T kernel implements symmetric 8-bit q / k")
                 qk8[key] = True
+                # qk.smooth_k: k is quantised as k - its mean over the tokens (exact under softmax; one more read of k per attention)
+                smooth[key] = bool(qk.get("smooth_k", False))
+            if sub is not None and sub.get("smooth_k", None) is not None:
+                raise ValueError(f"{key}.smooth_k: K smoothing is a property of the int8 q / k codes and is spelled {key}.qk.smooth_k"
+                                 + ("" if qk is not None else f"; this section has no {key}.qk for it to act on"))
             vq = sub.get("v", None) if sub is not None else None
             if vq is not None:  # v fake-quant per (head, channel) over all tokens (W/models/quant_opensora.py:438-440)
                 if not vq.get("sym", True):
@@ -168,7 +173,8 @@ class QuantWanModel(WanModel, QuantModel):
         self.hip_blocks = nn.ModuleList([WanAttentionBlockWithHipKernel.from_float(
             b, None, False, act_dtype, attn_qk8=qk8.get("attn", False), cross_attn_qk8=qk8.get("cross_attn", False),
             attn_v_bits=vb.get("attn"), cross_attn_v_bits=vb.get("cross_attn"), attn_map=amap.get("attn"),
-            cross_attn_map=amap.get("cross_attn"), fp_gemm=fp_gemm, name=f"blocks.{i}") for i, b in enumerate(self.blocks)])
+            cross_attn_map=amap.get("cross_attn"), fp_gemm=fp_gemm, name=f"blocks.{i}", attn_smooth_k=smooth.get("attn", False),
+            cross_attn_smooth_k=smooth.get("cross_attn", False)) for i, b in enumerate(self.blocks)])
         if load_path:
             sd = torch.load(load_path, map_location="cpu", weights_only=True)
             taken = taken_wo = 0

@@ -577,7 +577,8 @@ class _Attn(nn.Module):
 
 class WanAttentionBlockWithHipKernel(nn.Module):
     def __init__(self, dim, ffn_dim, num_heads, eps=1e-6, act_dtype=torch.bfloat16, attn_qk8=False, cross_attn_qk8=False,
-                 attn_v_bits=None, cross_attn_v_bits=None, attn_map=None, cross_attn_map=None, fp_gemm="torch"):
+                 attn_v_bits=None, cross_attn_v_bits=None, attn_map=None, cross_attn_map=None, fp_gemm="torch", attn_smooth_k=False,
+                 cross_attn_smooth_k=False):
         super().__init__()
         if fp_gemm not in FP_GEMMS:
             raise ValueError(f"fp_gemm={fp_gemm!r}: expected one of {FP_GEMMS}")
@@ -588,6 +589,13 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         # quant_config.attn.qk / cross_attn.qk (8-bit symmetric): q and k of that attention leave RMSNorm + RoPE as
         # per-(token, head) int8 codes and Q.K^T runs on the int8 matrix cores (Q/base/quant_attn.py:168-174)
         self.attn_qk8, self.cross_attn_qk8 = bool(attn_qk8), bool(cross_attn_qk8)
+        # quant_config.attn.qk.smooth_k / cross_attn.qk.smooth_k: k is quantised as k - mean over tokens (SageAttention's K smoothing;
+        # exact: a vector shared by all keys shifts every score of a query row alike, and softmax drops it).  q is never centred.
+        for key, on, qk8 in (("attn", attn_smooth_k, attn_qk8), ("cross_attn", cross_attn_smooth_k, cross_attn_qk8)):
+            if on and not qk8:
+                raise ValueError(f"{key}.qk.smooth_k without {key}.qk: K smoothing centres the int8 codes of k and has nothing to act on "
+                                 "when q / k stay 16-bit")
+        self.attn_smooth_k, self.cross_attn_smooth_k = bool(attn_smooth_k), bool(cross_attn_smooth_k)
         # quant_config.attn.v / cross_attn.v: v fake-quantised per (head, channel) over all tokens before the attention
         # (W/models/quant_opensora.py:438-440); P.V itself stays bf16 -- the reference's recipe has no integer P either
         self.attn_v_bits, self.cross_attn_v_bits = attn_v_bits, cross_attn_v_bits
@@ -603,7 +611,8 @@ class WanAttentionBlockWithHipKernel(nn.Module):
 
     @classmethod
     def from_float(cls, blk, n_bits=8, sym=False, act_dtype=torch.bfloat16, attn_qk8=False, cross_attn_qk8=False,
-                   attn_v_bits=None, cross_attn_v_bits=None, attn_map=None, cross_attn_map=None, fp_gemm="torch", name="block"):
+                   attn_v_bits=None, cross_attn_v_bits=None, attn_map=None, cross_attn_map=None, fp_gemm="torch", name="block",
+                   attn_smooth_k=False, cross_attn_smooth_k=False):
         """Build from a WanAttentionBlock (wan/modules/model.py) whose Linears are either plain nn.Linear
         (quantized here with plain per-channel W8 when n_bits is given, kept FP when n_bits is None) or qdiff
         QuantizedLinear variants (their codes / parameters / ViDiT transform are taken over as they are).
@@ -618,7 +627,7 @@ class WanAttentionBlockWithHipKernel(nn.Module):
                 "form, and running them dense would ignore the window.  Drop those keys from the quant config or build the model with "
                 "window_size=(-1, -1)")
         m = cls(blk.dim, blk.ffn_dim, blk.num_heads, blk.eps, act_dtype, attn_qk8, cross_attn_qk8, attn_v_bits,
-                cross_attn_v_bits, attn_map, cross_attn_map, fp_gemm).to(blk.modulation.device)
+                cross_attn_v_bits, attn_map, cross_attn_map, fp_gemm, attn_smooth_k, cross_attn_smooth_k).to(blk.modulation.device)
         m.window_size = window
         for name_ in ("self_attn", "cross_attn"):
             src, dst = getattr(blk, name_), getattr(m, name_)
@@ -684,15 +693,21 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         ca = self.cross_attn
         k = self._linear(ca.k, ctx)
         v = self._vq(self._linear(ca.v, ctx), self.cross_attn_v_bits, None)
-        k = self._prep_qk(k, ca.norm_k_weight, None, self.cross_attn_qk8, True)
+        k = self._prep_qk(k, ca.norm_k_weight, None, self.cross_attn_qk8, True, smooth=self.cross_attn_smooth_k)
         if memo is not None:
             memo[id(self)] = (k, v)
         return k, v
 
-    def _prep_qk(self, x, weight, rope, int8, for_keys):
-        """q or k behind its projection: RMSNorm + RoPE in place, or -- int8: attn.qk / cross_attn.qk -- the Q8Rows of that row."""
+    def _prep_qk(self, x, weight, rope, int8, for_keys, smooth=False, sp=None):
+        """q or k behind its projection: RMSNorm + RoPE in place, or -- int8: attn.qk / cross_attn.qk -- the Q8Rows of that row.
+        smooth (keys only, qk.smooth_k): the codes are those of k - centre, the centre being k's mean over the tokens -- column sums
+        first (a second read of x), under sequence parallelism all-reduced over the group (sp), then the centred quantiser."""
         if int8:
-            return ops.rmsnorm_rope_q8(x, weight, rope, self.head_dim, for_keys, eps=self.eps)
+            center = None
+            if smooth and for_keys:
+                colsum = ops.rmsnorm_rope_colsum(x, weight, rope, self.head_dim, eps=self.eps)
+                center = ops.center_of(colsum, x.shape[0]) if sp is None else sp.mean_rows(colsum, x.shape[0])
+            return ops.rmsnorm_rope_q8(x, weight, rope, self.head_dim, for_keys, eps=self.eps, center=center)
         return ops.rmsnorm_rope_(x, weight, rope, self.head_dim, eps=self.eps)
 
     def _attend(self, q, k, v, heads, k_len, q_len, map_cfg, window=(-1, -1)):
@@ -722,7 +737,8 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         chunks = [(a * d, b * d) for a, b in _head_chunks(C // d // sp.size, lp * sp.size, q.device)]
         if self.attn_qk8:
             def pack(x, weight, for_keys):
-                x8 = ops.rmsnorm_rope_q8(x, weight, rope, d, for_keys, eps=self.eps)
+                # (smooth_k: a rank holds a token shard of k, so the column sums are all-reduced before the centred quantiser)
+                x8 = self._prep_qk(x, weight, rope, True, for_keys, smooth=self.attn_smooth_k, sp=sp)
                 # scale planes [2, H, stride] -> [lp, H * 2]: a head's (delta, constant) pair travels with its codes
                 return x8.codes, x8.scales[:, :, :lp].permute(2, 1, 0).reshape(lp, 2 * (C // d))
 
@@ -784,7 +800,7 @@ class WanAttentionBlockWithHipKernel(nn.Module):
             o = self._self_attention_ulysses(q, h, rope, seq_len, sp)
         else:
             q = self._prep_qk(q, sa.norm_q_weight, rope, self.attn_qk8, False)
-            k = self._prep_qk(self._linear(sa.k, h), sa.norm_k_weight, rope, self.attn_qk8, True)
+            k = self._prep_qk(self._linear(sa.k, h), sa.norm_k_weight, rope, self.attn_qk8, True, smooth=self.attn_smooth_k)
             v = self._vq(self._linear(sa.v, h), self.attn_v_bits, seq_len)
             o = self._attend(q, k, v, H, seq_len, seq_len, self.attn_map, self.window_size)
         self._linear(sa.o, _FpSrc(o), gate=e[0, 2].contiguous(), residual=x)
