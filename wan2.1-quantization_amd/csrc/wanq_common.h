@@ -213,7 +213,8 @@ __device__ __forceinline__ void quant8_div_rne(const float (&x)[8], float s, flo
 //   near: |d| >= 0.5 - 5.1e-5.  RN(x * inv exact) can differ from rint(fl(x / s)) only when x / s lies within
 //       127 * 2^-24 (inv's rounding) + 2^-18 (the quotient's) = 1.2e-5 of a .5 boundary: the threshold keeps a 4x margin, and
 //       the flagged chunk (about 1e-4 of the elements) takes the true division, as above.
-// Bit-identical codes to quant8_div_rne on that domain (tests/test_gpu_rowwise.py: ties, near-ties, eps rows, golden vectors).
+// Bit-identical codes to quant8_div_rne on that domain (tests/test_gpu_rowwise.py: ties, near-ties, eps rows, golden vectors;
+// tests/test_gpu_quant_rows_probes.py: exact ties and their fp32 neighbours at every form of the ladder and in the wave kernel).
 constexpr float WANQ_QMAGIC = 12582912.0f;
 // The general form quantises x = fl(y * c) WITHOUT forming x: the codes of rne(fl(y * c) / s), c > 0 a per-launch constant (the
 // 1 / sqrt(n) of the Hadamard transform), from u = fma(y, cinv, M) with cinv = fl(c * inv).  The exact y * fl(c * inv) lies within
