@@ -30,6 +30,12 @@
 //
 // Determinism.  gemm_bf16.hip's summation order (gemm16_common.h), so with sw = 1 the output is bit-equal to wanq_gemm_bf16 on the
 // weight (c + zp) cast to the activation dtype.
+//
+// Tests.  tests/test_gpu_wq16_probes.py pins, on answers known bit for bit, what is this file's alone: the fragment cut (which
+// byte / nibble of which load reaches which (K-tile, kk, fq) slot of which channel, the decode up to c + zp = +-255) and the
+// group-row schedule below (row buffer g & 1 through its first reuse, the zp refresh, the fold, one K-tile per group), with a
+// numpy model of both kernels as written and its single-error mutants (profiles/wq16_probe_mutants.txt).  The shared epilogue:
+// tests/test_gpu_gemm16_probes.py.
 #include "gemm16_common.h"
 
 namespace wanq {
