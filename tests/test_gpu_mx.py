@@ -432,6 +432,30 @@ def test_repeated_calls_and_rows_in_launches_of_another_size_are_bit_equal(w_fmt
     assert torch.equal(call_abi(moved[0], w, moved[1], sw, w_fmt, torch.float32)[0], f32[200])
 
 
+def test_unit_scales_are_bit_equal_to_the_fp8_gemm_with_unit_scales():
+    """wanq_gemm_fp8 with sa = sw = 1.0 against wanq_gemm_mx with e4m3 weights and every scale byte 127, on the same random finite e4m3
+    codes: both issue the same matrix instruction with the same fragments and the same scale byte, and fmaf(acc * 1, 1, b) is acc + b,
+    so the outputs are EQUAL -- the shared K loop (csrc/gemm16_common.h) feeds both kernels alike.  Two m-tiles and two n-tiles with
+    clamped rows on both, three K-tiles (both LDS buffers reused); fp32 and bf16 output, bias, GELU, gate + residual"""
+    from test_gpu_fp8 import call_abi as fp8_abi
+
+    M, N, K = 130, 136, 384
+    g = gen_for(21)
+    a = torch.randint(0, 256, (M, K), device=DEV, generator=g, dtype=torch.uint8)
+    w = torch.randint(0, 256, (N, K), device=DEV, generator=g, dtype=torch.uint8)
+    a[(a & 0x7f) == 0x7f] = 0x3c
+    w[(w & 0x7f) == 0x7f] = 0xbc
+    bias = torch.randn(N, device=DEV, generator=g)
+    gate = torch.rand(N, device=DEV, generator=g) * 2 - 1
+    for out_dtype in (torch.float32, torch.bfloat16):
+        res = torch.randn(M, N, device=DEV, generator=g).to(out_dtype)
+        for b, gelu, gres in ((None, False, False), (bias, False, False), (bias, True, False), (bias, False, True), (bias, True, True)):
+            args = (out_dtype, b, gelu, gate if gres else None, res.clone() if gres else None)
+            y8 = fp8_abi(a, w, ones(M), ones(N), *args)
+            yx = call_abi(a, w, unit(M, K), unit(N, K), FP8, *args)
+            assert torch.isfinite(yx).all() and torch.equal(y8, yx), (out_dtype, b is not None, gelu, gres)
+
+
 def test_python_wrapper_refusals_carry_the_rule():
     from viditq_extension import qgemm
 

@@ -41,20 +41,13 @@
 namespace wanq {
 namespace {
 
-constexpr int QTILE = TM * TROW;  // one K-tile buffer: 16 KiB of token rows
-constexpr int QLDS = 2 * QTILE;
+constexpr int QLDS = 2 * XTILE;           // two K-tile buffers of token rows, 16 KiB each
+constexpr int GROW = TN * 4;              // one group row of the tile's channels, fp32
+constexpr int GLDS = QLDS + 4 * GROW;     // grouped: token buffers | sw rows 0, 1 | zp rows 0, 1
 
-struct WqGemmParams {
-  const uint16_t* a;
-  const uint8_t* w;
-  void* out;
-  const float* sw;
+struct WqGemmParams : Gemm16Params {  // sw: fp32 [N], grouped [K / g][N]; sa: unused
   const float* zp;
-  const void* bias;
-  const float* gate;
-  const void* residual;
-  int bias_dtype, epi;
-  int M, N, K, nt;
+  int tpg;  // grouped: K-tiles per group
 };
 
 // two integer-valued floats (|x| <= 256) -> one dword of the 16-bit operand type, exactly
@@ -76,40 +69,65 @@ __device__ __forceinline__ void cvt4(uint32_t u, float z, int& d0, int& d1) {
   d1 = pack2<F16IN>(f2, f3);
 }
 
-template <bool F16IN, bool W4, int OUT>
-__global__ void __launch_bounds__(256, 2) gemm_wq16_kernel(WqGemmParams p) {
-  __shared__ __attribute__((aligned(1024))) char smem[QLDS];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int tm = blockIdx.x / p.nt, tn = blockIdx.x - tm * p.nt;
-  const int m0 = tm * TM, n0 = tn * TN;
-  const int K = p.K, nk = K / TK;
+template <int OFF>
+__device__ __forceinline__ void dsr32(float& d, uint32_t addr) {
+  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF));
+}
 
-  const uint16_t* src[4];  // LDS-DMA sources (token rows only)
-  token_dma_sources(p.a, m0, p.M, K, wave, lane, src);
+// ---- GROUPED: group-wise scales (wanq_gemm_wq16_grouped): sw / zp are [K / g][N], one row per group of g input channels ----------
+//   part_g[m,n] = sum_{k in group g} a[m,k] (c[n,k] + zp[g,n]);  acc = fma(part_g, sw[g,n], acc), g ascending from acc = 0;
+//   y = acc + bias; GELU / gate + residual; one rounding (epilogue16<OUT, false>).
+// The plain kernel with a second accumulator set: the MFMAs of a group sum into part[4][4] in that kernel's order, and the last
+// K-tile of a group ((t + 1) 64 % g == 0) folds part into acc with the group's scale -- one fp32 fma per element -- and zeroes it.
+// The scale never touches the 16-bit operand.
+// Group rows.  Holding a group's 16 scales per lane in registers next to 128 accumulators, 32 + 32 operand dwords and the next
+// tile's codes spills (256 VGPRs, 16-48 bytes of scratch), so the rows of the workgroup's 128 channels travel as the token tile
+// does: one 4-byte LDS-DMA per wave and group (waves 0, 1: sw; waves 2, 3: zp; channels past N read channel N - 1) into one of two
+// 512-byte rows each behind the token buffers, ONE GROUP AHEAD -- the rows of group g + 1 are issued under the first K-tile of
+// group g, behind the barrier that ends every read of the buffer they replace (group g - 1's), and retired by the next tile's
+// vmcnt(0) + barrier, at least one K-tile before they are read.  A lane reads its 4 zp (channel j 16 + fr, the zadj of the
+// conversion) at the top of a group's first tile and its 4 float4 of sw (channels j 16 + 4 fq .. + 3) at the fold, when the operand
+// registers are dead.
+template <bool F16IN, bool W4, int OUT, bool GROUPED>
+__global__ void __launch_bounds__(256, 2) gemm_wq16_kernel(WqGemmParams p) {
+  __shared__ __attribute__((aligned(1024))) char smem[GROUPED ? GLDS : QLDS];
+  const Frame f(p.nt);
+  const int K = p.K, nk = K / TK, tpg = p.tpg, ng = GROUPED ? nk / tpg : 0;
+
+  const char* src[4];  // LDS-DMA sources (token rows only)
+  dma_sources(p.a, f.m0, p.M, (int64_t)K * 2, f, src);
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
-  auto issue = [&](int t) {
-    char* dst = smem + (t & 1) * QTILE + wave * 1024;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      __builtin_amdgcn_global_load_lds((glb_void*)(src[q] + t * TK), (lds_void*)(dst + q * 4096), 16, 0, 0);
+  // (the offset: k = t TK < K in int, then bytes; widened first it becomes a 64-bit induction variable per source)
+  auto issue = [&](int t) { dma_issue<4>(src, (int64_t)(t * TK) * 2, smem + (t & 1) * XTILE + f.wave * 1024); };
+
+  // ---- group rows: this wave's 64 channels of sw (waves 0, 1) or zp (waves 2, 3), lane l -> channel 64 (wave & 1) + l
+  const bool has_zp = p.zp != nullptr;
+  const bool grow_wave = f.wave < 2 || has_zp;
+  const int grow_n = f.n0 + f.wn * 64 + f.lane < p.N ? f.n0 + f.wn * 64 + f.lane : p.N - 1;
+  const float* grow_src = (f.wave < 2 ? static_cast<const float*>(p.sw) : p.zp) + grow_n;
+  auto issue_group = [&](int g) {
+    if (grow_wave)
+      __builtin_amdgcn_global_load_lds((glb_void*)(grow_src + (int64_t)g * p.N),
+                                       (lds_void*)(smem + QLDS + f.wm * 2 * GROW + (g & 1) * GROW + f.wn * 256), 4, 0, 0);
   };
+  const uint32_t sw_rd = lds0 + QLDS + f.wn * 256 + f.fq * 16;            // + (g & 1) GROW + 64 j: channels 16 j + 4 fq .. + 3
+  const uint32_t zp_rd = lds0 + QLDS + 2 * GROW + f.wn * 256 + f.fr * 4;  // + (g & 1) GROW + 64 j: channel 16 j + fr
 
   // ---- fragment geometry: lane l holds row (16-row block) + (l & 15), the 8 k of logical chunk 4 kk + (l >> 4)
-  const int fr = lane & 15, fq = lane >> 4;
-  const uint32_t rd0 = frag_addr(lds0, fr, fq, 0), rd1 = frag_addr(lds0, fr, fq, 1);
+  const uint32_t rd0 = frag_addr(lds0, f.fr, f.fq, 0), rd1 = frag_addr(lds0, f.fr, f.fq, 1);
 
   // ---- weight codes of this lane: channel block j, step kk -> W8: 8 bytes at k = 64 t + 32 kk + 8 fq; W4: dword fq of the 16-byte
   // group of codes 64 t + 32 kk .. + 31 (low nibbles = codes 8 fq .. + 3, high nibbles = codes 8 fq + 4 .. + 7)
   constexpr int CT = W4 ? TK / 2 : TK;  // bytes of codes per row and K-tile
+  constexpr float ZOFF = W4 ? 0.f : 128.f;
   const uint8_t* wp[4];
   float zadj[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int nr = n0 + wn * 64 + j * 16 + fr;
+    const int nr = f.n0 + f.wn * 64 + j * 16 + f.fr;
     const int n = nr < p.N ? nr : p.N - 1;
-    wp[j] = p.w + (int64_t)n * (W4 ? K / 2 : K) + fq * (CT / 8);
-    zadj[j] = (p.zp ? p.zp[n] : 0.f) - (W4 ? 0.f : 128.f);
+    wp[j] = static_cast<const uint8_t*>(p.w) + (int64_t)n * (W4 ? K / 2 : K) + f.fq * (CT / 8);
+    zadj[j] = GROUPED ? -ZOFF : (p.zp ? p.zp[n] : 0.f) - ZOFF;  // GROUPED: refreshed from the group's zp row
   }
   uint2 raw[2][4];  // W4 uses .x only
   auto load_codes = [&](int t) {
@@ -123,16 +141,30 @@ __global__ void __launch_bounds__(256, 2) gemm_wq16_kernel(WqGemmParams p) {
       }
   };
 
-  v4f acc[4][4];
+  v4f acc[4][4], part[4][4];  // part: GROUPED only
   zero_acc(acc);
+  zero_acc(part);
+  v4f (&sum)[4][4] = GROUPED ? part : acc;
 
   issue(0);
+  if constexpr (GROUPED) issue_group(0);
   load_codes(0);
+  int g = 0, tin = 0;  // GROUPED: group of tile t, and t's place in it
   for (int t = 0; t < nk; ++t) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     if (t + 1 < nk) issue(t + 1);
+    if (GROUPED && tin == 0) {
+      if (g + 1 < ng) issue_group(g + 1);
+      if (has_zp) {
+        const uint32_t za = zp_rd + (g & 1) * GROW;
+        float z0, z1, z2, z3;
+        dsr32<0>(z0, za); dsr32<64>(z1, za); dsr32<128>(z2, za); dsr32<192>(z3, za);
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(z0), "+v"(z1), "+v"(z2), "+v"(z3) : : "memory");
+        zadj[0] = z0 - ZOFF; zadj[1] = z1 - ZOFF; zadj[2] = z2 - ZOFF; zadj[3] = z3 - ZOFF;
+      }
+    }
     __builtin_amdgcn_sched_barrier(0);
     v4i wb[2][4];
 #pragma unroll
@@ -151,11 +183,10 @@ __global__ void __launch_bounds__(256, 2) gemm_wq16_kernel(WqGemmParams p) {
         wb[kk][j] = v4i{d0, d1, d2, d3};
       }
     load_codes(t + 1 < nk ? t + 1 : t);  // last tile: re-read itself (never used)
-    const uint32_t boff = (t & 1) * QTILE;
-    const uint32_t a0 = rd0 + boff + wm * 64 * TROW, a1 = rd1 + boff + wm * 64 * TROW;
+    const uint32_t xo = (t & 1) * XTILE + f.wm * 64 * TROW;
     v4i xa[2][4];
-    dsr<0>(xa[0][0], a0); dsr<16 * TROW>(xa[0][1], a0); dsr<32 * TROW>(xa[0][2], a0); dsr<48 * TROW>(xa[0][3], a0);
-    dsr<0>(xa[1][0], a1); dsr<16 * TROW>(xa[1][1], a1); dsr<32 * TROW>(xa[1][2], a1); dsr<48 * TROW>(xa[1][3], a1);
+    dsr4<TROW>(xa[0], rd0 + xo);
+    dsr4<TROW>(xa[1], rd1 + xo);
     // tied to the fragments: the MFMAs that read them cannot be scheduled above the wait (the compiler does not count the asm
     // reads in lgkmcnt), while the conversion of the codes stays free to interleave with the MFMAs
     asm volatile("s_waitcnt lgkmcnt(0)"
@@ -168,177 +199,8 @@ __global__ void __launch_bounds__(256, 2) gemm_wq16_kernel(WqGemmParams p) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = mfma<F16IN>(wb[kk][j], xa[kk][i], acc[i][j]);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-
-  epilogue16<OUT, true>(acc, m0, n0, wm, wn, fr, fq, p.M, p.N, p.sw, p.bias, p.bias_dtype, p.gate, p.residual, p.out, p.epi);
-}
-
-template <bool F16IN, bool W4, int OUT>
-int launch(const WqGemmParams& p, hipStream_t st) {
-  const int64_t tiles = (int64_t)((p.M + TM - 1) / TM) * p.nt;
-  hipLaunchKernelGGL((gemm_wq16_kernel<F16IN, W4, OUT>), dim3((unsigned)tiles), dim3(256), 0, st, p);
-  return check_launch("wanq_gemm_wq16");
-}
-
-template <bool F16IN, bool W4>
-int launch_out(const WqGemmParams& p, int out_dtype, hipStream_t st) {
-  switch (out_dtype) {
-    case WANQ_F16: return launch<F16IN, W4, WANQ_F16>(p, st);
-    case WANQ_BF16: return launch<F16IN, W4, WANQ_BF16>(p, st);
-    default: return launch<F16IN, W4, WANQ_F32>(p, st);
-  }
-}
-
-// ---- group-wise scales (wanq_gemm_wq16_grouped): sw / zp are [K / g][N], one row per group of g input channels -----------------
-//   part_g[m,n] = sum_{k in group g} a[m,k] (c[n,k] + zp[g,n]);  acc = fma(part_g, sw[g,n], acc), g ascending from acc = 0;
-//   y = acc + bias; GELU / gate + residual; one rounding (epilogue16<OUT, false>).
-// The kernel above with a second accumulator set: the MFMAs of a group sum into part[4][4] in that kernel's order, and the last
-// K-tile of a group ((t + 1) 64 % g == 0) folds part into acc with the group's scale -- one fp32 fma per element -- and zeroes it.
-// The scale never touches the 16-bit operand.
-// Group rows.  Holding a group's 16 scales per lane in registers next to 128 accumulators, 32 + 32 operand dwords and the next
-// tile's codes spills (256 VGPRs, 16-48 bytes of scratch), so the rows of the workgroup's 128 channels travel as the token tile
-// does: one 4-byte LDS-DMA per wave and group (waves 0, 1: sw; waves 2, 3: zp; channels past N read channel N - 1) into one of two
-// 512-byte rows each behind the token buffers, ONE GROUP AHEAD -- the rows of group g + 1 are issued under the first K-tile of
-// group g, behind the barrier that ends every read of the buffer they replace (group g - 1's), and retired by the next tile's
-// vmcnt(0) + barrier, at least one K-tile before they are read.  A lane reads its 4 zp (channel j 16 + fr, the zadj of the
-// conversion) at the top of a group's first tile and its 4 float4 of sw (channels j 16 + 4 fq .. + 3) at the fold, when the operand
-// registers are dead.
-struct WqGroupedParams {
-  WqGemmParams g;
-  int tpg;  // K-tiles per group
-};
-
-constexpr int GROW = TN * 4;              // one group row of the tile's channels, fp32
-constexpr int GLDS = QLDS + 4 * GROW;     // token buffers | sw rows 0, 1 | zp rows 0, 1
-
-template <int OFF>
-__device__ __forceinline__ void dsr32(float& d, uint32_t addr) {
-  asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF));
-}
-
-template <bool F16IN, bool W4, int OUT>
-__global__ void __launch_bounds__(256, 2) gemm_wq16_grouped_kernel(WqGroupedParams gp) {
-  const WqGemmParams& p = gp.g;
-  __shared__ __attribute__((aligned(1024))) char smem[GLDS];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int tm = blockIdx.x / p.nt, tn = blockIdx.x - tm * p.nt;
-  const int m0 = tm * TM, n0 = tn * TN;
-  const int K = p.K, nk = K / TK, tpg = gp.tpg, ng = nk / tpg;
-
-  const uint16_t* src[4];
-  token_dma_sources(p.a, m0, p.M, K, wave, lane, src);
-  const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
-  auto issue = [&](int t) {
-    char* dst = smem + (t & 1) * QTILE + wave * 1024;
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-      __builtin_amdgcn_global_load_lds((glb_void*)(src[q] + t * TK), (lds_void*)(dst + q * 4096), 16, 0, 0);
-  };
-
-  // ---- group rows: this wave's 64 channels of sw (waves 0, 1) or zp (waves 2, 3), lane l -> channel 64 (wave & 1) + l
-  const bool has_zp = p.zp != nullptr;
-  const bool grow_wave = wave < 2 || has_zp;
-  const float* grow_src;
-  {
-    const int nr = n0 + (wave & 1) * 64 + lane;
-    grow_src = (wave < 2 ? p.sw : p.zp) + (nr < p.N ? nr : p.N - 1);
-  }
-  auto issue_group = [&](int g) {
-    if (grow_wave)
-      __builtin_amdgcn_global_load_lds((glb_void*)(grow_src + (int64_t)g * p.N),
-                                       (lds_void*)(smem + QLDS + (wave >> 1) * 2 * GROW + (g & 1) * GROW + (wave & 1) * 256), 4, 0, 0);
-  };
-
-  // ---- fragment geometry: as gemm_wq16_kernel
-  const int fr = lane & 15, fq = lane >> 4;
-  const uint32_t rd0 = frag_addr(lds0, fr, fq, 0), rd1 = frag_addr(lds0, fr, fq, 1);
-  const uint32_t sw_rd = lds0 + QLDS + wn * 256 + fq * 16;             // + (g & 1) GROW + 64 j: channels 16 j + 4 fq .. + 3
-  const uint32_t zp_rd = lds0 + QLDS + 2 * GROW + wn * 256 + fr * 4;   // + (g & 1) GROW + 64 j: channel 16 j + fr
-
-  constexpr int CT = W4 ? TK / 2 : TK;
-  constexpr float ZOFF = W4 ? 0.f : 128.f;
-  const uint8_t* wp[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int nr = n0 + wn * 64 + j * 16 + fr;
-    const int n = nr < p.N ? nr : p.N - 1;
-    wp[j] = p.w + (int64_t)n * (W4 ? K / 2 : K) + fq * (CT / 8);
-  }
-  uint2 raw[2][4];
-  auto load_codes = [&](int t) {
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const uint8_t* s = wp[j] + (int64_t)t * CT + kk * (CT / 2);
-        if constexpr (W4) raw[kk][j].x = *reinterpret_cast<const uint32_t*>(s);
-        else raw[kk][j] = *reinterpret_cast<const uint2*>(s);
-      }
-  };
-
-  v4f acc[4][4], part[4][4];
-  zero_acc(acc);
-  zero_acc(part);
-  float zadj[4] = {-ZOFF, -ZOFF, -ZOFF, -ZOFF};
-
-  issue(0);
-  issue_group(0);
-  load_codes(0);
-  int g = 0, tin = 0;  // group of tile t, and t's place in it
-  for (int t = 0; t < nk; ++t) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    if (t + 1 < nk) issue(t + 1);
-    if (tin == 0) {
-      if (g + 1 < ng) issue_group(g + 1);
-      if (has_zp) {
-        const uint32_t za = zp_rd + (g & 1) * GROW;
-        float z0, z1, z2, z3;
-        dsr32<0>(z0, za); dsr32<64>(z1, za); dsr32<128>(z2, za); dsr32<192>(z3, za);
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(z0), "+v"(z1), "+v"(z2), "+v"(z3) : : "memory");
-        zadj[0] = z0 - ZOFF; zadj[1] = z1 - ZOFF; zadj[2] = z2 - ZOFF; zadj[3] = z3 - ZOFF;
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    const bool last = tin + 1 == tpg;
-    v4i wb[2][4];
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        uint32_t u0, u1;
-        if constexpr (W4) {
-          u0 = raw[kk][j].x & 0x0f0f0f0fu; u1 = (raw[kk][j].x >> 4) & 0x0f0f0f0fu;
-        } else {
-          u0 = raw[kk][j].x ^ 0x80808080u; u1 = raw[kk][j].y ^ 0x80808080u;
-        }
-        int d0, d1, d2, d3;
-        cvt4<F16IN>(u0, zadj[j], d0, d1);
-        cvt4<F16IN>(u1, zadj[j], d2, d3);
-        wb[kk][j] = v4i{d0, d1, d2, d3};
-      }
-    load_codes(t + 1 < nk ? t + 1 : t);  // last tile: re-read itself (never used)
-    const uint32_t boff = (t & 1) * QTILE;
-    const uint32_t a0 = rd0 + boff + wm * 64 * TROW, a1 = rd1 + boff + wm * 64 * TROW;
-    v4i xa[2][4];
-    dsr<0>(xa[0][0], a0); dsr<16 * TROW>(xa[0][1], a0); dsr<32 * TROW>(xa[0][2], a0); dsr<48 * TROW>(xa[0][3], a0);
-    dsr<0>(xa[1][0], a1); dsr<16 * TROW>(xa[1][1], a1); dsr<32 * TROW>(xa[1][2], a1); dsr<48 * TROW>(xa[1][3], a1);
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(xa[0][0]), "+v"(xa[0][1]), "+v"(xa[0][2]), "+v"(xa[0][3]), "+v"(xa[1][0]), "+v"(xa[1][1]), "+v"(xa[1][2]),
-                   "+v"(xa[1][3])
-                 :
-                 : "memory");
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) part[i][j] = mfma<F16IN>(wb[kk][j], xa[kk][i], part[i][j]);
-    if (last) {
+        for (int j = 0; j < 4; ++j) sum[i][j] = mfma<F16IN>(wb[kk][j], xa[kk][i], sum[i][j]);
+    if (GROUPED && ++tin == tpg) {  // the group's last tile: fold
       __builtin_amdgcn_sched_barrier(0);  // the scale reads stay behind the MFMAs: their operands are dead by then
       const uint32_t sa = sw_rd + (g & 1) * GROW;
       v4i sr[4];
@@ -356,29 +218,24 @@ __global__ void __launch_bounds__(256, 2) gemm_wq16_grouped_kernel(WqGroupedPara
       }
       ++g;
       tin = 0;
-    } else {
-      ++tin;
     }
     __builtin_amdgcn_sched_barrier(0);
   }
 
-  epilogue16<OUT, false>(acc, m0, n0, wm, wn, fr, fq, p.M, p.N, nullptr, p.bias, p.bias_dtype, p.gate, p.residual, p.out, p.epi);
+  epilogue16<OUT, !GROUPED>(acc, f, p);
 }
 
-template <bool F16IN, bool W4, int OUT>
-int launch_grouped(const WqGroupedParams& gp, hipStream_t st) {
-  const int64_t tiles = (int64_t)((gp.g.M + TM - 1) / TM) * gp.g.nt;
-  hipLaunchKernelGGL((gemm_wq16_grouped_kernel<F16IN, W4, OUT>), dim3((unsigned)tiles), dim3(256), 0, st, gp);
-  return check_launch("wanq_gemm_wq16_grouped");
-}
-
-template <bool F16IN, bool W4>
-int launch_grouped_out(const WqGroupedParams& gp, int out_dtype, hipStream_t st) {
-  switch (out_dtype) {
-    case WANQ_F16: return launch_grouped<F16IN, W4, WANQ_F16>(gp, st);
-    case WANQ_BF16: return launch_grouped<F16IN, W4, WANQ_BF16>(gp, st);
-    default: return launch_grouped<F16IN, W4, WANQ_F32>(gp, st);
-  }
+template <bool GROUPED>
+int launch_wq16(const WqGemmParams& p, int dtype, int w_bits, int out_dtype, hipStream_t st, const char* what) {
+  return with_out_dtype(out_dtype, [&](auto o) {
+    constexpr int OUT = decltype(o)::value;
+    const bool f16 = dtype == WANQ_F16;
+    if (w_bits == 4)
+      return f16 ? launch_tiles(gemm_wq16_kernel<true, true, OUT, GROUPED>, p, st, what)
+                 : launch_tiles(gemm_wq16_kernel<false, true, OUT, GROUPED>, p, st, what);
+    return f16 ? launch_tiles(gemm_wq16_kernel<true, false, OUT, GROUPED>, p, st, what)
+               : launch_tiles(gemm_wq16_kernel<false, false, OUT, GROUPED>, p, st, what);
+  });
 }
 
 }  // namespace
@@ -399,15 +256,8 @@ extern "C" int wanq_gemm_wq16(const void* a, const void* w, int dtype, int w_bit
   WANQ_REQUIRE(aligned(sw, 16) && aligned(zp, 16), WANQ_E_ARG, "%s: sw and zp must be 16-byte aligned", what);
   if (const int rc = check_gemm16_tail(what, bias, bias_dtype, gate, M, N)) return rc;
   if (M == 0) return WANQ_OK;
-  WqGemmParams p{};
-  p.a = static_cast<const uint16_t*>(a); p.w = static_cast<const uint8_t*>(w); p.out = out; p.sw = sw; p.zp = zp; p.bias = bias;
-  p.gate = (epi_flags & WANQ_EPI_GATE_RES) ? gate : nullptr;
-  p.residual = (epi_flags & WANQ_EPI_GATE_RES) ? residual : nullptr;
-  p.bias_dtype = bias_dtype; p.epi = epi_flags;
-  p.M = (int)M; p.N = N; p.K = K; p.nt = (N + TN - 1) / TN;
-  hipStream_t st = (hipStream_t)stream;
-  if (w_bits == 4) return dtype == WANQ_F16 ? launch_out<true, true>(p, out_dtype, st) : launch_out<false, true>(p, out_dtype, st);
-  return dtype == WANQ_F16 ? launch_out<true, false>(p, out_dtype, st) : launch_out<false, false>(p, out_dtype, st);
+  const WqGemmParams p{gemm16_params(a, w, nullptr, sw, out, bias, bias_dtype, gate, residual, epi_flags, M, N, K), zp, 0};
+  return launch_wq16<false>(p, dtype, w_bits, out_dtype, (hipStream_t)stream, what);
 }
 
 extern "C" int wanq_gemm_wq16_grouped(const void* a, const void* w, int dtype, int w_bits, const float* sw, const float* zp,
@@ -427,16 +277,7 @@ extern "C" int wanq_gemm_wq16_grouped(const void* a, const void* w, int dtype, i
   WANQ_REQUIRE(aligned(sw, 16) && aligned(zp, 16), WANQ_E_ARG, "%s: sw and zp must be 16-byte aligned", what);
   if (const int rc = check_gemm16_tail(what, bias, bias_dtype, gate, M, N)) return rc;
   if (M == 0) return WANQ_OK;
-  WqGroupedParams gp{};
-  WqGemmParams& p = gp.g;
-  p.a = static_cast<const uint16_t*>(a); p.w = static_cast<const uint8_t*>(w); p.out = out; p.sw = sw; p.zp = zp; p.bias = bias;
-  p.gate = (epi_flags & WANQ_EPI_GATE_RES) ? gate : nullptr;
-  p.residual = (epi_flags & WANQ_EPI_GATE_RES) ? residual : nullptr;
-  p.bias_dtype = bias_dtype; p.epi = epi_flags;
-  p.M = (int)M; p.N = N; p.K = K; p.nt = (N + TN - 1) / TN;
-  gp.tpg = group_size / TK;
-  hipStream_t st = (hipStream_t)stream;
-  if (w_bits == 4)
-    return dtype == WANQ_F16 ? launch_grouped_out<true, true>(gp, out_dtype, st) : launch_grouped_out<false, true>(gp, out_dtype, st);
-  return dtype == WANQ_F16 ? launch_grouped_out<true, false>(gp, out_dtype, st) : launch_grouped_out<false, false>(gp, out_dtype, st);
+  const WqGemmParams p{gemm16_params(a, w, nullptr, sw, out, bias, bias_dtype, gate, residual, epi_flags, M, N, K), zp,
+                       group_size / TK};
+  return launch_wq16<true>(p, dtype, w_bits, out_dtype, (hipStream_t)stream, what);
 }
