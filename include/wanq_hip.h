@@ -208,6 +208,25 @@ int wanq_gemm_wq16_grouped(const void* a, const void* w, int dtype, int w_bits, 
                            void* out, int out_dtype, const void* bias, int bias_dtype, const float* gate, const void* residual,
                            int epi_flags, int64_t M, int N, int K, void* stream);
 
+/* wanq_gemm_wq16 / wanq_gemm_wq16_grouped with a 16-bit low-rank side branch, y = x W^T + (x A^T) B^T: the low-rank compensation of
+ * the quantisation error (LoRC: B A the best rank-r approximation of W - W^) and LoRA adapters on a quantised Linear.  The caller
+ * computes t = x A^T (wanq_gemm_bf16 with N = R, rounded once to `dtype`); this entry adds t B^T INSIDE the GEMM, before GELU and
+ * gate + residual:
+ *   y0[m,n] = exactly what wanq_gemm_wq16 (group_size == 0: sw, zp fp32 [N]; fma(acc, sw[n], bias[n])) or wanq_gemm_wq16_grouped
+ *             (any other group_size: that entry's rules and [K / group_size][N] layouts; acc + bias[n]) computes before GELU
+ *   lr[m,n] = sum_r t[m,r] * b[n,r]      (fp32, on the 16-bit matrix cores of `dtype`, 64-deep r-tiles ascending, in an accumulator
+ *                                         set of its own: bit-equal to wanq_gemm_bf16(t, b) with an fp32 output)
+ *   y       = y0 + lr                    (one fp32 add);  GELU, gate + residual and the one rounding to out_dtype as above.
+ * t is [M, R] and b is [N, R], both of `dtype`, row-major and 16-byte aligned.  R % 64 == 0 and 64 <= R <= 256: a smaller rank is
+ * zero padded by the caller, and a zero column of t or b contributes exactly 0.  With t = 0 or b = 0 and finite operands the output
+ * is bit-equal to the entry without the branch (y0 + 0).  Every other argument and rule as for the two entries above; rows past M
+ * and channels past N are clamped in-kernel as there.  Anything else is refused (WANQ_E_SHAPE / WANQ_E_ARG, the message names the
+ * rule).  Determinism: the summation order of y0 is that of the entry without the branch and that of lr depends on R only, so a
+ * row gives the same bits in any launch and repeated calls are bit-identical. */
+int wanq_gemm_wq16_lowrank(const void* a, const void* w, int dtype, int w_bits, const float* sw, const float* zp, int group_size,
+                           const void* t, const void* b, int R, void* out, int out_dtype, const void* bias, int bias_dtype,
+                           const float* gate, const void* residual, int epi_flags, int64_t M, int N, int K, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * PTQ calibration reduction: running per-channel absmax over tokens,
  *   colmax[c] = max(colmax[c], max_r |x[r,c]|)        (colmax fp32[cols], caller zero-initialises)

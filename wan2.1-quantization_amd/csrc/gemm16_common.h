@@ -163,9 +163,10 @@ __device__ __forceinline__ void zero_acc(v4f (&acc)[4][4]) {
 }
 
 // epilogue, fp32: acc + bias, or with SCALED acc * sw + bias in one fma, or with TOKEN (gemm_fp8.hip) (acc * sa[m]) * sw + bias, the
-// per-token factor first and then one fma; GELU; residual + y * gate; one rounding to OUT
-template <int OUT, bool SCALED, bool TOKEN = false>
-__device__ __forceinline__ void epilogue16(const v4f (&acc)[4][4], const Frame& f, const Gemm16Params& p) {
+// per-token factor first and then one fma; with LOWRANK (gemm_wq16.hip) + lr, a second accumulator set, one fp32 add behind the bias;
+// GELU; residual + y * gate; one rounding to OUT
+template <int OUT, bool SCALED, bool TOKEN, bool LOWRANK>
+__device__ __forceinline__ void epilogue16(const v4f (&acc)[4][4], const v4f (&lr)[4][4], const Frame& f, const Gemm16Params& p) {
   static_assert(!TOKEN || SCALED, "the per-token factor comes with the per-channel one");
   const bool gelu = p.epi & WANQ_EPI_GELU, gres = p.epi & WANQ_EPI_GATE_RES;
 #pragma unroll
@@ -189,6 +190,7 @@ __device__ __forceinline__ void epilogue16(const v4f (&acc)[4][4], const Frame& 
         if constexpr (TOKEN) y[e] = __fmaf_rn(acc[i][j][e] * sm, s4[e], b4[e]);
         else if constexpr (SCALED) y[e] = __fmaf_rn(acc[i][j][e], s4[e], b4[e]);
         else y[e] = acc[i][j][e] + b4[e];
+        if constexpr (LOWRANK) y[e] += lr[i][j][e];
       }
       if (gelu) {
 #pragma unroll
@@ -203,6 +205,11 @@ __device__ __forceinline__ void epilogue16(const v4f (&acc)[4][4], const Frame& 
       store4_out<OUT>(p.out, o, y);
     }
   }
+}
+
+template <int OUT, bool SCALED, bool TOKEN = false>
+__device__ __forceinline__ void epilogue16(const v4f (&acc)[4][4], const Frame& f, const Gemm16Params& p) {
+  epilogue16<OUT, SCALED, TOKEN, false>(acc, acc, f, p);
 }
 
 // ---- the two-sided loop: policies in gemm_bf16.hip, gemm_fp8.hip and gemm_mx.hip (header comment: what a policy supplies) -----

@@ -31,6 +31,13 @@
 // Determinism.  gemm_bf16.hip's summation order (gemm16_common.h), so with sw = 1 the output is bit-equal to wanq_gemm_bf16 on the
 // weight (c + zp) cast to the activation dtype.
 //
+// Low-rank branch (wanq_gemm_wq16_lowrank; LOWRANK below): y = y0 + lr with y0 exactly what the plain / grouped kernel has before GELU
+// (fma(acc, sw[n], bias[n]) / acc + bias[n]) and lr[m,n] = sum_r t[m,r] b[n,r], t [M, R] and b [N, R] of the activation dtype, summed
+// in fp32 on the same MFMA, 64-deep r-tiles ascending, in an accumulator set of its own; then GELU, gate + residual, one rounding.
+// R % 64 == 0, 64 <= R <= 256.  For LoRC (b a = the best rank-r approximation of W - W_hat) and LoRA adapters on a quantised Linear;
+// t = x a^T is the caller's wanq_gemm_bf16 launch.  A zero branch leaves the flag-off kernel's bits; lr is bit-equal to
+// wanq_gemm_bf16(t, b) in fp32; a row's bits do not depend on M.  tests/test_gpu_wq16_lowrank.py.
+//
 // Tests.  tests/test_gpu_wq16_probes.py pins, on answers known bit for bit, what is this file's alone: the fragment cut (which
 // byte / nibble of which load reaches which (K-tile, kk, fq) slot of which channel, the decode up to c + zp = +-255) and the
 // group-row schedule below (row buffer g & 1 through its first reuse, the zp refresh, the fold, one K-tile per group), with a
@@ -48,6 +55,12 @@ constexpr int GLDS = QLDS + 4 * GROW;     // grouped: token buffers | sw rows 0,
 struct WqGemmParams : Gemm16Params {  // sw: fp32 [N], grouped [K / g][N]; sa: unused
   const float* zp;
   int tpg;  // grouped: K-tiles per group
+};
+
+struct WqLowRankParams : WqGemmParams {  // the low-rank branch: t [M, R], b [N, R] of the activation dtype
+  const void* t;
+  const void* b;
+  int R;
 };
 
 // two integer-valued floats (|x| <= 256) -> one dword of the 16-bit operand type, exactly
@@ -88,8 +101,20 @@ __device__ __forceinline__ void dsr32(float& d, uint32_t addr) {
 // vmcnt(0) + barrier, at least one K-tile before they are read.  A lane reads its 4 zp (channel j 16 + fr, the zadj of the
 // conversion) at the top of a group's first tile and its 4 float4 of sw (channels j 16 + 4 fq .. + 3) at the fold, when the operand
 // registers are dead.
-template <bool F16IN, bool W4, int OUT, bool GROUPED>
-__global__ void __launch_bounds__(256, 2) gemm_wq16_kernel(WqGemmParams p) {
+//
+// ---- LOWRANK: the 16-bit side branch (wanq_gemm_wq16_lowrank): y = y0 + lr, lr[m,n] = sum_r t[m,r] b[n,r] ----------------------
+// Behind the quantised K loop both token buffers are free, and a 64-deep slice of (t, b) is one K-tile of gemm_bf16.hip's shape:
+// the t rows of the tile's 128 tokens go into buffer 0 and the b rows of its 128 channels into buffer 1, by the same LDS-DMA into the
+// same swizzled 128-byte rows, and the same frag_addr reads feed 32 MFMAs (b as the A operand, as the weight is) into `part` -- idle
+// in the plain form, zero again behind the last fold in the grouped one.  Per low-rank tile:
+//   barrier (every wave has read both buffers) | issue the DMA of both halves | wait for this wave's DMA | barrier | 8 + 8 fragment
+//   reads | 32 MFMAs
+// The copy is NOT overlapped with MFMAs of the same workgroup (both buffers are its target); it overlaps with the other workgroup
+// on the CU.  The epilogue adds part behind the bias (epilogue16<.., LOWRANK>): one fp32 add, so a zero branch leaves the bits of the
+// flag-off kernel.  lr is summed r-tiles ascending in gemm_bf16.hip's order: bit-equal to wanq_gemm_bf16(t, b) with an fp32 output.
+template <bool F16IN, bool W4, int OUT, bool GROUPED, bool LOWRANK = false>
+__global__ void __launch_bounds__(256, 2)
+    gemm_wq16_kernel(std::conditional_t<LOWRANK, WqLowRankParams, WqGemmParams> p) {
   __shared__ __attribute__((aligned(1024))) char smem[GROUPED ? GLDS : QLDS];
   const Frame f(p.nt);
   const int K = p.K, nk = K / TK, tpg = p.tpg, ng = GROUPED ? nk / tpg : 0;
@@ -222,19 +247,50 @@ __global__ void __launch_bounds__(256, 2) gemm_wq16_kernel(WqGemmParams p) {
     __builtin_amdgcn_sched_barrier(0);
   }
 
-  epilogue16<OUT, !GROUPED>(acc, f, p);
+  if constexpr (LOWRANK) {
+    const char *tsrc[4], *bsrc[4];
+    dma_sources(p.t, f.m0, p.M, (int64_t)p.R * 2, f, tsrc);
+    dma_sources(p.b, f.n0, p.N, (int64_t)p.R * 2, f, bsrc);
+    const uint32_t xo = f.wm * 64 * TROW, wo = XTILE + f.wn * 64 * TROW;
+    for (int s = 0, ns = p.R / TK; s < ns; ++s) {
+      __builtin_amdgcn_s_barrier();  // the last K-tile's (the previous low-rank tile's) reads of both buffers are done
+      __builtin_amdgcn_sched_barrier(0);
+      dma_issue<4>(tsrc, (int64_t)(s * TK) * 2, smem + f.wave * 1024);
+      dma_issue<4>(bsrc, (int64_t)(s * TK) * 2, smem + XTILE + f.wave * 1024);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+      v4i xa[2][4], wb[2][4];
+      dsr4<TROW>(wb[0], rd0 + wo);
+      dsr4<TROW>(xa[0], rd0 + xo);
+      dsr4<TROW>(wb[1], rd1 + wo);
+      dsr4<TROW>(xa[1], rd1 + xo);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) part[i][j] = mfma<F16IN>(wb[kk][j], xa[kk][i], part[i][j]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    epilogue16<OUT, !GROUPED, false, true>(acc, part, f, p);
+  } else {
+    epilogue16<OUT, !GROUPED>(acc, f, p);
+  }
 }
 
-template <bool GROUPED>
-int launch_wq16(const WqGemmParams& p, int dtype, int w_bits, int out_dtype, hipStream_t st, const char* what) {
+template <bool GROUPED, bool LOWRANK = false, class KP>
+int launch_wq16(const KP& p, int dtype, int w_bits, int out_dtype, hipStream_t st, const char* what) {
   return with_out_dtype(out_dtype, [&](auto o) {
     constexpr int OUT = decltype(o)::value;
     const bool f16 = dtype == WANQ_F16;
     if (w_bits == 4)
-      return f16 ? launch_tiles(gemm_wq16_kernel<true, true, OUT, GROUPED>, p, st, what)
-                 : launch_tiles(gemm_wq16_kernel<false, true, OUT, GROUPED>, p, st, what);
-    return f16 ? launch_tiles(gemm_wq16_kernel<true, false, OUT, GROUPED>, p, st, what)
-               : launch_tiles(gemm_wq16_kernel<false, false, OUT, GROUPED>, p, st, what);
+      return f16 ? launch_tiles(gemm_wq16_kernel<true, true, OUT, GROUPED, LOWRANK>, p, st, what)
+                 : launch_tiles(gemm_wq16_kernel<false, true, OUT, GROUPED, LOWRANK>, p, st, what);
+    return f16 ? launch_tiles(gemm_wq16_kernel<true, false, OUT, GROUPED, LOWRANK>, p, st, what)
+               : launch_tiles(gemm_wq16_kernel<false, false, OUT, GROUPED, LOWRANK>, p, st, what);
   });
 }
 
@@ -280,4 +336,32 @@ extern "C" int wanq_gemm_wq16_grouped(const void* a, const void* w, int dtype, i
   const WqGemmParams p{gemm16_params(a, w, nullptr, sw, out, bias, bias_dtype, gate, residual, epi_flags, M, N, K), zp,
                        group_size / TK};
   return launch_wq16<true>(p, dtype, w_bits, out_dtype, (hipStream_t)stream, what);
+}
+
+extern "C" int wanq_gemm_wq16_lowrank(const void* a, const void* w, int dtype, int w_bits, const float* sw, const float* zp,
+                                      int group_size, const void* t, const void* b, int R, void* out, int out_dtype,
+                                      const void* bias, int bias_dtype, const float* gate, const void* residual, int epi_flags,
+                                      int64_t M, int N, int K, void* stream) {
+  const char* what = "wanq_gemm_wq16_lowrank";
+  WANQ_REQUIRE(a && w && out && sw, WANQ_E_ARG, "%s: a, w, out and sw must be non-NULL", what);
+  WANQ_REQUIRE(t && b, WANQ_E_ARG, "%s: t and b must be non-NULL", what);
+  WANQ_REQUIRE(dtype == WANQ_BF16 || dtype == WANQ_F16, WANQ_E_ARG, "%s: operand dtype %d must be BF16 or F16", what, dtype);
+  WANQ_REQUIRE(w_bits == 4 || w_bits == 8, WANQ_E_ARG, "%s: w_bits=%d must be 4 or 8", what, w_bits);
+  if (const int rc = check_gemm16_shapes(what, 64, a, w, out, out_dtype, bias, bias_dtype, gate, residual, epi_flags, M, N,
+                                         K))
+    return rc;
+  if (group_size != 0) {
+    WANQ_REQUIRE(group_size >= 64 && group_size % 64 == 0, WANQ_E_SHAPE, "%s: group_size=%d must be a positive multiple of 64",
+                 what, group_size);
+    WANQ_REQUIRE(K % group_size == 0, WANQ_E_SHAPE, "%s: K=%d must be a multiple of group_size=%d", what, K, group_size);
+  }
+  WANQ_REQUIRE(R >= 64 && R <= 256 && R % 64 == 0, WANQ_E_SHAPE, "%s: R=%d must be 64, 128, 192 or 256", what, R);
+  WANQ_REQUIRE(aligned(sw, 16) && aligned(zp, 16), WANQ_E_ARG, "%s: sw and zp must be 16-byte aligned", what);
+  WANQ_REQUIRE(aligned(t, 16) && aligned(b, 16), WANQ_E_ARG, "%s: t and b must be 16-byte aligned", what);
+  if (const int rc = check_gemm16_tail(what, bias, bias_dtype, gate, M, N)) return rc;
+  if (M == 0) return WANQ_OK;
+  const WqLowRankParams p{
+      {gemm16_params(a, w, nullptr, sw, out, bias, bias_dtype, gate, residual, epi_flags, M, N, K), zp, group_size / TK}, t, b, R};
+  return group_size ? launch_wq16<true, true>(p, dtype, w_bits, out_dtype, (hipStream_t)stream, what)
+                    : launch_wq16<false, true>(p, dtype, w_bits, out_dtype, (hipStream_t)stream, what);
 }

@@ -19,6 +19,7 @@ from ..config import ListConfig
 from ..quarot import quarot_utils
 from .base_quantizer import (FP8_FORMAT, MX_BLOCK, MX_FORMATS, MXFP4_FORMAT, MXFP8_FORMAT, DynamicQuantizer, Fp8Quantizer, MxQuantizer,
                              StaticQuantizer, fp8_decode, mx_decode)
+from .low_rank import RANK_MAX, LowRankBranch, fit_low_rank, padded_rank
 from .mixed_precision_quantizer import MixedPrecisionDynamicQuantizer, MixedPrecisionStaticQuantizer
 
 
@@ -26,13 +27,14 @@ from .mixed_precision_quantizer import MixedPrecisionDynamicQuantizer, MixedPrec
 _FORMAT_BITS = {FP8_FORMAT: (8, "e4m3"), MXFP8_FORMAT: (8, MXFP8_FORMAT), MXFP4_FORMAT: (4, MXFP4_FORMAT)}
 
 
-class QuantizedLinear(nn.Linear):
+class QuantizedLinear(LowRankBranch, nn.Linear):
     uses_mask = False
     uses_rotation = False
 
     def __init__(self, in_features, out_features, bias, device, quant_config, fp_module, module_name=None):
         super().__init__(in_features, out_features, bias, device)
         self.fp_module, self.q_cfg = fp_module, quant_config
+        self.low_rank = self._checked_low_rank(quant_config, module_name)  # `weight.low_rank`: the LoRC rank (low_rank.py), or None
         self.mx = None  # the weight's MX format name (`format: mxfp8_e4m3` / `mxfp4_e2m1`), set by _checked_format
         self.fp8 = self._checked_format(quant_config, module_name)
         # (an MX layer's `weight.group_size: 32` names the format's own block: there is no integer group-wise path behind it)
@@ -126,6 +128,43 @@ class QuantizedLinear(nn.Linear):
         if self.in_features % MX_BLOCK:
             raise ValueError(f"{name}: weight.format: {fw} needs in_features={self.in_features} to be a multiple of {MX_BLOCK}")
 
+    def _checked_low_rank(self, quant_config, module_name):
+        """`weight.low_rank` of the config (None: no low-rank branch), or the refusal of what has none, before any weight is
+        quantised: the message names the layer and the key.  The branch lives in the weight-only GEMM alone: a plain QuantizedLinear
+        with an integer StaticQuantizer (per channel or `group_size`) and no `act:` section."""
+        wq = quant_config.get("weight", None)
+        r = None if wq is None else wq.get("low_rank", None)
+        if r is None:
+            return None
+        name = module_name or type(self).__name__
+        if isinstance(r, bool) or not isinstance(r, int) or r <= 0:
+            raise ValueError(f"{name}: weight.low_rank={r!r} must be a positive integer")
+        if quant_config.get("act", None) is not None:
+            raise NotImplementedError(f"{name}: weight.low_rank with an `act:` section is not supported: the low-rank branch is summed "
+                                      "in the weight-only GEMM (16-bit activations); the int8, fp8 and MX GEMMs have none")
+        if wq.get("format", None) is not None:
+            raise NotImplementedError(f"{name}: weight.low_rank with weight.format={wq.get('format')!r} is not supported: the low-rank "
+                                      "branch goes with integer weight codes (StaticQuantizer)")
+        if isinstance(wq["n_bits"], ListConfig):
+            raise NotImplementedError(f"{name}: weight.low_rank with a bit-width list (MixedPrecisionStaticQuantizer) is not supported")
+        if self.uses_mask or self.uses_rotation:
+            raise NotImplementedError(f"{name}: weight.low_rank with {type(self).__name__} is not supported: the SmoothQuant / QuaRot "
+                                      "/ ViDiT layer classes condition an activation quantiser (leave the layer to the plain "
+                                      "QuantizedLinear)")
+        if r > min(self.in_features, self.out_features):
+            raise ValueError(f"{name}: weight.low_rank={r} exceeds min(out_features, in_features)="
+                             f"{min(self.in_features, self.out_features)}")
+        if padded_rank(r) > RANK_MAX:
+            raise ValueError(f"{name}: weight.low_rank={r} makes a padded rank of {padded_rank(r)}, above the GEMM's {RANK_MAX}")
+        return r
+
+    def _refuse_adapter(self):
+        if self.w_quantizer is None or self.a_quantizer is not None or self.fp8 or self.mx or self.uses_mask or self.uses_rotation \
+                or not isinstance(self.w_quantizer, StaticQuantizer):
+            raise NotImplementedError(f"{self._lr_name()}: set_low_rank needs a plain weight-only QuantizedLinear with integer codes "
+                                      "(a `weight:` section, no `act:` section, no format): the low-rank branch is summed in the "
+                                      "weight-only GEMM")
+
     def _checked_group_size(self, quant_config, module_name, device=None):
         """`weight.group_size` of the config (None: one scale per output channel), or the refusal of what has no group-wise form,
         before any weight is quantised: the message names the layer and the key.  `device`: where the layer's weight lives.  With an
@@ -153,10 +192,18 @@ class QuantizedLinear(nn.Linear):
 
     # ---- weight side --------------------------------------------------------------------------------
     def _requantize(self, w):
-        """weight.data <- fake-quant(w) and int_weight <- its integer codes, with the quantizer's current state."""
+        """weight.data <- fake-quant(w) and int_weight <- its integer codes, with the quantizer's current state.  With
+        `weight.low_rank: r` the LoRC factors are fitted here too, wherever the codes are (re)derived: the best rank-r approximation
+        of E = w - W_hat (low_rank.fit_low_rank: float64 SVD on the weight's device where this build has one, else on the host), kept
+        as the fp32 buffers lr_a [Rp, K] / lr_b [N, Rp].  weight.data stays W_hat, without the branch."""
         codes, deq = self.w_quantizer.codes_and_dequant(w.detach().float())
         self.weight.data = deq
         self.int_weight = codes
+        if self.low_rank is not None:
+            a, b = fit_low_rank(w.detach().double() - deq.double(), self.low_rank)
+            self.register_buffer("lr_a", a, persistent=False)  # (as `_codes`: saved by quantize_and_save_weight)
+            self.register_buffer("lr_b", b, persistent=False)
+            self._lr16 = None
 
     @property
     def packed_w4(self):
@@ -319,7 +366,12 @@ class QuantizedLinear(nn.Linear):
         (ViDiT-Q/quant_utils/qdiff/base/quant_layer.py:68-72 with a_quantizer None).  16-bit activations on the GPU go through
         wanq_gemm_wq16 -- with a `group_size` wanq_gemm_wq16_grouped -- on the integer codes (exact weight operand, scale in fp32);
         anything else, a group size the kernel does not take (not a multiple of 64) included, through the reference's own
-        expression, F.linear on the dequantised weight."""
+        expression, F.linear on the dequantised weight.
+        With a low-rank branch (`weight.low_rank` and / or `set_low_rank`; factors A16 [Rp, K], B16 [N, Rp] in the activation dtype):
+        on the GPU t = qgemm.fp_linear(x, A16), rounded once to that dtype, then wanq_gemm_wq16_lowrank adds t B16^T inside the
+        GEMM; otherwise the host expression F.linear(x, W_hat, bias) + F.linear((x @ A16^T).to(x.dtype), B16)."""
+        if self.low_rank is not None or self._adapter is not None:
+            return self._forward_low_rank(x)
         if x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and self._codes is not None and self._codes.is_cuda:
             x2 = x.reshape(-1, x.shape[-1])
             if qgemm.wq16_linear_refusal(x2.shape[0], self.out_features, self.in_features, self.group_size) is None:
@@ -333,6 +385,20 @@ class QuantizedLinear(nn.Linear):
         w = self.weight if self.weight.dtype == x.dtype else self.weight.to(x.dtype)
         b = self.bias if self.bias is None or self.bias.dtype == x.dtype else self.bias.to(x.dtype)
         return F.linear(x, w, b)
+
+    def _forward_low_rank(self, x):
+        a16, b16 = self.low_rank_operands(x.dtype, x.device)
+        if x.is_cuda and x.dtype in (torch.bfloat16, torch.float16) and self._codes is not None and self._codes.is_cuda:
+            x2 = x.reshape(-1, x.shape[-1]).contiguous()
+            if qgemm.wq16_lowrank_refusal(x2.shape[0], self.out_features, self.in_features, self.group_size, a16.shape[0]) is None:
+                codes, sw, zp, w4 = self.weight_only_operands()
+                bias = None if self.bias is None else self.bias.detach()
+                t = qgemm.fp_linear(x2, a16)
+                y = qgemm.wq16_lowrank_linear(x2, codes, sw, zp, self.group_size, t, b16, bias, w4=w4)
+                return y.view(*x.shape[:-1], self.out_features)
+        w = self.weight if self.weight.dtype == x.dtype else self.weight.to(x.dtype)
+        b = self.bias if self.bias is None or self.bias.dtype == x.dtype else self.bias.to(x.dtype)
+        return F.linear(x, w, b) + F.linear((x @ a16.t()).to(x.dtype), b16)
 
     # ---- PTQ hooks shared by the variants ------------------------------------------------------------
     def get_channel_mask(self, act_mask):

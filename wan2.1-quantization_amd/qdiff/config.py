@@ -12,7 +12,11 @@ The OCP Microscaling formats use the same key: `format: mxfp8_e4m3` (`n_bits: 8`
 (`n_bits: 4`) in `weight:` only -- one E8M0 power-of-two scale per block of 32 input channels on both sides, applied by the matrix
 cores (wanq_quant_rows_mx, wanq_gemm_mx).  The accepted pairs are weight mxfp8_e4m3 or mxfp4_e2m1 against act mxfp8_e4m3, `sym: True`,
 `weight.group_size` absent or 32; `act.format: mxfp4_e2m1`, an MX format against `fp8_e4m3` or against no format, a bit-width list,
-another group size and the SmoothQuant / QuaRot / ViDiT layer classes are refused by layer name."""
+another group size and the SmoothQuant / QuaRot / ViDiT layer classes are refused by layer name.
+`weight.low_rank: r` (a positive int, r <= min(N, K), at most 256 after padding to a multiple of 64): the best rank-r approximation
+of the quantisation error W - W_hat is kept in 16 bits beside the integer codes and added inside the weight-only GEMM
+(qdiff/base/low_rank.py, wanq_gemm_wq16_lowrank).  For a weight-only integer config only, per channel or with `group_size`: with an
+`act:` section, a `format:`, a bit-width list or a SmoothQuant / QuaRot / ViDiT layer class it is refused by layer name."""
 import yaml
 
 

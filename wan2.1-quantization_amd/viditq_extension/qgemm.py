@@ -365,6 +365,52 @@ def wq16_linear_refusal(M, N, K, group_size=None):
     return None
 
 
+LOWRANK_MAX = 256  # the largest (padded) rank wanq_gemm_wq16_lowrank takes; ranks are padded to multiples of 64
+
+
+def wq16_lowrank_linear(input, codes, scale_weight, zp, group_size, t, b, bias=None, out_dtype=None, gelu=False, gate=None,
+                        residual=None, out=None, w4=False):
+    """`wq16_linear` (group_size None or 0) or `wq16_grouped_linear` with a 16-bit low-rank side branch added inside the GEMM
+    (wanq_gemm_wq16_lowrank): y = epilogue(y0 + t[M,R] @ b[N,R]^T), y0 what that entry has before its GELU.  `t` and `b` have the
+    input's dtype; `t` is `fp_linear(input, A)` for the [R, K] factor A, rounded once to that dtype -- the rounding is part of the
+    definition.  R % 64 == 0, 64 <= R <= 256 (zero pad a smaller rank: a zero column contributes exactly 0).  The branch is summed in
+    fp32 in an accumulator set of its own and added once, behind the bias and before GELU and gate + residual."""
+    M, N, K = _check_operands16(input, "codes", codes, torch.uint8 if w4 else torch.int8)
+    _C.check_shape("codes", codes, N, K // 2 if w4 else K)
+    group_size = group_size or None
+    for name, x in (("t", t), ("b", b)):
+        _C.check_gpu(name, x)
+        _C.check_contig(name, x)
+        _C.check_dtype(name, x, input.dtype)
+        if x.dim() != 2:
+            raise RuntimeError(f"Tensor {name} must have dimension number (2)")
+    R = t.shape[1]
+    why = wq16_lowrank_refusal(M, N, K, group_size, R)
+    if why is not None:
+        raise RuntimeError(f"wq16_lowrank_linear: {why}")
+    _C.check_shape("t", t, M, R)
+    _C.check_shape("b", b, N, R)
+    if group_size is None:
+        _check_vec("scale_weight", scale_weight, N, (torch.float32,))
+        _check_vec("zp", zp, N, (torch.float32,))
+    else:
+        _check_group_params(K, N, group_size, scale_weight, zp)
+    return _launch16("wanq_gemm_wq16_lowrank", (_C.ptr(input), _C.ptr(codes), _C.dt(input), 4 if w4 else 8, _C.ptr(scale_weight),
+                                                _C.ptr(zp), int(group_size or 0), _C.ptr(t), _C.ptr(b), int(R)),
+                     (input, codes, scale_weight, zp, t, b), bias, out_dtype or input.dtype, gelu, gate, residual, out, M, N, K)
+
+
+def wq16_lowrank_refusal(M, N, K, group_size, R):
+    """Why wanq_gemm_wq16_lowrank would refuse an [M, K] x [N, K] product with a rank-R branch (None = accepted): the rules of
+    `wq16_linear_refusal` (group_size None or 0: the per-channel form), then R; see `fp_linear_refusal`."""
+    why = wq16_linear_refusal(M, N, K, group_size or None)
+    if why is not None:
+        return why
+    if not isinstance(R, int) or R < 64 or R > LOWRANK_MAX or R % 64:
+        return f"R={R} must be 64, 128, 192 or 256"
+    return None
+
+
 # ---- group-wise weight scales on the int8 matrix cores ---------------------------------------------------------------
 def w8a8_grouped_linear(input_i8, codes, scale_input, scale_weight, zp, group_size, bias=None, out_dtype=None, gelu=False, gate=None,
                         residual=None, out=None, w4=False):

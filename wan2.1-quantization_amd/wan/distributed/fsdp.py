@@ -4,7 +4,8 @@ Reference: shard_model() wraps every WanAttentionBlock in torch FSDP with FULL_S
 parameters and all-gathers a block's parameters right before its forward (ViDiT-Q/examples/Wan2.1/wan/distributed/fsdp.py:
 10-32, applied at wan/text2video.py:106-107).  Here the sharded state is the kernel-mode blocks' INTEGER weights -- int8 codes,
 or packed 4-bit nibbles, the only large tensors left after quantisation (scales, zero points, biases and norm weights are a
-few KB per layer and stay replicated):
+few KB per layer and stay replicated; so do the 16-bit low-rank factors of a weight-only Linear with `weight.low_rank`,
+(N + K) R 2 bytes against the N K / 2 of its 4-bit weight -- R = 64 of a 1536 x 1536 layer: a third of it):
 
   * every block's weight tensors are flattened into one byte string with a fixed layout (all blocks have the same shapes),
     padded to a multiple of P, and each rank keeps its 1/P slice (`shard`);

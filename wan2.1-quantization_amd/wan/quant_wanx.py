@@ -54,6 +54,9 @@ class QuantWanModel(WanModel, QuantModel):
         """Integer state dict of every quantized Linear (reference quant_wanx.py:137-185): `<name>.weight` int8,
         `<name>.scale_weight`, `<name>.zp_weight`, `<name>.bias`; fp_module / fp_weight entries are dropped; ViDiT /
         SmoothQuant / QuaRot layers also carry `<name>.act_premul` (= channel_mask * rotation signs).
+        A weight-only layer with `weight.low_rank` also carries `<name>.lr_a` [Rp, K] and `<name>.lr_b` [N, Rp], its LoRC factors
+        in fp32 (qdiff/base/low_rank.py); the loader takes them when the kernel-mode layer has the buffers and raises KeyError when
+        they are missing, or present without a buffer.  reference_format=True refuses such a layer by name.
 
         reference_format=False (default): parameters fp32 -- the precision the simulation path computes with.
         reference_format=True: byte-for-byte what the reference's `int_weight.pt` holds, so that its loader
@@ -77,6 +80,9 @@ class QuantWanModel(WanModel, QuantModel):
                     if mod.fp8 or mod.mx:
                         raise NotImplementedError(f"{name}: the reference's int_weight.pt format holds int8 codes (the layer is "
                                                   f"format: {mod.mx or 'fp8_e4m3'}; save with reference_format=False)")
+                    if mod.low_rank is not None or mod._adapter is not None:
+                        raise NotImplementedError(f"{name}: the reference's int_weight.pt format has no low-rank branch "
+                                                  "(weight.low_rank / set_low_rank; save with reference_format=False)")
                     if mod.group_size is not None:
                         raise NotImplementedError(f"{name}: the reference's int_weight.pt format has one scale per output channel "
                                                   "(weight.group_size is set; save with reference_format=False)")
@@ -104,6 +110,9 @@ class QuantWanModel(WanModel, QuantModel):
                                                    else wq.zero_point.reshape(-1).float().clone())
                     if mod.bias is not None:
                         sd[name + ".bias"] = mod.bias.detach().float().clone()
+                    if mod.low_rank is not None:  # the LoRC factors, fp32 [Rp, K] / [N, Rp] (an adapter is not part of the weights)
+                        sd[name + ".lr_a"] = mod.lr_a.detach().float().clone()
+                        sd[name + ".lr_b"] = mod.lr_b.detach().float().clone()
                 if premul is not None:
                     sd[name + ".act_premul"] = premul.clone()
                 skip.add(name)
@@ -196,8 +205,10 @@ class QuantWanModel(WanModel, QuantModel):
                     for buf, k, required in (("weight", "weight", True), ("scale_weight", "scale_weight", True),
                                              ("zp_weight", "zp_weight", lin.zp_weight is not None),
                                              ("bias", "bias", lin.bias is not None),
-                                             ("act_premul", "act_premul", lin.act_premul is not None)):
-                        dst = getattr(lin, buf)
+                                             ("act_premul", "act_premul", lin.act_premul is not None),
+                                             ("lr_a", "lr_a", getattr(lin, "lr_a", None) is not None),
+                                             ("lr_b", "lr_b", getattr(lin, "lr_b", None) is not None)):
+                        dst = getattr(lin, buf, None)
                         if f"{base}.{k}" not in sd:
                             if required:
                                 raise KeyError(f"{load_path}: missing {base}.{k}")

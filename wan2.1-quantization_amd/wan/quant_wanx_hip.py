@@ -15,6 +15,7 @@ WanSelfAttentionWithCudaKernel :331-474, WANT2VCrossAttentionWithCudaKernel :477
 import torch
 import torch.nn as nn
 
+from qdiff.base.low_rank import LowRankBranch, padded_rank
 from viditq_extension import fused, qgemm
 
 from . import ops
@@ -249,18 +250,25 @@ class HipLinearFp(_HipLinear):
         return _gelu_gate_residual(torch.nn.functional.linear(x, self.weight, self.bias), gelu, gate, residual)
 
 
-class HipLinearWq16(_HipLinearInt):
+class HipLinearWq16(LowRankBranch, _HipLinearInt):
     """A weight-only quantised Linear (a `weight:` section and no `act:` section: W8A16 / W4A16): HipLinearW8A8's integer codes,
     per-channel fp32 (delta, zero_point) and fp32 bias -- 4-bit codes stay packed, `zp_gemm` = zero_point - 8 -- against the
     block's 16-bit activations, through qgemm.wq16_linear (csrc/gemm_wq16.hip): the codes become MFMA fragments in registers,
     exactly, and delta is applied in the fp32 epilogue.  No activation transform and no activation quantiser.
     With a `group_size` (the config's `weight.group_size`, a multiple of 64 that divides in_features) the three parameter buffers are
     [K / group_size, N] and the product is qgemm.wq16_grouped_linear: one fp32 fma per group and element instead of one in all.
+    With a `low_rank` (the config's `weight.low_rank`) the optional buffers `lr_a` [Rp, K] / `lr_b` [N, Rp] hold the LoRC factors
+    in the activation dtype (qdiff/base/low_rank.py; Rp = low_rank rounded up to 64, zero padded), `set_low_rank` attaches a user
+    adapter behind them, and forward computes t = qgemm.fp_linear(x, A16) and calls qgemm.wq16_lowrank_linear: the branch is added
+    inside the GEMM, GELU and gate + residual stay fused.  Under --dit_fsdp `sharded` stays ("weight",): the factors are replicated,
+    (N + K) R 2 bytes against the N K / 2 of a 4-bit weight (R = 64 of a 1536 x 1536 layer: a third of it; of 8960 x 1536: a fifth).
     Counterpart of QuantizedLinear.forward with a_quantizer None (ViDiT-Q/quant_utils/qdiff/base/quant_layer.py:68-72)."""
     weight_only = True   # (its input is not quantised: the block's int8 producers and their prefetch skip it)
     act_premul = None
 
-    def __init__(self, in_features, out_features, bias=True, sym=False, w_bits=8, name="linear", group_size=None):
+    def __init__(self, in_features, out_features, bias=True, sym=False, w_bits=8, name="linear", group_size=None, low_rank=None,
+                 act_dtype=torch.bfloat16):
+        self.name = name
         if group_size is not None and (group_size < 64 or group_size % 64):
             raise NotImplementedError(f"{name}: weight.group_size={group_size} has no kernel-mode form: the group-wise weight-only GEMM "
                                       "takes groups that are multiples of 64 input channels (simulation mode runs any group size)")
@@ -268,10 +276,15 @@ class HipLinearWq16(_HipLinearInt):
         super().__init__(in_features, out_features, bias, sym, w_bits, None if why is not None else group_size)
         if why is not None:
             raise ValueError(f"{name}: the weight-only GEMM cannot take this layer ({out_features}, {in_features}): {why}")
+        self.low_rank = low_rank
+        rp = padded_rank(low_rank) if low_rank else 0
+        self.register_buffer("lr_a", torch.zeros(rp, in_features, dtype=act_dtype) if low_rank else None)
+        self.register_buffer("lr_b", torch.zeros(out_features, rp, dtype=act_dtype) if low_rank else None)
 
     @classmethod
-    def from_quantized(cls, ql, name="linear"):
-        """From a plain qdiff QuantizedLinear without an activation quantiser: same integer codes, same parameters."""
+    def from_quantized(cls, ql, name="linear", act_dtype=torch.bfloat16):
+        """From a plain qdiff QuantizedLinear without an activation quantiser: same integer codes, same parameters, and the same
+        low-rank factors (the LoRC buffers cast once to `act_dtype`, the adapter as attached)."""
         if ql.uses_mask or ql.uses_rotation:
             raise NotImplementedError(
                 f"{name}: a {type(ql).__name__} without an `act:` section has no kernel-mode form (its transform exists to "
@@ -280,7 +293,12 @@ class HipLinearWq16(_HipLinearInt):
         wq = ql.w_quantizer
         if wq.n_bits not in (4, 8):
             raise NotImplementedError(f"{name}: weight-only kernel mode stores 8-bit and packed 4-bit codes (n_bits={wq.n_bits})")
-        m = cls(ql.in_features, ql.out_features, ql.bias is not None, wq.sym, wq.n_bits, name, ql.group_size).to(ql.fp_module.weight.device)
+        m = cls(ql.in_features, ql.out_features, ql.bias is not None, wq.sym, wq.n_bits, name, ql.group_size, ql.low_rank,
+                act_dtype).to(ql.fp_module.weight.device)
+        if ql.low_rank is not None:
+            m.lr_a.copy_(ql.lr_a)
+            m.lr_b.copy_(ql.lr_b)
+        m._adapter = ql._adapter
         codes, sw, _, _ = ql.weight_only_operands()
         if tuple(codes.shape) != tuple(m.weight.shape) or codes.dtype != m.weight.dtype:
             raise ValueError(f"{name}: codes {tuple(codes.shape)} {codes.dtype} do not fit {tuple(m.weight.shape)} {m.weight.dtype}")
@@ -296,6 +314,11 @@ class HipLinearWq16(_HipLinearInt):
 
     def forward(self, x, out_dtype=None, gelu=False, gate=None, residual=None, out=None):
         """Reads `weight` as it is now (--dit_fsdp re-points it at views of the gathered buffer)."""
+        if self.low_rank is not None or self._adapter is not None:
+            a16, b16 = self.low_rank_operands(x.dtype, x.device)
+            return qgemm.wq16_lowrank_linear(x, self.weight, self.scale_weight, self.zp, self.group_size, qgemm.fp_linear(x, a16), b16,
+                                             self.bias, out_dtype, gelu=gelu, gate=gate, residual=residual, out=out,
+                                             w4=self.w_bits == 4)
         if self.group_size is not None:
             return qgemm.wq16_grouped_linear(x, self.weight, self.scale_weight, self.zp, self.group_size, self.bias, out_dtype,
                                              gelu=gelu, gate=gate, residual=residual, out=out, w4=self.w_bits == 4)
@@ -396,6 +419,8 @@ def _to_hip_linear(lin, n_bits, sym, act_dtype, fp_gemm="torch", name="linear"):
         cls = _HIP_LINEAR_OF.get(lin.kind)
         if cls is HipLinearWq16 and act_dtype not in (torch.bfloat16, torch.float16):
             raise ValueError(f"{name}: the weight-only GEMM takes bf16 or fp16 activations (act_dtype {act_dtype})")
+        if cls is HipLinearWq16:
+            return cls.from_quantized(lin, name, act_dtype)
         if cls is not None:
             return cls.from_quantized(lin, name)
         lin = lin.fp_module
