@@ -263,6 +263,28 @@ int wanq_row_minmax(const void* w, int w_dtype, float* row_min, float* row_max, 
 int wanq_weight_quant(const void* w, int w_dtype, const float* delta, const float* zp, int qmin, int qmax,
                       int8_t* q8, float* deq, int64_t rows, int cols, void* stream);
 
+/* The GPTQ weight solver (Frantar et al., 2022; qdiff/base/gptq.py drives it; csrc/gptq.hip): the grid of wanq_weight_quant is kept,
+ * only the choice of each code changes, so that the layer's output error on the calibration activations is minimised.
+ *   w      fp32 [N, K], row stride w_stride (elements): the working copy, updated in place
+ *   u      fp32 [K, K], row stride u_stride: the UPPER Cholesky factor of H^-1 (H = X^T X of the layer's calibration inputs)
+ *   delta, zp  fp32 [N, K / group_size] as StaticQuantizer holds them; group_size = 0: fp32 [N], one per row
+ *   qmin, qmax the range of the STORED codes (the quantiser's [-n-1, n] intersected with the bit-width's [-2^(b-1), 2^(b-1)-1],
+ *              SURVEY D9), so that the error pushed on is the error of what the checkpoint keeps
+ *   codes  int8 [N, K] (row stride K);  err  fp32 [N, cols] (row stride cols)
+ * wanq_gptq_block, for j = c0 .. c0+cols-1 in order (1 <= cols <= 128), every row on its own:
+ *   q = clamp(rne(w[j] / delta) - zp, qmin, qmax);  w_hat = (q + zp) delta;  codes[j] = q;  e = (w[j] - w_hat) / u[j,j];
+ *   err[n, j-c0] = e;  w[k] = w[k] - e u[j,k] for c0+cols > k > j;  w[j] = w_hat.
+ * wanq_gptq_propagate:  w[n, k] -= sum_{i < cols} err[n, i] u[c0+i, k]  for k >= c0+cols, the sum over i ascending from 0.
+ * Every operation is one fp32 IEEE operation, rounded once, never contracted into an fma (true divisions): a fixed function of
+ * the operands, bit-equal to the host model gptq_solve_host.  Columns before c0 are not touched.
+ * Refused before any launch (WANQ_E_ARG / WANQ_E_SHAPE, the message names the rule): NULL pointers, cols outside 1..128,
+ * c0 + cols > K, strides below K, a range that is not an int8 range, a group_size that does not divide K, an odd group_size or c0
+ * with a group_size (the kernel keeps two neighbouring columns per lane: a pair must lie in one group).  N = 0: WANQ_OK. */
+int wanq_gptq_block(float* w, int64_t w_stride, const float* u, int64_t u_stride, const float* delta, const float* zp,
+                    int group_size, int qmin, int qmax, int8_t* codes, float* err, int64_t N, int K, int c0, int cols, void* stream);
+int wanq_gptq_propagate(float* w, int64_t w_stride, const float* u, int64_t u_stride, const float* err,
+                        int64_t N, int K, int c0, int cols, void* stream);
+
 /* Reference-format int8 export of a weight matrix, all arithmetic in HALF precision as the reference does it:
  *   q8 = clamp( round( f16(w) / delta ) - zp, -128, 127 )   delta, zp: fp16 [rows]
  * Replaces quantize_and_save_weight_ (ViDiT-Q/examples/Wan2.1/wan/quant_wanx_cuda.py:39-53); bit-identical to it

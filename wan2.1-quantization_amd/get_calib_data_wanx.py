@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Calibration data collection -- entry point 2/4 (ViDiT-Q/examples/Wan2.1/get_calib_data_wanx.py): run the FP model
 with a forward hook on every nn.Linear that keeps the per-input-channel absmax (HIP reduction, running max on the
-device), and save {layer_name: [1, C_in]} to quant_config.calib_data.save_path."""
+device), and save {layer_name: [1, C_in]} to quant_config.calib_data.save_path.  With --hessian, or a `gptq:` section in the quant
+config, a second hook accumulates H = X^T X of the inputs (wan/calib.py GramHook) and {layer_name: fp32 [C_in, C_in]} is saved to
+calib_data.hessian_path (--hessian_path), for ptq_wanx.py's GPTQ solve."""
 import logging
 import os
 import sys
@@ -29,6 +31,15 @@ def main(args):
     t2v = WanT2V(cfg, args.ckpt_dir, device_id=local, rank=rank, plan=plan if sharded else None, context_file=args.context_file)
     hooks = calib.add_hooks(t2v.model, torch.nn.Linear)
     logging.info("hooked %d Linear layers", len(hooks))
+    # --hessian (implied by a `gptq:` section): H = X^T X of every Linear input the section names, for ptq_wanx.py's GPTQ solve
+    gptq = quant_config.get("gptq", None)
+    gram_hooks = None
+    if args.hessian or gptq is not None:
+        hessian_path = args.hessian_path or (quant_config.get("calib_data", None) or {}).get("hessian_path", None)
+        if hessian_path is None:
+            raise ValueError("--hessian needs a place to save to: --hessian_path, or calib_data.hessian_path in the quant config")
+        gram_hooks = calib.add_gram_hooks(t2v.model, "" if gptq is None else gptq.get("layer_name_regex", ""))
+        logging.info("collecting Hessians of %d Linear layers", len(gram_hooks))
     prompts = cli.read_prompts(args)
     if sharded:
         mine = prompts  # world = ulysses_size (x 2 with CFG parallelism): one group, every prompt
@@ -41,6 +52,13 @@ def main(args):
     os.makedirs(os.path.dirname(os.path.abspath(save_path)), exist_ok=True)
     data = calib.gather_and_save_activation(hooks, save_path)
     logging.info("saved calibration data of %d layers to %s", len(data), save_path)
+    if gram_hooks is not None:
+        os.makedirs(os.path.dirname(os.path.abspath(hessian_path)), exist_ok=True)
+        hs = calib.gather_and_save_hessians(gram_hooks, hessian_path)
+        distinct = {id(h): h for h in hs.values()}
+        logging.info("saved Hessians of %d layers (%d accumulators, %.1f MB, %d rows each at most) to %s", len(hs), len(distinct),
+                     sum(h.numel() * 4 for h in distinct.values()) / 1e6, max((h.acc.tokens for h in gram_hooks.values() if h.acc), default=0),
+                     hessian_path)
     return 0
 
 

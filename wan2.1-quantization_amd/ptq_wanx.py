@@ -10,6 +10,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch  # noqa: E402
 
 from qdiff import config as qcfg  # noqa: E402
+from qdiff.base import gptq  # noqa: E402
 from qdiff.base.quant_layer import QuantizedLinear  # noqa: E402
 from qdiff.utils import apply_func_to_submodules, seed_everything  # noqa: E402
 from wan import calib, cli  # noqa: E402
@@ -35,6 +36,14 @@ def main(args):
                                  if (m.uses_mask or m.uses_rotation) else None, full_name="", calib_data=calib_data)
     if quant_config.get("mixed_precision", None) is not None:
         model.bitwidth_refactor()
+    if quant_config.get("gptq", None) is not None:
+        # GPTQ (qdiff/base/gptq.py): the layers the section names get their codes from the solver, on the Hessians that
+        # get_calib_data_wanx.py --hessian saved; scales and zero points stay the round-to-nearest ones
+        hp = args.hessian_path or (quant_config.get("calib_data", None) or {}).get("hessian_path", None)
+        if hp is None:
+            raise ValueError("a `gptq:` section needs the Hessian file: --hessian_path, or calib_data.hessian_path in the quant config")
+        n = gptq.requantize_model_(model, quant_config, gptq.load_hessians(hp), hp)
+        logging.info("GPTQ: solved %d Linear layers on the Hessians of %s", n, hp)
     model.set_init_done()
     params = model.save_quant_param_dict()
     if rank == 0:

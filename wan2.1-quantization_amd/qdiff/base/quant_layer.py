@@ -19,6 +19,7 @@ from ..config import ListConfig
 from ..quarot import quarot_utils
 from .base_quantizer import (FP8_FORMAT, MX_BLOCK, MX_FORMATS, MXFP4_FORMAT, MXFP8_FORMAT, DynamicQuantizer, Fp8Quantizer, MxQuantizer,
                              StaticQuantizer, fp8_decode, mx_decode)
+from .gptq import BLOCK_MAX, gptq_prepare, gptq_section, gptq_solve
 from .low_rank import RANK_MAX, LowRankBranch, fit_low_rank, padded_rank
 from .mixed_precision_quantizer import MixedPrecisionDynamicQuantizer, MixedPrecisionStaticQuantizer
 
@@ -39,6 +40,7 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         self.fp8 = self._checked_format(quant_config, module_name)
         # (an MX layer's `weight.group_size: 32` names the format's own block: there is no integer group-wise path behind it)
         self.group_size = None if self.mx else self._checked_group_size(quant_config, module_name, fp_module.weight.device)
+        self.gptq = self._checked_gptq(quant_config, module_name)  # the `gptq:` section when it names this layer (gptq.py), or None
         self.w_quantizer = self.a_quantizer = None
         self.channel_mask = None
         self.rotation_signs = None
@@ -158,6 +160,35 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
             raise ValueError(f"{name}: weight.low_rank={r} makes a padded rank of {padded_rank(r)}, above the GEMM's {RANK_MAX}")
         return r
 
+    def _checked_gptq(self, quant_config, module_name):
+        """The config's `gptq:` section when its layer_name_regex matches this layer (None otherwise), or the refusal of what GPTQ has
+        no form for, before any weight is quantised: the message names the layer and the key.  GPTQ chooses integer codes on a
+        StaticQuantizer's grid for a plain QuantizedLinear."""
+        sec = gptq_section(quant_config, module_name)
+        if sec is None:
+            return None
+        name = module_name or type(self).__name__
+        wq = quant_config.get("weight", None)
+        if wq is None:
+            raise NotImplementedError(f"{name}: gptq needs a `weight:` section: it chooses the weight's integer codes")
+        if self.uses_mask or self.uses_rotation:
+            raise NotImplementedError(f"{name}: gptq with {type(self).__name__} is not supported: the SmoothQuant / QuaRot / ViDiT "
+                                      "layer classes re-derive their weight after a transform (leave the layer to the plain "
+                                      "QuantizedLinear)")
+        if wq.get("format", None) is not None:
+            raise NotImplementedError(f"{name}: gptq with weight.format={wq.get('format')!r} is not supported: GPTQ chooses integer "
+                                      "codes on a StaticQuantizer's grid")
+        if isinstance(wq["n_bits"], ListConfig):
+            raise NotImplementedError(f"{name}: gptq with a bit-width list (MixedPrecisionStaticQuantizer) is not supported")
+        damp, block = sec.get("damp", 0.01), sec.get("block", BLOCK_MAX)
+        if isinstance(damp, bool) or not isinstance(damp, (int, float)) or damp < 0:
+            raise ValueError(f"{name}: gptq.damp={damp!r} must be a non-negative number")
+        if isinstance(block, bool) or not isinstance(block, int) or not 1 <= block <= BLOCK_MAX:
+            raise ValueError(f"{name}: gptq.block={block!r} must be an integer in 1..{BLOCK_MAX}")
+        if self.group_size is not None and (self.group_size % 2 or block % 2):
+            raise ValueError(f"{name}: gptq with weight.group_size={self.group_size} needs an even group size and an even gptq.block")
+        return sec
+
     def _refuse_adapter(self):
         if self.w_quantizer is None or self.a_quantizer is not None or self.fp8 or self.mx or self.uses_mask or self.uses_rotation \
                 or not isinstance(self.w_quantizer, StaticQuantizer):
@@ -191,12 +222,13 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         return g
 
     # ---- weight side --------------------------------------------------------------------------------
-    def _requantize(self, w):
-        """weight.data <- fake-quant(w) and int_weight <- its integer codes, with the quantizer's current state.  With
+    def _requantize(self, w, precomputed=None):
+        """weight.data <- fake-quant(w) and int_weight <- its integer codes, with the quantizer's current state; `precomputed`: a
+        (codes, dequantised weight) pair chosen elsewhere on the quantiser's grid (GPTQ), taken instead of round-to-nearest.  With
         `weight.low_rank: r` the LoRC factors are fitted here too, wherever the codes are (re)derived: the best rank-r approximation
         of E = w - W_hat (low_rank.fit_low_rank: float64 SVD on the weight's device where this build has one, else on the host), kept
         as the fp32 buffers lr_a [Rp, K] / lr_b [N, Rp].  weight.data stays W_hat, without the branch."""
-        codes, deq = self.w_quantizer.codes_and_dequant(w.detach().float())
+        codes, deq = precomputed if precomputed is not None else self.w_quantizer.codes_and_dequant(w.detach().float())
         self.weight.data = deq
         self.int_weight = codes
         if self.low_rank is not None:
@@ -204,6 +236,39 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
             self.register_buffer("lr_a", a, persistent=False)  # (as `_codes`: saved by quantize_and_save_weight)
             self.register_buffer("lr_b", b, persistent=False)
             self._lr16 = None
+
+    def requantize_gptq_(self, H):
+        """Choose the layer's codes by GPTQ (qdiff/base/gptq.py) on its calibration Hessian H = X^T X (fp32 [K, K], from
+        get_calib_data_wanx.py --hessian).  Scales and zero points are derived from the original weight exactly as round-to-nearest
+        derives them (init_quant_params), so they are bit-equal to the round-to-nearest layer's; the codes and weight.data change,
+        and a `weight.low_rank` branch is fitted again, on GPTQ's residual.  In place; -> self."""
+        name = self.module_name or type(self).__name__
+        if self.gptq is None:
+            raise NotImplementedError(f"{name}: requantize_gptq_ needs a `gptq:` section whose layer_name_regex names the layer")
+        w = self.fp_module.weight.data.detach().float()
+        if tuple(H.shape) != (self.in_features, self.in_features):
+            raise ValueError(f"{name}: the Hessian is {tuple(H.shape)}, expected {(self.in_features, self.in_features)}")
+        self.w_quantizer.init_quant_params(w)
+        self.w_quantizer.init_done = True
+        U, w0 = gptq_prepare(H, w, float(self.gptq.get("damp", 0.01)))
+        codes, deq = gptq_solve(w0, U, self.w_quantizer, int(self.gptq.get("block", BLOCK_MAX)))
+        self._requantize(w, (codes, deq))
+        return self
+
+    def set_codes_(self, codes):
+        """Take integer codes chosen elsewhere on this layer's grid (a GPTQ checkpoint's `<name>.weight`: int8 [N, K], or the packed
+        nibbles of a 4-bit layer) instead of round-to-nearest ones: int_weight <- codes, weight.data <- (codes + zero_point) * delta."""
+        name = self.module_name or type(self).__name__
+        wq, N, K = self.w_quantizer, self.out_features, self.in_features
+        codes = codes.to(self.fp_module.weight.device)
+        if codes.dtype == torch.uint8:
+            codes = qgemm.unpack_w4(codes.contiguous(), bias=8)
+        if codes.dtype != torch.int8 or tuple(codes.shape) != (N, K):
+            raise ValueError(f"{name}: codes are {tuple(codes.shape)} {codes.dtype}, expected {(N, K)} int8 (or packed nibbles)")
+        G = wq.delta.numel() // N
+        deq = ((codes.float().view(N, G, -1) + wq.zero_point.float().view(N, G, 1)) * wq.delta.float().view(N, G, 1)).view(N, K)
+        self._requantize(self.fp_module.weight.data, (codes, deq))
+        return self
 
     @property
     def packed_w4(self):

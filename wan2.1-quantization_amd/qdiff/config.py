@@ -16,7 +16,12 @@ another group size and the SmoothQuant / QuaRot / ViDiT layer classes are refuse
 `weight.low_rank: r` (a positive int, r <= min(N, K), at most 256 after padding to a multiple of 64): the best rank-r approximation
 of the quantisation error W - W_hat is kept in 16 bits beside the integer codes and added inside the weight-only GEMM
 (qdiff/base/low_rank.py, wanq_gemm_wq16_lowrank).  For a weight-only integer config only, per channel or with `group_size`: with an
-`act:` section, a `format:`, a bit-width list or a SmoothQuant / QuaRot / ViDiT layer class it is refused by layer name."""
+`act:` section, a `format:`, a bit-width list or a SmoothQuant / QuaRot / ViDiT layer class it is refused by layer name.
+`gptq: {layer_name_regex: ..., damp: 0.01, block: 128}`, a top-level section in the style of `viditq:` / `smooth_quant:`: the layers
+the regex names get their integer codes from the GPTQ solver (qdiff/base/gptq.py) on the Hessians under `calib_data.hessian_path`
+instead of round-to-nearest; scales, zero points and everything downstream stay.  `damp` (relative to the mean of the Hessian's
+diagonal) and `block` (columns per solver launch, at most 128; even with a `weight.group_size`) default to GPTQ's published values.
+Refused by layer name: a SmoothQuant / QuaRot / ViDiT layer class, a `weight.format`, a bit-width list."""
 import yaml
 
 

@@ -11,6 +11,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch  # noqa: E402
 
 from qdiff import config as qcfg  # noqa: E402
+from qdiff.base import gptq  # noqa: E402
 from qdiff.utils import seed_everything  # noqa: E402
 from wan import cli  # noqa: E402
 from wan.configs import SIZE_CONFIGS  # noqa: E402
@@ -34,6 +35,12 @@ def main(args):
     model.load_quant_param_dict(params)
     if quant_config.get("mixed_precision", None) is not None:
         model.bitwidth_refactor()
+    if quant_config.get("gptq", None) is not None:
+        # a GPTQ checkpoint: the simulation-mode layers above re-derived round-to-nearest codes from the FP weight; the layers the
+        # section names take the solver's codes from the integer checkpoint instead (kernel mode loads that file below anyway)
+        iw = os.path.join(args.output_dir, "checkpoint", "int_weight.pt")
+        n = gptq.load_codes_(model, torch.load(iw, map_location="cpu", weights_only=True), iw)
+        logging.info("GPTQ: took the codes of %d Linear layers from %s", n, iw)
     model.set_init_done()
     if args.hardware:
         iw = os.path.join(args.output_dir, "checkpoint", "int_weight.pt")

@@ -301,6 +301,79 @@ def weight_quant(w, delta, zero_point, qmin, qmax, want_int8=True, want_dequant=
     return q8, dq
 
 
+def gram_accumulate_(H, x):
+    """H += x^T x in fp32, in place: the Hessian of a Linear's calibration inputs (GPTQ, qdiff/base/gptq.py).  H: fp32 [C, C] on the
+    GPU, C a multiple of 8; x: [rows, C] (or [..., C]) bf16 / fp16 -- an fp32 x is ROUNDED TO bf16 first, so its products are those of
+    the rounded values (accumulated in fp32).  One launch of wanq_gemm_bf16: x^T, a contiguous [C, rows] copy with the rows zero
+    padded to a multiple of 32, is both operands, the output is fp32 and the epilogue's residual + y * gate (gate = 1) adds into H.
+    The GEMM's summation order depends on K (= rows) alone, so the result is deterministic and H stays symmetric bit for bit."""
+    _C.check_gpu("H", H)
+    _C.check_contig("H", H)
+    _C.check_dtype("H", H, torch.float32)
+    rows, cols = _rows_cols("x", x)
+    _C.check_shape("H", H, cols, cols)
+    _C.check_same_device(H, x)
+    if cols % 8:
+        raise RuntimeError(f"gram_accumulate_: C={cols} must be a multiple of 8")
+    if rows == 0:
+        return H
+    x2 = x.reshape(rows, cols)
+    if x2.dtype == torch.float32:
+        x2 = x2.to(torch.bfloat16)
+    pad = (rows + 31) // 32 * 32
+    xt = torch.zeros(cols, pad, dtype=x2.dtype, device=x.device)
+    xt[:, :rows] = x2.t()
+    gate = torch.ones(cols, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _C.call("wanq_gemm_bf16", _C.ptr(xt), _C.ptr(xt), _C.dt(xt), _C.ptr(H), _C.F32, None, _C.F32, _C.ptr(gate), _C.ptr(H),
+                _C.EPI_GATE_RES, cols, cols, pad, _C.stream())
+    return H
+
+
+def _check_gptq(w, u, err, c0, cols):
+    for n, t in (("w", w), ("u", u), ("err", err)):
+        _C.check_gpu(n, t)
+        _C.check_dtype(n, t, torch.float32)
+        if t.dim() != 2 or t.stride(1) != 1:
+            raise RuntimeError(f"Tensor {n} must be a matrix with unit column stride")
+    N, K = w.shape
+    _C.check_shape("u", u, K, K)
+    _C.check_contig("err", err)
+    _C.check_shape("err", err, N, cols)
+    return N, K
+
+
+def gptq_block_(w, u, delta, zp, group_size, qmin, qmax, codes, err, c0, cols):
+    """One block of GPTQ columns in place (wanq_gptq_block): columns c0 .. c0+cols-1 of the fp32 working copy w [N, K] are quantised
+    in order on the grid delta / zp (fp32 [N, K / group_size]; group_size None or 0: [N]), each column's error scaled by u (the
+    upper Cholesky factor of H^-1, fp32 [K, K]) and pushed onto the later columns of the block; codes int8 [N, K] and err fp32
+    [N, cols] receive the codes and the scaled errors."""
+    N, K = _check_gptq(w, u, err, c0, cols)
+    g = int(group_size or 0)
+    for n, t in (("delta", delta), ("zp", zp)):
+        _C.check_gpu(n, t)
+        _C.check_dtype(n, t, torch.float32)
+        _C.check_contig(n, t)
+        if t.numel() != N * (K // g if g else 1):
+            raise RuntimeError(f"Tensor {n} must hold {N} x {K // g if g else 1} values, got {tuple(t.shape)}")
+    _C.check_gpu("codes", codes)
+    _C.check_dtype("codes", codes, torch.int8)
+    _C.check_contig("codes", codes)
+    _C.check_shape("codes", codes, N, K)
+    _C.check_same_device(w, u, delta, zp, codes, err)
+    with torch.cuda.device(w.device):
+        _C.call("wanq_gptq_block", _C.ptr(w), w.stride(0), _C.ptr(u), u.stride(0), _C.ptr(delta), _C.ptr(zp), g, int(qmin), int(qmax),
+                _C.ptr(codes), _C.ptr(err), N, K, int(c0), int(cols), _C.stream())
+
+
+def gptq_propagate_(w, u, err, c0, cols):
+    """w[:, k] -= sum_i err[:, i] u[c0 + i, k] for every column k >= c0 + cols, in place (wanq_gptq_propagate), i ascending."""
+    N, K = _check_gptq(w, u, err, c0, cols)
+    _C.check_same_device(w, u, err)
+    with torch.cuda.device(w.device):
+        _C.call("wanq_gptq_propagate", _C.ptr(w), w.stride(0), _C.ptr(u), u.stride(0), _C.ptr(err), N, K, int(c0), int(cols), _C.stream())
+
+
 def weight_export_f16(w, delta_f16, zp_f16):
     """int8 codes of `w` by the reference's half-precision export equation (quantize_and_save_weight_,
     ViDiT-Q/examples/Wan2.1/wan/quant_wanx_cuda.py:39-53): clamp(round(f16(w) / delta) - zp, -128, 127)."""

@@ -54,6 +54,9 @@ def build_parser(description, quant=False):
         p.add_argument("--quant_config", type=str, default=None, help="Quant config file name.")
         p.add_argument("--calib_data", type=str, default=None, help="overrides quant_config.calib_data.save_path")
         p.add_argument("--quant_params", type=str, default=None, help="checkpoint/quant_params.pth")
+        p.add_argument("--hessian", action="store_true", default=False,
+                       help="calibration: also collect H = X^T X of the Linear inputs (implied by a `gptq:` section in the quant config)")
+        p.add_argument("--hessian_path", type=str, default=None, help="overrides quant_config.calib_data.hessian_path")
         p.add_argument("--hardware", type=str2bool, default=True, help="kernel mode (if_hardware, quant_generate.py:372)")
         p.add_argument("--fp_gemm", type=str, default="torch", choices=["torch", "hip"],
                        help="kernel mode: GEMM of the Linears the quant config keeps floating point (hip = csrc/gemm_bf16.hip, fused epilogues)")

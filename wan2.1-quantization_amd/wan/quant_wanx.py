@@ -83,6 +83,10 @@ class QuantWanModel(WanModel, QuantModel):
                     if mod.low_rank is not None or mod._adapter is not None:
                         raise NotImplementedError(f"{name}: the reference's int_weight.pt format has no low-rank branch "
                                                   "(weight.low_rank / set_low_rank; save with reference_format=False)")
+                    if mod.gptq is not None:
+                        raise NotImplementedError(f"{name}: the reference's int_weight.pt format derives its codes from the FP weight "
+                                                  "by the reference's own half-precision equation; a `gptq:` layer's codes come "
+                                                  "from the solver (save with reference_format=False)")
                     if mod.group_size is not None:
                         raise NotImplementedError(f"{name}: the reference's int_weight.pt format has one scale per output channel "
                                                   "(weight.group_size is set; save with reference_format=False)")
