@@ -285,6 +285,31 @@ int wanq_gptq_block(float* w, int64_t w_stride, const float* u, int64_t u_stride
 int wanq_gptq_propagate(float* w, int64_t w_stride, const float* u, int64_t u_stride, const float* err,
                         int64_t N, int K, int c0, int cols, void* stream);
 
+/* wanq_gptq_block with a group per COLUMN (gptq.act_order: the solver visits the input channels in order of descending diag H, so
+ * the columns of w / u are a permutation of the channels and neighbouring columns lie in arbitrary groups):
+ *   delta, zp  fp32 [N, G] (row stride G);  g_idx  int32 [K] in device memory: column j is quantised on delta[n, g_idx[j]],
+ *              zp[n, g_idx[j]].  The kernel clamps every index into 0 .. G-1, so a bad map never reads outside delta / zp.
+ * Every other operand, the steps and their arithmetic are wanq_gptq_block's, operation for operation (one fp32 IEEE operation each,
+ * no fma, true divisions, the error pushed on in ascending column order): with g_idx[j] = j / group_size the two entries agree bit
+ * for bit, and both are bit-equal to the host model gptq_block_host on the same map.  There is no evenness rule on c0 or on the
+ * groups.  wanq_gptq_propagate does not depend on groups and serves both.
+ * Refused before any launch (WANQ_E_ARG / WANQ_E_SHAPE, the message names the rule): NULL pointers (g_idx among them), G < 1,
+ * cols outside 1..128, c0 + cols > K, strides below K, a range that is not an int8 range.  N = 0: WANQ_OK. */
+int wanq_gptq_block_gidx(float* w, int64_t w_stride, const float* u, int64_t u_stride, const float* delta, const float* zp,
+                         const int32_t* g_idx, int G, int qmin, int qmax, int8_t* codes, float* err, int64_t N, int K, int c0,
+                         int cols, void* stream);
+
+/* H += x^T x in fp32, in place: the Hessian of a Linear's calibration inputs (csrc/gram.hip).
+ *   x  row-major [rows, C], WANQ_BF16 or WANQ_F16, read as it lies (no transposed copy);  H  fp32 [C, C], row stride C.
+ * The contraction runs over the rows on v_mfma_f32_16x16x32_{bf16,f16}, 32 rows a step from row 0 upwards; rows past `rows` in the
+ * last step enter as exact zeros.  Only the 128 x 128 tile pairs (ti <= tj) are computed: an element's sum s is added to H[i, j]
+ * and, off the diagonal, the same s to H[j, i] (inside a diagonal tile only i <= j is taken), so a symmetric H stays symmetric
+ * bit for bit by construction.  The summation order of an element depends on `rows` alone: not on C, on the element's place or on
+ * where x lies.
+ * Refused before any launch: NULL x or H, x_dtype other than bf16 / fp16, rows < 0, C < 8 or C % 8 != 0, x or H not 16-byte
+ * aligned.  rows == 0: WANQ_OK, H untouched. */
+int wanq_gram_accumulate(const void* x, int x_dtype, float* H, int64_t rows, int C, void* stream);
+
 /* Reference-format int8 export of a weight matrix, all arithmetic in HALF precision as the reference does it:
  *   q8 = clamp( round( f16(w) / delta ) - zp, -128, 127 )   delta, zp: fp16 [rows]
  * Replaces quantize_and_save_weight_ (ViDiT-Q/examples/Wan2.1/wan/quant_wanx_cuda.py:39-53); bit-identical to it

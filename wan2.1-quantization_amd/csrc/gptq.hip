@@ -4,6 +4,8 @@
 // are quantised in order, and each column's error, scaled by the upper Cholesky factor u of H^-1, is pushed onto the columns
 // that are still free.  Two entries carry the loop of qdiff/base/gptq.py:
 //   wanq_gptq_block      columns c0 .. c0+cols-1 (cols <= 128), one after the other, the update kept inside the block;
+//   wanq_gptq_block_gidx the same block with a group per COLUMN (g_idx; act_order: the columns are a permutation of the input
+//                        channels, so neighbours lie in arbitrary groups);
 //   wanq_gptq_propagate  the block's errors applied to every column behind it, w[:, k] -= err . u[c0 .. c0+cols, k].
 //
 // Arithmetic.  Every operation is a single fp32 IEEE operation, rounded once and never contracted (the file is compiled with fp
@@ -18,6 +20,10 @@
 // plus a broadcast read of the diagonal, at LDS latency, and the image is fetched from L2 once per eight rows; the cached form
 // would send every wave through the vector memory path for the same 64 KiB (512 B per step) at several times the latency per
 // step.  Two workgroups fit a CU's 160 KiB.  Rows are independent: no atomics, no traffic between waves after the fill.
+//
+// wanq_gptq_block_gidx is the same kernel with a (delta, zero point) pair for each of a lane's two columns, fetched through the
+// column's entry of g_idx (clamped into 0 .. G-1): step j reads the pair of its own column, so no pair of columns has to share a
+// group and c0 may be odd.  The steps themselves are shared, operation for operation.
 #include "wanq_common.h"
 
 // no a * b + c of this file becomes an fma (hipcc contracts by default, and the __fmul_rn / __fadd_rn spellings do not stop it:
@@ -47,10 +53,12 @@ __device__ __forceinline__ float lane_read(float v, int lane) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
 
+// GIDX: the group of a column is its entry of g_idx (group_size unused); else the group of column k is k / group_size (0: one per row)
+template <bool GIDX>
 __global__ __launch_bounds__(GPTQ_WAVES * 64) void gptq_block_kernel(float* w, int64_t w_stride, const float* u, int64_t u_stride,
-                                                                      const float* delta, const float* zp, int group_size,
-                                                                      int groups, float qmin, float qmax, int8_t* codes,
-                                                                      float* err, int64_t N, int K, int c0, int cols) {
+                                                                      const float* delta, const float* zp, const int32_t* g_idx,
+                                                                      int group_size, int groups, float qmin, float qmax,
+                                                                      int8_t* codes, float* err, int64_t N, int K, int c0, int cols) {
   __shared__ float us[GPTQ_COLS * GPTQ_COLS];
   // the image: us[j][k] = u[c0 + j, c0 + k] for j, k < cols, zero elsewhere (a column past the block is never moved)
   for (int idx = threadIdx.x; idx < GPTQ_COLS * GPTQ_COLS; idx += GPTQ_WAVES * 64) {
@@ -65,15 +73,23 @@ __global__ __launch_bounds__(GPTQ_WAVES * 64) void gptq_block_kernel(float* w, i
   const bool v0 = l0 < cols, v1 = l1 < cols;
   float* wr = w + row * w_stride + c0;
   float x0 = v0 ? wr[l0] : 0.f, x1 = v1 ? wr[l1] : 0.f;
-  // both columns of a lane lie in one group (checked on the host); a lane without columns reads the block's first group
-  const int64_t p = row * groups + (group_size ? (c0 + (v0 ? l0 : 0)) / group_size : 0);
-  const float d = delta[p], z = zp[p];
+  float d0, z0, d1, z1;  // the grid of the lane's first and of its second column
+  if constexpr (GIDX) {
+    // a column's group is its entry of the map, clamped into 0 .. groups-1 (a bad map still reads inside delta / zp); a lane
+    // without a column reads the block's first column's
+    const int g0 = min(max(g_idx[c0 + (v0 ? l0 : 0)], 0), groups - 1), g1 = min(max(g_idx[c0 + (v1 ? l1 : 0)], 0), groups - 1);
+    d0 = delta[row * groups + g0], z0 = zp[row * groups + g0];
+    d1 = delta[row * groups + g1], z1 = zp[row * groups + g1];
+  } else {
+    // both columns of a lane lie in one group (checked on the host); a lane without columns reads the block's first group
+    const int64_t p = row * groups + (group_size ? (c0 + (v0 ? l0 : 0)) / group_size : 0);
+    d1 = d0 = delta[p], z1 = z0 = zp[p];
+  }
   float q0 = 0.f, q1 = 0.f, e0 = 0.f, e1 = 0.f;
   for (int jp = 0; 2 * jp < cols; ++jp) {
-    const float dj = lane_read(d, jp), zj = lane_read(z, jp);
     {  // column j = 2 jp: lane jp's first
       const int j = 2 * jp;
-      const GptqStep s = gptq_step(lane_read(x0, jp), dj, zj, qmin, qmax, us[j * GPTQ_COLS + j]);
+      const GptqStep s = gptq_step(lane_read(x0, jp), lane_read(d0, jp), lane_read(z0, jp), qmin, qmax, us[j * GPTQ_COLS + j]);
       const float2 ur = *reinterpret_cast<const float2*>(&us[j * GPTQ_COLS + l0]);
       if (lane > jp) x0 = x0 - s.e * ur.x;
       if (lane >= jp) x1 = x1 - s.e * ur.y;
@@ -85,7 +101,7 @@ __global__ __launch_bounds__(GPTQ_WAVES * 64) void gptq_block_kernel(float* w, i
     }
     if (2 * jp + 1 < cols) {  // column j = 2 jp + 1: lane jp's second
       const int j = 2 * jp + 1;
-      const GptqStep s = gptq_step(lane_read(x1, jp), dj, zj, qmin, qmax, us[j * GPTQ_COLS + j]);
+      const GptqStep s = gptq_step(lane_read(x1, jp), lane_read(d1, jp), lane_read(z1, jp), qmin, qmax, us[j * GPTQ_COLS + j]);
       const float2 ur = *reinterpret_cast<const float2*>(&us[j * GPTQ_COLS + l0]);
       if (lane > jp) {
         x0 = x0 - s.e * ur.x;
@@ -193,8 +209,23 @@ extern "C" int wanq_gptq_block(float* w, int64_t w_stride, const float* u, int64
   }
   if (N == 0) return WANQ_OK;
   const int groups = group_size ? K / group_size : 1;
-  gptq_block_kernel<<<dim3((unsigned)((N + GPTQ_WAVES - 1) / GPTQ_WAVES)), dim3(GPTQ_WAVES * 64), 0, (hipStream_t)stream>>>(
-      w, w_stride, u, u_stride, delta, zp, group_size, groups, (float)qmin, (float)qmax, codes, err, N, K, c0, cols);
+  gptq_block_kernel<false><<<dim3((unsigned)((N + GPTQ_WAVES - 1) / GPTQ_WAVES)), dim3(GPTQ_WAVES * 64), 0, (hipStream_t)stream>>>(
+      w, w_stride, u, u_stride, delta, zp, nullptr, group_size, groups, (float)qmin, (float)qmax, codes, err, N, K, c0, cols);
+  return check_launch(what);
+}
+
+extern "C" int wanq_gptq_block_gidx(float* w, int64_t w_stride, const float* u, int64_t u_stride, const float* delta, const float* zp,
+                                    const int32_t* g_idx, int G, int qmin, int qmax, int8_t* codes, float* err, int64_t N, int K,
+                                    int c0, int cols, void* stream) {
+  const char* what = "wanq_gptq_block_gidx";
+  WANQ_REQUIRE(delta && zp && codes && g_idx, WANQ_E_ARG, "%s: delta, zp, codes and g_idx must be non-NULL", what);
+  if (const int rc = check_gptq_common(what, w, w_stride, u, u_stride, err, N, K, c0, cols)) return rc;
+  WANQ_REQUIRE(qmin >= -128 && qmax <= 127 && qmin <= qmax, WANQ_E_ARG, "%s: qmin=%d, qmax=%d must be an int8 range", what, qmin,
+               qmax);
+  WANQ_REQUIRE(G >= 1, WANQ_E_SHAPE, "%s: G=%d must be at least 1 (the groups of a row of delta / zp)", what, G);
+  if (N == 0) return WANQ_OK;
+  gptq_block_kernel<true><<<dim3((unsigned)((N + GPTQ_WAVES - 1) / GPTQ_WAVES)), dim3(GPTQ_WAVES * 64), 0, (hipStream_t)stream>>>(
+      w, w_stride, u, u_stride, delta, zp, g_idx, 0, G, (float)qmin, (float)qmax, codes, err, N, K, c0, cols);
   return check_launch(what);
 }
 

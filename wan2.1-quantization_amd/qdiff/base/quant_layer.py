@@ -185,7 +185,11 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
             raise ValueError(f"{name}: gptq.damp={damp!r} must be a non-negative number")
         if isinstance(block, bool) or not isinstance(block, int) or not 1 <= block <= BLOCK_MAX:
             raise ValueError(f"{name}: gptq.block={block!r} must be an integer in 1..{BLOCK_MAX}")
-        if self.group_size is not None and (self.group_size % 2 or block % 2):
+        act_order = sec.get("act_order", False)
+        if not isinstance(act_order, bool):
+            raise ValueError(f"{name}: gptq.act_order={act_order!r} must be True or False")
+        # (act_order solves on wanq_gptq_block_gidx, which keeps a grid per column: no pair of columns has to share a group)
+        if not act_order and self.group_size is not None and (self.group_size % 2 or block % 2):
             raise ValueError(f"{name}: gptq with weight.group_size={self.group_size} needs an even group size and an even gptq.block")
         return sec
 
@@ -250,8 +254,13 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
             raise ValueError(f"{name}: the Hessian is {tuple(H.shape)}, expected {(self.in_features, self.in_features)}")
         self.w_quantizer.init_quant_params(w)
         self.w_quantizer.init_done = True
-        U, w0 = gptq_prepare(H, w, float(self.gptq.get("damp", 0.01)))
-        codes, deq = gptq_solve(w0, U, self.w_quantizer, int(self.gptq.get("block", BLOCK_MAX)))
+        damp, block = float(self.gptq.get("damp", 0.01)), int(self.gptq.get("block", BLOCK_MAX))
+        if self.gptq.get("act_order", False):  # channels in order of descending diag H; codes and deq come back in the original order
+            U, w0, perm = gptq_prepare(H, w, damp, act_order=True)
+            codes, deq = gptq_solve(w0, U, self.w_quantizer, block, act_order=True, perm=perm)
+        else:
+            U, w0 = gptq_prepare(H, w, damp)
+            codes, deq = gptq_solve(w0, U, self.w_quantizer, block)
         self._requantize(w, (codes, deq))
         return self
 

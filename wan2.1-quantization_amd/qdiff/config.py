@@ -21,6 +21,8 @@ of the quantisation error W - W_hat is kept in 16 bits beside the integer codes 
 the regex names get their integer codes from the GPTQ solver (qdiff/base/gptq.py) on the Hessians under `calib_data.hessian_path`
 instead of round-to-nearest; scales, zero points and everything downstream stay.  `damp` (relative to the mean of the Hessian's
 diagonal) and `block` (columns per solver launch, at most 128; even with a `weight.group_size`) default to GPTQ's published values.
+`act_order: True` (default False) solves the input channels in order of descending diag H on the same static groups; nothing
+downstream changes, and `block` / `weight.group_size` need not be even then.
 Refused by layer name: a SmoothQuant / QuaRot / ViDiT layer class, a `weight.format`, a bit-width list."""
 import yaml
 

@@ -69,6 +69,8 @@ PROTOTYPES = {
     "wanq_weight_export_f16": [_vp, _i, _vp, _vp, _vp, _i64, _i, _vp],
     "wanq_gptq_block": [_vp, _i64, _vp, _i64, _vp, _vp, _i, _i, _i, _vp, _vp, _i64, _i, _i, _i, _vp],
     "wanq_gptq_propagate": [_vp, _i64, _vp, _i64, _vp, _i64, _i, _i, _i, _vp],
+    "wanq_gptq_block_gidx": [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i64, _i, _i, _i, _vp],
+    "wanq_gram_accumulate": [_vp, _i, _vp, _i64, _i, _vp],
     "wanq_rmsnorm_rope": [_vp, _i, _vp, _vp, _vp, _i, _i64, _i, _i, _i64, _i64, _f, _vp],
     "wanq_fake_quant_cols": [_vp, _i, _vp, _vp, _i, _i, _i64, _i, _vp],
     "wanq_fake_quant_with_delta": [_vp, _i, _vp, _vp, _vp, _i, _i, _i64, _vp],

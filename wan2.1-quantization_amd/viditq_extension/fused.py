@@ -330,6 +330,32 @@ def gram_accumulate_(H, x):
     return H
 
 
+def gram_accumulate_onepass_(H, x):
+    """gram_accumulate_ in one pass over x as it lies (wanq_gram_accumulate, csrc/gram.hip): no transposed copy, and only the tile
+    pairs on and above the diagonal are multiplied, each sum added to H[i, j] and to H[j, i].  The same arguments and rules: H fp32
+    [C, C] on the GPU, C a multiple of 8; x [rows, C] (or [..., C]) bf16 / fp16, an fp32 x is ROUNDED TO bf16 first.  The summation
+    order of an element depends on the number of rows alone (it is not gram_accumulate_'s: the two agree to fp32 rounding, and
+    exactly where every partial sum is exact)."""
+    _C.check_gpu("H", H)
+    _C.check_contig("H", H)
+    _C.check_dtype("H", H, torch.float32)
+    rows, cols = _rows_cols("x", x)
+    _C.check_shape("H", H, cols, cols)
+    _C.check_same_device(H, x)
+    if cols % 8:
+        raise RuntimeError(f"gram_accumulate_onepass_: C={cols} must be a multiple of 8")
+    if rows == 0:
+        return H
+    x2 = x.reshape(rows, cols)
+    if x2.dtype == torch.float32:
+        x2 = x2.to(torch.bfloat16)
+    if x2.data_ptr() % 16:  # (a view that starts inside a 16-byte word: the kernel reads whole ones)
+        x2 = x2.clone()
+    with torch.cuda.device(x.device):
+        _C.call("wanq_gram_accumulate", _C.ptr(x2), _C.dt(x2), _C.ptr(H), rows, cols, _C.stream())
+    return H
+
+
 def _check_gptq(w, u, err, c0, cols):
     for n, t in (("w", w), ("u", u), ("err", err)):
         _C.check_gpu(n, t)
@@ -364,6 +390,31 @@ def gptq_block_(w, u, delta, zp, group_size, qmin, qmax, codes, err, c0, cols):
     with torch.cuda.device(w.device):
         _C.call("wanq_gptq_block", _C.ptr(w), w.stride(0), _C.ptr(u), u.stride(0), _C.ptr(delta), _C.ptr(zp), g, int(qmin), int(qmax),
                 _C.ptr(codes), _C.ptr(err), N, K, int(c0), int(cols), _C.stream())
+
+
+def gptq_block_gidx_(w, u, delta, zp, g_idx, qmin, qmax, codes, err, c0, cols):
+    """gptq_block_ with a group per column (wanq_gptq_block_gidx; gptq.act_order): delta / zp fp32 [N, G], g_idx int32 [K] on the
+    GPU, column j of w is quantised on delta[:, g_idx[j]] / zp[:, g_idx[j]] (an index outside 0..G-1 is clamped by the kernel).
+    No evenness rule on c0 or on the groups."""
+    N, K = _check_gptq(w, u, err, c0, cols)
+    for n, t in (("delta", delta), ("zp", zp)):
+        _C.check_gpu(n, t)
+        _C.check_dtype(n, t, torch.float32)
+        _C.check_contig(n, t)
+        if t.dim() != 2 or t.shape[0] != N or t.shape[1] < 1 or t.shape != delta.shape:
+            raise RuntimeError(f"Tensor {n} must be [{N}, G] with G >= 1 (delta and zp alike), got {tuple(t.shape)}")
+    _C.check_gpu("g_idx", g_idx)
+    _C.check_dtype("g_idx", g_idx, torch.int32)
+    _C.check_contig("g_idx", g_idx)
+    _C.check_shape("g_idx", g_idx, K)
+    _C.check_gpu("codes", codes)
+    _C.check_dtype("codes", codes, torch.int8)
+    _C.check_contig("codes", codes)
+    _C.check_shape("codes", codes, N, K)
+    _C.check_same_device(w, u, delta, zp, g_idx, codes, err)
+    with torch.cuda.device(w.device):
+        _C.call("wanq_gptq_block_gidx", _C.ptr(w), w.stride(0), _C.ptr(u), u.stride(0), _C.ptr(delta), _C.ptr(zp), _C.ptr(g_idx),
+                delta.shape[1], int(qmin), int(qmax), _C.ptr(codes), _C.ptr(err), N, K, int(c0), int(cols), _C.stream())
 
 
 def gptq_propagate_(w, u, err, c0, cols):

@@ -47,10 +47,18 @@ class GramAccumulator:
         c = x.shape[-1]
         x2 = x.reshape(-1, c)
         if x2.dtype not in (torch.float16, torch.bfloat16):
-            x2 = x2.to(torch.bfloat16)  # (fused.gram_accumulate_ rounds an fp32 input to bf16 itself; stated here for every other type)
+            x2 = x2.to(torch.bfloat16)  # (the kernel's wrapper rounds an fp32 input to bf16 itself; stated here for every other type)
         if self.H is None:
             self.H = torch.zeros(c, c, dtype=torch.float32, device=x.device)
-        fused.gram_accumulate_(self.H, x2.contiguous())
+        # The one-pass kernel (x as it lies, upper tile pairs only) launches T (T + 1) / 2 workgroups, T = ceil(C / 128).  Measured
+        # against the two-sided GEMM on a transposed copy (profiles/gptq.txt): 0.70x / 0.97x of its time at C = 8960 (2485
+        # workgroups; 32760 / 3120 rows), 1.5-1.6x at C = 1536 (78 workgroups leave most of the 256 CUs idle).  Nothing in between
+        # is measured; the switch is put where every CU gets a workgroup.
+        t = (c + 127) // 128
+        if t * (t + 1) // 2 >= torch.cuda.get_device_properties(x.device).multi_processor_count:
+            fused.gram_accumulate_onepass_(self.H, x2.contiguous())
+        else:
+            fused.gram_accumulate_(self.H, x2.contiguous())
         self.tokens += x2.shape[0]
 
 
