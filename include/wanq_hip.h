@@ -102,6 +102,17 @@ enum { WANQ_MX_E4M3 = 0, WANQ_MX_E2M1 = 1 };
 int wanq_quant_rows_mx(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int fmt, int act,
                        void* stream);
 
+/* wanq_quant_rows_mx behind a block Hadamard rotation: the same arguments and rules (both fmt values), and after the optional GELU and
+ * before the block maximum every block of 32 columns is replaced by its UNNORMALISED Sylvester-Hadamard transform x H, H[i][j] =
+ * (-1)^popcount(i & j).  Computed in fp32 by five butterfly stages in the order h = 1, 2, 4, 8, 16: for every pair (i, i + h) with bit
+ * h of i clear, (x_i, x_{i+h}) <- (x_i + x_{i+h}, x_i - x_{i+h}).  Additions and subtractions only, one rounding each, so the host
+ * restatement in the same order (mx_hadamard32_host, and mx_quant_rows_host(had32=True), qdiff/base/base_quantizer.py) is bit-equal.
+ * H is symmetric and H H = 32 I: a layer whose activations go through this entry quantises its weight as w / 32 through it too,
+ * (x H)(w H / 32)^T = x w^T, and the GEMM needs no inverse rotation (config `mx: {block_hadamard: True}`).
+ * No reference counterpart. */
+int wanq_quant_rows_mx_had32(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int fmt, int act,
+                             void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * LayerNorm (no bias, optional gamma) -> optional adaLN modulate -> fp output OR int8 quant (+sum).
  *   y = (x - mean) * rstd * gamma;  y = y * (1 + mscale[b]) + mshift[b]   (b = row / rows_per_batch)
@@ -583,6 +594,21 @@ int wanq_gemm_fp8(const uint8_t* a, const uint8_t* w, const float* sa, const flo
 int wanq_gemm_mx(const uint8_t* a, const uint8_t* w, const uint8_t* sa_u8, const uint8_t* sw_u8, int w_fmt, void* out, int out_dtype,
                  const void* bias, int bias_dtype, const float* gate, const void* residual, int epi_flags, int64_t M, int N, int K,
                  void* stream);
+
+/* W4A4 MX GEMM: MXFP4 (e2m1) activations against MXFP4 (e2m1) weights, both from wanq_quant_rows_mx (fmt WANQ_MX_E2M1) or both from
+ * wanq_quant_rows_mx_had32, on v_mfma_scale_f32_16x16x128_f8f6f4 with both operands 4 bits wide (the instruction's fp4 rate).
+ * Semantics, epilogue, shape rules and determinism statement are wanq_gemm_mx's, word for word:
+ *   acc[m,n] = sum_b 2^(sa[m,b] - 127) 2^(sw[n,b] - 127) sum_{k in block b} a[m,k] * w[n,k];  y = acc + bias[n];  GELU;
+ *   residual + y * gate;  one rounding to out_dtype.
+ * a: packed nibbles [M, K / 2], w: packed nibbles [N, K / 2], even k in the low nibble.  sa_u8 [M, K / 32], sw_u8 [N, K / 32]: E8M0
+ * bytes, 4-byte aligned.  Any M >= 1 (M == 0 returns WANQ_OK); N % 8 == 0; K % 128 == 0.  a, w, out and residual 16-byte aligned, gate
+ * and bias aligned to 4 elements.  Anything else is refused (WANQ_E_SHAPE / WANQ_E_ARG, the message names the rule).
+ * Determinism: one kernel form, no split-K; the summation order of element (m, n) depends on K only, so a row gives the same bits at
+ * any m and in a launch of any M, and repeated calls are bit-identical.
+ * No reference counterpart. */
+int wanq_gemm_mx4(const uint8_t* a, const uint8_t* w, const uint8_t* sa_u8, const uint8_t* sw_u8, void* out, int out_dtype,
+                  const void* bias, int bias_dtype, const float* gate, const void* residual, int epi_flags, int64_t M, int N, int K,
+                  void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Step-level elementwise work of the denoising loop in one kernel:  out[o] = sum_i coef[o][i] * in[i]  over fp32 tensors of

@@ -1,6 +1,7 @@
 // What the four tile GEMMs outside the int8 family share.  gemm_bf16.hip (bf16 / fp16 operands), gemm_fp8.hip (e4m3, fp32 row and
 // channel scales) and gemm_mx.hip (OCP MX: e4m3 tokens against e4m3 or packed e2m1 weights, E8M0 block scales) copy BOTH halves of
-// a K-tile into LDS and are one kernel, gemm_tile_kernel below, with a policy each; gemm_wq16.hip (integer weight codes converted
+// a K-tile into LDS and are one kernel, gemm_tile_kernel below, with a policy each (gemm_mx.hip's W4A4 form, packed e2m1 on both
+// sides, is one more policy of it); gemm_wq16.hip (integer weight codes converted
 // in registers, plain and group-wise) copies the token half only and has its own loop.  All four use the tile geometry, Frame, the
 // LDS-DMA sources and issue, the fragment addresses and reads, epilogue16, the launch parameters and helpers and the argument rules
 // of the extern "C" entries; gemm_tile_kernel is used by the first three.
@@ -14,7 +15,7 @@
 // bias / gate loads and the stores are 4-wide vectors.
 //
 // The two-sided loop (gemm_tile_kernel).  Token rows 0-127 and weight rows 128-255 of a K-tile share one buffer (32 KiB; 24 KiB with
-// e2m1 weights), two buffers, one barrier per K-tile:
+// e2m1 weights, 16 KiB with e2m1 tokens too), two buffers, one barrier per K-tile:
 //   wait for this wave's DMA of tile t | barrier | issue the DMA of tile t+1 into the other buffer | 16 fragment reads of tile t
 //   | the policy's MFMA block
 // so the copy of tile t+1 runs under the reads and MFMAs of tile t, and the buffer it overwrites was last read before every wave
@@ -23,6 +24,9 @@
 //   TKE, KMUL            elements of a K-tile and the entry's K multiple; when KMUL is half of TKE a last tile may be half deep: its
 //                        second 16-byte step is then read from the first step's addresses and `half` tells the MFMA block
 //   WROW                 bytes of a weight row per K-tile: TROW, or W4ROW for gemm_mx.hip's packed e2m1 rows (their own swizzle)
+//   XROW                 bytes of a token row per K-tile, likewise: W4ROW (with WROW == W4ROW only) for gemm_mx.hip's e2m1 tokens, whose
+//                        half is then the same 128 rows of 64 B, the same two DMA instructions per wave and the same swizzle and
+//                        one-chunk fragment read as the packed weight half
 //   Side                 per-tile values a lane loads itself, one tile ahead behind the DMA (gemm_mx.hip's scale dwords), or NoSide
 //   mma                  the MFMA block of one K-tile
 //
@@ -219,26 +223,40 @@ struct NoSide {
   __device__ __forceinline__ void shift() {}
 };
 
-// packed e2m1 weight rows (64 B, four to a 256-B bank line): logical chunk c at physical chunk c ^ w4_swz(row); gemm_mx.hip
+// packed e2m1 rows (64 B, four to a 256-B bank line): logical chunk c at physical chunk c ^ w4_swz(row); gemm_mx.hip
 __device__ __forceinline__ int w4_swz(int r) {
   const int u = (r >> 2) & 3;
   return u ^ ((u & 1) << 1);
 }
 
+// LDS-DMA sources of a half of 128 packed e2m1 rows x 64 B: instruction q (0-1) of this wave fills rows 16 g .. 16 g + 15, g = 4 q +
+// wave, lane l row 16 g + (l >> 2), physical chunk l & 3.  `pitch` bytes per row of `base`; rows past `rows` read row rows - 1.
+__device__ __forceinline__ void dma_sources4(const void* base, int row0, int rows, int pitch, const Frame& f, const char* (&src)[4]) {
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int r = 16 * (4 * q + f.wave) + (f.lane >> 2);
+    const int c = (f.lane & 3) ^ w4_swz(r);
+    const int row = row0 + r < rows ? row0 + r : rows - 1;
+    src[q] = static_cast<const char*>(base) + (int64_t)row * pitch + c * 16;
+  }
+}
+
 template <class P>
 __global__ void __launch_bounds__(256, 2) gemm_tile_kernel(Gemm16Params p) {
-  constexpr bool W4 = P::WROW == W4ROW, SHORT = P::KMUL < P::TKE;
-  constexpr int TILE = XTILE + TN * P::WROW;  // one K-tile buffer: token rows, then weight rows
-  static_assert((W4 || P::WROW == TROW) && (P::KMUL == P::TKE || (P::KMUL * 2 == P::TKE && !W4)), "no such geometry");
+  constexpr bool W4 = P::WROW == W4ROW, X4 = P::XROW == W4ROW, SHORT = P::KMUL < P::TKE;
+  constexpr int XT = TM * P::XROW, TILE = XT + TN * P::WROW;  // one K-tile buffer: token rows, then weight rows
+  static_assert((W4 || P::WROW == TROW) && (X4 ? W4 : P::XROW == TROW) && (P::KMUL == P::TKE || (P::KMUL * 2 == P::TKE && !W4)),
+                "no such geometry");
   __shared__ __attribute__((aligned(1024))) char smem[2 * TILE];
   const Frame f(p.nt);
   const int K = p.K, nk = (K + P::TKE - P::KMUL) / P::TKE;  // K % KMUL == 0
 
-  // ---- LDS-DMA sources: token rows and 128-B weight rows as dma_sources has them; e2m1 weight rows: instruction q (0-1) fills rows
-  // 16 g .. 16 g + 15, g = 4 q + wave, lane l row 16 g + (l >> 2), physical chunk l & 3
+  // ---- LDS-DMA sources: 128-B token and weight rows as dma_sources has them, packed e2m1 rows as dma_sources4
   const char *src[4], *wsrc[4];
-  const int kc = dma_sources(p.a, f.m0, p.M, (int64_t)K * TROW / P::TKE, f, src);
-  if constexpr (W4) {
+  int kc = 0;  // (the token half's logical chunk: what a half-deep last tile asks about)
+  if constexpr (X4) dma_sources4(p.a, f.m0, p.M, K / 2, f, src);
+  else kc = dma_sources(p.a, f.m0, p.M, (int64_t)K * TROW / P::TKE, f, src);
+  if constexpr (W4 && !X4) {  // (dma_sources4 written out: the form the W4A8 kernels were built and measured with)
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int r = 16 * (4 * q + f.wave) + (f.lane >> 2);
@@ -246,6 +264,8 @@ __global__ void __launch_bounds__(256, 2) gemm_tile_kernel(Gemm16Params p) {
       const int n = f.n0 + r < p.N ? f.n0 + r : p.N - 1;
       wsrc[q] = static_cast<const char*>(p.w) + (int64_t)n * (K / 2) + c * 16;
     }
+  } else if constexpr (W4) {
+    dma_sources4(p.w, f.n0, p.N, K / 2, f, wsrc);
   } else {
     dma_sources(p.w, f.n0, p.N, (int64_t)K * TROW / P::TKE, f, wsrc);
   }
@@ -255,8 +275,8 @@ __global__ void __launch_bounds__(256, 2) gemm_tile_kernel(Gemm16Params p) {
     int h = 2 * t;
     if constexpr (SHORT) h = t * P::TKE + kc * (P::TKE / 8) < K ? 2 * t : 2 * t - 1;
     char* dst = smem + (t & 1) * TILE + f.wave * 1024;
-    dma_issue<4>(src, (int64_t)h * (TROW / 2), dst);
-    dma_issue<TN * P::WROW / 4096>(wsrc, (int64_t)h * (P::WROW / 2), dst + XTILE);
+    dma_issue<XT / 4096>(src, (int64_t)h * (P::XROW / 2), dst);
+    dma_issue<TN * P::WROW / 4096>(wsrc, (int64_t)h * (P::WROW / 2), dst + XT);
   };
 
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
@@ -279,13 +299,14 @@ __global__ void __launch_bounds__(256, 2) gemm_tile_kernel(Gemm16Params p) {
       side.load(t + 1);
     }
     __builtin_amdgcn_sched_barrier(0);
-    const uint32_t xo = (t & 1) * TILE + f.wm * 64 * TROW, wo = (t & 1) * TILE + XTILE + f.wn * 64 * P::WROW;
-    v4i xa[2][4], wb[2][4];  // [16-byte step][16-row block]; an e2m1 weight fragment is wb[0] alone
+    const uint32_t xo = (t & 1) * TILE + f.wm * 64 * P::XROW, wo = (t & 1) * TILE + XT + f.wn * 64 * P::WROW;
+    v4i xa[2][4], wb[2][4];  // [16-byte step][16-row block]; an e2m1 fragment is wb[0] / xa[0] alone
     if constexpr (W4) dsr4<W4ROW>(wb[0], rdw4 + wo);
     else dsr4<TROW>(wb[0], rd0 + wo);
-    dsr4<TROW>(xa[0], rd0 + xo);
+    if constexpr (X4) dsr4<W4ROW>(xa[0], rdw4 + xo);
+    else dsr4<TROW>(xa[0], rd0 + xo);
     if constexpr (!W4) dsr4<TROW>(wb[1], rd1 + wo);
-    dsr4<TROW>(xa[1], rd1 + xo);
+    if constexpr (!X4) dsr4<TROW>(xa[1], rd1 + xo);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     P::mma(acc, wb, xa, side, SHORT && t * P::TKE + P::KMUL >= K);

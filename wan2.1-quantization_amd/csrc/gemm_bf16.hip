@@ -12,7 +12,7 @@ namespace {
 
 template <bool F16IN, int OUT_>
 struct FpPolicy {
-  static constexpr int OUT = OUT_, TKE = TK, KMUL = 32, WROW = TROW;
+  static constexpr int OUT = OUT_, TKE = TK, KMUL = 32, WROW = TROW, XROW = TROW;
   static constexpr bool SCALED = false, TOKEN = false;
   using Side = NoSide;
 

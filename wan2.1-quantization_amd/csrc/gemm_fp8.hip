@@ -33,7 +33,7 @@ __device__ __forceinline__ v4f mfma128(const v4i& w0, const v4i& w1, const v4i& 
 
 template <int OUT_>
 struct Fp8Policy {
-  static constexpr int OUT = OUT_, TKE = 128, KMUL = KSTEP8, WROW = TROW;
+  static constexpr int OUT = OUT_, TKE = 128, KMUL = KSTEP8, WROW = TROW, XROW = TROW;
   static constexpr bool SCALED = true, TOKEN = true;
   using Side = NoSide;
 

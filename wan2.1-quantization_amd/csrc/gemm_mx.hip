@@ -1,5 +1,6 @@
-// OCP MX GEMM: MXFP8 (e4m3) activations against MXFP8 (e4m3) or MXFP4 (e2m1) weights, one E8M0 power-of-two scale per row and block
-// of 32 input channels on either side (HipLinearMx), with the fused epilogue of the 16-bit GEMMs:
+// OCP MX GEMMs: MXFP8 (e4m3) activations against MXFP8 (e4m3) or MXFP4 (e2m1) weights (wanq_gemm_mx), and MXFP4 activations against
+// MXFP4 weights (wanq_gemm_mx4, W4A4), one E8M0 power-of-two scale per row and block of 32 input channels on either side
+// (HipLinearMx), with the fused epilogue of the 16-bit GEMMs:
 //   acc[m,n] = sum_b 2^(sa[m,b]-127) 2^(sw[n,b]-127) sum_{k in b} a[m,k] w[n,k]  on v_mfma_scale_f32_16x16x128_f8f6f4, which applies
 //   both block scales itself; fp32 accumulation.   y = acc + bias;  GELU;  residual + y * gate;  one rounding to out
 //   (epilogue16<.., false>: no fp32 row or channel scale is left to apply).
@@ -28,8 +29,14 @@
 // each of its four token rows and four weight rows once per K-tile -- for tile t + 1 right behind the DMA of tile t + 1, so the
 // wait that covers the DMA covers them -- and shifts it right by 8 fq: byte 0 (op_sel 0) is then the byte of its own (row, block).
 //
-// Matrix instruction.  The weight is the first operand: cbsz 0 (e4m3, eight fragment registers) or 4 (e2m1, the first four), the
-// token operand stays e4m3 (blgp 0).
+// Matrix instruction.  The weight is the first operand: cbsz 0 (e4m3, eight fragment registers) or 4 (e2m1, the first four); the
+// token operand is the second: blgp 0 (e4m3) or 4 (e2m1).
+//
+// W4A4 (wanq_gemm_mx4).  The token half is what the packed weight half is: 128 rows of 64 B, two DMA instructions per wave, w4_swz,
+// one ds_read_b128 of chunk fq per fragment, registers 4-7 zero.  A wave reads token rows wm * 64 + i * 16 + fr exactly as it reads
+// weight rows wn * 64 + j * 16 + fr, so the bank derivation above holds for both halves.  A K-tile buffer is 16 KiB, a fragment
+// set 8 reads instead of 12 (16), and with both operands 4 bits wide the instruction runs at the fp4 rate, twice the rate any
+// e4m3 operand holds it to.  The scale dwords do not change.  128-deep K-tile, one MFMA per accumulator and barrier.
 //
 // Summation order of element (m, n): K-tiles ascending, inside an MFMA the hardware's own.  It depends on K only.
 #include "gemm16_common.h"
@@ -39,8 +46,13 @@ namespace {
 
 constexpr int TKX = 128;  // elements of a K-tile: four blocks of 32, one MFMA
 
-template <bool FP4>
+template <bool FP4, bool A4>
 __device__ __forceinline__ v4f mfma_mx(const v4i& w0, const v4i& w1, const v4i& x0, const v4i& x1, v4f c, int sw, int sa) {
+  if constexpr (A4) {
+    static_assert(FP4, "e2m1 tokens go with e2m1 weights");
+    const v8i w = {w0.x, w0.y, w0.z, w0.w, 0, 0, 0, 0}, x = {x0.x, x0.y, x0.z, x0.w, 0, 0, 0, 0};
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(w, x, c, 4, 4, 0, sw, 0, sa);
+  }
   const v8i x = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
   if constexpr (FP4) {
     const v8i w = {w0.x, w0.y, w0.z, w0.w, 0, 0, 0, 0};
@@ -83,9 +95,9 @@ struct MxScales {
   }
 };
 
-template <int OUT_, bool FP4>
+template <int OUT_, bool FP4, bool A4 = false>
 struct MxPolicy {
-  static constexpr int OUT = OUT_, TKE = TKX, KMUL = TKX, WROW = FP4 ? W4ROW : TROW;
+  static constexpr int OUT = OUT_, TKE = TKX, KMUL = TKX, WROW = FP4 ? W4ROW : TROW, XROW = A4 ? W4ROW : TROW;
   static constexpr bool SCALED = false, TOKEN = false;
   using Side = MxScales;
 
@@ -94,7 +106,7 @@ struct MxPolicy {
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        acc[i][j] = mfma_mx<FP4>(wb[0][j], wb[FP4 ? 0 : 1][j], xa[0][i], xa[1][i], acc[i][j], s.sw_cur[j], s.sa_cur[i]);
+        acc[i][j] = mfma_mx<FP4, A4>(wb[0][j], wb[FP4 ? 0 : 1][j], xa[0][i], xa[A4 ? 0 : 1][i], acc[i][j], s.sw_cur[j], s.sa_cur[i]);
   }
 };
 
@@ -121,5 +133,22 @@ extern "C" int wanq_gemm_mx(const uint8_t* a, const uint8_t* w, const uint8_t* s
     constexpr int OUT = decltype(o)::value;
     return w_fmt == WANQ_MX_E2M1 ? launch_tiles(gemm_tile_kernel<MxPolicy<OUT, true>>, p, st, what)
                                  : launch_tiles(gemm_tile_kernel<MxPolicy<OUT, false>>, p, st, what);
+  });
+}
+
+extern "C" int wanq_gemm_mx4(const uint8_t* a, const uint8_t* w, const uint8_t* sa_u8, const uint8_t* sw_u8, void* out, int out_dtype,
+                             const void* bias, int bias_dtype, const float* gate, const void* residual, int epi_flags, int64_t M, int N,
+                             int K, void* stream) {
+  const char* what = "wanq_gemm_mx4";
+  WANQ_REQUIRE(a && w && out && sa_u8 && sw_u8, WANQ_E_ARG, "%s: a, w, sa_u8, sw_u8 and out must be non-NULL", what);
+  if (const int rc = check_gemm16_shapes(what, TKX, a, w, out, out_dtype, bias, bias_dtype, gate, residual, epi_flags, M, N, K))
+    return rc;
+  WANQ_REQUIRE(aligned(sa_u8, 4) && aligned(sw_u8, 4), WANQ_E_ARG, "%s: sa_u8 and sw_u8 must be 4-byte aligned", what);
+  if (const int rc = check_gemm16_tail(what, bias, bias_dtype, gate, M, N)) return rc;
+  if (M == 0) return WANQ_OK;
+  const Gemm16Params p = gemm16_params(a, w, sa_u8, sw_u8, out, bias, bias_dtype, gate, residual, epi_flags, M, N, K);
+  hipStream_t st = (hipStream_t)stream;
+  return with_out_dtype(out_dtype, [&](auto o) {
+    return launch_tiles(gemm_tile_kernel<MxPolicy<decltype(o)::value, true, true>>, p, st, what);
   });
 }

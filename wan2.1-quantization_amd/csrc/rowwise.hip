@@ -335,6 +335,11 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const Fp8RowParams 
 // behind the clamp as in the fp8 quantiser, e2m1 by seven comparisons against the midpoints (> where the tie goes down to the even
 // code, >= where it goes up).  e4m3 codes leave as 8-byte chunks, e2m1 codes as one dword of eight nibbles (even k low), the scale
 // byte from the quad's first lane.
+// HAD (wanq_quant_rows_mx_had32): behind the GELU and in front of the block maximum every block is replaced by its unnormalised 32-point
+// Sylvester-Hadamard transform, five fp32 butterfly stages h = 1, 2, 4, 8, 16 with (x_i, x_{i+h}) <- (x_i + x_{i+h}, x_i - x_{i+h})
+// for bit h of i clear.  Element i of a block is chunk element i & 7 of quad lane i >> 3: stages 1, 2, 4 stay inside the chunk, stages
+// 8 and 16 are the quad exchanges the maximum uses, the lane with the bit set keeping partner - own.  Additions and subtractions
+// only, one rounding each, in a fixed order: bit-equal to mx_hadamard32_host.  Still no LDS and no barrier.
 struct MxRowParams {
   const void* x;
   int x_dtype;
@@ -352,7 +357,29 @@ __device__ __forceinline__ uint32_t e2m1_code(float t) {
   return mag | ((__float_as_uint(t) >> 28) & 8u);
 }
 
-template <int WPR, int NCH, bool FP4>
+// one butterfly stage inside a chunk: H = 1, 2 or 4
+template <int H>
+__device__ __forceinline__ void had_stage(float (&v)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    if (j & H) continue;
+    const float a = v[j], b = v[j + H];
+    v[j] = a + b;
+    v[j + H] = a - b;
+  }
+}
+
+// one butterfly stage across the quad: MASK = 1 (h = 8) or 2 (h = 16)
+template <int MASK>
+__device__ __forceinline__ void had_stage_quad(float (&v)[8], bool upper) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float o = lane_xor_dpp<MASK>(v[j]);
+    v[j] = upper ? o - v[j] : v[j] + o;
+  }
+}
+
+template <int WPR, int NCH, bool FP4, bool HAD = false>
 __global__ __launch_bounds__(256) void quant_rows_mx_kernel(const MxRowParams p) {
   RowFrame<WPR, NCH> f;
   if (f.surplus(p.rows)) return;
@@ -371,6 +398,13 @@ __global__ __launch_bounds__(256) void quant_rows_mx_kernel(const MxRowParams p)
   }
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
+    if constexpr (HAD) {
+      had_stage<1>(v[i]);
+      had_stage<2>(v[i]);
+      had_stage<4>(v[i]);
+      had_stage_quad<1>(v[i], f.lane & 1);
+      had_stage_quad<2>(v[i], f.lane & 2);
+    }
     float m = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(v[i][j]));
@@ -464,24 +498,34 @@ extern "C" int wanq_quant_rows_fp8(const void* x, int x_dtype, uint8_t* q, float
   return check_launch("wanq_quant_rows_fp8");
 }
 
-extern "C" int wanq_quant_rows_mx(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int fmt, int act,
-                                  void* stream) {
-  WANQ_REQUIRE(x && q && scale_u8, WANQ_E_ARG, "wanq_quant_rows_mx: x, q and scale_u8 must be non-NULL");
-  WANQ_REQUIRE(is_fp(x_dtype), WANQ_E_ARG, "wanq_quant_rows_mx: bad x dtype %d", x_dtype);
-  WANQ_REQUIRE(fmt == WANQ_MX_E4M3 || fmt == WANQ_MX_E2M1, WANQ_E_ARG, "wanq_quant_rows_mx: fmt=%d must be WANQ_MX_E4M3 or WANQ_MX_E2M1",
-               fmt);
-  WANQ_REQUIRE(act == 0 || act == 1, WANQ_E_ARG, "wanq_quant_rows_mx: act must be 0 or 1");
-  if (int e = check_rows_cols("wanq_quant_rows_mx", rows, cols)) return e;
-  WANQ_REQUIRE(cols % 32 == 0, WANQ_E_SHAPE, "wanq_quant_rows_mx: cols=%d must be a multiple of 32 (one scale per block of 32)", cols);
-  WANQ_REQUIRE((reinterpret_cast<uintptr_t>(q) & 15) == 0, WANQ_E_ARG, "wanq_quant_rows_mx: q must be 16-byte aligned");
+template <bool HAD>
+static int quant_rows_mx_entry(const char* what, const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int fmt,
+                               int act, void* stream) {
+  WANQ_REQUIRE(x && q && scale_u8, WANQ_E_ARG, "%s: x, q and scale_u8 must be non-NULL", what);
+  WANQ_REQUIRE(is_fp(x_dtype), WANQ_E_ARG, "%s: bad x dtype %d", what, x_dtype);
+  WANQ_REQUIRE(fmt == WANQ_MX_E4M3 || fmt == WANQ_MX_E2M1, WANQ_E_ARG, "%s: fmt=%d must be WANQ_MX_E4M3 or WANQ_MX_E2M1", what, fmt);
+  WANQ_REQUIRE(act == 0 || act == 1, WANQ_E_ARG, "%s: act must be 0 or 1", what);
+  if (int e = check_rows_cols(what, rows, cols)) return e;
+  WANQ_REQUIRE(cols % 32 == 0, WANQ_E_SHAPE, "%s: cols=%d must be a multiple of 32 (one scale per block of 32)", what, cols);
+  WANQ_REQUIRE((reinterpret_cast<uintptr_t>(q) & 15) == 0, WANQ_E_ARG, "%s: q must be 16-byte aligned", what);
   if (rows == 0) return WANQ_OK;
   const MxRowParams p{x, x_dtype, q, scale_u8, rows, cols, act};
   row_ladder(cols, rows, [&](auto wpr, auto nch, dim3 grid) {
     constexpr int W = decltype(wpr)::value, NC = decltype(nch)::value;
-    if (fmt == WANQ_MX_E2M1) hipLaunchKernelGGL((quant_rows_mx_kernel<W, NC, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((quant_rows_mx_kernel<W, NC, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    if (fmt == WANQ_MX_E2M1) hipLaunchKernelGGL((quant_rows_mx_kernel<W, NC, true, HAD>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((quant_rows_mx_kernel<W, NC, false, HAD>), grid, dim3(256), 0, (hipStream_t)stream, p);
   });
-  return check_launch("wanq_quant_rows_mx");
+  return check_launch(what);
+}
+
+extern "C" int wanq_quant_rows_mx(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int fmt, int act,
+                                  void* stream) {
+  return quant_rows_mx_entry<false>("wanq_quant_rows_mx", x, x_dtype, q, scale_u8, rows, cols, fmt, act, stream);
+}
+
+extern "C" int wanq_quant_rows_mx_had32(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int fmt,
+                                        int act, void* stream) {
+  return quant_rows_mx_entry<true>("wanq_quant_rows_mx_had32", x, x_dtype, q, scale_u8, rows, cols, fmt, act, stream);
 }
 
 extern "C" int wanq_layernorm_rows(const void* x, int x_dtype, const void* gamma, const void* mshift,

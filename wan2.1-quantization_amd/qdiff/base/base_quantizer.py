@@ -263,11 +263,30 @@ def mx_unpack_e2m1(packed):
     return torch.stack((packed & 0xf, packed >> 4), dim=-1).reshape(*packed.shape[:-1], packed.shape[-1] * 2)
 
 
-def mx_quant_rows_host(x, fmt, gelu=False):
+def mx_hadamard32_host(x):
+    """x [..., cols] fp32 with every block of 32 columns replaced by its unnormalised Sylvester-Hadamard transform, x_block H with
+    H[i][j] = (-1)^popcount(i & j): five butterfly stages in fp32, in the order h = 1, 2, 4, 8, 16, each (x_i, x_{i+h}) <- (x_i +
+    x_{i+h}, x_i - x_{i+h}) for bit h of i clear.  Only additions and subtractions, one rounding each, in the order
+    wanq_quant_rows_mx_had32 performs them: this is the definition that entry is bit-equal to.  H is symmetric and H H = 32 I."""
+    x = x.float()
+    if x.shape[-1] % MX_BLOCK:
+        raise ValueError(f"mx_hadamard32: cols={x.shape[-1]} must be a multiple of {MX_BLOCK}")
+    v = x.reshape(-1, MX_BLOCK)
+    h = 1
+    while h < MX_BLOCK:
+        v = v.reshape(-1, MX_BLOCK // (2 * h), 2, h)
+        a, b = v[:, :, 0, :], v[:, :, 1, :]
+        v = torch.stack((a + b, a - b), dim=2)
+        h *= 2
+    return v.reshape(x.shape)
+
+
+def mx_quant_rows_host(x, fmt, gelu=False, had32=False):
     """(codes uint8, scale bytes uint8 [rows, cols / 32]) of the block quantiser, in torch on x's device.  Per block: amax, E = its
     biased fp32 exponent field, s = clamp(E - emax, 0, 254), c = rne(clamp(x 2^(127 - s), -max, max)).  The scaling is done in
     float64, where it is exact; the one rounding is the cast to e4m3fn (this torch build rounds to nearest even and keeps subnormals)
-    or, for e2m1, the comparison against the seven midpoints with ties to the even code."""
+    or, for e2m1, the comparison against the seven midpoints with ties to the even code.  `had32`: the blocks go through
+    mx_hadamard32_host behind the GELU and in front of the block maximum (wanq_quant_rows_mx_had32)."""
     emax, vmax, _ = _MX_SPEC[fmt]
     x = x.float()
     if gelu:
@@ -275,6 +294,8 @@ def mx_quant_rows_host(x, fmt, gelu=False):
     rows, cols = x.shape
     if cols % MX_BLOCK:
         raise ValueError(f"mx_quant_rows: cols={cols} must be a multiple of {MX_BLOCK}")
+    if had32:
+        x = mx_hadamard32_host(x)
     xb = x.reshape(rows, cols // MX_BLOCK, MX_BLOCK)
     amax = xb.abs().amax(dim=-1).contiguous()
     s = (((amax.view(torch.int32) >> 23) & 0xff) - emax).clamp(0, 254)
@@ -288,11 +309,12 @@ def mx_quant_rows_host(x, fmt, gelu=False):
     return codes, s.to(torch.uint8)
 
 
-def mx_quant_rows(x, fmt, gelu=False):
-    """The block quantiser: on the GPU wanq_quant_rows_mx, in host memory the host expression it is bit-equal to."""
+def mx_quant_rows(x, fmt, gelu=False, had32=False):
+    """The block quantiser: on the GPU wanq_quant_rows_mx (`had32`: wanq_quant_rows_mx_had32), in host memory the host expression it is
+    bit-equal to."""
     if x.is_cuda:
-        return fused.quant_rows_mx(x.contiguous(), fmt, gelu)
-    return mx_quant_rows_host(x, fmt, gelu)
+        return fused.quant_rows_mx(x.contiguous(), fmt, gelu, had32)
+    return mx_quant_rows_host(x, fmt, gelu, had32)
 
 
 def mx_decode(codes, scale_u8, fmt, dtype=torch.float32):
@@ -313,15 +335,21 @@ class MxQuantizer(BaseQuantizer):
     """`format: mxfp8_e4m3` / `mxfp4_e2m1` of a `weight:` or `act:` section (n_bits 8 / 4, sym True): one E8M0 scale byte per row and
     block of 32 input channels, e4m3 bytes or packed e2m1 nibbles.  `scale_u8` [rows, cols / 32] holds the bytes as the GEMM reads
     them; `delta` = 2^(scale_u8 - 127) and `zero_point` zeros keep the integer quantisers' names (save / load_quant_param_dict).
-    Nothing is fitted or calibrated: the scales are a function of the tensor alone and are derived again at every call."""
+    Nothing is fitted or calibrated: the scales are a function of the tensor alone and are derived again at every call.
+    `had32` (the config's `mx: {block_hadamard: True}`): every block is quantised behind its unnormalised 32-point Hadamard
+    transform, and the codes, the scales and `dequantize` all live in that rotated domain.  A `weight_side` quantiser then takes
+    w / 32 (an exact power of two), so that (x H)(w H / 32)^T = x w^T: rotated activations against the rotated weight need no inverse."""
 
-    def __init__(self, quant_config):
+    def __init__(self, quant_config, had32=False, weight_side=False):
         super().__init__(quant_config)
         self.format = quant_config["format"]
+        self.had32, self.weight_side = bool(had32), bool(weight_side)
         self.register_buffer("scale_u8", None, persistent=False)
 
     def codes_and_scale(self, x, gelu=False):
-        codes, s = mx_quant_rows(x, self.format, gelu)
+        if self.had32 and self.weight_side:
+            x = x.float() * 0.03125
+        codes, s = mx_quant_rows(x, self.format, gelu, self.had32)
         self.scale_u8 = s
         self.delta = _pow2_f64(s.long() - 127).float()
         self.zero_point = torch.zeros_like(self.delta)

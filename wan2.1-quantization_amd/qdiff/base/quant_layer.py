@@ -37,7 +37,9 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         self.fp_module, self.q_cfg = fp_module, quant_config
         self.low_rank = self._checked_low_rank(quant_config, module_name)  # `weight.low_rank`: the LoRC rank (low_rank.py), or None
         self.mx = None  # the weight's MX format name (`format: mxfp8_e4m3` / `mxfp4_e2m1`), set by _checked_format
+        self.mx_act = None  # ... and the activation's
         self.fp8 = self._checked_format(quant_config, module_name)
+        self.mx_had32 = self._checked_mx_section(quant_config, module_name)  # `mx: {block_hadamard: True}`, W4A4 MX layers only
         # (an MX layer's `weight.group_size: 32` names the format's own block: there is no integer group-wise path behind it)
         self.group_size = None if self.mx else self._checked_group_size(quant_config, module_name, fp_module.weight.device)
         self.gptq = self._checked_gptq(quant_config, module_name)  # the `gptq:` section when it names this layer (gptq.py), or None
@@ -49,8 +51,9 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         self._zp_gemm = self._wq16_vecs = None
         if quant_config.get("weight", None) is not None:
             wq = quant_config["weight"]
-            self.w_quantizer = (MxQuantizer if self.mx else Fp8Quantizer if self.fp8 else
-                                MixedPrecisionStaticQuantizer if isinstance(wq["n_bits"], ListConfig) else StaticQuantizer)(wq)
+            self.w_quantizer = MxQuantizer(wq, self.mx_had32, weight_side=True) if self.mx else \
+                (Fp8Quantizer if self.fp8 else
+                 MixedPrecisionStaticQuantizer if isinstance(wq["n_bits"], ListConfig) else StaticQuantizer)(wq)
             self._requantize(fp_module.weight.data)
             self.w_quantizer.init_done = True
         else:
@@ -59,8 +62,9 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         self.bias = fp_module.bias
         if quant_config.get("act", None) is not None:
             aq = quant_config["act"]
-            self.a_quantizer = (MxQuantizer if self.mx else Fp8Quantizer if self.fp8 else
-                                MixedPrecisionDynamicQuantizer if isinstance(aq["n_bits"], ListConfig) else DynamicQuantizer)(aq)
+            self.a_quantizer = MxQuantizer(aq, self.mx_had32) if self.mx else \
+                (Fp8Quantizer if self.fp8 else
+                 MixedPrecisionDynamicQuantizer if isinstance(aq["n_bits"], ListConfig) else DynamicQuantizer)(aq)
         self.use_kernel = False
         self.quant_mode = True
         self.module_name = module_name
@@ -77,10 +81,10 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         for sec, f in (("weight", fw), ("act", fa)):
             if f is not None and f not in _FORMAT_BITS:
                 raise ValueError(f"{name}: {sec}.format={f!r} is not a known format (the format keys are {FP8_FORMAT!r}, "
-                                 f"{MXFP8_FORMAT!r} and, for weights, {MXFP4_FORMAT!r})")
+                                 f"{MXFP8_FORMAT!r} and {MXFP4_FORMAT!r})")
         if fw in MX_FORMATS or fa in MX_FORMATS:
             self._check_mx_format(name, wq, aq, fw, fa)
-            self.mx = fw
+            self.mx, self.mx_act = fw, fa
             return False
         if fw is None or fa is None:
             raise NotImplementedError(f"{name}: format: {FP8_FORMAT} must be set in both the `weight:` and the `act:` section (it is "
@@ -111,16 +115,22 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
                                       "QuantizedLinear)")
 
     def _check_mx_format(self, name, wq, aq, fw, fa):
-        """The accepted OCP MX pairs are (weight mxfp8_e4m3, act mxfp8_e4m3) and (weight mxfp4_e2m1, act mxfp8_e4m3), with n_bits 8 / 4,
-        sym True and weight.group_size absent or 32 (the format's block); everything else is refused by layer name."""
+        """The accepted OCP MX pairs are (weight mxfp8_e4m3, act mxfp8_e4m3), (weight mxfp4_e2m1, act mxfp8_e4m3) and the W4A4 pair
+        (weight mxfp4_e2m1, act mxfp4_e2m1), with n_bits 8 / 4, sym True and weight.group_size absent or 32 (the format's block);
+        everything else is refused by layer name."""
         if fa == MXFP4_FORMAT:
-            raise NotImplementedError(f"{name}: act.format: {MXFP4_FORMAT} is not supported: no fp4 activation quantiser path is built "
-                                      f"yet (the MX GEMM takes {MXFP8_FORMAT} activations)")
+            built = f"(the built pair is weight {MXFP4_FORMAT} n_bits 4 against act {MXFP4_FORMAT} n_bits 4)"
+            if not isinstance(aq["n_bits"], ListConfig) and aq["n_bits"] == 8:
+                raise NotImplementedError(f"{name}: act.format: {MXFP4_FORMAT} with act.n_bits: 8 is not supported: no fp4 activation "
+                                          f"quantiser path is built yet for 8-bit codes {built}")
+            if fw in (MXFP8_FORMAT, FP8_FORMAT):
+                raise NotImplementedError(f"{name}: act.format: {MXFP4_FORMAT} against weight.format: {fw} is not supported: no fp4 "
+                                          f"activation quantiser path is built yet for an e4m3 weight {built}")
         if fw not in MX_FORMATS or fa not in MX_FORMATS:
             sec, other = ("weight", fw) if fw not in MX_FORMATS else ("act", fa)
             raise NotImplementedError(f"{name}: an MX format on one side needs an MX format on the other ({sec}.format is "
-                                      f"{other!r}): the MX GEMM takes block-scaled codes on both sides, weight {MXFP8_FORMAT} or "
-                                      f"{MXFP4_FORMAT} against act {MXFP8_FORMAT}")
+                                      f"{other!r}): the MX GEMMs take block-scaled codes on both sides, weight {MXFP8_FORMAT} or "
+                                      f"{MXFP4_FORMAT} against act {MXFP8_FORMAT}, or weight {MXFP4_FORMAT} against act {MXFP4_FORMAT}")
         self._check_format_sections(name, (("weight", wq, fw), ("act", aq, fa)))
         g = wq.get("group_size", None)
         if g is not None and (isinstance(g, bool) or g != MX_BLOCK):
@@ -129,6 +139,26 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         self._refuse_format_on_a_transformed_layer(name)
         if self.in_features % MX_BLOCK:
             raise ValueError(f"{name}: weight.format: {fw} needs in_features={self.in_features} to be a multiple of {MX_BLOCK}")
+
+    def _checked_mx_section(self, quant_config, module_name):
+        """`mx.block_hadamard` of the config (False without the section): both sides of the layer are quantised behind a 32-point
+        Hadamard rotation of every MX block (MxQuantizer).  Accepted only with the W4A4 pair, weight mxfp4_e2m1 against act
+        mxfp4_e2m1; with any other pair, or without a format, it is refused by layer name.  Unknown keys of the section are refused."""
+        sec = quant_config.get("mx", None)
+        if sec is None:
+            return False
+        name = module_name or type(self).__name__
+        unknown = [k for k in sec.keys() if k != "block_hadamard"]
+        if unknown:
+            raise ValueError(f"{name}: mx.{unknown[0]} is not a known key of the `mx:` section (it has one: block_hadamard)")
+        on = sec.get("block_hadamard", False)
+        if not isinstance(on, bool):
+            raise ValueError(f"{name}: mx.block_hadamard={on!r} must be True or False")
+        if on and not (self.mx == MXFP4_FORMAT and self.mx_act == MXFP4_FORMAT):
+            pair = f"weight.format {self.mx!r} against act.format {self.mx_act!r}" if self.mx else "no MX format"
+            raise NotImplementedError(f"{name}: mx.block_hadamard: True is not supported with {pair}: the block rotation is built for "
+                                      f"the W4A4 pair only (weight.format: {MXFP4_FORMAT} against act.format: {MXFP4_FORMAT})")
+        return on
 
     def _checked_low_rank(self, quant_config, module_name):
         """`weight.low_rank` of the config (None: no low-rank branch), or the refusal of what has none, before any weight is
@@ -385,17 +415,19 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
     def _forward_format(self, x2, out_dtype, bias):
         """`format: fp8_e4m3`: the activation is quantised per token to e4m3 (Fp8Quantizer) and multiplied by the layer's e4m3 weight
         codes, one fp32 scale per token and per output channel.  `format: mxfp8_e4m3` activations against `mxfp8_e4m3` / `mxfp4_e2m1`
-        weights: quantised per block of 32 channels (MxQuantizer), both sides' E8M0 scales applied by the matrix cores.  On the GPU
+        weights, or `format: mxfp4_e2m1` activations against `mxfp4_e2m1` weights (W4A4, optionally behind `mx.block_hadamard`):
+        quantised per block of 32 channels (MxQuantizer), both sides' E8M0 scales applied by the matrix cores.  On the GPU
         these are kernel mode's two entries per format, fused.quant_rows_fp8 + qgemm.fp8_linear and fused.quant_rows_mx +
-        qgemm.mx_linear.  In host memory, and for a shape the GEMM refuses, the same numbers through torch: F.linear of the
+        qgemm.mx_linear / qgemm.mx4_linear.  In host memory, and for a shape the GEMM refuses, the same numbers through torch: F.linear of the
         dequantised activation and the dequantised weight, in fp32."""
         a_q, a_s = self.a_quantizer.codes_and_scale(x2)
-        refusal, gemm, fmt = (qgemm.mx_linear_refusal, qgemm.mx_linear, (self.mx,)) if self.mx else \
-            (qgemm.fp8_linear_refusal, qgemm.fp8_linear, ())
+        refusal, gemm, fmt = (qgemm.mx4_linear_refusal, qgemm.mx4_linear, ()) if self.mx_act == MXFP4_FORMAT else \
+            (qgemm.mx_linear_refusal, qgemm.mx_linear, (self.mx,)) if self.mx else (qgemm.fp8_linear_refusal, qgemm.fp8_linear, ())
         if x2.is_cuda and refusal(x2.shape[0], self.out_features, self.in_features, *fmt) is None:
             w_s = self.w_quantizer.scale_u8 if self.mx else self.w_quantizer.delta.reshape(-1).float().contiguous()
             return gemm(a_q, self._codes, a_s, w_s, *fmt, bias, out_dtype=out_dtype)
-        a = mx_decode(a_q, a_s, MXFP8_FORMAT) if self.mx else fp8_decode(a_q) * a_s.unsqueeze(-1)
+        # (with mx.block_hadamard the decoded activation and weight.data are both in the rotated domain: their product is x w^T's)
+        a = mx_decode(a_q, a_s, self.mx_act) if self.mx else fp8_decode(a_q) * a_s.unsqueeze(-1)
         return F.linear(a, self.weight.data.float(), bias).to(out_dtype)
 
     def _forward_grouped(self, x2, out_dtype, bias):

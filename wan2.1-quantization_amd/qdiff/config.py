@@ -8,11 +8,15 @@ section the layer's weight must be on the GPU; QuantizedLinear refuses everythin
 token (absmax / 448) instead of int8 codes, on wanq_gemm_fp8; `n_bits: 8, sym: True` stay as written.  Refused by layer name when
 the layer is built: the key in only one section, with `group_size`, with `sym: False`, with `n_bits` other than 8 or a bit-width
 list, and on a SmoothQuant / QuaRot / ViDiT layer.
-The OCP Microscaling formats use the same key: `format: mxfp8_e4m3` (`n_bits: 8`) in `act:` and in `weight:`, `format: mxfp4_e2m1`
-(`n_bits: 4`) in `weight:` only -- one E8M0 power-of-two scale per block of 32 input channels on both sides, applied by the matrix
-cores (wanq_quant_rows_mx, wanq_gemm_mx).  The accepted pairs are weight mxfp8_e4m3 or mxfp4_e2m1 against act mxfp8_e4m3, `sym: True`,
-`weight.group_size` absent or 32; `act.format: mxfp4_e2m1`, an MX format against `fp8_e4m3` or against no format, a bit-width list,
-another group size and the SmoothQuant / QuaRot / ViDiT layer classes are refused by layer name.
+The OCP Microscaling formats use the same key: `format: mxfp8_e4m3` (`n_bits: 8`) and `format: mxfp4_e2m1` (`n_bits: 4`) in `act:` and
+in `weight:` -- one E8M0 power-of-two scale per block of 32 input channels on both sides, applied by the matrix cores
+(wanq_quant_rows_mx, wanq_gemm_mx, wanq_gemm_mx4).  The accepted pairs are weight mxfp8_e4m3 or mxfp4_e2m1 against act mxfp8_e4m3, and
+the W4A4 pair weight mxfp4_e2m1 against act mxfp4_e2m1, `sym: True`, `weight.group_size` absent or 32; `act.format: mxfp4_e2m1` with
+`n_bits: 8` or against an e4m3 weight, an MX format against `fp8_e4m3` or against no format, a bit-width list, another group size and
+the SmoothQuant / QuaRot / ViDiT layer classes are refused by layer name.
+`mx: {block_hadamard: True}`, a top-level section: both sides of every MX Linear are quantised behind the unnormalised 32-point
+Hadamard transform of each block of 32 input channels (wanq_quant_rows_mx_had32; the weight as w / 32, so the product is unchanged and
+nothing is rotated back).  Accepted only with the W4A4 pair; with any other pair, or without a format, refused by layer name.
 `weight.low_rank: r` (a positive int, r <= min(N, K), at most 256 after padding to a multiple of 64): the best rank-r approximation
 of the quantisation error W - W_hat is kept in 16 bits beside the integer codes and added inside the weight-only GEMM
 (qdiff/base/low_rank.py, wanq_gemm_wq16_lowrank).  For a weight-only integer config only, per channel or with `group_size`: with an

@@ -58,6 +58,8 @@ PROTOTYPES = {
     "wanq_gemm_fp8": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
     "wanq_quant_rows_mx": [_vp, _i, _vp, _vp, _i64, _i, _i, _i, _vp],
     "wanq_gemm_mx": [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
+    "wanq_quant_rows_mx_had32": [_vp, _i, _vp, _vp, _i64, _i, _i, _i, _vp],
+    "wanq_gemm_mx4": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
     "wanq_lincomb":[_i, _i, _vp, _vp, _vp, _i64, _vp],
     "wanq_linear_f32": [_vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp],
     "wanq_time_sinusoid": [_vp, _i, _vp, _i, _i, _vp],

@@ -91,11 +91,13 @@ def quant_rows_fp8(x, gelu=False):
     return codes, scale
 
 
-def quant_rows_mx(x, fmt="mxfp8_e4m3", gelu=False):
+def quant_rows_mx(x, fmt="mxfp8_e4m3", gelu=False, had32=False):
     """OCP MX block quantisation (wanq_quant_rows_mx): -> (codes uint8, scale bytes uint8 [rows, cols / 32]), one E8M0 scale per block
     of 32 columns: s = clamp(E(amax) - emax, 0, 254), codes = rne(clamp(x 2^(127 - s), -max, max)).  fmt "mxfp8_e4m3": codes of x's
     shape, e4m3fn bit patterns; "mxfp4_e2m1": [rows, cols / 2], two e2m1 nibbles per byte, even column low.  `gelu`: the tanh-GELU of
-    the int8 quantiser applied to x first.  Activations (e4m3), and a weight [N, K] once at conversion (either format)."""
+    the int8 quantiser applied to x first.  Activations (either format), and a weight [N, K] once at conversion (either format).
+    `had32` (wanq_quant_rows_mx_had32): every block is replaced by its unnormalised 32-point Hadamard transform behind the GELU and
+    in front of the block maximum."""
     if fmt not in _C.MX_FMT:
         raise RuntimeError(f"quant_rows_mx: fmt={fmt!r} must be one of {tuple(_C.MX_FMT)}")
     rows, cols = _rows_cols("x", x)
@@ -105,8 +107,19 @@ def quant_rows_mx(x, fmt="mxfp8_e4m3", gelu=False):
     codes = torch.empty((*x.shape[:-1], cols // 2 if code else cols), dtype=torch.uint8, device=x.device)
     scale = torch.empty((*x.shape[:-1], cols // 32), dtype=torch.uint8, device=x.device)
     with torch.cuda.device(x.device):
-        _C.call("wanq_quant_rows_mx", _C.ptr(x), _C.dt(x), _C.ptr(codes), _C.ptr(scale), rows, cols, code, 1 if gelu else 0, _C.stream())
+        _C.call("wanq_quant_rows_mx_had32" if had32 else "wanq_quant_rows_mx", _C.ptr(x), _C.dt(x), _C.ptr(codes), _C.ptr(scale), rows,
+                cols, code, 1 if gelu else 0, _C.stream())
     return codes, scale
+
+
+def quant_rows_mxfp4(x, gelu=False):
+    """`quant_rows_mx` to packed e2m1 codes: the activation form "mxfp4" of a W4A4 layer."""
+    return quant_rows_mx(x, "mxfp4_e2m1", gelu)
+
+
+def quant_rows_mxfp4_h32(x, gelu=False):
+    """`quant_rows_mx` to packed e2m1 codes behind the block Hadamard rotation: the activation form "mxfp4_h32"."""
+    return quant_rows_mx(x, "mxfp4_e2m1", gelu, had32=True)
 
 
 def _layernorm(output, input, weight, shift_msa, scale_msa, sum_output, scaling, epsilon, quant):

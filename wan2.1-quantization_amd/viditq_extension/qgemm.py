@@ -529,3 +529,31 @@ def mx_linear_refusal(M, N, K, w_fmt="mxfp8_e4m3"):
     if w_fmt not in _C.MX_FMT:
         return f"w_fmt={w_fmt!r} must be one of {tuple(_C.MX_FMT)}"
     return _shape_refusal(M, N, K, MX_K_STEP, bounded=True)
+
+
+# ---- OCP MX W4A4: MXFP4 (e2m1) activations x MXFP4 weights, E8M0 block scales ---------------------------------------------------------
+def mx4_linear(a_q, w_q, a_scale, w_scale, bias=None, out_dtype=None, gelu=False, gate=None, residual=None, out=None):
+    """`mx_linear` with both operands 4 bits wide (wanq_gemm_mx4, csrc/gemm_mx.hip): a_q uint8 [M, K / 2] and w_q uint8 [N, K / 2], packed
+    e2m1 nibbles, a_scale uint8 [M, K / 32], w_scale uint8 [N, K / 32], all as `fused.quant_rows_mx(fmt="mxfp4_e2m1")` writes them (both
+    sides with `had32`, or neither).  The accumulation, epilogue, shape rules (K % 128 == 0, N % 8 == 0) and determinism are
+    `mx_linear`'s.  Not counted by the int8 timer (`set_timer`)."""
+    for name, t in (("a_q", a_q), ("w_q", w_q), ("a_scale", a_scale), ("w_scale", w_scale)):
+        if t is None:
+            raise RuntimeError(f"mx4_linear: {name} must be given")
+        _check_mat(name, t, torch.uint8)
+    M, K = a_q.shape[0], a_q.shape[1] * 2
+    N = w_q.shape[0]
+    why = mx4_linear_refusal(M, N, K)
+    if why is not None:
+        raise RuntimeError(f"mx4_linear: {why}")
+    _C.check_shape("w_q", w_q, N, K // 2)
+    _C.check_shape("a_scale", a_scale, M, K // 32)
+    _C.check_shape("w_scale", w_scale, N, K // 32)
+    return _launch16("wanq_gemm_mx4", (_C.ptr(a_q), _C.ptr(w_q), _C.ptr(a_scale), _C.ptr(w_scale)), (a_q, w_q, a_scale, w_scale), bias,
+                     out_dtype or torch.bfloat16, gelu, gate, residual, out, M, N, K)
+
+
+def mx4_linear_refusal(M, N, K):
+    """Why wanq_gemm_mx4 would refuse an [M, K] x [N, K] product (None = accepted): the shape rules of include/wanq_hip.h in the order
+    the entry checks them; see `fp_linear_refusal`."""
+    return _shape_refusal(M, N, K, MX_K_STEP, bounded=True)

@@ -114,6 +114,8 @@ class QuantWanModel(WanModel, QuantModel):
                                                    else wq.zero_point.reshape(-1).float().clone())
                     if mod.bias is not None:
                         sd[name + ".bias"] = mod.bias.detach().float().clone()
+                    if mod.mx_had32:  # codes made behind the block Hadamard rotation (mx.block_hadamard): recorded with the layer
+                        sd[name + ".mx_had32"] = torch.ones(1, dtype=torch.uint8)
                     if mod.low_rank is not None:  # the LoRC factors, fp32 [Rp, K] / [N, Rp] (an adapter is not part of the weights)
                         sd[name + ".lr_a"] = mod.lr_a.detach().float().clone()
                         sd[name + ".lr_b"] = mod.lr_b.detach().float().clone()
@@ -206,10 +208,18 @@ class QuantWanModel(WanModel, QuantModel):
                     if weight_only and f"{base}.scale_weight" in sd and sd[f"{base}.scale_weight"].dtype == torch.float16:
                         raise NotImplementedError(f"{load_path}: {base} is a weight-only layer and the file is in the reference's "
                                                   "int_weight.pt format, which is W8A8 only (save with reference_format=False)")
+                    # an MX layer's codes are those of one rotation setting: `<name>.mx_had32` says the file's (absent: unrotated)
+                    rec = sd.get(f"{base}.mx_had32", None)
+                    had_file, had_layer = rec is not None and bool(rec.reshape(-1)[0] != 0), bool(getattr(lin, "had32", False))
+                    if had_file != had_layer:
+                        raise ValueError(f"{load_path}: {base} holds codes quantised {'behind' if had_file else 'without'} the block "
+                                         f"Hadamard rotation (mx.block_hadamard) and the model's layer was built "
+                                         f"{'with' if had_layer else 'without'} it: the two are not interchangeable")
                     for buf, k, required in (("weight", "weight", True), ("scale_weight", "scale_weight", True),
                                              ("zp_weight", "zp_weight", lin.zp_weight is not None),
                                              ("bias", "bias", lin.bias is not None),
                                              ("act_premul", "act_premul", lin.act_premul is not None),
+                                             ("mx_had32", "mx_had32", had_layer),
                                              ("lr_a", "lr_a", getattr(lin, "lr_a", None) is not None),
                                              ("lr_b", "lr_b", getattr(lin, "lr_b", None) is not None)):
                         dst = getattr(lin, buf, None)

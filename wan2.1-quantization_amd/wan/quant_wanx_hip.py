@@ -40,7 +40,7 @@ class _HipLinear(nn.Module):
     fp8 = False
     mx = None              # HipLinearMx: the weight's MX format name
     weight_only = False
-    act_form = "fp"        # what its input is made into: "fp" (16 bits, no quantiser), "int8", "fp8" or "mxfp8"
+    act_form = "fp"        # what its input is made into: "fp" (16 bits, no quantiser), "int8", "fp8", "mxfp8", "mxfp4" or "mxfp4_h32"
     act_key = "fp"         # layers with the same key share one copy of their input
     plain_rows = False     # its quantiser takes the source's row without a transform, so it can apply the FFN's GELU itself
     rot = act_quantizer = None
@@ -383,26 +383,40 @@ class HipLinearFp8(_HipLinearCodes):
 
 
 class HipLinearMx(_HipLinearCodes):
-    """An OCP MX Linear (`format: mxfp8_e4m3` activations against `mxfp8_e4m3` / `mxfp4_e2m1` weights): `weight` uint8 [N, K] e4m3
-    bytes or [N, K / 2] packed e2m1 nibbles, `scale_weight` uint8 [N, K / 32] E8M0 bytes, both from wanq_quant_rows_mx; `bias` fp32.
-    Its input is the block's activation quantised per block of 32 channels by the same entry (codes + scale bytes), and the product is
-    qgemm.mx_linear (csrc/gemm_mx.hip) with GELU and gate + residual in its epilogue."""
+    """An OCP MX Linear (`format: mxfp8_e4m3` activations against `mxfp8_e4m3` / `mxfp4_e2m1` weights, or with `a_fmt` "mxfp4_e2m1"
+    the W4A4 pair): `weight` uint8 [N, K] e4m3 bytes or [N, K / 2] packed e2m1 nibbles, `scale_weight` uint8 [N, K / 32] E8M0 bytes,
+    both from wanq_quant_rows_mx; `bias` fp32.  Its input is the block's activation quantised per block of 32 channels by the same
+    entry (codes + scale bytes), and the product is qgemm.mx_linear, or qgemm.mx4_linear for e2m1 activations (csrc/gemm_mx.hip),
+    with GELU and gate + residual in its epilogue.  `had32` (W4A4 only, the config's `mx.block_hadamard`): the weight codes were
+    made behind the block Hadamard rotation and the input is quantised behind it too (activation form "mxfp4_h32"); the layer then
+    holds the one-element uint8 buffer `mx_had32`, which travels with its codes in the integer checkpoint."""
     act_form = act_key = "mxfp8"
     sharded = ("weight", "scale_weight")   # the scale bytes are a thirty-second or a sixteenth of the weight's
 
-    def __init__(self, in_features, out_features, bias=True, w_fmt="mxfp8_e4m3", name="linear"):
-        super().__init__(in_features, out_features, bias, w_fmt, qgemm.mx_linear_refusal(1, out_features, in_features, w_fmt),
+    def __init__(self, in_features, out_features, bias=True, w_fmt="mxfp8_e4m3", name="linear", a_fmt="mxfp8_e4m3", had32=False):
+        a4 = a_fmt == "mxfp4_e2m1"
+        if a_fmt not in ("mxfp8_e4m3", "mxfp4_e2m1") or (a4 and w_fmt != "mxfp4_e2m1") or (had32 and not a4):
+            raise NotImplementedError(f"{name}: no MX GEMM takes weight {w_fmt} against act {a_fmt}" + (" behind the block rotation" if had32 else ""))
+        why = qgemm.mx4_linear_refusal(1, out_features, in_features) if a4 else qgemm.mx_linear_refusal(1, out_features, in_features, w_fmt)
+        super().__init__(in_features, out_features, bias, w_fmt, why,
                          in_features // 2 if w_fmt == "mxfp4_e2m1" else in_features, (out_features, in_features // 32), torch.uint8, name)
-        self.mx = w_fmt
+        self.mx, self.a_fmt, self.had32 = w_fmt, a_fmt, bool(had32)
+        if a4:
+            self.act_form = self.act_key = "mxfp4_h32" if had32 else "mxfp4"
+        if had32:
+            self.register_buffer("mx_had32", torch.ones(1, dtype=torch.uint8))
 
     @classmethod
     def from_quantized(cls, ql, name="linear"):
         """From a plain qdiff QuantizedLinear built with an MX format: the same codes and scale bytes."""
-        m = cls(ql.in_features, ql.out_features, ql.bias is not None, ql.mx, name).to(ql.fp_module.weight.device)
+        m = cls(ql.in_features, ql.out_features, ql.bias is not None, ql.mx, name, ql.mx_act, ql.mx_had32).to(ql.fp_module.weight.device)
         return m._take(ql, ql.w_quantizer.scale_u8, name)
 
     def forward(self, a_q, a_scale, out_dtype=torch.bfloat16, gelu=False, gate=None, residual=None, out=None):
         """Reads `weight` and `scale_weight` as they are now (--dit_fsdp re-points them at views of the gathered buffer)."""
+        if self.a_fmt == "mxfp4_e2m1":
+            return qgemm.mx4_linear(a_q, self.weight, a_scale, self.scale_weight, self.bias, out_dtype, gelu=gelu, gate=gate,
+                                    residual=residual, out=out)
         return qgemm.mx_linear(a_q, self.weight, a_scale, self.scale_weight, self.mx, self.bias, out_dtype, gelu=gelu, gate=gate,
                                residual=residual, out=out)
 
@@ -430,7 +444,7 @@ def _to_hip_linear(lin, n_bits, sym, act_dtype, fp_gemm="torch", name="linear"):
 
 
 # activation form -> the fused row quantiser that makes it, (codes, scales) = f(rows, gelu=); a new form adds its entry here
-_ROW_QUANTISERS = {"fp8": "quant_rows_fp8", "mxfp8": "quant_rows_mx"}
+_ROW_QUANTISERS = {"fp8": "quant_rows_fp8", "mxfp8": "quant_rows_mx", "mxfp4": "quant_rows_mxfp4", "mxfp4_h32": "quant_rows_mxfp4_h32"}
 
 
 class _Src:
@@ -438,7 +452,7 @@ class _Src:
 
     def rows(self, form):
         """(codes, scales) of this activation in `form` for every consumer of it (HipLinearFp8: e4m3 codes + fp32 scale;
-        HipLinearMx: e4m3 codes + E8M0 scale bytes), quantised from what `_plain_row` hands over."""
+        HipLinearMx: e4m3 or packed e2m1 codes + E8M0 scale bytes), quantised from what `_plain_row` hands over."""
         if form not in self.cache:
             x, gelu = self._plain_row()
             self.cache[form] = getattr(fused, _ROW_QUANTISERS[form])(x, gelu=gelu)
