@@ -98,7 +98,7 @@ int wanq_quant_rows_fp8(const void* x, int x_dtype, uint8_t* q, float* scale, in
  * gets s = 255 - emax and unspecified codes for the infinite elements.  Nothing is trapped; no test pins these.
  * Bit-identical to the host expression mx_quant_rows of qdiff/base/base_quantizer.py.
  * No reference counterpart: the reference's Linear formats are integer ones. */
-enum { WANQ_MX_E4M3 = 0, WANQ_MX_E2M1 = 1 };
+enum { WANQ_MX_E4M3 = 0, WANQ_MX_E2M1 = 1, WANQ_MX_E2M3 = 2 };   /* E2M3: wanq_quant_rows_mx6 / wanq_gemm_mx6 only */
 int wanq_quant_rows_mx(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int fmt, int act,
                        void* stream);
 
@@ -112,6 +112,21 @@ int wanq_quant_rows_mx(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8
  * No reference counterpart. */
 int wanq_quant_rows_mx_had32(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int fmt, int act,
                              void* stream);
+
+/* OCP MXFP6 (e2m3) block quantisation: wanq_quant_rows_mx's row frame, GELU option, block maximum and argument rules, to 6-bit codes.
+ * The format (WANQ_MX_E2M3; config name mxfp6_e2m3fn: finite only), defined here and as a host expression in
+ * qdiff/base/base_quantizer.py:
+ *   code  6 bits: sign in bit 5, E in bits 3-4 (bias 1), M in bits 0-2.  E = 0: M / 8;  E > 0: 2^(E - 1) (1 + M / 8).  Largest
+ *         magnitude 7.5; no inf, no NaN; the magnitude codes 0-31 ascend with the value.
+ *   s     = clamp(E(amax) - 2, 0, 254): emax 2 as for e2m1, so a row's scale bytes are those wanq_quant_rows_mx(fmt E2M1) writes.
+ *   c     : t = clamp(ldexp(x, 127 - s), -7.5, 7.5);  quantum q = 1/8 for |t| < 2, 1/4 for |t| < 4, else 1/2;  |c| = rne(|t| / q) q,
+ *           ONE rounding, ties to the even code.  -0 and negative values that round to zero keep their sign bit.
+ *   q     [rows, 3 cols / 4] bytes: block b of a row is bytes 24 b .. 24 b + 23, element j of the block bits 6 j .. 6 j + 5 of that
+ *         192-bit little-endian string.  This is the order in which v_mfma_scale_f32_16x16x128_f8f6f4 takes a 6-bit operand's six
+ *         registers (one block per lane group; probes A of tests/test_gpu_mx6.py), so wanq_gemm_mx6 never re-packs anything.
+ * scale_u8: uint8 [rows, cols / 32].  x, cols, act, alignment of q (16 bytes) and the non-finite behaviour: wanq_quant_rows_mx's.
+ * Bit-identical to the host expression mx_quant_rows_host(fmt "mxfp6_e2m3fn").  No reference counterpart. */
+int wanq_quant_rows_mx6(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int act, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * LayerNorm (no bias, optional gamma) -> optional adaLN modulate -> fp output OR int8 quant (+sum).
@@ -607,6 +622,21 @@ int wanq_gemm_mx(const uint8_t* a, const uint8_t* w, const uint8_t* sa_u8, const
  * any m and in a launch of any M, and repeated calls are bit-identical.
  * No reference counterpart. */
 int wanq_gemm_mx4(const uint8_t* a, const uint8_t* w, const uint8_t* sa_u8, const uint8_t* sw_u8, void* out, int out_dtype,
+                  const void* bias, int bias_dtype, const float* gate, const void* residual, int epi_flags, int64_t M, int N, int K,
+                  void* stream);
+
+/* MXFP6 GEMMs, W6A6 and W4A6: e2m3 activations (wanq_quant_rows_mx6) against e2m3 weights (w_fmt WANQ_MX_E2M3, the same entry once
+ * at conversion) or packed e2m1 weights (w_fmt WANQ_MX_E2M1, wanq_quant_rows_mx), on v_mfma_scale_f32_16x16x128_f8f6f4 with no
+ * operand 8 bits wide (the instruction's fp4 rate).  Semantics, epilogue, shape rules and determinism statement are wanq_gemm_mx4's:
+ *   acc[m,n] = sum_b 2^(sa[m,b] - 127) 2^(sw[n,b] - 127) sum_{k in block b} a[m,k] * w[n,k];  y = acc + bias[n];  GELU;
+ *   residual + y * gate;  one rounding to out_dtype.
+ * a: packed e2m3 codes [M, 3 K / 4].  w: packed e2m3 codes [N, 3 K / 4] or packed e2m1 nibbles [N, K / 2].  sa_u8 [M, K / 32], sw_u8
+ * [N, K / 32]: E8M0 bytes, 4-byte aligned.  Any M >= 1 (M == 0 returns WANQ_OK); N % 8 == 0; K % 128 == 0 (a row and a K-tile's 96
+ * bytes are then 16-byte aligned).  a, w, out and residual 16-byte aligned, gate and bias aligned to 4 elements.  Any other w_fmt
+ * and anything else is refused (WANQ_E_SHAPE / WANQ_E_ARG, the message names the rule).
+ * Determinism: one kernel form per w_fmt, no split-K; the summation order of element (m, n) depends on K only.
+ * No reference counterpart. */
+int wanq_gemm_mx6(const uint8_t* a, const uint8_t* w, const uint8_t* sa_u8, const uint8_t* sw_u8, int w_fmt, void* out, int out_dtype,
                   const void* bias, int bias_dtype, const float* gate, const void* residual, int epi_flags, int64_t M, int N, int K,
                   void* stream);
 

@@ -1,7 +1,7 @@
 // What the four tile GEMMs outside the int8 family share.  gemm_bf16.hip (bf16 / fp16 operands), gemm_fp8.hip (e4m3, fp32 row and
 // channel scales) and gemm_mx.hip (OCP MX: e4m3 tokens against e4m3 or packed e2m1 weights, E8M0 block scales) copy BOTH halves of
 // a K-tile into LDS and are one kernel, gemm_tile_kernel below, with a policy each (gemm_mx.hip's W4A4 form, packed e2m1 on both
-// sides, is one more policy of it); gemm_wq16.hip (integer weight codes converted
+// sides, and its W6A6 / W4A6 forms, packed e2m3 tokens, are further policies of it); gemm_wq16.hip (integer weight codes converted
 // in registers, plain and group-wise) copies the token half only and has its own loop.  All four use the tile geometry, Frame, the
 // LDS-DMA sources and issue, the fragment addresses and reads, epilogue16, the launch parameters and helpers and the argument rules
 // of the extern "C" entries; gemm_tile_kernel is used by the first three.
@@ -23,10 +23,12 @@
 //   OUT, SCALED, TOKEN   the epilogue16 instantiation
 //   TKE, KMUL            elements of a K-tile and the entry's K multiple; when KMUL is half of TKE a last tile may be half deep: its
 //                        second 16-byte step is then read from the first step's addresses and `half` tells the MFMA block
-//   WROW                 bytes of a weight row per K-tile: TROW, or W4ROW for gemm_mx.hip's packed e2m1 rows (their own swizzle)
+//   WROW                 bytes of a weight row per K-tile: TROW, W4ROW for gemm_mx.hip's packed e2m1 rows (their own swizzle), or
+//                        W6ROW (96 B) for its packed e2m3 rows: three DMA instructions per wave, w6_swz, three ds_read_b64 per
+//                        fragment, and mma6 in place of mma (gemm_mx.hip has the derivation)
 //   XROW                 bytes of a token row per K-tile, likewise: W4ROW (with WROW == W4ROW only) for gemm_mx.hip's e2m1 tokens, whose
 //                        half is then the same 128 rows of 64 B, the same two DMA instructions per wave and the same swizzle and
-//                        one-chunk fragment read as the packed weight half
+//                        one-chunk fragment read as the packed weight half; W6ROW (with WROW == W6ROW or W4ROW) for its e2m3 tokens
 //   Side                 per-tile values a lane loads itself, one tile ahead behind the DMA (gemm_mx.hip's scale dwords), or NoSide
 //   mma                  the MFMA block of one K-tile
 //
@@ -42,6 +44,7 @@
 namespace wanq {
 namespace {
 
+typedef int v2i __attribute__((ext_vector_type(2)));
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -54,6 +57,7 @@ constexpr int TM = 128, TN = 128, TK = 64;
 constexpr int TROW = TK * 2;      // bytes of one LDS row
 constexpr int XTILE = TM * TROW;  // a half of a K-tile buffer (128 rows): 16 KiB
 constexpr int W4ROW = TROW / 2;   // bytes of a packed e2m1 weight row of a K-tile
+constexpr int W6ROW = 96;         // bytes of a packed e2m3 row of a K-tile: four blocks of 32 six-bit codes (gemm_mx.hip)
 
 // launch parameters of all four files; sa / sw: fp32 (gemm_fp8.hip, and sw of gemm_wq16.hip), E8M0 bytes (gemm_mx.hip) or null
 struct Gemm16Params {
@@ -88,6 +92,21 @@ __device__ __forceinline__ void dsr(v4i& d, uint32_t addr) {
 template <int ROW>
 __device__ __forceinline__ void dsr4(v4i (&d)[4], uint32_t addr) {
   dsr<0>(d[0], addr); dsr<16 * ROW>(d[1], addr); dsr<32 * ROW>(d[2], addr); dsr<48 * ROW>(d[3], addr);
+}
+
+// packed e2m3 rows (W6ROW): one 8-byte piece of a fragment (gemm_mx.hip: a 24-byte block is three of them, 8-byte aligned only)
+template <int OFF>
+__device__ __forceinline__ void dsr64(v2i& d, uint32_t addr) {
+  asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF));
+}
+
+// piece p of the e2m3 fragment of each of a wave's four 16-row blocks, addr[p] as frag6_addr gives it
+__device__ __forceinline__ void dsr4x6(v2i (&d)[3][4], const uint32_t (&addr)[3], uint32_t off) {
+#pragma unroll
+  for (int p = 0; p < 3; ++p) {
+    dsr64<0>(d[p][0], addr[p] + off); dsr64<16 * W6ROW>(d[p][1], addr[p] + off);
+    dsr64<32 * W6ROW>(d[p][2], addr[p] + off); dsr64<48 * W6ROW>(d[p][3], addr[p] + off);
+  }
 }
 
 template <bool F16IN>
@@ -241,11 +260,35 @@ __device__ __forceinline__ void dma_sources4(const void* base, int row0, int row
   }
 }
 
+// packed e2m3 rows (96 B, the third geometry; gemm_mx.hip has the bank derivation): LDS 16-byte chunk g of a half is row g / 6,
+// physical chunk g % 6 = logical chunk c ^ w6_swz(row).  c ^ 1 stays inside the row's six chunks.
+__device__ __forceinline__ int w6_swz(int r) { return (r >> 3) & 1; }
+
+// LDS-DMA sources of a half of 128 packed e2m3 rows x 96 B = 768 chunks: instruction q (0-2) of this wave fills chunks 64 g .. 64 g +
+// 63, g = 4 q + wave, lane l chunk 64 g + l.  `pitch` bytes per row of `base`; rows past `rows` read row rows - 1.
+__device__ __forceinline__ void dma_sources6(const void* base, int row0, int rows, int64_t pitch, const Frame& f, const char* (&src)[4]) {
+#pragma unroll
+  for (int q = 0; q < 3; ++q) {
+    const int g = 64 * (4 * q + f.wave) + f.lane, r = g / 6;
+    const int c = (g - 6 * r) ^ w6_swz(r);
+    const int row = row0 + r < rows ? row0 + r : rows - 1;
+    src[q] = static_cast<const char*>(base) + row * pitch + c * 16;
+  }
+}
+
+// an e2m3 fragment: the 24 bytes of block fq of row fr, as the 8-byte pieces p = 0, 1, 2: bytes 8 (3 fq + p) of the row, i.e. half
+// (3 fq + p) & 1 of logical chunk (3 fq + p) >> 1
+__device__ __forceinline__ uint32_t frag6_addr(uint32_t lds0, int fr, int fq, int p) {
+  const int s = 3 * fq + p;
+  return lds0 + fr * W6ROW + (((s >> 1) ^ w6_swz(fr)) << 4) + ((s & 1) << 3);
+}
+
 template <class P>
 __global__ void __launch_bounds__(256, 2) gemm_tile_kernel(Gemm16Params p) {
-  constexpr bool W4 = P::WROW == W4ROW, X4 = P::XROW == W4ROW, SHORT = P::KMUL < P::TKE;
+  constexpr bool W4 = P::WROW == W4ROW, X4 = P::XROW == W4ROW, W6 = P::WROW == W6ROW, X6 = P::XROW == W6ROW, SHORT = P::KMUL < P::TKE;
   constexpr int XT = TM * P::XROW, TILE = XT + TN * P::WROW;  // one K-tile buffer: token rows, then weight rows
-  static_assert((W4 || P::WROW == TROW) && (X4 ? W4 : P::XROW == TROW) && (P::KMUL == P::TKE || (P::KMUL * 2 == P::TKE && !W4)),
+  static_assert((W4 || W6 || P::WROW == TROW) && (X4 ? W4 : X6 ? (W4 || W6) : (P::XROW == TROW && !W6)) &&
+                    (P::KMUL == P::TKE || (P::KMUL * 2 == P::TKE && !W4 && !W6)),
                 "no such geometry");
   __shared__ __attribute__((aligned(1024))) char smem[2 * TILE];
   const Frame f(p.nt);
@@ -254,9 +297,12 @@ __global__ void __launch_bounds__(256, 2) gemm_tile_kernel(Gemm16Params p) {
   // ---- LDS-DMA sources: 128-B token and weight rows as dma_sources has them, packed e2m1 rows as dma_sources4
   const char *src[4], *wsrc[4];
   int kc = 0;  // (the token half's logical chunk: what a half-deep last tile asks about)
-  if constexpr (X4) dma_sources4(p.a, f.m0, p.M, K / 2, f, src);
+  if constexpr (X6) dma_sources6(p.a, f.m0, p.M, (int64_t)K * W6ROW / P::TKE, f, src);
+  else if constexpr (X4) dma_sources4(p.a, f.m0, p.M, K / 2, f, src);
   else kc = dma_sources(p.a, f.m0, p.M, (int64_t)K * TROW / P::TKE, f, src);
-  if constexpr (W4 && !X4) {  // (dma_sources4 written out: the form the W4A8 kernels were built and measured with)
+  if constexpr (W6) {
+    dma_sources6(p.w, f.n0, p.N, (int64_t)K * W6ROW / P::TKE, f, wsrc);
+  } else if constexpr (W4 && !X4 && !X6) {  // (dma_sources4 written out: the form the W4A8 kernels were built and measured with)
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int r = 16 * (4 * q + f.wave) + (f.lane >> 2);
@@ -282,6 +328,11 @@ __global__ void __launch_bounds__(256, 2) gemm_tile_kernel(Gemm16Params p) {
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
   const uint32_t rd0 = frag_addr(lds0, f.fr, f.fq, 0), rd1 = frag_addr(lds0, f.fr, f.fq, 1);
   const uint32_t rdw4 = lds0 + f.fr * W4ROW + ((f.fq ^ w4_swz(f.fr)) << 4);  // an e2m1 fragment: the one chunk fq of its row
+  uint32_t rd6[3] = {0, 0, 0};  // an e2m3 fragment: three 8-byte pieces of block fq of its row
+  if constexpr (W6 || X6) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) rd6[q] = frag6_addr(lds0, f.fr, f.fq, q);
+  }
   typename P::Side side(p, f);
 
   v4f acc[4][4];
@@ -301,15 +352,25 @@ __global__ void __launch_bounds__(256, 2) gemm_tile_kernel(Gemm16Params p) {
     __builtin_amdgcn_sched_barrier(0);
     const uint32_t xo = (t & 1) * TILE + f.wm * 64 * P::XROW, wo = (t & 1) * TILE + XT + f.wn * 64 * P::WROW;
     v4i xa[2][4], wb[2][4];  // [16-byte step][16-row block]; an e2m1 fragment is wb[0] / xa[0] alone
-    if constexpr (W4) dsr4<W4ROW>(wb[0], rdw4 + wo);
-    else dsr4<TROW>(wb[0], rd0 + wo);
-    if constexpr (X4) dsr4<W4ROW>(xa[0], rdw4 + xo);
-    else dsr4<TROW>(xa[0], rd0 + xo);
-    if constexpr (!W4) dsr4<TROW>(wb[1], rd1 + wo);
-    if constexpr (!X4) dsr4<TROW>(xa[1], rd1 + xo);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    P::mma(acc, wb, xa, side, SHORT && t * P::TKE + P::KMUL >= K);
+    if constexpr (W6 || X6) {
+      v2i x6[3][4], w6[3][4];  // [8-byte piece][16-row block] of an e2m3 fragment
+      if constexpr (W6) dsr4x6(w6, rd6, wo);
+      else dsr4<W4ROW>(wb[0], rdw4 + wo);
+      dsr4x6(x6, rd6, xo);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      P::mma6(acc, wb[0], w6, x6, side);
+    } else {
+      if constexpr (W4) dsr4<W4ROW>(wb[0], rdw4 + wo);
+      else dsr4<TROW>(wb[0], rd0 + wo);
+      if constexpr (X4) dsr4<W4ROW>(xa[0], rdw4 + xo);
+      else dsr4<TROW>(xa[0], rd0 + xo);
+      if constexpr (!W4) dsr4<TROW>(wb[1], rd1 + wo);
+      if constexpr (!X4) dsr4<TROW>(xa[1], rd1 + xo);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      P::mma(acc, wb, xa, side, SHORT && t * P::TKE + P::KMUL >= K);
+    }
     __builtin_amdgcn_sched_barrier(0);
   }
 

@@ -335,6 +335,10 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const Fp8RowParams 
 // behind the clamp as in the fp8 quantiser, e2m1 by seven comparisons against the midpoints (> where the tie goes down to the even
 // code, >= where it goes up).  e4m3 codes leave as 8-byte chunks, e2m1 codes as one dword of eight nibbles (even k low), the scale
 // byte from the quad's first lane.
+// FP6 (wanq_quant_rows_mx6, e2m3): the scale of e2m1 (emax 2); the code is rne(|t| / q) + {0, 8, 16} with the binade's quantum q = 1/8,
+// 1/4, 1/2 (one v_rndne_f32 of an exact product; the magnitude codes ascend with the value, so a carry into the next binade is the
+// next code).  A lane's eight codes are 48 bits and the quad's 192 bits are the block's 24 bytes: lane k of the quad takes the low
+// dword and high half-word of lane k + 1 by one DPP quad rotation each and lanes 0-2 store the aligned 8-byte words 0-2 of the block.
 // HAD (wanq_quant_rows_mx_had32): behind the GELU and in front of the block maximum every block is replaced by its unnormalised 32-point
 // Sylvester-Hadamard transform, five fp32 butterfly stages h = 1, 2, 4, 8, 16 with (x_i, x_{i+h}) <- (x_i + x_{i+h}, x_i - x_{i+h})
 // for bit h of i clear.  Element i of a block is chunk element i & 7 of quad lane i >> 3: stages 1, 2, 4 stay inside the chunk, stages
@@ -355,6 +359,17 @@ __device__ __forceinline__ uint32_t e2m1_code(float t) {
   const uint32_t mag = (uint32_t)(a > 0.25f) + (uint32_t)(a >= 0.75f) + (uint32_t)(a > 1.25f) + (uint32_t)(a >= 1.75f) +
                        (uint32_t)(a > 2.5f) + (uint32_t)(a >= 3.5f) + (uint32_t)(a > 5.0f);
   return mag | ((__float_as_uint(t) >> 28) & 8u);
+}
+
+__device__ __forceinline__ uint32_t e2m3_code(float t) {
+  const float a = fminf(fabsf(t), 7.5f);
+  const float r = a < 2.0f ? rintf(a * 8.0f) : a < 4.0f ? rintf(a * 4.0f) + 8.0f : rintf(a * 2.0f) + 16.0f;
+  return (uint32_t)r | ((__float_as_uint(t) >> 26) & 32u);
+}
+
+// the value of the quad's next lane (lane 3: lane 0's, unused)
+__device__ __forceinline__ uint32_t quad_next_dpp(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x39, 0xf, 0xf, true);  // quad_perm:[1,2,3,0]
 }
 
 // one butterfly stage inside a chunk: H = 1, 2 or 4
@@ -379,13 +394,14 @@ __device__ __forceinline__ void had_stage_quad(float (&v)[8], bool upper) {
   }
 }
 
-template <int WPR, int NCH, bool FP4, bool HAD = false>
+template <int WPR, int NCH, bool FP4, bool HAD = false, bool FP6 = false>
 __global__ __launch_bounds__(256) void quant_rows_mx_kernel(const MxRowParams p) {
+  static_assert(!(FP6 && (FP4 || HAD)), "e2m3 is a format of its own, without the rotation");
   RowFrame<WPR, NCH> f;
   if (f.surplus(p.rows)) return;
   const int C = p.cols;
   const int64_t rbase = f.row * (int64_t)C;
-  constexpr int EMAX = FP4 ? 2 : 8;
+  constexpr int EMAX = FP4 || FP6 ? 2 : 8;
 
   float v[NCH][8];
   bool ok[NCH];
@@ -417,7 +433,18 @@ __global__ __launch_bounds__(256) void quant_rows_mx_kernel(const MxRowParams p)
 #pragma unroll
     for (int j = 0; j < 8; ++j) t[j] = ldexpf(v[i][j], 127 - s);
     const int col = f.col(i);
-    if constexpr (FP4) {
+    if constexpr (FP6) {
+      uint64_t c = 0;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) c |= (uint64_t)e2m3_code(t[j]) << (6 * j);
+      const uint32_t lo = (uint32_t)c, hi = (uint32_t)(c >> 32);  // 48 bits: bits 48 k .. 48 k + 47 of the block, k the quad lane
+      const uint32_t nlo = quad_next_dpp(lo), nhi = quad_next_dpp(hi);
+      const int k = (col >> 3) & 3;
+      const uint2 w = k == 0 ? make_uint2(lo, hi | (nlo << 16))
+                    : k == 1 ? make_uint2((lo >> 16) | (hi << 16), nlo)
+                             : make_uint2(hi | (nlo << 16), (nlo >> 16) | (nhi << 16));
+      if (k < 3) *reinterpret_cast<uint2*>(p.q + ((rbase + col) >> 5) * 24 + 8 * k) = w;
+    } else if constexpr (FP4) {
       uint32_t w = 0;
 #pragma unroll
       for (int j = 0; j < 8; ++j) w |= e2m1_code(t[j]) << (4 * j);
@@ -526,6 +553,24 @@ extern "C" int wanq_quant_rows_mx(const void* x, int x_dtype, uint8_t* q, uint8_
 extern "C" int wanq_quant_rows_mx_had32(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int fmt,
                                         int act, void* stream) {
   return quant_rows_mx_entry<true>("wanq_quant_rows_mx_had32", x, x_dtype, q, scale_u8, rows, cols, fmt, act, stream);
+}
+
+extern "C" int wanq_quant_rows_mx6(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int act,
+                                   void* stream) {
+  const char* what = "wanq_quant_rows_mx6";
+  WANQ_REQUIRE(x && q && scale_u8, WANQ_E_ARG, "%s: x, q and scale_u8 must be non-NULL", what);
+  WANQ_REQUIRE(is_fp(x_dtype), WANQ_E_ARG, "%s: bad x dtype %d", what, x_dtype);
+  WANQ_REQUIRE(act == 0 || act == 1, WANQ_E_ARG, "%s: act must be 0 or 1", what);
+  if (int e = check_rows_cols(what, rows, cols)) return e;
+  WANQ_REQUIRE(cols % 32 == 0, WANQ_E_SHAPE, "%s: cols=%d must be a multiple of 32 (one scale per block of 32)", what, cols);
+  WANQ_REQUIRE((reinterpret_cast<uintptr_t>(q) & 15) == 0, WANQ_E_ARG, "%s: q must be 16-byte aligned", what);
+  if (rows == 0) return WANQ_OK;
+  const MxRowParams p{x, x_dtype, q, scale_u8, rows, cols, act};
+  row_ladder(cols, rows, [&](auto wpr, auto nch, dim3 grid) {
+    hipLaunchKernelGGL((quant_rows_mx_kernel<decltype(wpr)::value, decltype(nch)::value, false, false, true>), grid, dim3(256), 0,
+                       (hipStream_t)stream, p);
+  });
+  return check_launch(what);
 }
 
 extern "C" int wanq_layernorm_rows(const void* x, int x_dtype, const void* gamma, const void* mshift,

@@ -237,11 +237,14 @@ class Fp8Quantizer(BaseQuantizer):
 # One E8M0 power-of-two scale per block of 32 consecutive input channels (include/wanq_hip.h, wanq_quant_rows_mx).  Repository-
 # defined; the reference has no counterpart.  What follows is the host expression of the format: what simulation mode runs in host
 # memory and what the GPU entry is bit-equal to.
-MXFP8_FORMAT, MXFP4_FORMAT = "mxfp8_e4m3", "mxfp4_e2m1"
-MX_FORMATS = (MXFP8_FORMAT, MXFP4_FORMAT)
+MXFP8_FORMAT, MXFP4_FORMAT, MXFP6_FORMAT = "mxfp8_e4m3", "mxfp4_e2m1", "mxfp6_e2m3fn"
+MX_FORMATS = (MXFP8_FORMAT, MXFP4_FORMAT, MXFP6_FORMAT)
 MX_BLOCK = 32
-_MX_SPEC = {MXFP8_FORMAT: (8, 448.0, 0), MXFP4_FORMAT: (2, 6.0, 1)}   # emax, largest magnitude, the `fmt` code of the C ABI
+# emax, largest magnitude, the `fmt` code of the C ABI (WANQ_MX_E2M3 = 2 is wanq_quant_rows_mx6's and wanq_gemm_mx6's alone)
+_MX_SPEC = {MXFP8_FORMAT: (8, 448.0, 0), MXFP4_FORMAT: (2, 6.0, 1), MXFP6_FORMAT: (2, 7.5, 2)}
 E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+# the 32 e2m3 magnitudes by code: E in bits 3-4 (bias 1), M in bits 0-2; E = 0: M / 8, else 2^(E - 1) (1 + M / 8)
+E2M3_VALUES = tuple((c & 7) / 8 if c < 8 else 2.0 ** ((c >> 3) - 1) * (1 + (c & 7) / 8) for c in range(32))
 
 
 def mx_fmt_code(fmt):
@@ -261,6 +264,23 @@ def mx_pack_e2m1(codes):
 def mx_unpack_e2m1(packed):
     """[rows, cols / 2] bytes -> [rows, cols] 4-bit codes"""
     return torch.stack((packed & 0xf, packed >> 4), dim=-1).reshape(*packed.shape[:-1], packed.shape[-1] * 2)
+
+
+def mx_pack_e2m3(codes):
+    """[rows, cols] 6-bit codes -> [rows, 3 cols / 4] bytes: block b of 32 codes is bytes 24 b .. 24 b + 23, element j of the block in bits
+    6 j .. 6 j + 5 of that 192-bit little-endian string.  Four codes make three bytes and 32 is a multiple of 4, so this is the
+    little-endian packing of the whole row."""
+    c = codes.to(torch.int32).reshape(*codes.shape[:-1], codes.shape[-1] // 4, 4)
+    w = c[..., 0] | (c[..., 1] << 6) | (c[..., 2] << 12) | (c[..., 3] << 18)
+    return torch.stack((w & 0xff, (w >> 8) & 0xff, w >> 16), dim=-1).to(torch.uint8).reshape(*codes.shape[:-1], codes.shape[-1] // 4 * 3)
+
+
+def mx_unpack_e2m3(packed):
+    """[rows, 3 cols / 4] bytes -> [rows, cols] 6-bit codes"""
+    b = packed.to(torch.int32).reshape(*packed.shape[:-1], packed.shape[-1] // 3, 3)
+    w = b[..., 0] | (b[..., 1] << 8) | (b[..., 2] << 16)
+    return torch.stack((w & 63, (w >> 6) & 63, (w >> 12) & 63, w >> 18), dim=-1).to(torch.uint8).reshape(
+        *packed.shape[:-1], packed.shape[-1] // 3 * 4)
 
 
 def mx_hadamard32_host(x):
@@ -285,9 +305,13 @@ def mx_quant_rows_host(x, fmt, gelu=False, had32=False):
     """(codes uint8, scale bytes uint8 [rows, cols / 32]) of the block quantiser, in torch on x's device.  Per block: amax, E = its
     biased fp32 exponent field, s = clamp(E - emax, 0, 254), c = rne(clamp(x 2^(127 - s), -max, max)).  The scaling is done in
     float64, where it is exact; the one rounding is the cast to e4m3fn (this torch build rounds to nearest even and keeps subnormals)
-    or, for e2m1, the comparison against the seven midpoints with ties to the even code.  `had32`: the blocks go through
-    mx_hadamard32_host behind the GELU and in front of the block maximum (wanq_quant_rows_mx_had32)."""
+    or, for e2m1, the comparison against the seven midpoints with ties to the even code, or, for e2m3 (`mxfp6_e2m3fn`, include/wanq_hip.h:
+    wanq_quant_rows_mx6), rne(|t| / q) with the binade's quantum q = 1/8 for |t| < 2, 1/4 for |t| < 4, else 1/2 -- the magnitude codes
+    ascend with the value, so the code is that integer plus 0, 8 or 16 and the tie goes to the even code.  `had32`: the blocks go
+    through mx_hadamard32_host behind the GELU and in front of the block maximum (wanq_quant_rows_mx_had32; not for e2m3)."""
     emax, vmax, _ = _MX_SPEC[fmt]
+    if had32 and fmt == MXFP6_FORMAT:
+        raise ValueError(f"mx_quant_rows: {MXFP6_FORMAT} has no had32 form")
     x = x.float()
     if gelu:
         x = torch.nn.functional.gelu(x, approximate="tanh")
@@ -302,6 +326,10 @@ def mx_quant_rows_host(x, fmt, gelu=False, had32=False):
     t = (xb.double() * _pow2_f64(127 - s).unsqueeze(-1)).clamp(-vmax, vmax).reshape(rows, cols)
     if fmt == MXFP8_FORMAT:
         codes = t.float().to(torch.float8_e4m3fn).view(torch.uint8)
+    elif fmt == MXFP6_FORMAT:
+        a = t.abs()
+        mag = torch.where(a < 2, torch.round(a * 8), torch.where(a < 4, torch.round(a * 4) + 8, torch.round(a * 2) + 16))
+        codes = mx_pack_e2m3(mag.to(torch.uint8) | (torch.signbit(t).to(torch.uint8) << 5))
     else:
         a = t.abs()
         mag = ((a > 0.25).to(torch.uint8) + (a >= 0.75) + (a > 1.25) + (a >= 1.75) + (a > 2.5) + (a >= 3.5) + (a > 5.0)).to(torch.uint8)
@@ -322,6 +350,10 @@ def mx_decode(codes, scale_u8, fmt, dtype=torch.float32):
     result is a normal fp32 number, as for anything the quantiser wrote)."""
     if fmt == MXFP8_FORMAT:
         v = fp8_decode(codes).double()
+    elif fmt == MXFP6_FORMAT:
+        c = mx_unpack_e2m3(codes).long()
+        lut = torch.tensor(E2M3_VALUES, dtype=torch.float64, device=codes.device)
+        v = lut[c & 31] * (1 - 2 * (c >> 5)).double()
     else:
         c = mx_unpack_e2m1(codes).long()
         lut = torch.tensor(E2M1_VALUES, dtype=torch.float64, device=codes.device)
@@ -332,8 +364,8 @@ def mx_decode(codes, scale_u8, fmt, dtype=torch.float32):
 
 
 class MxQuantizer(BaseQuantizer):
-    """`format: mxfp8_e4m3` / `mxfp4_e2m1` of a `weight:` or `act:` section (n_bits 8 / 4, sym True): one E8M0 scale byte per row and
-    block of 32 input channels, e4m3 bytes or packed e2m1 nibbles.  `scale_u8` [rows, cols / 32] holds the bytes as the GEMM reads
+    """`format: mxfp8_e4m3` / `mxfp6_e2m3fn` / `mxfp4_e2m1` of a `weight:` or `act:` section (n_bits 8 / 6 / 4, sym True): one E8M0 scale
+    byte per row and block of 32 input channels, e4m3 bytes, packed e2m3 codes (three bytes per four) or packed e2m1 nibbles.  `scale_u8` [rows, cols / 32] holds the bytes as the GEMM reads
     them; `delta` = 2^(scale_u8 - 127) and `zero_point` zeros keep the integer quantisers' names (save / load_quant_param_dict).
     Nothing is fitted or calibrated: the scales are a function of the tensor alone and are derived again at every call.
     `had32` (the config's `mx: {block_hadamard: True}`): every block is quantised behind its unnormalised 32-point Hadamard

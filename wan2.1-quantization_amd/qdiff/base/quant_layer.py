@@ -17,7 +17,7 @@ from viditq_extension import qgemm
 
 from ..config import ListConfig
 from ..quarot import quarot_utils
-from .base_quantizer import (FP8_FORMAT, MX_BLOCK, MX_FORMATS, MXFP4_FORMAT, MXFP8_FORMAT, DynamicQuantizer, Fp8Quantizer, MxQuantizer,
+from .base_quantizer import (FP8_FORMAT, MX_BLOCK, MX_FORMATS, MXFP4_FORMAT, MXFP6_FORMAT, MXFP8_FORMAT, DynamicQuantizer, Fp8Quantizer, MxQuantizer,
                              StaticQuantizer, fp8_decode, mx_decode)
 from .gptq import BLOCK_MAX, gptq_prepare, gptq_section, gptq_solve
 from .low_rank import RANK_MAX, LowRankBranch, fit_low_rank, padded_rank
@@ -25,7 +25,7 @@ from .mixed_precision_quantizer import MixedPrecisionDynamicQuantizer, MixedPrec
 
 
 # format key -> (its n_bits, its name in "... is one N-bit format")
-_FORMAT_BITS = {FP8_FORMAT: (8, "e4m3"), MXFP8_FORMAT: (8, MXFP8_FORMAT), MXFP4_FORMAT: (4, MXFP4_FORMAT)}
+_FORMAT_BITS = {FP8_FORMAT: (8, "e4m3"), MXFP8_FORMAT: (8, MXFP8_FORMAT), MXFP4_FORMAT: (4, MXFP4_FORMAT), MXFP6_FORMAT: (6, MXFP6_FORMAT)}
 
 
 class QuantizedLinear(LowRankBranch, nn.Linear):
@@ -81,7 +81,8 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         for sec, f in (("weight", fw), ("act", fa)):
             if f is not None and f not in _FORMAT_BITS:
                 raise ValueError(f"{name}: {sec}.format={f!r} is not a known format (the format keys are {FP8_FORMAT!r}, "
-                                 f"{MXFP8_FORMAT!r} and {MXFP4_FORMAT!r})")
+                                 f"{MXFP8_FORMAT!r} and {MXFP4_FORMAT!r}); OCP MXFP6 e2m3, a finite-only format, is spelled "
+                                 f"{MXFP6_FORMAT!r}")
         if fw in MX_FORMATS or fa in MX_FORMATS:
             self._check_mx_format(name, wq, aq, fw, fa)
             self.mx, self.mx_act = fw, fa
@@ -115,9 +116,19 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
                                       "QuantizedLinear)")
 
     def _check_mx_format(self, name, wq, aq, fw, fa):
-        """The accepted OCP MX pairs are (weight mxfp8_e4m3, act mxfp8_e4m3), (weight mxfp4_e2m1, act mxfp8_e4m3) and the W4A4 pair
-        (weight mxfp4_e2m1, act mxfp4_e2m1), with n_bits 8 / 4, sym True and weight.group_size absent or 32 (the format's block);
-        everything else is refused by layer name."""
+        """The accepted OCP MX pairs are (weight mxfp8_e4m3, act mxfp8_e4m3), (weight mxfp4_e2m1, act mxfp8_e4m3), the W4A4 pair
+        (weight mxfp4_e2m1, act mxfp4_e2m1) and the two with e2m3 activations, W6A6 (weight mxfp6_e2m3fn, act mxfp6_e2m3fn) and W4A6
+        (weight mxfp4_e2m1, act mxfp6_e2m3fn), with n_bits 8 / 6 / 4, sym True and weight.group_size absent or 32 (the format's
+        block); everything else is refused by layer name."""
+        if MXFP6_FORMAT in (fw, fa):
+            built = (f"(the built pairs with {MXFP6_FORMAT} are weight {MXFP6_FORMAT} n_bits 6 or weight {MXFP4_FORMAT} n_bits 4 against "
+                     f"act {MXFP6_FORMAT} n_bits 6: wanq_gemm_mx6)")
+            if fw == MXFP6_FORMAT and fa in (MXFP8_FORMAT, MXFP4_FORMAT, FP8_FORMAT):
+                raise NotImplementedError(f"{name}: weight.format: {MXFP6_FORMAT} against act.format: {fa} is not supported: no GEMM takes "
+                                          f"e2m3 weights against {'8-bit' if fa != MXFP4_FORMAT else 'e2m1'} activations {built}")
+            if fa == MXFP6_FORMAT and fw in (MXFP8_FORMAT, FP8_FORMAT):
+                raise NotImplementedError(f"{name}: act.format: {MXFP6_FORMAT} against weight.format: {fw} is not supported: an e4m3 "
+                                          f"weight would hold the matrix cores to the fp8 rate {built}")
         if fa == MXFP4_FORMAT:
             built = f"(the built pair is weight {MXFP4_FORMAT} n_bits 4 against act {MXFP4_FORMAT} n_bits 4)"
             if not isinstance(aq["n_bits"], ListConfig) and aq["n_bits"] == 8:
@@ -130,7 +141,8 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
             sec, other = ("weight", fw) if fw not in MX_FORMATS else ("act", fa)
             raise NotImplementedError(f"{name}: an MX format on one side needs an MX format on the other ({sec}.format is "
                                       f"{other!r}): the MX GEMMs take block-scaled codes on both sides, weight {MXFP8_FORMAT} or "
-                                      f"{MXFP4_FORMAT} against act {MXFP8_FORMAT}, or weight {MXFP4_FORMAT} against act {MXFP4_FORMAT}")
+                                      f"{MXFP4_FORMAT} against act {MXFP8_FORMAT}, or weight {MXFP4_FORMAT} against act {MXFP4_FORMAT}, or weight "
+                                      f"{MXFP6_FORMAT} or {MXFP4_FORMAT} against act {MXFP6_FORMAT}")
         self._check_format_sections(name, (("weight", wq, fw), ("act", aq, fa)))
         g = wq.get("group_size", None)
         if g is not None and (isinstance(g, bool) or g != MX_BLOCK):
@@ -154,6 +166,10 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         on = sec.get("block_hadamard", False)
         if not isinstance(on, bool):
             raise ValueError(f"{name}: mx.block_hadamard={on!r} must be True or False")
+        if on and MXFP6_FORMAT in (self.mx, self.mx_act):
+            raise NotImplementedError(f"{name}: mx.block_hadamard: True is not supported with weight.format {self.mx!r} against "
+                                      f"act.format {self.mx_act!r}: no rotating e2m3 quantiser is built; the block rotation is built for "
+                                      f"the W4A4 pair only (weight.format: {MXFP4_FORMAT} against act.format: {MXFP4_FORMAT})")
         if on and not (self.mx == MXFP4_FORMAT and self.mx_act == MXFP4_FORMAT):
             pair = f"weight.format {self.mx!r} against act.format {self.mx_act!r}" if self.mx else "no MX format"
             raise NotImplementedError(f"{name}: mx.block_hadamard: True is not supported with {pair}: the block rotation is built for "
@@ -415,13 +431,15 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
     def _forward_format(self, x2, out_dtype, bias):
         """`format: fp8_e4m3`: the activation is quantised per token to e4m3 (Fp8Quantizer) and multiplied by the layer's e4m3 weight
         codes, one fp32 scale per token and per output channel.  `format: mxfp8_e4m3` activations against `mxfp8_e4m3` / `mxfp4_e2m1`
-        weights, or `format: mxfp4_e2m1` activations against `mxfp4_e2m1` weights (W4A4, optionally behind `mx.block_hadamard`):
+        weights, `format: mxfp4_e2m1` activations against `mxfp4_e2m1` weights (W4A4, optionally behind `mx.block_hadamard`), or
+        `format: mxfp6_e2m3fn` activations against `mxfp6_e2m3fn` / `mxfp4_e2m1` weights (W6A6 / W4A6, qgemm.mx6_linear):
         quantised per block of 32 channels (MxQuantizer), both sides' E8M0 scales applied by the matrix cores.  On the GPU
         these are kernel mode's two entries per format, fused.quant_rows_fp8 + qgemm.fp8_linear and fused.quant_rows_mx +
         qgemm.mx_linear / qgemm.mx4_linear.  In host memory, and for a shape the GEMM refuses, the same numbers through torch: F.linear of the
         dequantised activation and the dequantised weight, in fp32."""
         a_q, a_s = self.a_quantizer.codes_and_scale(x2)
-        refusal, gemm, fmt = (qgemm.mx4_linear_refusal, qgemm.mx4_linear, ()) if self.mx_act == MXFP4_FORMAT else \
+        refusal, gemm, fmt = (qgemm.mx6_linear_refusal, qgemm.mx6_linear, (self.mx,)) if self.mx_act == MXFP6_FORMAT else \
+            (qgemm.mx4_linear_refusal, qgemm.mx4_linear, ()) if self.mx_act == MXFP4_FORMAT else \
             (qgemm.mx_linear_refusal, qgemm.mx_linear, (self.mx,)) if self.mx else (qgemm.fp8_linear_refusal, qgemm.fp8_linear, ())
         if x2.is_cuda and refusal(x2.shape[0], self.out_features, self.in_features, *fmt) is None:
             w_s = self.w_quantizer.scale_u8 if self.mx else self.w_quantizer.delta.reshape(-1).float().contiguous()

@@ -14,6 +14,10 @@ in `weight:` -- one E8M0 power-of-two scale per block of 32 input channels on bo
 the W4A4 pair weight mxfp4_e2m1 against act mxfp4_e2m1, `sym: True`, `weight.group_size` absent or 32; `act.format: mxfp4_e2m1` with
 `n_bits: 8` or against an e4m3 weight, an MX format against `fp8_e4m3` or against no format, a bit-width list, another group size and
 the SmoothQuant / QuaRot / ViDiT layer classes are refused by layer name.
+`format: mxfp6_e2m3fn` (`n_bits: 6`; the spelling torch and ml_dtypes use for finite-only formats; `mxfp6_e2m3` is not a key) in `act:`,
+against `weight:` mxfp6_e2m3fn (W6A6) or mxfp4_e2m1 (W4A6): OCP MXFP6 e2m3 codes, 32 to 24 bytes, under the block scales of e2m1
+(wanq_quant_rows_mx6, wanq_gemm_mx6).  An e2m3 weight against an e4m3 or e2m1 activation, an e4m3 weight against an e2m3 activation
+and `mx.block_hadamard` with either are refused by layer name.
 `mx: {block_hadamard: True}`, a top-level section: both sides of every MX Linear are quantised behind the unnormalised 32-point
 Hadamard transform of each block of 32 input channels (wanq_quant_rows_mx_had32; the weight as w / 32, so the product is unchanged and
 nothing is rotated back).  Accepted only with the W4A4 pair; with any other pair, or without a format, refused by layer name.

@@ -40,6 +40,8 @@ _vp, _i, _i64, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_floa
 # name -> argtypes, exactly include/wanq_hip.h
 # `fmt` / `w_fmt` codes of wanq_quant_rows_mx / wanq_gemm_mx (WANQ_MX_E4M3, WANQ_MX_E2M1) by the config's format names
 MX_FMT = {"mxfp8_e4m3": 0, "mxfp4_e2m1": 1}
+# `w_fmt` codes of wanq_gemm_mx6 (WANQ_MX_E2M3, WANQ_MX_E2M1); wanq_quant_rows_mx6 writes the first
+MX6_FMT = {"mxfp6_e2m3fn": 2, "mxfp4_e2m1": 1}
 
 PROTOTYPES = {
     "wanq_quant_rows": [_vp, _i, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp],
@@ -60,6 +62,8 @@ PROTOTYPES = {
     "wanq_gemm_mx": [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
     "wanq_quant_rows_mx_had32": [_vp, _i, _vp, _vp, _i64, _i, _i, _i, _vp],
     "wanq_gemm_mx4": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
+    "wanq_quant_rows_mx6": [_vp, _i, _vp, _vp, _i64, _i, _i, _vp],
+    "wanq_gemm_mx6": [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
     "wanq_lincomb":[_i, _i, _vp, _vp, _vp, _i64, _vp],
     "wanq_linear_f32": [_vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp],
     "wanq_time_sinusoid": [_vp, _i, _vp, _i, _i, _vp],

@@ -97,7 +97,11 @@ def quant_rows_mx(x, fmt="mxfp8_e4m3", gelu=False, had32=False):
     shape, e4m3fn bit patterns; "mxfp4_e2m1": [rows, cols / 2], two e2m1 nibbles per byte, even column low.  `gelu`: the tanh-GELU of
     the int8 quantiser applied to x first.  Activations (either format), and a weight [N, K] once at conversion (either format).
     `had32` (wanq_quant_rows_mx_had32): every block is replaced by its unnormalised 32-point Hadamard transform behind the GELU and
-    in front of the block maximum."""
+    in front of the block maximum.
+    fmt "mxfp6_e2m3fn" (wanq_quant_rows_mx6, no `had32`): [rows, 3 cols / 4], 32 six-bit e2m3 codes per 24 bytes, element j of a block
+    in bits 6 j .. 6 j + 5 of its little-endian string; the scale bytes are those of "mxfp4_e2m1"."""
+    if fmt == "mxfp6_e2m3fn":
+        return _quant_rows_mx6(x, gelu, had32)
     if fmt not in _C.MX_FMT:
         raise RuntimeError(f"quant_rows_mx: fmt={fmt!r} must be one of {tuple(_C.MX_FMT)}")
     rows, cols = _rows_cols("x", x)
@@ -110,6 +114,24 @@ def quant_rows_mx(x, fmt="mxfp8_e4m3", gelu=False, had32=False):
         _C.call("wanq_quant_rows_mx_had32" if had32 else "wanq_quant_rows_mx", _C.ptr(x), _C.dt(x), _C.ptr(codes), _C.ptr(scale), rows,
                 cols, code, 1 if gelu else 0, _C.stream())
     return codes, scale
+
+
+def _quant_rows_mx6(x, gelu, had32):
+    if had32:
+        raise RuntimeError("quant_rows_mx: fmt='mxfp6_e2m3fn' has no had32 form (the block rotation is built for mxfp4_e2m1 / mxfp8_e4m3)")
+    rows, cols = _rows_cols("x", x)
+    if cols % 32:
+        raise RuntimeError(f"quant_rows_mx: cols={cols} must be a multiple of 32")
+    codes = torch.empty((*x.shape[:-1], cols // 4 * 3), dtype=torch.uint8, device=x.device)
+    scale = torch.empty((*x.shape[:-1], cols // 32), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _C.call("wanq_quant_rows_mx6", _C.ptr(x), _C.dt(x), _C.ptr(codes), _C.ptr(scale), rows, cols, 1 if gelu else 0, _C.stream())
+    return codes, scale
+
+
+def quant_rows_mxfp6(x, gelu=False):
+    """`quant_rows_mx` to packed e2m3 codes: the activation form "mxfp6" of a W6A6 / W4A6 layer."""
+    return quant_rows_mx(x, "mxfp6_e2m3fn", gelu)
 
 
 def quant_rows_mxfp4(x, gelu=False):

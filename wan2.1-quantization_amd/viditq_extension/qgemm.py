@@ -557,3 +557,38 @@ def mx4_linear_refusal(M, N, K):
     """Why wanq_gemm_mx4 would refuse an [M, K] x [N, K] product (None = accepted): the shape rules of include/wanq_hip.h in the order
     the entry checks them; see `fp_linear_refusal`."""
     return _shape_refusal(M, N, K, MX_K_STEP, bounded=True)
+
+
+# ---- OCP MX W6A6 / W4A6: MXFP6 (e2m3) activations x MXFP6 / MXFP4 weights, E8M0 block scales ------------------------------------------
+def mx6_linear(a_q, w_q, a_scale, w_scale, w_fmt="mxfp6_e2m3fn", bias=None, out_dtype=None, gelu=False, gate=None, residual=None,
+               out=None):
+    """`mx_linear` with e2m3 activations and no operand 8 bits wide (wanq_gemm_mx6, csrc/gemm_mx.hip): a_q uint8 [M, 3 K / 4] packed
+    e2m3 codes; w_q uint8 [N, 3 K / 4] packed e2m3 codes (w_fmt "mxfp6_e2m3fn") or [N, K / 2] packed e2m1 nibbles ("mxfp4_e2m1");
+    a_scale uint8 [M, K / 32], w_scale uint8 [N, K / 32], all as `fused.quant_rows_mx` writes them.  The accumulation, epilogue, shape
+    rules (K % 128 == 0, N % 8 == 0) and determinism are `mx_linear`'s.  Not counted by the int8 timer (`set_timer`)."""
+    if w_fmt not in _C.MX6_FMT:
+        raise RuntimeError(f"mx6_linear: w_fmt={w_fmt!r} must be one of {tuple(_C.MX6_FMT)}")
+    for name, t in (("a_q", a_q), ("w_q", w_q), ("a_scale", a_scale), ("w_scale", w_scale)):
+        if t is None:
+            raise RuntimeError(f"mx6_linear: {name} must be given")
+        _check_mat(name, t, torch.uint8)
+    if a_q.shape[1] % 3:
+        raise RuntimeError(f"mx6_linear: a_q has {a_q.shape[1]} bytes per row, not 3 K / 4 of any K")
+    M, K = a_q.shape[0], a_q.shape[1] // 3 * 4
+    N = w_q.shape[0]
+    why = mx6_linear_refusal(M, N, K, w_fmt)
+    if why is not None:
+        raise RuntimeError(f"mx6_linear: {why}")
+    _C.check_shape("w_q", w_q, N, K // 2 if _C.MX6_FMT[w_fmt] == 1 else K // 4 * 3)
+    _C.check_shape("a_scale", a_scale, M, K // 32)
+    _C.check_shape("w_scale", w_scale, N, K // 32)
+    return _launch16("wanq_gemm_mx6", (_C.ptr(a_q), _C.ptr(w_q), _C.ptr(a_scale), _C.ptr(w_scale), _C.MX6_FMT[w_fmt]),
+                     (a_q, w_q, a_scale, w_scale), bias, out_dtype or torch.bfloat16, gelu, gate, residual, out, M, N, K)
+
+
+def mx6_linear_refusal(M, N, K, w_fmt="mxfp6_e2m3fn"):
+    """Why wanq_gemm_mx6 would refuse an [M, K] x [N, K] product (None = accepted): the shape rules of include/wanq_hip.h in the order
+    the entry checks them; see `fp_linear_refusal`."""
+    if w_fmt not in _C.MX6_FMT:
+        return f"w_fmt={w_fmt!r} must be one of {tuple(_C.MX6_FMT)}"
+    return _shape_refusal(M, N, K, MX_K_STEP, bounded=True)

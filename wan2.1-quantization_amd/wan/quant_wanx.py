@@ -13,6 +13,7 @@ import torch.nn as nn
 
 from qdiff.base.quant_layer import QuantizedLinear
 from qdiff.base.quant_model import QuantModel
+from viditq_extension import _C
 
 from .modules.model import WanModel
 from .quant_wanx_hip import WanAttentionBlockWithHipKernel, _FpSrc
@@ -104,7 +105,8 @@ class QuantWanModel(WanModel, QuantModel):
                     # 8-bit: int8 [N, K]; 4-bit: uint8 [N, K/2], the packed nibbles exactly as the GEMM reads them; format: fp8_e4m3:
                     # uint8 [N, K], the e4m3 bytes, with their per-channel scales
                     # (weight.group_size: the parameters as the group-wise GEMM reads them, [K / g, N]); format: mxfp8_e4m3 /
-                    # mxfp4_e2m1: uint8 [N, K] e4m3 bytes / uint8 [N, K/2] packed e2m1 nibbles, scale_weight uint8 [N, K/32] E8M0 bytes
+                    # mxfp4_e2m1: uint8 [N, K] e4m3 bytes / uint8 [N, K/2] packed e2m1 nibbles, scale_weight uint8 [N, K/32] E8M0 bytes;
+                    # mxfp6_e2m3fn: uint8 [N, 3K/4] packed e2m3 codes, and `mx_fmt` with either weight of an e2m3-activation layer
                     grouped = mod.group_size is not None
                     sd[name + ".weight"] = mod._codes.clone()
                     sd[name + ".scale_weight"] = (wq.scale_u8.clone() if mod.mx else
@@ -114,6 +116,8 @@ class QuantWanModel(WanModel, QuantModel):
                                                    else wq.zero_point.reshape(-1).float().clone())
                     if mod.bias is not None:
                         sd[name + ".bias"] = mod.bias.detach().float().clone()
+                    if mod.mx_act == "mxfp6_e2m3fn":  # W6A6 / W4A6: the (weight, act) format codes of wanq_gemm_mx6, recorded with the layer
+                        sd[name + ".mx_fmt"] = torch.tensor([_C.MX6_FMT[mod.mx], _C.MX6_FMT[mod.mx_act]], dtype=torch.uint8)
                     if mod.mx_had32:  # codes made behind the block Hadamard rotation (mx.block_hadamard): recorded with the layer
                         sd[name + ".mx_had32"] = torch.ones(1, dtype=torch.uint8)
                     if mod.low_rank is not None:  # the LoRC factors, fp32 [Rp, K] / [N, Rp] (an adapter is not part of the weights)
@@ -215,7 +219,14 @@ class QuantWanModel(WanModel, QuantModel):
                         raise ValueError(f"{load_path}: {base} holds codes quantised {'behind' if had_file else 'without'} the block "
                                          f"Hadamard rotation (mx.block_hadamard) and the model's layer was built "
                                          f"{'with' if had_layer else 'without'} it: the two are not interchangeable")
+                    # an e2m3-activation layer records its (weight, act) formats in `<name>.mx_fmt`; no other layer has the key
+                    rec, own = sd.get(f"{base}.mx_fmt", None), getattr(lin, "mx_fmt", None)
+                    if (rec is None) != (own is None) or (rec is not None and rec.reshape(-1).tolist() != own.reshape(-1).tolist()):
+                        said = lambda v: "no mx_fmt (not an MXFP6 layer)" if v is None else f"mx_fmt {v.reshape(-1).tolist()}"  # noqa: E731
+                        raise ValueError(f"{load_path}: {base} was saved with {said(rec)} and the model's layer was built with "
+                                         f"{said(own)} ((weight, act) codes of wanq_gemm_mx6: 2 = mxfp6_e2m3fn, 1 = mxfp4_e2m1)")
                     for buf, k, required in (("weight", "weight", True), ("scale_weight", "scale_weight", True),
+                                             ("mx_fmt", "mx_fmt", own is not None),
                                              ("zp_weight", "zp_weight", lin.zp_weight is not None),
                                              ("bias", "bias", lin.bias is not None),
                                              ("act_premul", "act_premul", lin.act_premul is not None),

@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from qdiff.base.low_rank import LowRankBranch, padded_rank
-from viditq_extension import fused, qgemm
+from viditq_extension import _C, fused, qgemm
 
 from . import ops
 from .modules.model import WanModel
@@ -40,7 +40,7 @@ class _HipLinear(nn.Module):
     fp8 = False
     mx = None              # HipLinearMx: the weight's MX format name
     weight_only = False
-    act_form = "fp"        # what its input is made into: "fp" (16 bits, no quantiser), "int8", "fp8", "mxfp8", "mxfp4" or "mxfp4_h32"
+    act_form = "fp"        # what its input is made into: "fp" (16 bits, no quantiser), "int8", "fp8", "mxfp8", "mxfp6", "mxfp4" or "mxfp4_h32"
     act_key = "fp"         # layers with the same key share one copy of their input
     plain_rows = False     # its quantiser takes the source's row without a transform, so it can apply the FFN's GELU itself
     rot = act_quantizer = None
@@ -389,20 +389,29 @@ class HipLinearMx(_HipLinearCodes):
     entry (codes + scale bytes), and the product is qgemm.mx_linear, or qgemm.mx4_linear for e2m1 activations (csrc/gemm_mx.hip),
     with GELU and gate + residual in its epilogue.  `had32` (W4A4 only, the config's `mx.block_hadamard`): the weight codes were
     made behind the block Hadamard rotation and the input is quantised behind it too (activation form "mxfp4_h32"); the layer then
-    holds the one-element uint8 buffer `mx_had32`, which travels with its codes in the integer checkpoint."""
+    holds the one-element uint8 buffer `mx_had32`, which travels with its codes in the integer checkpoint.  `a_fmt` "mxfp6_e2m3fn"
+    (W6A6 / W4A6): `weight` uint8 [N, 3 K / 4] packed e2m3 codes (w_fmt "mxfp6_e2m3fn", from wanq_quant_rows_mx6) or the packed e2m1
+    nibbles, the input quantised to e2m3 (activation form "mxfp6"), the product qgemm.mx6_linear; the layer then holds the uint8
+    buffer `mx_fmt` = (w_fmt code, a_fmt code), which records the formats in the integer checkpoint."""
     act_form = act_key = "mxfp8"
     sharded = ("weight", "scale_weight")   # the scale bytes are a thirty-second or a sixteenth of the weight's
 
     def __init__(self, in_features, out_features, bias=True, w_fmt="mxfp8_e4m3", name="linear", a_fmt="mxfp8_e4m3", had32=False):
-        a4 = a_fmt == "mxfp4_e2m1"
-        if a_fmt not in ("mxfp8_e4m3", "mxfp4_e2m1") or (a4 and w_fmt != "mxfp4_e2m1") or (had32 and not a4):
+        a4, a6, w6 = a_fmt == "mxfp4_e2m1", a_fmt == "mxfp6_e2m3fn", w_fmt == "mxfp6_e2m3fn"
+        if a_fmt not in ("mxfp8_e4m3", "mxfp4_e2m1", "mxfp6_e2m3fn") or (a4 and w_fmt != "mxfp4_e2m1") or (had32 and not a4) or \
+                (a6 and w_fmt not in ("mxfp6_e2m3fn", "mxfp4_e2m1")) or (w6 and not a6):
             raise NotImplementedError(f"{name}: no MX GEMM takes weight {w_fmt} against act {a_fmt}" + (" behind the block rotation" if had32 else ""))
-        why = qgemm.mx4_linear_refusal(1, out_features, in_features) if a4 else qgemm.mx_linear_refusal(1, out_features, in_features, w_fmt)
+        why = qgemm.mx6_linear_refusal(1, out_features, in_features, w_fmt) if a6 else \
+            qgemm.mx4_linear_refusal(1, out_features, in_features) if a4 else qgemm.mx_linear_refusal(1, out_features, in_features, w_fmt)
         super().__init__(in_features, out_features, bias, w_fmt, why,
-                         in_features // 2 if w_fmt == "mxfp4_e2m1" else in_features, (out_features, in_features // 32), torch.uint8, name)
+                         in_features // 2 if w_fmt == "mxfp4_e2m1" else in_features // 4 * 3 if w6 else in_features,
+                         (out_features, in_features // 32), torch.uint8, name)
         self.mx, self.a_fmt, self.had32 = w_fmt, a_fmt, bool(had32)
         if a4:
             self.act_form = self.act_key = "mxfp4_h32" if had32 else "mxfp4"
+        if a6:
+            self.act_form = self.act_key = "mxfp6"
+            self.register_buffer("mx_fmt", torch.tensor([_C.MX6_FMT[w_fmt], _C.MX6_FMT[a_fmt]], dtype=torch.uint8))
         if had32:
             self.register_buffer("mx_had32", torch.ones(1, dtype=torch.uint8))
 
@@ -414,6 +423,9 @@ class HipLinearMx(_HipLinearCodes):
 
     def forward(self, a_q, a_scale, out_dtype=torch.bfloat16, gelu=False, gate=None, residual=None, out=None):
         """Reads `weight` and `scale_weight` as they are now (--dit_fsdp re-points them at views of the gathered buffer)."""
+        if self.a_fmt == "mxfp6_e2m3fn":
+            return qgemm.mx6_linear(a_q, self.weight, a_scale, self.scale_weight, self.mx, self.bias, out_dtype, gelu=gelu, gate=gate,
+                                    residual=residual, out=out)
         if self.a_fmt == "mxfp4_e2m1":
             return qgemm.mx4_linear(a_q, self.weight, a_scale, self.scale_weight, self.bias, out_dtype, gelu=gelu, gate=gate,
                                     residual=residual, out=out)
@@ -444,7 +456,8 @@ def _to_hip_linear(lin, n_bits, sym, act_dtype, fp_gemm="torch", name="linear"):
 
 
 # activation form -> the fused row quantiser that makes it, (codes, scales) = f(rows, gelu=); a new form adds its entry here
-_ROW_QUANTISERS = {"fp8": "quant_rows_fp8", "mxfp8": "quant_rows_mx", "mxfp4": "quant_rows_mxfp4", "mxfp4_h32": "quant_rows_mxfp4_h32"}
+_ROW_QUANTISERS = {"fp8": "quant_rows_fp8", "mxfp8": "quant_rows_mx", "mxfp4": "quant_rows_mxfp4", "mxfp4_h32": "quant_rows_mxfp4_h32",
+                   "mxfp6": "quant_rows_mxfp6"}
 
 
 class _Src:
@@ -452,7 +465,7 @@ class _Src:
 
     def rows(self, form):
         """(codes, scales) of this activation in `form` for every consumer of it (HipLinearFp8: e4m3 codes + fp32 scale;
-        HipLinearMx: e4m3 or packed e2m1 codes + E8M0 scale bytes), quantised from what `_plain_row` hands over."""
+        HipLinearMx: e4m3, packed e2m3 or packed e2m1 codes + E8M0 scale bytes), quantised from what `_plain_row` hands over."""
         if form not in self.cache:
             x, gelu = self._plain_row()
             self.cache[form] = getattr(fused, _ROW_QUANTISERS[form])(x, gelu=gelu)
