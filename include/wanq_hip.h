@@ -113,6 +113,23 @@ int wanq_quant_rows_mx(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8
 int wanq_quant_rows_mx_had32(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int fmt, int act,
                              void* stream);
 
+/* The MXFP4 (e2m1) row quantiser and, in the same pass over x, the down-projection of a 16-bit low-rank branch (csrc/quant_project.hip;
+ * the producer of wanq_gemm_mx4_lowrank):
+ *   q, scale_u8   what wanq_quant_rows_mx (fmt WANQ_MX_E2M1) writes for the same x and act -- with had32 = 1 what
+ *                 wanq_quant_rows_mx_had32 writes -- bit for bit (one definition of the per-block arithmetic, csrc/mx_block.h)
+ *   xt            = round_T(act(x)): the GELU in fp32 as the quantiser applies it, then ONE rounding to T = dtype16 (for a 16-bit x of
+ *                 dtype T with act = 0 the identity).  The row BEFORE the Hadamard rotation: the branch lives in the unrotated space
+ *   t[m, r]       = round_T(sum_k xt[m, k] a16[r, k]), r < R, fp32 on v_mfma_f32_16x16x32_{bf16,f16}, k ascending in 32-deep steps
+ * x: F16 | BF16 | F32 [rows, cols].  a16: [R, cols] of dtype16 (WANQ_BF16 | WANQ_F16).  t: [rows, ldt] of dtype16; columns 0 .. R - 1 of
+ * every row are written, the others are left alone (t may be a column window of a wider buffer: pass the window's first element and
+ * the buffer's pitch).  cols % 128 == 0, cols <= 16384;  R % 64 == 0, 64 <= R <= 256;  ldt >= R, ldt % 8 == 0;  x, a16, t and q 16-byte
+ * aligned;  rows >= 0 (rows == 0 returns WANQ_OK).  Anything else is refused (WANQ_E_SHAPE / WANQ_E_ARG, the message names the rule).
+ * x is read once; a workgroup owns whole rows.  Determinism: no split over k, no atomics; the summation order of t[m, r] depends on
+ * cols only, so a row gives the same bits at any m and in a launch of any `rows`.
+ * No reference counterpart. */
+int wanq_quant_rows_mx4_project(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, const void* a16, int dtype16, int R, void* t,
+                                int ldt, int64_t rows, int cols, int act, int had32, void* stream);
+
 /* OCP MXFP6 (e2m3) block quantisation: wanq_quant_rows_mx's row frame, GELU option, block maximum and argument rules, to 6-bit codes.
  * The format (WANQ_MX_E2M3; config name mxfp6_e2m3fn: finite only), defined here and as a host expression in
  * qdiff/base/base_quantizer.py:
@@ -624,6 +641,20 @@ int wanq_gemm_mx(const uint8_t* a, const uint8_t* w, const uint8_t* sa_u8, const
 int wanq_gemm_mx4(const uint8_t* a, const uint8_t* w, const uint8_t* sa_u8, const uint8_t* sw_u8, void* out, int out_dtype,
                   const void* bias, int bias_dtype, const float* gate, const void* residual, int epi_flags, int64_t M, int N, int K,
                   void* stream);
+
+/* wanq_gemm_mx4 with a 16-bit low-rank branch summed into the same fp32 accumulators, in front of the epilogue:
+ *   acc[m,n] = (wanq_gemm_mx4's sum) + sum_r t[m,r] * b[n,r];  y = acc + bias[n];  GELU;  residual + y * gate;  one rounding to out_dtype.
+ * t: [M, ldt] and b: [N, R], both of dtype16 (WANQ_BF16 | WANQ_F16); columns 0 .. R - 1 of t are read (a column window of a wider buffer:
+ * its first element and the buffer's pitch).  The branch runs as R / 32 further steps of the K loop on v_mfma_f32_16x16x32_{bf16,f16}
+ * (csrc/gemm_mx.hip).  For LoRC factors of the MXFP4 quantisation error and LoRA adapters; t comes from wanq_quant_rows_mx4_project.
+ * Every rule of wanq_gemm_mx4, and:  t and b non-NULL and 16-byte aligned;  R % 64 == 0, 64 <= R <= 256;  ldt >= R, ldt % 8 == 0.
+ * Anything else is refused (WANQ_E_SHAPE / WANQ_E_ARG, the message names the rule).
+ * Determinism: K-tiles ascending, then rank slices ascending; the summation order of element (m, n) depends on (K, R) only.  A zero t
+ * or a zero b adds exact zeros: the output then has the values of wanq_gemm_mx4.
+ * No reference counterpart. */
+int wanq_gemm_mx4_lowrank(const uint8_t* a, const uint8_t* w, const uint8_t* sa_u8, const uint8_t* sw_u8, const void* t, int ldt,
+                          const void* b, int dtype16, int R, void* out, int out_dtype, const void* bias, int bias_dtype,
+                          const float* gate, const void* residual, int epi_flags, int64_t M, int N, int K, void* stream);
 
 /* MXFP6 GEMMs, W6A6 and W4A6: e2m3 activations (wanq_quant_rows_mx6) against e2m3 weights (w_fmt WANQ_MX_E2M3, the same entry once
  * at conversion) or packed e2m1 weights (w_fmt WANQ_MX_E2M1, wanq_quant_rows_mx), on v_mfma_scale_f32_16x16x128_f8f6f4 with no

@@ -31,6 +31,9 @@
 //                        one-chunk fragment read as the packed weight half; W6ROW (with WROW == W6ROW or W4ROW) for its e2m3 tokens
 //   Side                 per-tile values a lane loads itself, one tile ahead behind the DMA (gemm_mx.hip's scale dwords), or NoSide
 //   mma                  the MFMA block of one K-tile
+//   LOWRANK (optional)   true: behind the K-tiles run R / 32 more iterations of the loop on the same buffers, one per 32-rank slice of
+//                        t (token half) and b (weight half), with mma_lr in place of mma and no Side values; the parameters are
+//                        GemmLrParams.  XROW == WROW == W4ROW only (gemm_mx.hip has the geometry).  Absent or false: nothing changes
 //
 // Determinism.  Every output element is summed by one lane, over k in K-tile order and within a tile in the instruction's own
 // order (16-bit: two 32-deep MFMA steps with the same k -> fragment-slot assignment in both 16-bit files): its fp32 summation order
@@ -71,6 +74,13 @@ struct Gemm16Params {
   const void* residual;
   int bias_dtype, epi;
   int M, N, K, nt;
+};
+
+// ... and of a policy with LOWRANK (gemm_mx.hip: wanq_gemm_mx4_lowrank): t [M, ldt] and b [N, R] of one 16-bit dtype
+struct GemmLrParams : Gemm16Params {
+  const void* t;
+  const void* b;
+  int ldt, R;
 };
 
 // this thread's place: its wave's 64 x 64 quarter (wm, wn) of the workgroup's tile at (m0, n0), its fragment row fr and lane group fq
@@ -283,13 +293,21 @@ __device__ __forceinline__ uint32_t frag6_addr(uint32_t lds0, int fr, int fq, in
   return lds0 + fr * W6ROW + (((s >> 1) ^ w6_swz(fr)) << 4) + ((s & 1) << 3);
 }
 
+template <class P, class = void>
+struct policy_lowrank : std::false_type {};
 template <class P>
-__global__ void __launch_bounds__(256, 2) gemm_tile_kernel(Gemm16Params p) {
+struct policy_lowrank<P, std::enable_if_t<P::LOWRANK>> : std::true_type {};
+
+template <class P>
+__global__ void __launch_bounds__(256, 2)
+    gemm_tile_kernel(std::conditional_t<policy_lowrank<P>::value, GemmLrParams, Gemm16Params> p) {
+  constexpr bool LR = policy_lowrank<P>::value;
   constexpr bool W4 = P::WROW == W4ROW, X4 = P::XROW == W4ROW, W6 = P::WROW == W6ROW, X6 = P::XROW == W6ROW, SHORT = P::KMUL < P::TKE;
   constexpr int XT = TM * P::XROW, TILE = XT + TN * P::WROW;  // one K-tile buffer: token rows, then weight rows
   static_assert((W4 || W6 || P::WROW == TROW) && (X4 ? W4 : X6 ? (W4 || W6) : (P::XROW == TROW && !W6)) &&
                     (P::KMUL == P::TKE || (P::KMUL * 2 == P::TKE && !W4 && !W6)),
                 "no such geometry");
+  static_assert(!LR || (W4 && X4), "a low-rank slice is a K-tile of 64-byte rows");
   __shared__ __attribute__((aligned(1024))) char smem[2 * TILE];
   const Frame f(p.nt);
   const int K = p.K, nk = (K + P::TKE - P::KMUL) / P::TKE;  // K % KMUL == 0
@@ -325,6 +343,20 @@ __global__ void __launch_bounds__(256, 2) gemm_tile_kernel(Gemm16Params p) {
     dma_issue<TN * P::WROW / 4096>(wsrc, (int64_t)h * (P::WROW / 2), dst + XT);
   };
 
+  // LOWRANK: slice s of t and b, where K-tile nk + s would be
+  const char *tsrc[4], *bsrc[4];
+  if constexpr (LR) {
+    dma_sources4(p.t, f.m0, p.M, 2 * p.ldt, f, tsrc);
+    dma_sources4(p.b, f.n0, p.N, 2 * p.R, f, bsrc);
+  }
+  auto issue_lr = [&](int s) {
+    if constexpr (LR) {
+      char* dst = smem + ((nk + s) & 1) * TILE + f.wave * 1024;
+      dma_issue<2>(tsrc, (int64_t)s * W4ROW, dst);
+      dma_issue<2>(bsrc, (int64_t)s * W4ROW, dst + XT);
+    }
+  };
+
   const uint32_t lds0 = (uint32_t)(uintptr_t)smem;
   const uint32_t rd0 = frag_addr(lds0, f.fr, f.fq, 0), rd1 = frag_addr(lds0, f.fr, f.fq, 1);
   const uint32_t rdw4 = lds0 + f.fr * W4ROW + ((f.fq ^ w4_swz(f.fr)) << 4);  // an e2m1 fragment: the one chunk fq of its row
@@ -348,6 +380,8 @@ __global__ void __launch_bounds__(256, 2) gemm_tile_kernel(Gemm16Params p) {
     if (t + 1 < nk) {
       issue(t + 1);
       side.load(t + 1);
+    } else if constexpr (LR) {
+      issue_lr(0);  // under the last quantised tile's MFMAs
     }
     __builtin_amdgcn_sched_barrier(0);
     const uint32_t xo = (t & 1) * TILE + f.wm * 64 * P::XROW, wo = (t & 1) * TILE + XT + f.wn * 64 * P::WROW;
@@ -372,6 +406,24 @@ __global__ void __launch_bounds__(256, 2) gemm_tile_kernel(Gemm16Params p) {
       P::mma(acc, wb, xa, side, SHORT && t * P::TKE + P::KMUL >= K);
     }
     __builtin_amdgcn_sched_barrier(0);
+  }
+
+  if constexpr (LR) {
+    for (int s = 0, ns = p.R / 32; s < ns; ++s) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+      if (s + 1 < ns) issue_lr(s + 1);
+      __builtin_amdgcn_sched_barrier(0);
+      const uint32_t bo = ((nk + s) & 1) * TILE;
+      v4i xa[4], wb[4];
+      dsr4<W4ROW>(wb, rdw4 + bo + XT + f.wn * 64 * W4ROW);
+      dsr4<W4ROW>(xa, rdw4 + bo + f.wm * 64 * W4ROW);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      P::mma_lr(acc, wb, xa);
+      __builtin_amdgcn_sched_barrier(0);
+    }
   }
 
   epilogue16<P::OUT, P::SCALED, P::TOKEN>(acc, f, p);

@@ -61,7 +61,20 @@
 // alone.  A fragment set is 24 ds_read_b64 (W6A6) or 12 + 4 ds_read_b128 (W4A6); the pieces are assembled into the operand
 // registers behind the wait, without a move (the K loop holds none).
 //
-// Summation order of element (m, n): K-tiles ascending, inside an MFMA the hardware's own.  It depends on K only.
+// Low-rank branch (wanq_gemm_mx4_lowrank, MxLrPolicy).  acc += sum_r t[m, r] b[n, r], t [M, ldt] and b [N, R] of one 16-bit dtype,
+// into the SAME accumulators: MxPolicy leaves nothing to scale in the epilogue (SCALED and TOKEN false, the scaled MFMA applied both
+// block scales), so acc is the plain fp32 product and a 16-bit MFMA adds to it -- no second accumulator set (gemm_wq16.hip's form
+// pays 58 VGPRs and a wave of occupancy for one), and bias, GELU and gate + residual see the sum.  Geometry: a 32-rank slice of a t
+// or b row is 64 B, what a packed e2m1 row of a K-tile is, and lane (fr, fq)'s chunk fq of it is elements 8 fq .. 8 fq + 7: that
+// lane's operand of v_mfma_f32_16x16x32_{bf16,f16}.  So slice s is K-tile nk + s of the same loop (gemm16_common.h, LOWRANK): the two
+// 16 KiB buffers, dma_sources4 with pitches 2 ldt and 2 R bytes, w4_swz, one ds_read_b128 of chunk fq per fragment -- the bank
+// derivation of the W4A4 halves above holds unchanged, the rows are the same 64 B -- then 16 mfma<F16IN> in place of the scaled ones.
+// No scale dwords are loaded for these steps.  Slice 0 is issued under the last quantised tile's MFMAs, so no copy of the branch is
+// waited for with nothing of the workgroup to hide it; each further slice under the MFMAs of the one before.  R % 64 == 0, 64 <= R
+// <= 256, ldt >= R, ldt % 8 == 0: t may be a column window of a wider buffer (several consumers of one wanq_quant_rows_mx4_project).
+//
+// Summation order of element (m, n): K-tiles ascending, inside an MFMA the hardware's own; then, with the branch, rank slices
+// ascending.  It depends on K (and R) only.
 #include "gemm16_common.h"
 
 namespace wanq {
@@ -130,6 +143,19 @@ struct MxPolicy {
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         acc[i][j] = mfma_mx<FP4, A4>(wb[0][j], wb[FP4 ? 0 : 1][j], xa[0][i], xa[A4 ? 0 : 1][i], acc[i][j], s.sw_cur[j], s.sa_cur[i]);
+  }
+};
+
+// W4A4 with the low-rank branch: the K-tiles of MxPolicy<OUT, true, true>, then R / 32 slices of 16-bit t against b
+template <int OUT_, bool F16IN>
+struct MxLrPolicy : MxPolicy<OUT_, true, true> {
+  static constexpr bool LOWRANK = true;
+
+  static __device__ __forceinline__ void mma_lr(v4f (&acc)[4][4], const v4i (&wb)[4], const v4i (&xa)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = mfma<F16IN>(wb[j], xa[i], acc[i][j]);
   }
 };
 
@@ -203,6 +229,31 @@ extern "C" int wanq_gemm_mx4(const uint8_t* a, const uint8_t* w, const uint8_t* 
   hipStream_t st = (hipStream_t)stream;
   return with_out_dtype(out_dtype, [&](auto o) {
     return launch_tiles(gemm_tile_kernel<MxPolicy<decltype(o)::value, true, true>>, p, st, what);
+  });
+}
+
+extern "C" int wanq_gemm_mx4_lowrank(const uint8_t* a, const uint8_t* w, const uint8_t* sa_u8, const uint8_t* sw_u8, const void* t,
+                                     int ldt, const void* b, int dtype16, int R, void* out, int out_dtype, const void* bias,
+                                     int bias_dtype, const float* gate, const void* residual, int epi_flags, int64_t M, int N, int K,
+                                     void* stream) {
+  const char* what = "wanq_gemm_mx4_lowrank";
+  WANQ_REQUIRE(a && w && out && sa_u8 && sw_u8, WANQ_E_ARG, "%s: a, w, sa_u8, sw_u8 and out must be non-NULL", what);
+  WANQ_REQUIRE(t && b, WANQ_E_ARG, "%s: t and b must be non-NULL", what);
+  WANQ_REQUIRE(dtype16 == WANQ_BF16 || dtype16 == WANQ_F16, WANQ_E_ARG, "%s: dtype16=%d must be BF16 or F16", what, dtype16);
+  if (const int rc = check_gemm16_shapes(what, TKX, a, w, out, out_dtype, bias, bias_dtype, gate, residual, epi_flags, M, N, K))
+    return rc;
+  WANQ_REQUIRE(R >= 64 && R <= 256 && R % 64 == 0, WANQ_E_SHAPE, "%s: R=%d must be a multiple of 64 in [64, 256]", what, R);
+  WANQ_REQUIRE(ldt >= R && ldt % 8 == 0, WANQ_E_SHAPE, "%s: ldt=%d must be a multiple of 8 and at least R=%d", what, ldt, R);
+  WANQ_REQUIRE(aligned(sa_u8, 4) && aligned(sw_u8, 4), WANQ_E_ARG, "%s: sa_u8 and sw_u8 must be 4-byte aligned", what);
+  WANQ_REQUIRE(aligned(t, 16) && aligned(b, 16), WANQ_E_ARG, "%s: t and b must be 16-byte aligned", what);
+  if (const int rc = check_gemm16_tail(what, bias, bias_dtype, gate, M, N)) return rc;
+  if (M == 0) return WANQ_OK;
+  const GemmLrParams p{gemm16_params(a, w, sa_u8, sw_u8, out, bias, bias_dtype, gate, residual, epi_flags, M, N, K), t, b, ldt, R};
+  hipStream_t st = (hipStream_t)stream;
+  return with_out_dtype(out_dtype, [&](auto o) {
+    constexpr int OUT = decltype(o)::value;
+    return dtype16 == WANQ_F16 ? launch_tiles(gemm_tile_kernel<MxLrPolicy<OUT, true>>, p, st, what)
+                               : launch_tiles(gemm_tile_kernel<MxLrPolicy<OUT, false>>, p, st, what);
   });
 }
 

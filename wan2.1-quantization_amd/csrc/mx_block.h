@@ -1,0 +1,92 @@
+// The per-block arithmetic of the OCP MX row quantisers, one definition for rowwise.hip (quant_rows_mx_kernel) and quant_project.hip
+// (quant_project_kernel): the optional 32-point Hadamard rotation, the block maximum, the E8M0 scale byte, the exact scaling and the
+// e2m1 code.  A block of 32 consecutive columns is four 8-element chunks held by four lanes; which four, and how they exchange a
+// register, is the caller's layout and comes in as XL:
+//   XL::x8(v)   the value of the lane that holds the chunk 8 elements away (chunk index ^ 1)
+//   XL::x16(v)  ... 16 elements away (chunk index ^ 2)
+// rowwise.hip: the four lanes of an aligned quad, DPP quad permutes.  quant_project.hip: lanes fr, fr + 16, fr + 32, fr + 48 of the
+// MFMA's token operand layout, v_permlane16_swap / v_permlane32_swap.  The operations per element and their order are the same in
+// both, so codes and scale bytes are bit-equal (mx_hadamard32_host, mx_quant_rows_host).
+#pragma once
+#include "wanq_common.h"
+
+namespace wanq {
+
+__device__ __forceinline__ uint32_t e2m1_code(float t) {
+  const float a = fminf(fabsf(t), 6.0f);
+  const uint32_t mag = (uint32_t)(a > 0.25f) + (uint32_t)(a >= 0.75f) + (uint32_t)(a > 1.25f) + (uint32_t)(a >= 1.75f) +
+                       (uint32_t)(a > 2.5f) + (uint32_t)(a >= 3.5f) + (uint32_t)(a > 5.0f);
+  return mag | ((__float_as_uint(t) >> 28) & 8u);
+}
+
+// one butterfly stage inside a chunk: H = 1, 2 or 4
+template <int H>
+__device__ __forceinline__ void had_stage(float (&v)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    if (j & H) continue;
+    const float a = v[j], b = v[j + H];
+    v[j] = a + b;
+    v[j + H] = a - b;
+  }
+}
+
+// the quad of rowwise.hip: chunk index = lane & 3
+struct MxQuadLanes {
+  static __device__ __forceinline__ float x8(float v) { return lane_xor_dpp<1>(v); }
+  static __device__ __forceinline__ float x16(float v) { return lane_xor_dpp<2>(v); }
+};
+
+// one butterfly stage across the block's lanes: h = 8 (FAR false) or 16 (FAR true); the lane with the bit set keeps partner - own
+template <class XL, bool FAR>
+__device__ __forceinline__ void had_stage_lanes(float (&v)[8], bool upper) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float o = FAR ? XL::x16(v[j]) : XL::x8(v[j]);
+    v[j] = upper ? o - v[j] : v[j] + o;
+  }
+}
+
+// the five stages h = 1, 2, 4, 8, 16 of the unnormalised Sylvester-Hadamard transform of a block; c: this lane's chunk index (0-3)
+template <class XL>
+__device__ __forceinline__ void mx_block_hadamard(float (&v)[8], int c) {
+  had_stage<1>(v);
+  had_stage<2>(v);
+  had_stage<4>(v);
+  had_stage_lanes<XL, false>(v, c & 1);
+  had_stage_lanes<XL, true>(v, c & 2);
+}
+
+// max |x| over the block, in all four lanes
+template <class XL>
+__device__ __forceinline__ float mx_block_amax(const float (&v)[8]) {
+  float m = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(v[j]));
+  m = fmaxf(m, XL::x8(m));
+  m = fmaxf(m, XL::x16(m));
+  return m;
+}
+
+// s = clamp(E(amax) - emax, 0, 254)
+template <int EMAX>
+__device__ __forceinline__ int mx_block_scale(float amax) {
+  const int s = (int)((__float_as_uint(amax) >> 23) & 0xffu) - EMAX;
+  return s < 0 ? 0 : (s > 254 ? 254 : s);
+}
+
+// t = x 2^(127 - s), exact
+__device__ __forceinline__ void mx_block_scaled(const float (&v)[8], int s, float (&t)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) t[j] = ldexpf(v[j], 127 - s);
+}
+
+// eight e2m1 codes of a scaled chunk as one dword, even k in the low nibble
+__device__ __forceinline__ uint32_t e2m1_pack8(const float (&t)[8]) {
+  uint32_t w = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) w |= e2m1_code(t[j]) << (4 * j);
+  return w;
+}
+
+}  // namespace wanq

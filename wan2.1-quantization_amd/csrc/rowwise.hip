@@ -1,5 +1,6 @@
 // Row-wise HBM-bound kernels of the denoising step: per-token int8 quantisation, LayerNorm+modulate(+quant), gate-residual.
 // Layout, row frame, reduction and dispatch ladder: row_frame.h.  (Calibration and once-per-model kernels: quant_tools.hip.)
+#include "mx_block.h"
 #include "row_frame.h"
 
 namespace wanq {
@@ -344,6 +345,7 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const Fp8RowParams 
 // for bit h of i clear.  Element i of a block is chunk element i & 7 of quad lane i >> 3: stages 1, 2, 4 stay inside the chunk, stages
 // 8 and 16 are the quad exchanges the maximum uses, the lane with the bit set keeping partner - own.  Additions and subtractions
 // only, one rounding each, in a fixed order: bit-equal to mx_hadamard32_host.  Still no LDS and no barrier.
+// The per-block arithmetic itself is mx_block.h, shared with quant_project.hip (the same codes from another lane layout).
 struct MxRowParams {
   const void* x;
   int x_dtype;
@@ -354,13 +356,6 @@ struct MxRowParams {
   int act;
 };
 
-__device__ __forceinline__ uint32_t e2m1_code(float t) {
-  const float a = fminf(fabsf(t), 6.0f);
-  const uint32_t mag = (uint32_t)(a > 0.25f) + (uint32_t)(a >= 0.75f) + (uint32_t)(a > 1.25f) + (uint32_t)(a >= 1.75f) +
-                       (uint32_t)(a > 2.5f) + (uint32_t)(a >= 3.5f) + (uint32_t)(a > 5.0f);
-  return mag | ((__float_as_uint(t) >> 28) & 8u);
-}
-
 __device__ __forceinline__ uint32_t e2m3_code(float t) {
   const float a = fminf(fabsf(t), 7.5f);
   const float r = a < 2.0f ? rintf(a * 8.0f) : a < 4.0f ? rintf(a * 4.0f) + 8.0f : rintf(a * 2.0f) + 16.0f;
@@ -370,28 +365,6 @@ __device__ __forceinline__ uint32_t e2m3_code(float t) {
 // the value of the quad's next lane (lane 3: lane 0's, unused)
 __device__ __forceinline__ uint32_t quad_next_dpp(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x39, 0xf, 0xf, true);  // quad_perm:[1,2,3,0]
-}
-
-// one butterfly stage inside a chunk: H = 1, 2 or 4
-template <int H>
-__device__ __forceinline__ void had_stage(float (&v)[8]) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    if (j & H) continue;
-    const float a = v[j], b = v[j + H];
-    v[j] = a + b;
-    v[j + H] = a - b;
-  }
-}
-
-// one butterfly stage across the quad: MASK = 1 (h = 8) or 2 (h = 16)
-template <int MASK>
-__device__ __forceinline__ void had_stage_quad(float (&v)[8], bool upper) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float o = lane_xor_dpp<MASK>(v[j]);
-    v[j] = upper ? o - v[j] : v[j] + o;
-  }
 }
 
 template <int WPR, int NCH, bool FP4, bool HAD = false, bool FP6 = false>
@@ -414,24 +387,12 @@ __global__ __launch_bounds__(256) void quant_rows_mx_kernel(const MxRowParams p)
   }
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
-    if constexpr (HAD) {
-      had_stage<1>(v[i]);
-      had_stage<2>(v[i]);
-      had_stage<4>(v[i]);
-      had_stage_quad<1>(v[i], f.lane & 1);
-      had_stage_quad<2>(v[i], f.lane & 2);
-    }
-    float m = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(v[i][j]));
-    m = fmaxf(m, lane_xor_dpp<1>(m));
-    m = fmaxf(m, lane_xor_dpp<2>(m));
+    if constexpr (HAD) mx_block_hadamard<MxQuadLanes>(v[i], f.lane);
+    const float m = mx_block_amax<MxQuadLanes>(v[i]);
     if (!ok[i]) continue;
-    int s = (int)((__float_as_uint(m) >> 23) & 0xffu) - EMAX;
-    s = s < 0 ? 0 : (s > 254 ? 254 : s);
+    const int s = mx_block_scale<EMAX>(m);
     float t[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) t[j] = ldexpf(v[i][j], 127 - s);
+    mx_block_scaled(v[i], s, t);
     const int col = f.col(i);
     if constexpr (FP6) {
       uint64_t c = 0;
@@ -445,10 +406,7 @@ __global__ __launch_bounds__(256) void quant_rows_mx_kernel(const MxRowParams p)
                              : make_uint2(hi | (nlo << 16), (nlo >> 16) | (nhi << 16));
       if (k < 3) *reinterpret_cast<uint2*>(p.q + ((rbase + col) >> 5) * 24 + 8 * k) = w;
     } else if constexpr (FP4) {
-      uint32_t w = 0;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) w |= e2m1_code(t[j]) << (4 * j);
-      *reinterpret_cast<uint32_t*>(p.q + ((rbase + col) >> 1)) = w;
+      *reinterpret_cast<uint32_t*>(p.q + ((rbase + col) >> 1)) = e2m1_pack8(t);
     } else {
 #pragma unroll
       for (int j = 0; j < 8; ++j) t[j] = __builtin_amdgcn_fmed3f(t[j], -FP8_E4M3_MAX, FP8_E4M3_MAX);

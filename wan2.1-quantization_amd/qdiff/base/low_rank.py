@@ -1,5 +1,6 @@
 """The 16-bit low-rank side branch of a weight-only quantised Linear, y = x W_hat^T + (x A^T) B^T, shared by the simulation-mode layer
-(QuantizedLinear) and the kernel-mode one (HipLinearWq16).  Two uses, one operator (wanq_gemm_wq16_lowrank):
+(QuantizedLinear) and the kernel-mode ones (HipLinearWq16, and HipLinearMx for the W4A4 MXFP4 pair: y = Q(x) W_hat^T + (x A^T) B^T).  Two
+uses, one operator (wanq_gemm_wq16_lowrank; wanq_gemm_mx4_lowrank behind wanq_quant_rows_mx4_project):
 
   * LoRC, the low-rank compensation of the quantisation error (ZeroQuant-V2, L2QER): with E = W - W_hat, B A is the best rank-r
     approximation of E (Eckart-Young), kept in 16 bits beside the integer codes.  The config key `weight.low_rank: r`.

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from viditq_extension import qgemm
+from viditq_extension import fused, qgemm
 
 from ..config import ListConfig
 from ..quarot import quarot_utils
@@ -26,6 +26,14 @@ from .mixed_precision_quantizer import MixedPrecisionDynamicQuantizer, MixedPrec
 
 # format key -> (its n_bits, its name in "... is one N-bit format")
 _FORMAT_BITS = {FP8_FORMAT: (8, "e4m3"), MXFP8_FORMAT: (8, MXFP8_FORMAT), MXFP4_FORMAT: (4, MXFP4_FORMAT), MXFP6_FORMAT: (6, MXFP6_FORMAT)}
+
+
+def _hadamard32(device):
+    """H[i][j] = (-1)^popcount(i & j), float64 [32, 32]: the block rotation of MxQuantizer(had32=True)"""
+    i = torch.arange(MX_BLOCK, device=device)
+    bits = (i[:, None] & i[None, :])
+    pop = sum((bits >> k) & 1 for k in range(5))
+    return (1 - 2 * (pop & 1)).double()
 
 
 class QuantizedLinear(LowRankBranch, nn.Linear):
@@ -178,8 +186,9 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
 
     def _checked_low_rank(self, quant_config, module_name):
         """`weight.low_rank` of the config (None: no low-rank branch), or the refusal of what has none, before any weight is
-        quantised: the message names the layer and the key.  The branch lives in the weight-only GEMM alone: a plain QuantizedLinear
-        with an integer StaticQuantizer (per channel or `group_size`) and no `act:` section."""
+        quantised: the message names the layer and the key.  The branch has two hosts: the weight-only GEMM (a plain QuantizedLinear
+        with an integer StaticQuantizer, per channel or `group_size`, and no `act:` section) and the W4A4 MX GEMM (weight.format and
+        act.format both mxfp4_e2m1, with or without `mx.block_hadamard`)."""
         wq = quant_config.get("weight", None)
         r = None if wq is None else wq.get("low_rank", None)
         if r is None:
@@ -187,10 +196,13 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         name = module_name or type(self).__name__
         if isinstance(r, bool) or not isinstance(r, int) or r <= 0:
             raise ValueError(f"{name}: weight.low_rank={r!r} must be a positive integer")
-        if quant_config.get("act", None) is not None:
+        aq = quant_config.get("act", None)
+        # the W4A4 MX pair carries the branch too (wanq_gemm_mx4_lowrank); every other quantised activation is refused as before
+        mx4 = aq is not None and wq.get("format", None) == MXFP4_FORMAT and aq.get("format", None) == MXFP4_FORMAT
+        if aq is not None and not mx4:
             raise NotImplementedError(f"{name}: weight.low_rank with an `act:` section is not supported: the low-rank branch is summed "
                                       "in the weight-only GEMM (16-bit activations); the int8, fp8 and MX GEMMs have none")
-        if wq.get("format", None) is not None:
+        if wq.get("format", None) is not None and not mx4:
             raise NotImplementedError(f"{name}: weight.low_rank with weight.format={wq.get('format')!r} is not supported: the low-rank "
                                       "branch goes with integer weight codes (StaticQuantizer)")
         if isinstance(wq["n_bits"], ListConfig):
@@ -240,6 +252,8 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         return sec
 
     def _refuse_adapter(self):
+        if self._mx4_pair and not (self.uses_mask or self.uses_rotation):
+            return
         if self.w_quantizer is None or self.a_quantizer is not None or self.fp8 or self.mx or self.uses_mask or self.uses_rotation \
                 or not isinstance(self.w_quantizer, StaticQuantizer):
             raise NotImplementedError(f"{self._lr_name()}: set_low_rank needs a plain weight-only QuantizedLinear with integer codes "
@@ -271,6 +285,11 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
             raise ValueError(f"{name}: weight.group_size={g} does not divide in_features={self.in_features}")
         return g
 
+    @property
+    def _mx4_pair(self):
+        """The W4A4 MX pair: the second host of the low-rank branch."""
+        return self.mx == MXFP4_FORMAT and self.mx_act == MXFP4_FORMAT
+
     # ---- weight side --------------------------------------------------------------------------------
     def _requantize(self, w, precomputed=None):
         """weight.data <- fake-quant(w) and int_weight <- its integer codes, with the quantizer's current state; `precomputed`: a
@@ -282,7 +301,10 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         self.weight.data = deq
         self.int_weight = codes
         if self.low_rank is not None:
-            a, b = fit_low_rank(w.detach().double() - deq.double(), self.low_rank)
+            w_hat = deq.double()
+            if self.mx and self.w_quantizer.had32:  # deq is (w / 32) H block by block; H H = 32 I, so W_hat = deq H
+                w_hat = (w_hat.reshape(-1, MX_BLOCK) @ _hadamard32(w_hat.device)).reshape(deq.shape)
+            a, b = fit_low_rank(w.detach().double() - w_hat, self.low_rank)
             self.register_buffer("lr_a", a, persistent=False)  # (as `_codes`: saved by quantize_and_save_weight)
             self.register_buffer("lr_b", b, persistent=False)
             self._lr16 = None
@@ -437,6 +459,8 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         these are kernel mode's two entries per format, fused.quant_rows_fp8 + qgemm.fp8_linear and fused.quant_rows_mx +
         qgemm.mx_linear / qgemm.mx4_linear.  In host memory, and for a shape the GEMM refuses, the same numbers through torch: F.linear of the
         dequantised activation and the dequantised weight, in fp32."""
+        if self._mx4_pair and (self.low_rank is not None or self._adapter is not None):
+            return self._forward_mx4_low_rank(x2, out_dtype, bias)
         a_q, a_s = self.a_quantizer.codes_and_scale(x2)
         refusal, gemm, fmt = (qgemm.mx6_linear_refusal, qgemm.mx6_linear, (self.mx,)) if self.mx_act == MXFP6_FORMAT else \
             (qgemm.mx4_linear_refusal, qgemm.mx4_linear, ()) if self.mx_act == MXFP4_FORMAT else \
@@ -447,6 +471,22 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         # (with mx.block_hadamard the decoded activation and weight.data are both in the rotated domain: their product is x w^T's)
         a = mx_decode(a_q, a_s, self.mx_act) if self.mx else fp8_decode(a_q) * a_s.unsqueeze(-1)
         return F.linear(a, self.weight.data.float(), bias).to(out_dtype)
+
+    def _forward_mx4_low_rank(self, x2, out_dtype, bias):
+        """The W4A4 MX layer with a low-rank branch (`weight.low_rank` and / or `set_low_rank`; factors A16 [Rp, K], B16 [N, Rp] in T =
+        the activation's dtype when that is 16 bits wide, else bf16): y = Q(x) W_hat^T + t B16^T + bias with t = round_T(round_T(x)
+        A16^T), the row rounded once to T in front of the rotation and the product summed in fp32.  On the GPU one producer,
+        fused.quant_rows_mxfp4_project (codes, scale bytes and t in one pass over x), and qgemm.mx4_lowrank_linear; in host memory, and
+        for a shape they refuse, the same numbers through torch with the same roundings."""
+        T = x2.dtype if x2.dtype in (torch.bfloat16, torch.float16) else torch.bfloat16
+        a16, b16 = self.low_rank_operands(T, x2.device)
+        if x2.is_cuda and qgemm.mx4_lowrank_refusal(x2.shape[0], self.out_features, self.in_features, a16.shape[0]) is None:
+            a_q, a_s, t = fused.quant_rows_mxfp4_project(x2.contiguous(), a16, had32=self.mx_had32)
+            return qgemm.mx4_lowrank_linear(a_q, self._codes, a_s, self.w_quantizer.scale_u8, t, b16, bias, out_dtype=out_dtype)
+        a_q, a_s = self.a_quantizer.codes_and_scale(x2)
+        t = (x2.to(T).float() @ a16.float().t()).to(T)
+        y = F.linear(mx_decode(a_q, a_s, self.mx_act), self.weight.data.float()) + t.float() @ b16.float().t()
+        return (y if bias is None else y + bias).to(out_dtype)
 
     def _forward_grouped(self, x2, out_dtype, bias):
         """A `weight.group_size` with an `act:` section: the activation is quantised per token as in `_forward_int8` and multiplied on

@@ -144,6 +144,43 @@ def quant_rows_mxfp4_h32(x, gelu=False):
     return quant_rows_mx(x, "mxfp4_e2m1", gelu, had32=True)
 
 
+def quant_rows_mxfp4_project(x, a16, gelu=False, had32=False, ldt=None, out=None):
+    """`quant_rows_mxfp4` (`had32`: `quant_rows_mxfp4_h32`) and, in the same pass over x, the down-projection of a 16-bit low-rank
+    branch (wanq_quant_rows_mx4_project, csrc/quant_project.hip): -> (codes, scales, t).  codes and scales are the plain quantiser's,
+    bit for bit.  a16 [R, cols] bf16 or fp16;  t [rows, R] of a16's dtype, t = round(round(gelu(x)) @ a16^T): the row is rounded once to
+    a16's dtype behind the GELU and in front of the rotation, the product is summed in fp32 and rounded once.  With `ldt` (>= R, a
+    multiple of 8) t is the buffer [rows, ldt] whose columns 0 .. R - 1 are written: several consumers' factors stacked along r give
+    each its column window.  `out`: an existing [rows, R] window to write t into (unit column stride; its row pitch is ldt), returned
+    as t.  cols % 128 == 0, R % 64 == 0, 64 <= R <= 256."""
+    rows, cols = _rows_cols("x", x)
+    _C.check_gpu("a16", a16)
+    _C.check_contig("a16", a16)
+    _C.check_dtype("a16", a16, torch.bfloat16, torch.float16)
+    if a16.dim() != 2 or a16.shape[1] != cols:
+        raise RuntimeError(f"quant_rows_mxfp4_project: a16 must be [R, {cols}], got {tuple(a16.shape)}")
+    R = a16.shape[0]
+    if out is not None:
+        _C.check_gpu("out", out)
+        if out.dtype != a16.dtype or tuple(out.shape) != (rows, R) or out.stride(1) != 1:
+            raise RuntimeError(f"quant_rows_mxfp4_project: out must be [{rows}, {R}] of a16's dtype with unit column stride")
+        ldt = out.stride(0)
+    ldt = R if ldt is None else int(ldt)
+    if cols % 128:
+        raise RuntimeError(f"quant_rows_mxfp4_project: cols={cols} must be a multiple of 128")
+    if R < 64 or R > 256 or R % 64:
+        raise RuntimeError(f"quant_rows_mxfp4_project: R={R} must be a multiple of 64 in [64, 256]")
+    if ldt < R or ldt % 8:
+        raise RuntimeError(f"quant_rows_mxfp4_project: ldt={ldt} must be a multiple of 8 and at least R={R}")
+    _C.check_same_device(x, a16)
+    codes = torch.empty((rows, cols // 2), dtype=torch.uint8, device=x.device)
+    scale = torch.empty((rows, cols // 32), dtype=torch.uint8, device=x.device)
+    t = out if out is not None else torch.empty((rows, ldt), dtype=a16.dtype, device=x.device)
+    with torch.cuda.device(x.device):
+        _C.call("wanq_quant_rows_mx4_project", _C.ptr(x), _C.dt(x), _C.ptr(codes), _C.ptr(scale), _C.ptr(a16), _C.dt(a16), R, _C.ptr(t),
+                ldt, rows, cols, 1 if gelu else 0, 1 if had32 else 0, _C.stream())
+    return codes, scale, t
+
+
 def _layernorm(output, input, weight, shift_msa, scale_msa, sum_output, scaling, epsilon, quant):
     rows, cols = _rows_cols("input", input)
     _C.check_gpu("output", output)

@@ -559,6 +559,52 @@ def mx4_linear_refusal(M, N, K):
     return _shape_refusal(M, N, K, MX_K_STEP, bounded=True)
 
 
+def mx4_lowrank_linear(a_q, w_q, a_scale, w_scale, t, b, bias=None, out_dtype=None, gelu=False, gate=None, residual=None, out=None):
+    """`mx4_linear` with a 16-bit low-rank branch summed into the same accumulators (wanq_gemm_mx4_lowrank, csrc/gemm_mx.hip):
+    y = epilogue(y0 + t[M,R] @ b[N,R]^T), y0 what `mx4_linear` has before its bias.  `t` (from `fused.quant_rows_mxfp4_project`) and `b`
+    share a dtype, bf16 or fp16; `t` may be a column window [M, R] of a wider buffer (stride(1) == 1, stride(0) % 8 == 0, 16-byte
+    aligned).  R % 64 == 0, 64 <= R <= 256 (zero pad a smaller rank).  The branch is added before GELU and gate + residual."""
+    for name, x in (("a_q", a_q), ("w_q", w_q), ("a_scale", a_scale), ("w_scale", w_scale)):
+        if x is None:
+            raise RuntimeError(f"mx4_lowrank_linear: {name} must be given")
+        _check_mat(name, x, torch.uint8)
+    M, K = a_q.shape[0], a_q.shape[1] * 2
+    N = w_q.shape[0]
+    for name, x in (("t", t), ("b", b)):
+        _C.check_gpu(name, x)
+        _C.check_dtype(name, x, torch.bfloat16, torch.float16)
+        if x.dim() != 2:
+            raise RuntimeError(f"Tensor {name} must have dimension number (2)")
+    _C.check_contig("b", b)
+    R = b.shape[1]
+    why = mx4_lowrank_refusal(M, N, K, R)
+    if why is not None:
+        raise RuntimeError(f"mx4_lowrank_linear: {why}")
+    if t.dtype != b.dtype or tuple(t.shape) != (M, R) or t.stride(1) != 1 or t.stride(0) < R or t.stride(0) % 8:
+        raise RuntimeError(f"mx4_lowrank_linear: t must be [{M}, {R}] of b's dtype with unit column stride and a row pitch that is a "
+                           f"multiple of 8 (got {tuple(t.shape)} {t.dtype}, strides {tuple(t.stride())})")
+    _C.check_shape("w_q", w_q, N, K // 2)
+    _C.check_shape("a_scale", a_scale, M, K // 32)
+    _C.check_shape("w_scale", w_scale, N, K // 32)
+    _C.check_shape("b", b, N, R)
+    return _launch16("wanq_gemm_mx4_lowrank", (_C.ptr(a_q), _C.ptr(w_q), _C.ptr(a_scale), _C.ptr(w_scale), _C.ptr(t), int(t.stride(0)),
+                                               _C.ptr(b), _C.dt(b), int(R)),
+                     (a_q, w_q, a_scale, w_scale, t, b), bias, out_dtype or torch.bfloat16, gelu, gate, residual, out, M, N, K)
+
+
+def mx4_lowrank_refusal(M, N, K, R):
+    """Why wanq_gemm_mx4_lowrank (and wanq_quant_rows_mx4_project in front of it) would refuse an [M, K] x [N, K] product with a rank-R
+    branch (None = accepted): the rules of `mx4_linear_refusal`, the producer's K <= 16384, then R; see `fp_linear_refusal`."""
+    why = mx4_linear_refusal(M, N, K)
+    if why is not None:
+        return why
+    if K > 16384:
+        return f"K={K} must be at most 16384 (wanq_quant_rows_mx4_project keeps a row panel's columns in one workgroup)"
+    if not isinstance(R, int) or R < 64 or R > LOWRANK_MAX or R % 64:
+        return f"R={R} must be a multiple of 64 in [64, {LOWRANK_MAX}]"
+    return None
+
+
 # ---- OCP MX W6A6 / W4A6: MXFP6 (e2m3) activations x MXFP6 / MXFP4 weights, E8M0 block scales ------------------------------------------
 def mx6_linear(a_q, w_q, a_scale, w_scale, w_fmt="mxfp6_e2m3fn", bias=None, out_dtype=None, gelu=False, gate=None, residual=None,
                out=None):

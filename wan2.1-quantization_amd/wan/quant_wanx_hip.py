@@ -57,6 +57,10 @@ class _HipLinear(nn.Module):
         """The leading arguments of forward, made from a source (_LnSrc / _FpSrc) in the form this layer consumes."""
         return (src.fp(),)
 
+    def extras(self, src):
+        """Keyword arguments of forward that come from the source too (HipLinearMx with a low-rank branch: `t`)."""
+        return {}
+
 
 class _HipLinearInt(_HipLinear):
     """The buffers HipLinearW8A8 and HipLinearWq16 both hold (described there), and the zero point their GEMMs take."""
@@ -382,7 +386,7 @@ class HipLinearFp8(_HipLinearCodes):
                                 residual=residual, out=out)
 
 
-class HipLinearMx(_HipLinearCodes):
+class HipLinearMx(LowRankBranch, _HipLinearCodes):
     """An OCP MX Linear (`format: mxfp8_e4m3` activations against `mxfp8_e4m3` / `mxfp4_e2m1` weights, or with `a_fmt` "mxfp4_e2m1"
     the W4A4 pair): `weight` uint8 [N, K] e4m3 bytes or [N, K / 2] packed e2m1 nibbles, `scale_weight` uint8 [N, K / 32] E8M0 bytes,
     both from wanq_quant_rows_mx; `bias` fp32.  Its input is the block's activation quantised per block of 32 channels by the same
@@ -392,11 +396,18 @@ class HipLinearMx(_HipLinearCodes):
     holds the one-element uint8 buffer `mx_had32`, which travels with its codes in the integer checkpoint.  `a_fmt` "mxfp6_e2m3fn"
     (W6A6 / W4A6): `weight` uint8 [N, 3 K / 4] packed e2m3 codes (w_fmt "mxfp6_e2m3fn", from wanq_quant_rows_mx6) or the packed e2m1
     nibbles, the input quantised to e2m3 (activation form "mxfp6"), the product qgemm.mx6_linear; the layer then holds the uint8
-    buffer `mx_fmt` = (w_fmt code, a_fmt code), which records the formats in the integer checkpoint."""
+    buffer `mx_fmt` = (w_fmt code, a_fmt code), which records the formats in the integer checkpoint.
+    With a `low_rank` (W4A4 only, the config's `weight.low_rank`) the buffers `lr_a` [Rp, K] / `lr_b` [N, Rp] hold the LoRC factors in
+    `act_dtype` (qdiff/base/low_rank.py), `set_low_rank` attaches a user adapter behind them, the input comes from the source's
+    `project` -- the quantiser and the down-projection t = x A16^T in one pass (fused.quant_rows_mxfp4_project), one launch for all
+    consumers of the source -- and the product is qgemm.mx4_lowrank_linear: the branch is summed in the GEMM's own accumulators.
+    Under --dit_fsdp the factors are replicated (`sharded` names the codes and the scale bytes only)."""
     act_form = act_key = "mxfp8"
     sharded = ("weight", "scale_weight")   # the scale bytes are a thirty-second or a sixteenth of the weight's
 
-    def __init__(self, in_features, out_features, bias=True, w_fmt="mxfp8_e4m3", name="linear", a_fmt="mxfp8_e4m3", had32=False):
+    def __init__(self, in_features, out_features, bias=True, w_fmt="mxfp8_e4m3", name="linear", a_fmt="mxfp8_e4m3", had32=False,
+                 low_rank=None, act_dtype=torch.bfloat16):
+        self.name = name
         a4, a6, w6 = a_fmt == "mxfp4_e2m1", a_fmt == "mxfp6_e2m3fn", w_fmt == "mxfp6_e2m3fn"
         if a_fmt not in ("mxfp8_e4m3", "mxfp4_e2m1", "mxfp6_e2m3fn") or (a4 and w_fmt != "mxfp4_e2m1") or (had32 and not a4) or \
                 (a6 and w_fmt not in ("mxfp6_e2m3fn", "mxfp4_e2m1")) or (w6 and not a6):
@@ -414,15 +425,51 @@ class HipLinearMx(_HipLinearCodes):
             self.register_buffer("mx_fmt", torch.tensor([_C.MX6_FMT[w_fmt], _C.MX6_FMT[a_fmt]], dtype=torch.uint8))
         if had32:
             self.register_buffer("mx_had32", torch.ones(1, dtype=torch.uint8))
+        if low_rank and not a4:
+            raise NotImplementedError(f"{name}: weight.low_rank goes with the W4A4 pair only (weight {w_fmt} against act {a_fmt})")
+        if act_dtype not in (torch.bfloat16, torch.float16):
+            raise ValueError(f"{name}: the low-rank branch takes bf16 or fp16 factors (act_dtype {act_dtype})")
+        self.low_rank, self.act_dtype = low_rank, act_dtype
+        rp = padded_rank(low_rank) if low_rank else 0
+        self.register_buffer("lr_a", torch.zeros(rp, in_features, dtype=act_dtype) if low_rank else None)
+        self.register_buffer("lr_b", torch.zeros(out_features, rp, dtype=act_dtype) if low_rank else None)
+
+    def _refuse_adapter(self):
+        if self.a_fmt != "mxfp4_e2m1":
+            raise NotImplementedError(f"{self._lr_name()}: set_low_rank needs the W4A4 pair (weight {self.mx} against act {self.a_fmt}): "
+                                      "only wanq_gemm_mx4_lowrank sums a low-rank branch")
+
+    @property
+    def has_branch(self):
+        return self.low_rank is not None or self._adapter is not None
 
     @classmethod
-    def from_quantized(cls, ql, name="linear"):
-        """From a plain qdiff QuantizedLinear built with an MX format: the same codes and scale bytes."""
-        m = cls(ql.in_features, ql.out_features, ql.bias is not None, ql.mx, name, ql.mx_act, ql.mx_had32).to(ql.fp_module.weight.device)
+    def from_quantized(cls, ql, name="linear", act_dtype=torch.bfloat16):
+        """From a plain qdiff QuantizedLinear built with an MX format: the same codes and scale bytes, and the same low-rank factors
+        (the LoRC buffers cast once to `act_dtype`, the adapter as attached)."""
+        m = cls(ql.in_features, ql.out_features, ql.bias is not None, ql.mx, name, ql.mx_act, ql.mx_had32, ql.low_rank,
+                act_dtype if act_dtype in (torch.bfloat16, torch.float16) else torch.bfloat16).to(ql.fp_module.weight.device)
+        if ql.low_rank is not None:
+            m.lr_a.copy_(ql.lr_a)
+            m.lr_b.copy_(ql.lr_b)
+        m._adapter = ql._adapter
         return m._take(ql, ql.w_quantizer.scale_u8, name)
 
-    def forward(self, a_q, a_scale, out_dtype=torch.bfloat16, gelu=False, gate=None, residual=None, out=None):
-        """Reads `weight` and `scale_weight` as they are now (--dit_fsdp re-points them at views of the gathered buffer)."""
+    def operands(self, src):
+        if self.has_branch:
+            src.project([self])  # (codes and scales come from the pass that makes t)
+        return src.rows(self.act_form)
+
+    def extras(self, src):
+        return {"t": src.projected(self)} if self.has_branch else {}
+
+    def forward(self, a_q, a_scale, out_dtype=torch.bfloat16, gelu=False, gate=None, residual=None, out=None, t=None):
+        """`t`: with a low-rank branch, this layer's window of the source's projection (`extras`).  Reads `weight` and `scale_weight`
+        as they are now (--dit_fsdp re-points them at views of the gathered buffer)."""
+        if self.has_branch:
+            _, b16 = self.low_rank_operands(self.act_dtype, a_q.device)
+            return qgemm.mx4_lowrank_linear(a_q, self.weight, a_scale, self.scale_weight, t, b16, self.bias, out_dtype, gelu=gelu,
+                                            gate=gate, residual=residual, out=out)
         if self.a_fmt == "mxfp6_e2m3fn":
             return qgemm.mx6_linear(a_q, self.weight, a_scale, self.scale_weight, self.mx, self.bias, out_dtype, gelu=gelu, gate=gate,
                                     residual=residual, out=out)
@@ -445,7 +492,7 @@ def _to_hip_linear(lin, n_bits, sym, act_dtype, fp_gemm="torch", name="linear"):
         cls = _HIP_LINEAR_OF.get(lin.kind)
         if cls is HipLinearWq16 and act_dtype not in (torch.bfloat16, torch.float16):
             raise ValueError(f"{name}: the weight-only GEMM takes bf16 or fp16 activations (act_dtype {act_dtype})")
-        if cls is HipLinearWq16:
+        if cls is HipLinearWq16 or cls is HipLinearMx:
             return cls.from_quantized(lin, name, act_dtype)
         if cls is not None:
             return cls.from_quantized(lin, name)
@@ -471,12 +518,46 @@ class _Src:
             self.cache[form] = getattr(fused, _ROW_QUANTISERS[form])(x, gelu=gelu)
         return self.cache[form]
 
+    def project(self, lins):
+        """Serve every consumer in `lins` that carries a low-rank branch (HipLinearMx.has_branch) with ONE pass over this activation:
+        their down factors A16 are stacked along r while the total stays <= 256 and the form (rotated or not) is the same, the
+        producer (fused.quant_rows_mxfp4_project) runs once, (codes, scales) are cached under the form for every consumer of it and
+        each consumer's t is a column window of the stacked buffer.  What does not fit the stack gets a launch of its own."""
+        todo = [(l, l.low_rank_operands(l.act_dtype, self.device)[0]) for l in lins
+                if getattr(l, "has_branch", False) and ("t", id(l)) not in self.cache]
+        while todo:
+            first, group, total = todo[0][0], [], 0
+            for l, a in todo:
+                if l.act_form == first.act_form and l.act_dtype == first.act_dtype and total + a.shape[0] <= qgemm.LOWRANK_MAX:
+                    group.append(l)
+                    total += a.shape[0]
+            a16s = [a for l, a in todo if l in group]
+            todo = [(l, a) for l, a in todo if l not in group]
+            # the stacked factor is constant between weight updates: made once per group, kept on its first consumer
+            key = tuple((id(a), a._version) for a in a16s)
+            if len(group) > 1 and first.__dict__.get("_lr_stack", (None,))[0] != key:
+                first.__dict__["_lr_stack"] = (key, torch.cat(a16s, 0))
+            x, gelu = self._plain_row()
+            codes, scales, t = fused.quant_rows_mxfp4_project(x, a16s[0] if len(group) == 1 else first.__dict__["_lr_stack"][1], gelu=gelu,
+                                                              had32=first.had32)
+            self.cache.setdefault(first.act_form, (codes, scales))
+            r0 = 0
+            for l, a in zip(group, a16s):
+                self.cache[("t", id(l))] = t[:, r0:r0 + a.shape[0]]
+                r0 += a.shape[0]
+
+    def projected(self, lin):
+        """t for a consumer with a low-rank branch; `project` made it, here if not before."""
+        self.project([lin])
+        return self.cache[("t", id(lin))]
+
 
 class _LnSrc(_Src):
     """Lazy activation = LayerNorm(x) (* gamma) * (1 + scale) + shift, materialised per consumer format."""
 
     def __init__(self, blk, x, gamma, shift, scale):
         self.blk, self.x, self.gamma, self.shift, self.scale, self.cache = blk, x, gamma, shift, scale, {}
+        self.device = x.device
 
     def int8(self, lin):
         key = lin.act_key
@@ -552,6 +633,7 @@ class _FpSrc(_Src):
 
     def __init__(self, t, fp_dtype=None, gelu=False):
         self.t, self.cache, self.fp_dtype, self.gelu = t, {}, fp_dtype, gelu
+        self.device = t.device
         # `derived`: what consumers computed from this source and may reuse while the source lives (the text context is the same
         # tensor in every denoising step: a block's cross-attention k / v of it are kept here, keyed by the block)
         self.derived = None
@@ -707,10 +789,10 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         out_dtype = out_dtype or self.act_dtype
         if lin.act_quantizer is not None:
             return self._linear_any_act(lin, src, out_dtype, gelu, gate, residual)
-        a = lin.operands(src)
+        a, kw = lin.operands(src), lin.extras(src)
         if residual is not None:  # (the gate is a contiguous fp32 [C] at every call site: a modulation row, or `ones_gate`)
-            return lin(*a, torch.float32, gate=gate, residual=residual, out=residual)
-        return lin(*a, out_dtype, gelu=gelu)
+            return lin(*a, torch.float32, gate=gate, residual=residual, out=residual, **kw)
+        return lin(*a, out_dtype, gelu=gelu, **kw)
 
     def _linear_any_act(self, lin, src, out_dtype, gelu, gate, residual):
         """A quantised Linear whose activation quantiser is not the fused producers' (asymmetric, below 8 bits, the mixed-precision
@@ -743,6 +825,7 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         if memo is not None and id(self) in memo:
             return memo[id(self)]
         ca = self.cross_attn
+        ctx.project([ca.k, ca.v])
         k = self._linear(ca.k, ctx)
         v = self._vq(self._linear(ca.v, ctx), self.cross_attn_v_bits, None)
         k = self._prep_qk(k, ca.norm_k_weight, None, self.cross_attn_qk8, True, smooth=self.cross_attn_smooth_k)
@@ -847,6 +930,7 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         # ---- self attention: LN*(1+e1)+e0 -> q,k,v -> RMSNorm+RoPE -> attention -> o (+gate, +residual)
         h = _LnSrc(self, x, None, e[:, 0], e[:, 1])
         h.prefetch([sa.q, sa.k, sa.v])  # one pass over x for the three ViDiT-transformed int8 inputs
+        h.project([sa.q, sa.k, sa.v])   # ... and for the three W4A4 inputs with a low-rank branch: codes and all three t
         q = self._linear(sa.q, h)
         if sp is not None and sp.size > 1:
             o = self._self_attention_ulysses(q, h, rope, seq_len, sp)
