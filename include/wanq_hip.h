@@ -130,6 +130,25 @@ int wanq_quant_rows_mx_had32(const void* x, int x_dtype, uint8_t* q, uint8_t* sc
 int wanq_quant_rows_mx4_project(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, const void* a16, int dtype16, int R, void* t,
                                 int ldt, int64_t rows, int cols, int act, int had32, void* stream);
 
+/* The mixed MX row format and its quantiser: a W4A4 MX layer with outlier channels.  A layer carries a channel order `perm` (int32
+ * [cols], a permutation of 0 .. cols - 1) and a count n8 (n8 % 128 == 0, n8 >= 128, cols - n8 >= 128).  BOTH operands of its GEMM are
+ * stored in permuted order, column j of a stored row being channel perm[j]:
+ *   q        [rows, n8 + (cols - n8) / 2] bytes: the first n8 bytes of a row are the e4m3 codes of x[:, perm[:n8]], the others the
+ *            packed e2m1 nibbles of x[:, perm[n8:]], even k in the low nibble
+ *   scale_u8 [rows, cols / 32]: one E8M0 byte per block of 32 PERMUTED channels; blocks below n8 / 32 by the rule of fmt WANQ_MX_E4M3
+ *            (emax 8), the others by that of WANQ_MX_E2M1 (emax 2)
+ * i.e. wanq_quant_rows_mx(fmt E4M3) of the first column gather beside wanq_quant_rows_mx(fmt E2M1) of the second, bit for bit (one
+ * definition of the per-block arithmetic, csrc/mx_block.h; host expression mx_quant_rows_mixed_host, qdiff/base/base_quantizer.py).
+ * The permutation is applied on chip (csrc/quant_mixed.hip): whole rows are copied global -> LDS once, coalesced, 16 bytes per lane,
+ * and read from LDS at their permuted places; perm is read once per workgroup.  act: 0 = identity, 1 = tanh-GELU in fp32 (elementwise:
+ * it commutes with the gather).  perm is trusted to be a permutation; an index outside [0, cols) is clamped into the row.
+ * The argument rules of wanq_quant_rows_mx, and: cols % 128 == 0, 256 <= cols <= 16384; the n8 rules above; perm non-NULL; x, q and
+ * perm 16-byte aligned, scale_u8 4-byte aligned;  rows == 0 returns WANQ_OK.  Anything else is refused (WANQ_E_SHAPE / WANQ_E_ARG, the
+ * message names the rule).  A row's bytes do not depend on rows or on the row's place in the launch.
+ * No reference counterpart. */
+int wanq_quant_rows_mx_mixed(const void* x, int x_dtype, const int32_t* perm, int n8, uint8_t* q, uint8_t* scale_u8, int64_t rows,
+                             int cols, int act, void* stream);
+
 /* OCP MXFP6 (e2m3) block quantisation: wanq_quant_rows_mx's row frame, GELU option, block maximum and argument rules, to 6-bit codes.
  * The format (WANQ_MX_E2M3; config name mxfp6_e2m3fn: finite only), defined here and as a host expression in
  * qdiff/base/base_quantizer.py:
@@ -655,6 +674,23 @@ int wanq_gemm_mx4(const uint8_t* a, const uint8_t* w, const uint8_t* sa_u8, cons
 int wanq_gemm_mx4_lowrank(const uint8_t* a, const uint8_t* w, const uint8_t* sa_u8, const uint8_t* sw_u8, const void* t, int ldt,
                           const void* b, int dtype16, int R, void* out, int out_dtype, const void* bias, int bias_dtype,
                           const float* gate, const void* residual, int epi_flags, int64_t M, int N, int K, void* stream);
+
+/* W4A4 MX GEMM with outlier channels, over the mixed MX row format of wanq_quant_rows_mx_mixed on both sides (a and w in the SAME
+ * permuted channel order; the weight goes through the quantiser once at conversion, on w[:, perm]):
+ *   acc[m,n] = sum_b 2^(sa[m,b] - 127) 2^(sw[n,b] - 127) sum_{k in block b} a[m,k] * w[n,k]   over all K / 32 permuted blocks;
+ *   y = acc + bias[n];  GELU;  residual + y * gate;  one rounding to out_dtype.
+ * One K loop on v_mfma_scale_f32_16x16x128_f8f6f4 (csrc/gemm_mx_mixed.hip): n8 / 128 K-tiles with e4m3 on both sides, then (K - n8) /
+ * 128 K-tiles with e2m1 on both sides at the fp4 rate, into the same accumulators.  Semantics, epilogue, shape rules and determinism
+ * statement are wanq_gemm_mx4's.  a: [M, n8 + (K - n8) / 2] bytes, w: [N, n8 + (K - n8) / 2] bytes, sa_u8 [M, K / 32], sw_u8 [N, K /
+ * 32], 4-byte aligned.  Any M >= 1 (M == 0 returns WANQ_OK); N % 8 == 0; K % 128 == 0; n8 % 128 == 0, 128 <= n8 <= K - 128.  a, w, out
+ * and residual 16-byte aligned, gate and bias aligned to 4 elements.  Anything else is refused (WANQ_E_SHAPE / WANQ_E_ARG, the message
+ * names the rule).
+ * Determinism: one kernel form, no split-K; K-tiles ascending in permuted order, so the summation order of element (m, n) depends on
+ * (K, n8) only: a row gives the same bits at any m and in a launch of any M, and repeated calls are bit-identical.
+ * No reference counterpart. */
+int wanq_gemm_mx_mixed(const uint8_t* a, const uint8_t* w, const uint8_t* sa_u8, const uint8_t* sw_u8, int n8, void* out,
+                       int out_dtype, const void* bias, int bias_dtype, const float* gate, const void* residual, int epi_flags,
+                       int64_t M, int N, int K, void* stream);
 
 /* MXFP6 GEMMs, W6A6 and W4A6: e2m3 activations (wanq_quant_rows_mx6) against e2m3 weights (w_fmt WANQ_MX_E2M3, the same entry once
  * at conversion) or packed e2m1 weights (w_fmt WANQ_MX_E2M1, wanq_quant_rows_mx), on v_mfma_scale_f32_16x16x128_f8f6f4 with no

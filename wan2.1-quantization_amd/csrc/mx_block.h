@@ -89,4 +89,19 @@ __device__ __forceinline__ uint32_t e2m1_pack8(const float (&t)[8]) {
   return w;
 }
 
+// eight e4m3fn codes of a scaled chunk as two dwords: the clamp to +-448, then the packed hardware conversion (round to nearest even,
+// subnormal codes kept).  A COPY of the e4m3 branch of quant_rows_mx_kernel (rowwise.hip), which keeps its own lines so that its
+// instruction stream does not move: the two must be kept in step (tests/test_gpu_mx_mixed.py holds this one to the host expression
+// that tests/test_gpu_mx.py holds the other to)
+__device__ __forceinline__ uint2 e4m3_pack8(const float (&t)[8]) {
+  float c[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) c[j] = __builtin_amdgcn_fmed3f(t[j], -448.0f, 448.0f);
+  int lo = __builtin_amdgcn_cvt_pk_fp8_f32(c[0], c[1], 0, false);
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(c[2], c[3], lo, true);
+  int hi = __builtin_amdgcn_cvt_pk_fp8_f32(c[4], c[5], 0, false);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(c[6], c[7], hi, true);
+  return make_uint2((uint32_t)lo, (uint32_t)hi);
+}
+
 }  // namespace wanq

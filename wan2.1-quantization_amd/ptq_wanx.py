@@ -28,12 +28,14 @@ def main(args):
     model = QuantWanModel.from_float(fp, quant_config)
     del fp
     model.quant_layer_refactor()
-    if any(quant_config.get(k, None) is not None for k in ("viditq", "smooth_quant", "quarot")):
+    mx_sec = quant_config.get("mx", None)
+    outliers = mx_sec is not None and mx_sec.get("outlier_channels", None) is not None  # the order comes from the calibration absmax
+    if outliers or any(quant_config.get(k, None) is not None for k in ("viditq", "smooth_quant", "quarot")):
         calib_data = torch.load(args.calib_data or quant_config.calib_data.save_path, weights_only=True)
         g = torch.Generator().manual_seed(args.base_seed)
         apply_func_to_submodules(model, class_type=QuantizedLinear,
                                  function=lambda m, full_name, calib_data: calib.init_rotation_and_channel_mask_(m, full_name, calib_data, g)
-                                 if (m.uses_mask or m.uses_rotation) else None, full_name="", calib_data=calib_data)
+                                 if (m.uses_mask or m.uses_rotation or m.mx_n8 is not None) else None, full_name="", calib_data=calib_data)
     if quant_config.get("mixed_precision", None) is not None:
         model.bitwidth_refactor()
     if quant_config.get("gptq", None) is not None:

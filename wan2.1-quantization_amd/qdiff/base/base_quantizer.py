@@ -363,6 +363,40 @@ def mx_decode(codes, scale_u8, fmt, dtype=torch.float32):
     return v.reshape(rows, cols).to(dtype)
 
 
+# ---- the mixed MX row format: outlier channels in MXFP8, the rest in MXFP4 (include/wanq_hip.h, wanq_quant_rows_mx_mixed) -----------
+def mx_mixed_check(cols, perm, n8, what="mx_mixed"):
+    """The format's rules: n8 a multiple of 128 with 128 <= n8 <= cols - 128, perm an integer permutation of range(cols)."""
+    if isinstance(n8, bool) or not isinstance(n8, int) or n8 < 128 or n8 % 128 or cols - n8 < 128 or cols % 128:
+        raise ValueError(f"{what}: n8={n8!r} must be a multiple of 128 with 128 <= n8 <= cols - 128 (cols={cols}, a multiple of 128)")
+    if perm.dim() != 1 or perm.numel() != cols or perm.dtype not in (torch.int32, torch.int64) or \
+            not torch.equal(perm.long().sort().values, torch.arange(cols, device=perm.device)):
+        raise ValueError(f"{what}: perm must be an integer permutation of range({cols})")
+
+
+def mx_quant_rows_mixed_host(x, perm, n8, gelu=False):
+    """(codes uint8 [rows, n8 + (cols - n8) / 2], scale bytes uint8 [rows, cols / 32]) of the mixed MX row format: nothing more than
+    mx_quant_rows_host applied to the two column gathers, concatenated -- mxfp8_e4m3 of x[:, perm[:n8]], then mxfp4_e2m1 of
+    x[:, perm[n8:]].  The GELU is elementwise, so it is applied by the two calls."""
+    mx_mixed_check(x.shape[-1], perm, n8, "mx_quant_rows_mixed")
+    p = perm.long()
+    c8, s8 = mx_quant_rows_host(x[:, p[:n8]], MXFP8_FORMAT, gelu)
+    c4, s4 = mx_quant_rows_host(x[:, p[n8:]], MXFP4_FORMAT, gelu)
+    return torch.cat((c8, c4), dim=1), torch.cat((s8, s4), dim=1)
+
+
+def mx_quant_rows_mixed(x, perm, n8, gelu=False):
+    """The mixed quantiser: on the GPU wanq_quant_rows_mx_mixed, in host memory the host expression it is bit-equal to."""
+    if x.is_cuda:
+        return fused.quant_rows_mx_mixed(x.contiguous(), perm.to(device=x.device, dtype=torch.int32), n8, gelu)
+    return mx_quant_rows_mixed_host(x, perm, n8, gelu)
+
+
+def mx_decode_mixed(codes, scale_u8, n8, dtype=torch.float32):
+    """Dequantised values [rows, cols] of mixed codes + scale bytes, in PERMUTED channel order (column j is channel perm[j])."""
+    return torch.cat((mx_decode(codes[:, :n8], scale_u8[:, :n8 // MX_BLOCK], MXFP8_FORMAT, dtype),
+                      mx_decode(codes[:, n8:], scale_u8[:, n8 // MX_BLOCK:], MXFP4_FORMAT, dtype)), dim=1)
+
+
 class MxQuantizer(BaseQuantizer):
     """`format: mxfp8_e4m3` / `mxfp6_e2m3fn` / `mxfp4_e2m1` of a `weight:` or `act:` section (n_bits 8 / 6 / 4, sym True): one E8M0 scale
     byte per row and block of 32 input channels, e4m3 bytes, packed e2m3 codes (three bytes per four) or packed e2m1 nibbles.  `scale_u8` [rows, cols / 32] holds the bytes as the GEMM reads

@@ -18,7 +18,7 @@ from viditq_extension import fused, qgemm
 from ..config import ListConfig
 from ..quarot import quarot_utils
 from .base_quantizer import (FP8_FORMAT, MX_BLOCK, MX_FORMATS, MXFP4_FORMAT, MXFP6_FORMAT, MXFP8_FORMAT, DynamicQuantizer, Fp8Quantizer, MxQuantizer,
-                             StaticQuantizer, fp8_decode, mx_decode)
+                             StaticQuantizer, _pow2_f64, fp8_decode, mx_decode, mx_decode_mixed, mx_quant_rows_mixed)
 from .gptq import BLOCK_MAX, gptq_prepare, gptq_section, gptq_solve
 from .low_rank import RANK_MAX, LowRankBranch, fit_low_rank, padded_rank
 from .mixed_precision_quantizer import MixedPrecisionDynamicQuantizer, MixedPrecisionStaticQuantizer
@@ -46,6 +46,8 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         self.low_rank = self._checked_low_rank(quant_config, module_name)  # `weight.low_rank`: the LoRC rank (low_rank.py), or None
         self.mx = None  # the weight's MX format name (`format: mxfp8_e4m3` / `mxfp4_e2m1`), set by _checked_format
         self.mx_act = None  # ... and the activation's
+        self.mx_n8 = None  # `mx: {outlier_channels: n8}`: the first n8 channels of the order `mx_perm` are kept in MXFP8
+        self.register_buffer("mx_perm", None, persistent=False)  # int32 [K], chosen from calibration statistics (select_outlier_perm)
         self.fp8 = self._checked_format(quant_config, module_name)
         self.mx_had32 = self._checked_mx_section(quant_config, module_name)  # `mx: {block_hadamard: True}`, W4A4 MX layers only
         # (an MX layer's `weight.group_size: 32` names the format's own block: there is no integer group-wise path behind it)
@@ -168,10 +170,12 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         if sec is None:
             return False
         name = module_name or type(self).__name__
-        unknown = [k for k in sec.keys() if k != "block_hadamard"]
+        unknown = [k for k in sec.keys() if k not in ("block_hadamard", "outlier_channels")]
         if unknown:
-            raise ValueError(f"{name}: mx.{unknown[0]} is not a known key of the `mx:` section (it has one: block_hadamard)")
+            raise ValueError(f"{name}: mx.{unknown[0]} is not a known key of the `mx:` section (it has two: block_hadamard, "
+                             "outlier_channels)")
         on = sec.get("block_hadamard", False)
+        self.mx_n8 = self._checked_outlier_channels(sec, on, name)
         if not isinstance(on, bool):
             raise ValueError(f"{name}: mx.block_hadamard={on!r} must be True or False")
         if on and MXFP6_FORMAT in (self.mx, self.mx_act):
@@ -183,6 +187,29 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
             raise NotImplementedError(f"{name}: mx.block_hadamard: True is not supported with {pair}: the block rotation is built for "
                                       f"the W4A4 pair only (weight.format: {MXFP4_FORMAT} against act.format: {MXFP4_FORMAT})")
         return on
+
+    def _checked_outlier_channels(self, sec, had32, name):
+        """`mx.outlier_channels: n8` (None without the key): the n8 input channels with the largest calibration absmax are kept in
+        MXFP8 on both sides, the others in MXFP4 (wanq_gemm_mx_mixed).  Accepted only with the W4A4 pair; refused by layer name with
+        `mx.block_hadamard`, with `weight.low_rank`, and for an n8 that is not a multiple of 128 in [128, in_features - 128]."""
+        n8 = sec.get("outlier_channels", None)
+        if n8 is None:
+            return None
+        if not self._mx4_pair:
+            pair = f"weight.format {self.mx!r} against act.format {self.mx_act!r}" if self.mx else "no MX format"
+            raise NotImplementedError(f"{name}: mx.outlier_channels is not supported with {pair}: the outlier channels are built for "
+                                      f"the W4A4 pair only (weight.format: {MXFP4_FORMAT} against act.format: {MXFP4_FORMAT})")
+        if had32 is True:
+            raise NotImplementedError(f"{name}: mx.outlier_channels with mx.block_hadamard: True is not supported: the rotation mixes "
+                                      "the channels of a block, and the mixed quantiser has no rotating form")
+        if self.low_rank is not None:
+            raise NotImplementedError(f"{name}: mx.outlier_channels with weight.low_rank is not supported: wanq_gemm_mx_mixed sums no "
+                                      "low-rank branch")
+        K = self.in_features
+        if isinstance(n8, bool) or not isinstance(n8, int) or n8 < 128 or n8 % 128 or K - n8 < 128 or K % 128:
+            raise ValueError(f"{name}: mx.outlier_channels={n8!r} must be a multiple of 128 with 128 <= n8 <= in_features - 128 "
+                             f"(in_features={K}, a multiple of 128)")
+        return n8
 
     def _checked_low_rank(self, quant_config, module_name):
         """`weight.low_rank` of the config (None: no low-rank branch), or the refusal of what has none, before any weight is
@@ -252,6 +279,9 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         return sec
 
     def _refuse_adapter(self):
+        if self.mx_n8 is not None:
+            raise NotImplementedError(f"{self._lr_name()}: set_low_rank with mx.outlier_channels is not supported: wanq_gemm_mx_mixed "
+                                      "sums no low-rank branch")
         if self._mx4_pair and not (self.uses_mask or self.uses_rotation):
             return
         if self.w_quantizer is None or self.a_quantizer is not None or self.fp8 or self.mx or self.uses_mask or self.uses_rotation \
@@ -297,6 +327,8 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         `weight.low_rank: r` the LoRC factors are fitted here too, wherever the codes are (re)derived: the best rank-r approximation
         of E = w - W_hat (low_rank.fit_low_rank: float64 SVD on the weight's device where this build has one, else on the host), kept
         as the fp32 buffers lr_a [Rp, K] / lr_b [N, Rp].  weight.data stays W_hat, without the branch."""
+        if self.mx_n8 is not None:
+            return self._requantize_mixed(w)
         codes, deq = precomputed if precomputed is not None else self.w_quantizer.codes_and_dequant(w.detach().float())
         self.weight.data = deq
         self.int_weight = codes
@@ -308,6 +340,50 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
             self.register_buffer("lr_a", a, persistent=False)  # (as `_codes`: saved by quantize_and_save_weight)
             self.register_buffer("lr_b", b, persistent=False)
             self._lr16 = None
+
+    def _requantize_mixed(self, w):
+        """`mx.outlier_channels`: the codes are the mixed quantiser's on w in the order `mx_perm` (wanq_quant_rows_mx_mixed; in host
+        memory the host expression on w[:, perm]), weight.data their decode put back into the original channel order.  Before the
+        order is chosen (select_outlier_perm) there are no codes and weight.data is the FP weight."""
+        if self.mx_perm is None:
+            self.weight.data, self.int_weight = w.detach().float(), None
+            return
+        codes, s = mx_quant_rows_mixed(w.detach().float(), self.mx_perm, self.mx_n8)
+        deq = torch.empty_like(w, dtype=torch.float32)
+        deq[:, self.mx_perm.long()] = mx_decode_mixed(codes, s, self.mx_n8)
+        self.weight.data, self.int_weight = deq, codes
+        wq = self.w_quantizer
+        wq.scale_u8, wq.delta = s, _pow2_f64(s.long() - 127).float()
+        wq.zero_point = torch.zeros_like(wq.delta)
+
+    def select_outlier_perm(self, act_mask):
+        """The channel order of an `mx.outlier_channels` layer from the calibration absmax of its INPUT (the vector PTQ hands to
+        get_channel_mask): the n8 channels with the largest absmax first, ties to the lower index, then the others; both segments in
+        ascending original order.  Input statistics only, so every consumer of one activation gets the same order.  The weight is
+        quantised again in that order."""
+        if self.mx_n8 is None:
+            raise NotImplementedError(f"{self.module_name or type(self).__name__}: select_outlier_perm needs mx.outlier_channels")
+        a = act_mask.reshape(-1).float()
+        if a.numel() != self.in_features:
+            raise ValueError(f"{self.module_name or type(self).__name__}: the activation statistics have {a.numel()} channels, expected "
+                             f"{self.in_features}")
+        order = torch.sort(-a.cpu(), stable=True).indices
+        top = torch.zeros(self.in_features, dtype=torch.bool)
+        top[order[:self.mx_n8]] = True
+        idx = torch.arange(self.in_features)
+        self.mx_perm = torch.cat((idx[top], idx[~top])).to(device=self.fp_module.weight.device, dtype=torch.int32)
+        self._requantize(self.fp_module.weight.data)
+
+    def _forward_mx_mixed(self, x2, out_dtype, bias):
+        """`mx.outlier_channels` in simulation mode: both operands are decoded (the activation from the mixed quantiser's codes, in
+        permuted order; the weight is weight.data) and multiplied in fp32.  Kernel mode (HipLinearMx) runs wanq_gemm_mx_mixed."""
+        if self.mx_perm is None:
+            raise RuntimeError(f"{self.module_name or type(self).__name__}: mx.outlier_channels needs calibration activation statistics "
+                               "and none were given (PTQ: get_channel_mask(act_mask) / select_outlier_perm); the outlier channels "
+                               "are chosen from the input's absmax, there is no weight-only proxy")
+        a_q, a_s = mx_quant_rows_mixed(x2, self.mx_perm, self.mx_n8)
+        a = mx_decode_mixed(a_q, a_s, self.mx_n8)
+        return F.linear(a, self.weight.data.float()[:, self.mx_perm.long()], bias).to(out_dtype)
 
     def requantize_gptq_(self, H):
         """Choose the layer's codes by GPTQ (qdiff/base/gptq.py) on its calibration Hessian H = X^T X (fp32 [K, K], from
@@ -459,6 +535,8 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         these are kernel mode's two entries per format, fused.quant_rows_fp8 + qgemm.fp8_linear and fused.quant_rows_mx +
         qgemm.mx_linear / qgemm.mx4_linear.  In host memory, and for a shape the GEMM refuses, the same numbers through torch: F.linear of the
         dequantised activation and the dequantised weight, in fp32."""
+        if self.mx_n8 is not None:
+            return self._forward_mx_mixed(x2, out_dtype, bias)
         if self._mx4_pair and (self.low_rank is not None or self._adapter is not None):
             return self._forward_mx4_low_rank(x2, out_dtype, bias)
         a_q, a_s = self.a_quantizer.codes_and_scale(x2)
@@ -567,6 +645,8 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
     # ---- PTQ hooks shared by the variants ------------------------------------------------------------
     def get_channel_mask(self, act_mask):
         """w_absmax_in**alpha / act_absmax**(1-alpha) (viditq_quant_layer.py:30-35, sq_quant_layer.py:27-32)."""
+        if self.mx_n8 is not None:  # an outlier-channel MX layer takes the same statistics for its channel order
+            return self.select_outlier_perm(act_mask)
         wm = self.fp_module.weight.data.float().abs().amax(dim=0)
         self.channel_mask = (wm.abs() ** self.alpha) / (act_mask.to(wm.device).float().abs() ** (1 - self.alpha))
         assert not torch.isnan(self.channel_mask).any() and not torch.isinf(self.channel_mask).any(), "bad channel mask"

@@ -64,6 +64,8 @@ PROTOTYPES = {
     "wanq_gemm_mx4": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
     "wanq_quant_rows_mx4_project": [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i64, _i, _i, _i, _vp],
     "wanq_gemm_mx4_lowrank": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
+    "wanq_quant_rows_mx_mixed": [_vp, _i, _vp, _i, _vp, _vp, _i64, _i, _i, _vp],
+    "wanq_gemm_mx_mixed": [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
     "wanq_quant_rows_mx6": [_vp, _i, _vp, _vp, _i64, _i, _i, _vp],
     "wanq_gemm_mx6": [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
     "wanq_lincomb":[_i, _i, _vp, _vp, _vp, _i64, _vp],

@@ -144,6 +144,30 @@ def quant_rows_mxfp4_h32(x, gelu=False):
     return quant_rows_mx(x, "mxfp4_e2m1", gelu, had32=True)
 
 
+def quant_rows_mx_mixed(x, perm, n8, gelu=False):
+    """The row quantiser of the mixed MX format (wanq_quant_rows_mx_mixed, csrc/quant_mixed.hip): -> (codes uint8 [rows, n8 + (cols -
+    n8) / 2], scale bytes uint8 [rows, cols / 32]).  The row is gathered into the channel order `perm` (int32 [cols], a permutation,
+    on x's device) on chip; its first n8 permuted channels become e4m3 bytes, the others packed e2m1 nibbles, one E8M0 byte per block
+    of 32 permuted channels: `quant_rows_mx` of the two column gathers, concatenated, bit for bit.  cols % 128 == 0, cols <= 16384,
+    n8 % 128 == 0, 128 <= n8 <= cols - 128.  `perm` is trusted to be a permutation (an index outside the row is clamped into it)."""
+    rows, cols = _rows_cols("x", x)
+    _C.check_gpu("perm", perm)
+    _C.check_contig("perm", perm)
+    _C.check_dtype("perm", perm, torch.int32)
+    _C.check_shape("perm", perm, cols)
+    _C.check_same_device(x, perm)
+    if cols % 128 or cols > 16384:
+        raise RuntimeError(f"quant_rows_mx_mixed: cols={cols} must be a multiple of 128, at most 16384")
+    if isinstance(n8, bool) or not isinstance(n8, int) or n8 < 128 or n8 % 128 or cols - n8 < 128:
+        raise RuntimeError(f"quant_rows_mx_mixed: n8={n8!r} must be a multiple of 128 with 128 <= n8 <= cols - 128 (cols={cols})")
+    codes = torch.empty((*x.shape[:-1], n8 + (cols - n8) // 2), dtype=torch.uint8, device=x.device)
+    scale = torch.empty((*x.shape[:-1], cols // 32), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _C.call("wanq_quant_rows_mx_mixed", _C.ptr(x), _C.dt(x), _C.ptr(perm), n8, _C.ptr(codes), _C.ptr(scale), rows, cols,
+                1 if gelu else 0, _C.stream())
+    return codes, scale
+
+
 def quant_rows_mxfp4_project(x, a16, gelu=False, had32=False, ldt=None, out=None):
     """`quant_rows_mxfp4` (`had32`: `quant_rows_mxfp4_h32`) and, in the same pass over x, the down-projection of a 16-bit low-rank
     branch (wanq_quant_rows_mx4_project, csrc/quant_project.hip): -> (codes, scales, t).  codes and scales are the plain quantiser's,

@@ -559,6 +559,39 @@ def mx4_linear_refusal(M, N, K):
     return _shape_refusal(M, N, K, MX_K_STEP, bounded=True)
 
 
+# ---- OCP MX W4A4 with outlier channels: the first n8 permuted channels MXFP8, the rest MXFP4 ------------------------------------------
+def mx_mixed_linear(a_q, w_q, a_scale, w_scale, n8, bias=None, out_dtype=None, gelu=False, gate=None, residual=None, out=None):
+    """`mx4_linear` over the mixed MX row format (wanq_gemm_mx_mixed, csrc/gemm_mx_mixed.hip): a_q uint8 [M, n8 + (K - n8) / 2] and w_q
+    uint8 [N, n8 + (K - n8) / 2], the first n8 bytes of a row e4m3 codes and the rest packed e2m1 nibbles, both in ONE permuted channel
+    order; a_scale uint8 [M, K / 32], w_scale uint8 [N, K / 32], as `fused.quant_rows_mx_mixed` writes them.  One K loop: n8 / 128 tiles
+    at the fp8 rate, then (K - n8) / 128 at the fp4 rate, into the same accumulators.  The accumulation, epilogue, shape rules (K % 128
+    == 0, N % 8 == 0) and determinism are `mx_linear`'s, and n8 % 128 == 0, 128 <= n8 <= K - 128.  Not counted by the int8 timer."""
+    for name, t in (("a_q", a_q), ("w_q", w_q), ("a_scale", a_scale), ("w_scale", w_scale)):
+        if t is None:
+            raise RuntimeError(f"mx_mixed_linear: {name} must be given")
+        _check_mat(name, t, torch.uint8)
+    M, N, K = a_q.shape[0], w_q.shape[0], a_scale.shape[1] * 32
+    why = mx_mixed_linear_refusal(M, N, K, n8)
+    if why is not None:
+        raise RuntimeError(f"mx_mixed_linear: {why}")
+    _C.check_shape("a_q", a_q, M, n8 + (K - n8) // 2)
+    _C.check_shape("w_q", w_q, N, n8 + (K - n8) // 2)
+    _C.check_shape("w_scale", w_scale, N, K // 32)
+    return _launch16("wanq_gemm_mx_mixed", (_C.ptr(a_q), _C.ptr(w_q), _C.ptr(a_scale), _C.ptr(w_scale), int(n8)),
+                     (a_q, w_q, a_scale, w_scale), bias, out_dtype or torch.bfloat16, gelu, gate, residual, out, M, N, K)
+
+
+def mx_mixed_linear_refusal(M, N, K, n8):
+    """Why wanq_gemm_mx_mixed would refuse an [M, K] x [N, K] product with n8 outlier channels (None = accepted): the rules of
+    `mx4_linear_refusal`, then n8; see `fp_linear_refusal`."""
+    why = mx4_linear_refusal(M, N, K)
+    if why is not None:
+        return why
+    if isinstance(n8, bool) or not isinstance(n8, int) or n8 < MX_K_STEP or n8 % MX_K_STEP or K - n8 < MX_K_STEP:
+        return f"n8={n8!r} must be a multiple of {MX_K_STEP} with {MX_K_STEP} <= n8 <= K - {MX_K_STEP} (K={K})"
+    return None
+
+
 def mx4_lowrank_linear(a_q, w_q, a_scale, w_scale, t, b, bias=None, out_dtype=None, gelu=False, gate=None, residual=None, out=None):
     """`mx4_linear` with a 16-bit low-rank branch summed into the same accumulators (wanq_gemm_mx4_lowrank, csrc/gemm_mx.hip):
     y = epilogue(y0 + t[M,R] @ b[N,R]^T), y0 what `mx4_linear` has before its bias.  `t` (from `fused.quant_rows_mxfp4_project`) and `b`

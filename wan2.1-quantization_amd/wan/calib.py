@@ -158,7 +158,7 @@ def init_rotation_and_channel_mask_(module, full_name, calib_data, generator=Non
     """ptq_wanx.py:334-344: act_mask = max over calls, floor 1e-3, then mask -> rotation -> re-quantised weight."""
     act_mask = calib_data[full_name].max(dim=0)[0].to(module.fp_module.weight.device)
     act_mask = torch.where(act_mask < 1e-3, torch.full_like(act_mask, 1e-3), act_mask)
-    if getattr(module, "uses_mask", False):
+    if getattr(module, "uses_mask", False) or getattr(module, "mx_n8", None) is not None:  # (mx.outlier_channels: the channel order)
         module.get_channel_mask(act_mask)
     if getattr(module, "uses_rotation", False):
         module.get_rotation_matrix(generator)

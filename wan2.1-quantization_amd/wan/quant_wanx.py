@@ -108,6 +108,9 @@ class QuantWanModel(WanModel, QuantModel):
                     # mxfp4_e2m1: uint8 [N, K] e4m3 bytes / uint8 [N, K/2] packed e2m1 nibbles, scale_weight uint8 [N, K/32] E8M0 bytes;
                     # mxfp6_e2m3fn: uint8 [N, 3K/4] packed e2m3 codes, and `mx_fmt` with either weight of an e2m3-activation layer
                     grouped = mod.group_size is not None
+                    if mod.mx_n8 is not None and mod.mx_perm is None:
+                        raise RuntimeError(f"{name}: mx.outlier_channels needs calibration activation statistics and none were given: "
+                                           "the layer has no channel order and no codes to save (PTQ: get_channel_mask(act_mask))")
                     sd[name + ".weight"] = mod._codes.clone()
                     sd[name + ".scale_weight"] = (wq.scale_u8.clone() if mod.mx else
                                                   wq.delta.float().t().contiguous() if grouped else wq.delta.reshape(-1).float().clone())
@@ -120,6 +123,9 @@ class QuantWanModel(WanModel, QuantModel):
                         sd[name + ".mx_fmt"] = torch.tensor([_C.MX6_FMT[mod.mx], _C.MX6_FMT[mod.mx_act]], dtype=torch.uint8)
                     if mod.mx_had32:  # codes made behind the block Hadamard rotation (mx.block_hadamard): recorded with the layer
                         sd[name + ".mx_had32"] = torch.ones(1, dtype=torch.uint8)
+                    if mod.mx_n8 is not None:  # mx.outlier_channels: the channel order and the count, recorded with the mixed codes
+                        sd[name + ".mx_perm"] = mod.mx_perm.detach().to(torch.int32).cpu().clone()
+                        sd[name + ".mx_n8"] = torch.tensor([mod.mx_n8], dtype=torch.int32)
                     if mod.low_rank is not None:  # the LoRC factors, fp32 [Rp, K] / [N, Rp] (an adapter is not part of the weights)
                         sd[name + ".lr_a"] = mod.lr_a.detach().float().clone()
                         sd[name + ".lr_b"] = mod.lr_b.detach().float().clone()
@@ -225,12 +231,20 @@ class QuantWanModel(WanModel, QuantModel):
                         said = lambda v: "no mx_fmt (not an MXFP6 layer)" if v is None else f"mx_fmt {v.reshape(-1).tolist()}"  # noqa: E731
                         raise ValueError(f"{load_path}: {base} was saved with {said(rec)} and the model's layer was built with "
                                          f"{said(own)} ((weight, act) codes of wanq_gemm_mx6: 2 = mxfp6_e2m3fn, 1 = mxfp4_e2m1)")
+                    # an outlier-channel layer's codes are those of one (n8, order): the file says its n8, the order is loaded
+                    n8_file, n8_layer = sd.get(f"{base}.mx_n8", None), getattr(lin, "n8", None)
+                    n8_file = None if n8_file is None else int(n8_file.reshape(-1)[0])
+                    if n8_file != n8_layer:
+                        raise ValueError(f"{load_path}: {base} was saved with mx.outlier_channels {n8_file} and the model's layer was "
+                                         f"built with {n8_layer}")
                     for buf, k, required in (("weight", "weight", True), ("scale_weight", "scale_weight", True),
                                              ("mx_fmt", "mx_fmt", own is not None),
                                              ("zp_weight", "zp_weight", lin.zp_weight is not None),
                                              ("bias", "bias", lin.bias is not None),
                                              ("act_premul", "act_premul", lin.act_premul is not None),
                                              ("mx_had32", "mx_had32", had_layer),
+                                             ("mx_perm", "mx_perm", getattr(lin, "n8", None) is not None),
+                                             ("mx_n8", "mx_n8", getattr(lin, "n8", None) is not None),
                                              ("lr_a", "lr_a", getattr(lin, "lr_a", None) is not None),
                                              ("lr_b", "lr_b", getattr(lin, "lr_b", None) is not None)):
                         dst = getattr(lin, buf, None)
@@ -255,6 +269,7 @@ class QuantWanModel(WanModel, QuantModel):
                         taken, load_path, taken_wo)
         for i, hb in enumerate(self.hip_blocks):
             hb.block_index = i
+            hb.check_shared_orders()
         self.__dict__.pop("_mod_all", None)
         return self
 

@@ -401,25 +401,39 @@ class HipLinearMx(LowRankBranch, _HipLinearCodes):
     `act_dtype` (qdiff/base/low_rank.py), `set_low_rank` attaches a user adapter behind them, the input comes from the source's
     `project` -- the quantiser and the down-projection t = x A16^T in one pass (fused.quant_rows_mxfp4_project), one launch for all
     consumers of the source -- and the product is qgemm.mx4_lowrank_linear: the branch is summed in the GEMM's own accumulators.
-    Under --dit_fsdp the factors are replicated (`sharded` names the codes and the scale bytes only)."""
+    Under --dit_fsdp the factors are replicated (`sharded` names the codes and the scale bytes only).
+    With `n8` (W4A4 only, the config's `mx.outlier_channels`) the layer holds the int32 buffer `mx_perm` [K], its channel order, and
+    `mx_n8`; `weight` is uint8 [N, n8 + (K - n8) / 2] in the mixed MX row format (include/wanq_hip.h), the input is made by
+    fused.quant_rows_mx_mixed in the same order (activation form "mxmix<n8>", one launch for every consumer of the source; consumers
+    under one form must hold the same order) and the product is qgemm.mx_mixed_linear (csrc/gemm_mx_mixed.hip).  Both buffers travel
+    with the codes in the integer checkpoint and are replicated under --dit_fsdp."""
     act_form = act_key = "mxfp8"
     sharded = ("weight", "scale_weight")   # the scale bytes are a thirty-second or a sixteenth of the weight's
 
     def __init__(self, in_features, out_features, bias=True, w_fmt="mxfp8_e4m3", name="linear", a_fmt="mxfp8_e4m3", had32=False,
-                 low_rank=None, act_dtype=torch.bfloat16):
+                 low_rank=None, act_dtype=torch.bfloat16, n8=None):
         self.name = name
         a4, a6, w6 = a_fmt == "mxfp4_e2m1", a_fmt == "mxfp6_e2m3fn", w_fmt == "mxfp6_e2m3fn"
         if a_fmt not in ("mxfp8_e4m3", "mxfp4_e2m1", "mxfp6_e2m3fn") or (a4 and w_fmt != "mxfp4_e2m1") or (had32 and not a4) or \
                 (a6 and w_fmt not in ("mxfp6_e2m3fn", "mxfp4_e2m1")) or (w6 and not a6):
             raise NotImplementedError(f"{name}: no MX GEMM takes weight {w_fmt} against act {a_fmt}" + (" behind the block rotation" if had32 else ""))
+        if n8 is not None and (not a4 or had32 or low_rank):
+            raise NotImplementedError(f"{name}: mx.outlier_channels goes with the plain W4A4 pair only (no block rotation, no low-rank "
+                                      f"branch; weight {w_fmt} against act {a_fmt})")
         why = qgemm.mx6_linear_refusal(1, out_features, in_features, w_fmt) if a6 else \
+            qgemm.mx_mixed_linear_refusal(1, out_features, in_features, n8) if n8 is not None else \
             qgemm.mx4_linear_refusal(1, out_features, in_features) if a4 else qgemm.mx_linear_refusal(1, out_features, in_features, w_fmt)
         super().__init__(in_features, out_features, bias, w_fmt, why,
+                         n8 + (in_features - n8) // 2 if n8 is not None else
                          in_features // 2 if w_fmt == "mxfp4_e2m1" else in_features // 4 * 3 if w6 else in_features,
                          (out_features, in_features // 32), torch.uint8, name)
-        self.mx, self.a_fmt, self.had32 = w_fmt, a_fmt, bool(had32)
+        self.mx, self.a_fmt, self.had32, self.n8 = w_fmt, a_fmt, bool(had32), n8
         if a4:
             self.act_form = self.act_key = "mxfp4_h32" if had32 else "mxfp4"
+        if n8 is not None:
+            self.act_form = self.act_key = f"mxmix{n8}"
+            self.register_buffer("mx_perm", torch.arange(in_features, dtype=torch.int32))
+            self.register_buffer("mx_n8", torch.tensor([n8], dtype=torch.int32))
         if a6:
             self.act_form = self.act_key = "mxfp6"
             self.register_buffer("mx_fmt", torch.tensor([_C.MX6_FMT[w_fmt], _C.MX6_FMT[a_fmt]], dtype=torch.uint8))
@@ -447,8 +461,13 @@ class HipLinearMx(LowRankBranch, _HipLinearCodes):
     def from_quantized(cls, ql, name="linear", act_dtype=torch.bfloat16):
         """From a plain qdiff QuantizedLinear built with an MX format: the same codes and scale bytes, and the same low-rank factors
         (the LoRC buffers cast once to `act_dtype`, the adapter as attached)."""
+        if ql.mx_n8 is not None and ql.mx_perm is None:
+            raise RuntimeError(f"{name}: mx.outlier_channels needs calibration activation statistics and none were given: the layer "
+                               "has no channel order yet (PTQ: get_channel_mask(act_mask) / select_outlier_perm)")
         m = cls(ql.in_features, ql.out_features, ql.bias is not None, ql.mx, name, ql.mx_act, ql.mx_had32, ql.low_rank,
-                act_dtype if act_dtype in (torch.bfloat16, torch.float16) else torch.bfloat16).to(ql.fp_module.weight.device)
+                act_dtype if act_dtype in (torch.bfloat16, torch.float16) else torch.bfloat16, ql.mx_n8).to(ql.fp_module.weight.device)
+        if ql.mx_n8 is not None:
+            m.mx_perm.copy_(ql.mx_perm)
         if ql.low_rank is not None:
             m.lr_a.copy_(ql.lr_a)
             m.lr_b.copy_(ql.lr_b)
@@ -456,6 +475,8 @@ class HipLinearMx(LowRankBranch, _HipLinearCodes):
         return m._take(ql, ql.w_quantizer.scale_u8, name)
 
     def operands(self, src):
+        if self.n8 is not None:
+            return src.rows_mixed(self)
         if self.has_branch:
             src.project([self])  # (codes and scales come from the pass that makes t)
         return src.rows(self.act_form)
@@ -470,6 +491,9 @@ class HipLinearMx(LowRankBranch, _HipLinearCodes):
             _, b16 = self.low_rank_operands(self.act_dtype, a_q.device)
             return qgemm.mx4_lowrank_linear(a_q, self.weight, a_scale, self.scale_weight, t, b16, self.bias, out_dtype, gelu=gelu,
                                             gate=gate, residual=residual, out=out)
+        if self.n8 is not None:
+            return qgemm.mx_mixed_linear(a_q, self.weight, a_scale, self.scale_weight, self.n8, self.bias, out_dtype, gelu=gelu,
+                                         gate=gate, residual=residual, out=out)
         if self.a_fmt == "mxfp6_e2m3fn":
             return qgemm.mx6_linear(a_q, self.weight, a_scale, self.scale_weight, self.mx, self.bias, out_dtype, gelu=gelu, gate=gate,
                                     residual=residual, out=out)
@@ -516,6 +540,18 @@ class _Src:
         if form not in self.cache:
             x, gelu = self._plain_row()
             self.cache[form] = getattr(fused, _ROW_QUANTISERS[form])(x, gelu=gelu)
+        return self.cache[form]
+
+    def rows_mixed(self, lin):
+        """(codes, scales) of this activation in the mixed MX row format of `lin` (HipLinearMx with `n8`: form "mxmix<n8>", channel order
+        lin.mx_perm), one quantiser launch for every consumer of the form.  That the consumers of one activation hold one order is
+        checked where the blocks are built and loaded (WanAttentionBlockWithHipKernel.check_shared_orders), not per forward: a later
+        consumer is served the FIRST consumer's order without a check here, so a block that lets further layers share a source must
+        add that group to check_shared_orders."""
+        form = lin.act_form
+        if form not in self.cache:
+            x, gelu = self._plain_row()
+            self.cache[form] = fused.quant_rows_mx_mixed(x, lin.mx_perm, lin.n8, gelu=gelu)
         return self.cache[form]
 
     def project(self, lins):
@@ -742,6 +778,17 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         self.register_buffer("norm3_weight", torch.ones(dim))
         self.register_buffer("norm3_bias", torch.zeros(dim))
         self.register_buffer("ones_gate", torch.ones(dim))
+
+    def check_shared_orders(self):
+        """The consumers of one activation share its quantised copy, so `mx.outlier_channels` layers among them must hold one channel
+        order (it is a function of that activation's statistics alone): q / k / v of the self-attention, k / v of the cross-attention.
+        Raises by layer name otherwise.  Called once the blocks are built and again after a checkpoint was loaded into them."""
+        for group in ((self.self_attn.q, self.self_attn.k, self.self_attn.v), (self.cross_attn.k, self.cross_attn.v)):
+            mixed = [l for l in group if getattr(l, "n8", None) is not None]
+            for l in mixed[1:]:
+                if l.n8 == mixed[0].n8 and not torch.equal(l.mx_perm, mixed[0].mx_perm):
+                    raise ValueError(f"{l.name} and {mixed[0].name} consume one activation and hold different channel orders (mx_perm): "
+                                     "the order is a function of the input's statistics and must be shared")
 
     @classmethod
     def from_float(cls, blk, n_bits=8, sym=False, act_dtype=torch.bfloat16, attn_qk8=False, cross_attn_qk8=False,
