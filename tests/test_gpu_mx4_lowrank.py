@@ -189,7 +189,7 @@ def test_kernel_mode_blocks_share_one_producer_launch_per_source_and_match_simul
     model.hardware_forward_refactor()
     calls, real = [], fused.quant_rows_mxfp4_project
     monkeypatch.setattr(fused, "quant_rows_mxfp4_project", lambda x, a16, **kw: calls.append(a16.shape[0]) or real(x, a16, **kw))
-    monkeypatch.setattr(fused, "quant_rows_mxfp4", lambda *a, **k: pytest.fail("a layer with a branch went to the plain quantiser"))
+    monkeypatch.setattr(fused, "quant_rows_mx", lambda *a, **k: pytest.fail("a layer with a branch went to the plain quantiser"))
     hw = model([lat0], t, [ctx], seq_len)[0].float().clone()
     # per block: q + k + v (stacked, 192 ranks), self_attn.o, cross_attn.q, the context's k + v (128), cross_attn.o, ffn.0, ffn.2
     assert sorted(calls) == sorted([192, 64, 64, 128, 64, 64, 64] * 2), calls

@@ -2,8 +2,9 @@
 WanAttentionBlockWithHipKernel._linear, which producer makes its operands from an _LnSrc and from an _FpSrc, that a second consumer of
 a source reuses them, the out dtype, the GELU flag, that the fp32 stream goes in as `out`; the FFN's late-GELU rule over every ordered
 pair of kinds; what the integer checkpoint holds and what `--dit_fsdp` shards, per kind; QuantizedLinear's kind for every shipped
-config.  Nothing is launched: the qgemm entries and the fused producers are replaced by recorders that return empty tensors of the
-right shape and dtype.  The numbers themselves: tests/test_gpu_block.py and the per-format GPU suites."""
+config; and the same for every form of HipLinearMx (MX_FORMS), each built from a QuantizedLinear of its shipped config.  Nothing is
+launched: the qgemm entries and the fused producers are replaced by recorders that return empty tensors of the right shape and
+dtype.  The numbers themselves: tests/test_gpu_block.py and the per-format GPU suites."""
 import glob
 import inspect
 import itertools
@@ -16,7 +17,9 @@ from test_fp8_abi import PKG, lib  # noqa: F401 (`lib`: builds the library on a 
 
 K, N, ROWS = 128, 256, 200   # in_features, out_features; a row count that is no multiple of a tile
 BF16, F32 = torch.bfloat16, torch.float32
-ENTRIES = ("w8a8_linear", "w8a8_grouped_linear", "fp_linear", "wq16_linear", "wq16_grouped_linear", "fp8_linear", "mx_linear")
+ENTRIES = ("w8a8_linear", "w8a8_grouped_linear", "fp_linear", "wq16_linear", "wq16_grouped_linear", "fp8_linear", "mx_linear", "mx4_linear",
+           "mx6_linear", "mx_mixed_linear", "mx4_lowrank_linear")
+MX_BLOCK_BYTES = {"mxfp8_e4m3": 32, "mxfp6_e2m3fn": 24, "mxfp4_e2m1": 16}   # bytes of 32 codes, by format
 
 
 # ---- the layer properties this file reads ------------------------------------------------------------------------------------------
@@ -86,10 +89,21 @@ def rec(lib, monkeypatch):  # noqa: F811
         prods.append(("quant_rows_fp8", x.dtype, gelu))
         return torch.empty(x.shape, dtype=torch.uint8), torch.empty(x.shape[0], dtype=F32)
 
-    def rows_mx(x, fmt="mxfp8_e4m3", gelu=False):
-        prods.append(("quant_rows_mx", x.dtype, gelu))
-        assert fmt == "mxfp8_e4m3"
-        return torch.empty(x.shape, dtype=torch.uint8), torch.empty(x.shape[0], x.shape[1] // 32, dtype=torch.uint8)
+    def rows_mx(x, fmt="mxfp8_e4m3", gelu=False, had32=False):
+        """(the e4m3 form without a rotation is recorded as it always was; every other form adds its fmt and had32)"""
+        prods.append(("quant_rows_mx", x.dtype, gelu) + (() if (fmt, had32) == ("mxfp8_e4m3", False) else (fmt, had32)))
+        return (torch.empty(x.shape[0], x.shape[1] // 32 * MX_BLOCK_BYTES[fmt], dtype=torch.uint8),
+                torch.empty(x.shape[0], x.shape[1] // 32, dtype=torch.uint8))
+
+    def rows_mx_mixed(x, perm, n8, gelu=False):
+        prods.append(("quant_rows_mx_mixed", x.dtype, gelu, perm, n8))
+        return (torch.empty(x.shape[0], n8 + (x.shape[1] - n8) // 2, dtype=torch.uint8),
+                torch.empty(x.shape[0], x.shape[1] // 32, dtype=torch.uint8))
+
+    def rows_mxfp4_project(x, a16, gelu=False, had32=False, ldt=None, out=None):
+        prods.append(("quant_rows_mxfp4_project", x.dtype, gelu, had32, a16))
+        return (torch.empty(x.shape[0], x.shape[1] // 2, dtype=torch.uint8), torch.empty(x.shape[0], x.shape[1] // 32, dtype=torch.uint8),
+                torch.empty(x.shape[0], a16.shape[0], dtype=a16.dtype))
 
     def to_int8(name):
         def call(t, *a):
@@ -99,6 +113,8 @@ def rec(lib, monkeypatch):  # noqa: F811
 
     monkeypatch.setattr(fused, "quant_rows_fp8", rows_fp8)
     monkeypatch.setattr(fused, "quant_rows_mx", rows_mx)
+    monkeypatch.setattr(fused, "quant_rows_mx_mixed", rows_mx_mixed)
+    monkeypatch.setattr(fused, "quant_rows_mxfp4_project", rows_mxfp4_project)
     for name in ("quant_sum", "gelu_quant_sum", "rotate_quant"):
         monkeypatch.setattr(fused, name, to_int8(name))
     monkeypatch.setattr(fused, "gate_residual_into_", lambda residual, y, gate: prods.append(("gate_residual_into_", residual)))
@@ -279,6 +295,175 @@ def test_fsdp_slots_follow_the_layers_sharded_names_in_layer_order(blk, kind):
     blk.ffn0, blk.ffn2 = lins[8:]
     slots = _weight_slots(blk)
     assert [(id(o), a) for o, a in slots] == [(id(l), a) for l in lins for a in EXPECT[kind][4]]
+
+
+# ---- every form of HipLinearMx, built from a QuantizedLinear of its shipped config -------------------------------------------------------
+FP8, FP6, FP4 = "mxfp8_e4m3", "mxfp6_e2m3fn", "mxfp4_e2m1"
+# form -> (config, in_features, entry, how its input is made: the row quantiser's (fmt, had32), "project" or "mixed"; act form;
+#          weight columns; the buffers it registers beyond weight / scale_weight / bias, in order)
+MX_FORMS = {
+    "w8a8": ("w8a8_mxfp8_all_linears", K, "mx_linear", (FP8, False), "mxfp8", K, []),
+    "w4a8": ("w4a8_mxfp4_all_linears", K, "mx_linear", (FP8, False), "mxfp8", K // 2, []),
+    "w4a4": ("mx/w4a4_mxfp4_all_linears", K, "mx4_linear", (FP4, False), "mxfp4", K // 2, []),
+    "w4a4_h32": ("mx/w4a4_mxfp4_had32_all_linears", K, "mx4_linear", (FP4, True), "mxfp4_h32", K // 2, ["mx_had32"]),
+    "w6a6": ("mx/w6a6_mxfp6_all_linears", K, "mx6_linear", (FP6, False), "mxfp6", K // 4 * 3, ["mx_fmt"]),
+    "w4a6": ("mx/w4a6_mxfp4_mxfp6_all_linears", K, "mx6_linear", (FP6, False), "mxfp6", K // 2, ["mx_fmt"]),
+    "w4a4_lr": ("lowrank/w4a4_mxfp4_lr32_all_linears", K, "mx4_lowrank_linear", "project", "mxfp4", K // 2, ["lr_a", "lr_b"]),
+    "w4a4_h32_lr": ("lowrank/w4a4_mxfp4_had32_lr32_all_linears", K, "mx4_lowrank_linear", "project", "mxfp4_h32", K // 2,
+                    ["mx_had32", "lr_a", "lr_b"]),
+    "w4a4_o128": ("mx/w4a4_mxfp4_o128_all_linears", 256, "mx_mixed_linear", "mixed", "mxmix128", 128 + 64, ["mx_perm", "mx_n8"]),
+}
+MX_W_FMT = {"w8a8": FP8, "w6a6": FP6}   # (every other form: e2m1 weights)
+_QL = {}
+
+
+def make_mx(form, name="blocks.0.self_attn.q"):
+    """a HipLinearMx of `form`, converted from a QuantizedLinear of the shipped config (made once per form and name, in host memory)"""
+    from qdiff import config as qcfg
+    from qdiff.base.quant_layer import QuantizedLinear
+    from wan.quant_wanx_hip import _to_hip_linear
+
+    cfg_name, k = MX_FORMS[form][:2]
+    if (form, name) not in _QL:
+        g = torch.Generator().manual_seed(5)
+        fp = torch.nn.Linear(k, N)
+        fp.weight.data.copy_(torch.randn(N, k, generator=g) * k ** -0.5)
+        ql = QuantizedLinear(k, N, True, "cpu", qcfg.load(os.path.join(PKG, "quant_configs", cfg_name + ".yaml")), fp, module_name=name)
+        if ql.mx_n8 is not None:   # the order of an outlier layer: from a seeded calibration absmax, the same for every layer made here
+            ql.select_outlier_perm(torch.rand(k, generator=torch.Generator().manual_seed(6)))
+        _QL[form, name] = ql
+    return _to_hip_linear(_QL[form, name], None, False, BF16, "torch", name)
+
+
+def mx_sources(blk, k, gelu=False):
+    from wan.quant_wanx_hip import _FpSrc, _LnSrc
+
+    return {"ln": _LnSrc(blk, torch.zeros(ROWS, k), None, torch.zeros(1, k), torch.zeros(1, k)),
+            "fp": _FpSrc(torch.zeros(ROWS, k, dtype=BF16), gelu=gelu)}
+
+
+def _mx_producers(lin, how, row_dtype, gelu=False):
+    """what one consumer of a fresh source asks of the producers, behind the _LnSrc's fp32 row when there is one"""
+    if how == "project":
+        return [("quant_rows_mxfp4_project", row_dtype, gelu, lin.had32, lin.lr_a)]
+    if how == "mixed":
+        return [("quant_rows_mx_mixed", row_dtype, gelu, lin.mx_perm, 128)]
+    return [("quant_rows_mx", row_dtype, gelu) + (() if how == (FP8, False) else how)]
+
+
+def _same(got, want):
+    """producer records compared with tensors by identity (a perm or a factor is the layer's own buffer, not a copy)"""
+    return len(got) == len(want) and all(len(g) == len(w) and all(a is b if isinstance(b, torch.Tensor) else a == b for a, b in zip(g, w))
+                                         for g, w in zip(got, want))
+
+
+@pytest.mark.parametrize("src_name", ["ln", "fp"])
+@pytest.mark.parametrize("form", sorted(MX_FORMS))
+def test_every_mx_form_reaches_its_entry_with_operands_made_once(rec, blk, form, src_name):
+    gemms, prods = rec
+    _, k, entry, how, act_form, w_cols, _ = MX_FORMS[form]
+    lin = make_mx(form)
+    assert lin.act_form == lin.act_key == act_form and lin.plain_rows
+    src = mx_sources(blk, k)[src_name]
+    y = blk._linear(lin, src)
+    ln = [("layernorm_nobias_t2i_fuse", F32)] if src_name == "ln" else []
+    assert _same(prods, ln + _mx_producers(lin, how, F32 if src_name == "ln" else BF16)), prods
+    assert [g[0] for g in gemms] == [entry] and y.dtype == BF16 and tuple(y.shape) == (ROWS, N)
+    args = gemms[0][1]
+    assert args["out_dtype"] == BF16 and args["gelu"] is False and args["gate"] is None and args["residual"] is None and args["out"] is None
+    assert args["w_q"] is lin.weight and args["w_scale"] is lin.scale_weight and args["bias"] is lin.bias
+    a_cols = {"mxfp8": k, "mxfp6": k // 4 * 3, "mxfp4": k // 2, "mxfp4_h32": k // 2, "mxmix128": 128 + (k - 128) // 2}[act_form]
+    assert tuple(args["a_q"].shape) == (ROWS, a_cols) and tuple(args["a_scale"].shape) == (ROWS, k // 32)
+    assert tuple(lin.weight.shape) == (N, w_cols)
+    if entry in ("mx_linear", "mx6_linear"):
+        assert args["w_fmt"] == lin.mx == MX_W_FMT.get(form, FP4)
+    if entry == "mx_mixed_linear":
+        assert args["n8"] == 128
+    if entry == "mx4_lowrank_linear":
+        assert args["b"] is lin.lr_b and tuple(args["t"].shape) == (ROWS, 64) and args["t"].dtype == BF16
+    # a second consumer of the same source and form is served the copy; with a branch it asks for its own t, and gets the same codes
+    n = len(prods)
+    other = make_mx(form, "blocks.0.self_attn.k")
+    blk._linear(other, src)
+    assert gemms[1][1]["a_q"] is args["a_q"] and gemms[1][1]["a_scale"] is args["a_scale"]
+    assert _same(prods[n:], _mx_producers(other, how, F32 if src_name == "ln" else BF16) if how == "project" else [])
+    blk._linear(lin, src)        # ... and the first consumer again: nothing is made twice
+    assert len(prods) == n + (how == "project")
+    if how == "project":
+        assert gemms[2][1]["t"] is args["t"]
+
+
+@pytest.mark.parametrize("form", sorted(MX_FORMS))
+def test_every_mx_form_with_gelu_and_with_gate_and_residual(rec, blk, form):
+    gemms, prods = rec
+    k, how = MX_FORMS[form][1], MX_FORMS[form][3]
+    lin = make_mx(form)
+    blk._linear(lin, mx_sources(blk, k)["fp"], gelu=True)
+    assert gemms[0][1]["gelu"] is True and gemms[0][1]["out_dtype"] == BF16
+    gate, stream = torch.ones(N), torch.zeros(ROWS, N)
+    assert blk._linear(lin, mx_sources(blk, k)["ln"], gate=gate, residual=stream) is stream
+    args = gemms[1][1]
+    assert args["out_dtype"] == F32 and args["gelu"] is False and args["gate"] is gate and args["residual"] is stream and args["out"] is stream
+    del prods[:]                 # a pre-activation source hands the GELU to the producer of the form
+    blk._linear(lin, mx_sources(blk, k, gelu=True)["fp"])
+    assert _same(prods, _mx_producers(lin, how, BF16, gelu=True)) and gemms[2][1]["gelu"] is False
+    assert not any(p[0] == "gate_residual_into_" for p in prods)
+
+
+@pytest.mark.parametrize("form", ["w4a4_lr", "w4a4_h32_lr"])
+def test_q_k_v_with_branches_get_one_projection_of_the_stacked_factor(rec, blk, form):
+    gemms, prods = rec
+    lins = [make_mx(form, f"blocks.0.self_attn.{l}") for l in "qkv"]
+    src = mx_sources(blk, K)["fp"]
+    src.project(lins)
+    assert len(prods) == 1 and prods[0][:4] == ("quant_rows_mxfp4_project", BF16, False, form == "w4a4_h32_lr")
+    stacked = prods[0][4]
+    assert tuple(stacked.shape) == (192, K) and torch.equal(stacked, torch.cat([l.lr_a for l in lins], 0))
+    for i, lin in enumerate(lins):
+        blk._linear(lin, src)
+        t = gemms[i][1]["t"]
+        assert tuple(t.shape) == (ROWS, 64) and t.stride() == (192, 1) and t.storage_offset() == 64 * i
+        assert t._base is gemms[0][1]["t"]._base and gemms[i][1]["a_q"] is gemms[0][1]["a_q"] and gemms[i][1]["b"] is lin.lr_b
+    assert len(prods) == 1       # the three GEMMs asked for nothing more
+    src2 = mx_sources(blk, K)["fp"]     # the stacked factor is kept on its first consumer: the next source gets the same tensor
+    src2.project(lins)
+    assert prods[1][4] is stacked
+
+
+@pytest.mark.parametrize("form", sorted(MX_FORMS))
+def test_every_mx_form_holds_its_buffers_and_shards_its_codes(form):
+    _, k, _, _, _, w_cols, extra = MX_FORMS[form]
+    lin = make_mx(form)
+    ql = _QL[form, "blocks.0.self_attn.q"]
+    assert tuple(lin.weight.shape) == (N, w_cols) and lin.weight.dtype == torch.uint8 and torch.equal(lin.weight, ql._codes)
+    assert tuple(lin.scale_weight.shape) == (N, k // 32) and lin.scale_weight.dtype == torch.uint8
+    assert [n for n, _ in lin.named_buffers()] == ["weight", "scale_weight", "bias"] + extra
+    assert tuple(_sharded(lin)) == ("weight", "scale_weight") and bool(_checkpointed(lin))
+    assert lin.act_premul is None and lin.zp_weight is None and not lin.quantized and not lin.fp8 and not lin.weight_only
+    if "mx_fmt" in extra:
+        assert lin.mx_fmt.dtype == torch.uint8 and lin.mx_fmt.tolist() == [2 if form == "w6a6" else 1, 2]
+    if "mx_had32" in extra:
+        assert lin.mx_had32.dtype == torch.uint8 and lin.mx_had32.tolist() == [1] and lin.had32 is True
+    if "mx_n8" in extra:
+        assert lin.mx_n8.dtype == torch.int32 and lin.mx_n8.tolist() == [128] and lin.n8 == 128
+        assert lin.mx_perm.dtype == torch.int32 and torch.equal(lin.mx_perm, ql.mx_perm) and sorted(lin.mx_perm.tolist()) == list(range(k))
+    if "lr_a" in extra:
+        assert tuple(lin.lr_a.shape) == (64, k) and tuple(lin.lr_b.shape) == (N, 64) and lin.lr_a.dtype == lin.lr_b.dtype == BF16
+        assert lin.low_rank == 32 and lin.has_branch
+    else:
+        assert not lin.has_branch
+
+
+def test_late_gelu_of_every_mx_form_against_every_form_and_kind():
+    """true exactly when both layers consume one activation form: W8A8 with W4A8 (and the KINDS' "mxfp8" / "mxfp4", which are those two), W4A4
+    with its low-rank form, each rotated form with the other, W6A6 with W4A6, the outlier form with itself; never with another kind"""
+    forms = {f: make_mx(f) for f in MX_FORMS}
+    act = {f: MX_FORMS[f][4] for f in MX_FORMS}
+    for a, b in itertools.product(MX_FORMS, MX_FORMS):
+        assert bool(_late_gelu(forms[a], forms[b])) is (act[a] == act[b]), (a, b)
+    for f, kind in itertools.product(MX_FORMS, KINDS):
+        want = act[f] == "mxfp8" and kind in ("mxfp8", "mxfp4")
+        assert bool(_late_gelu(forms[f], make(kind))) is want and bool(_late_gelu(make(kind), forms[f])) is want, (f, kind)
 
 
 # ---- QuantizedLinear names its kind ---------------------------------------------------------------------------------------------------

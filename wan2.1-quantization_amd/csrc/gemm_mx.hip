@@ -147,20 +147,18 @@ extern "C" int wanq_gemm_mx(const uint8_t* a, const uint8_t* w, const uint8_t* s
                             int out_dtype, const void* bias, int bias_dtype, const float* gate, const void* residual, int epi_flags,
                             int64_t M, int N, int K, void* stream) {
   const char* what = "wanq_gemm_mx";
-  WANQ_REQUIRE(a && w && out && sa_u8 && sw_u8, WANQ_E_ARG, "%s: a, w, sa_u8, sw_u8 and out must be non-NULL", what);
-  WANQ_REQUIRE(w_fmt == WANQ_MX_E4M3 || w_fmt == WANQ_MX_E2M1, WANQ_E_ARG, "%s: w_fmt=%d must be WANQ_MX_E4M3 or WANQ_MX_E2M1", what,
-               w_fmt);
-  if (const int rc = check_gemm16_shapes(what, TKX, a, w, out, out_dtype, bias, bias_dtype, gate, residual, epi_flags, M, N, K))
-    return rc;
-  WANQ_REQUIRE(aligned(sa_u8, 4) && aligned(sw_u8, 4), WANQ_E_ARG, "%s: sa_u8 and sw_u8 must be 4-byte aligned", what);
-  if (const int rc = check_gemm16_tail(what, bias, bias_dtype, gate, M, N)) return rc;
-  if (M == 0) return WANQ_OK;
-  const Gemm16Params p = gemm16_params(a, w, sa_u8, sw_u8, out, bias, bias_dtype, gate, residual, epi_flags, M, N, K);
-  hipStream_t st = (hipStream_t)stream;
-  return with_out_dtype(out_dtype, [&](auto o) {
-    constexpr int OUT = decltype(o)::value;
-    return w_fmt == WANQ_MX_E2M1 ? launch_tiles(gemm_tile_kernel<MxPolicy<OUT, true>>, p, st, what)
-                                 : launch_tiles(gemm_tile_kernel<MxPolicy<OUT, false>>, p, st, what);
+  const auto rules = [&](MxRulesAt at) {
+    if (at == MX_BEFORE_SHAPES)
+      WANQ_REQUIRE(w_fmt == WANQ_MX_E4M3 || w_fmt == WANQ_MX_E2M1, WANQ_E_ARG, "%s: w_fmt=%d must be WANQ_MX_E4M3 or WANQ_MX_E2M1", what,
+                   w_fmt);
+    return WANQ_OK;
+  };
+  return mx_gemm_entry(what, a, w, sa_u8, sw_u8, out, out_dtype, bias, bias_dtype, gate, residual, epi_flags, M, N, K, stream, rules, [&](const Gemm16Params& p, hipStream_t st) {
+    return with_out_dtype(out_dtype, [&](auto o) {
+      constexpr int OUT = decltype(o)::value;
+      return w_fmt == WANQ_MX_E2M1 ? launch_tiles(gemm_tile_kernel<MxPolicy<OUT, true>>, p, st, what)
+                                   : launch_tiles(gemm_tile_kernel<MxPolicy<OUT, false>>, p, st, what);
+    });
   });
 }
 
@@ -168,16 +166,10 @@ extern "C" int wanq_gemm_mx4(const uint8_t* a, const uint8_t* w, const uint8_t* 
                              const void* bias, int bias_dtype, const float* gate, const void* residual, int epi_flags, int64_t M, int N,
                              int K, void* stream) {
   const char* what = "wanq_gemm_mx4";
-  WANQ_REQUIRE(a && w && out && sa_u8 && sw_u8, WANQ_E_ARG, "%s: a, w, sa_u8, sw_u8 and out must be non-NULL", what);
-  if (const int rc = check_gemm16_shapes(what, TKX, a, w, out, out_dtype, bias, bias_dtype, gate, residual, epi_flags, M, N, K))
-    return rc;
-  WANQ_REQUIRE(aligned(sa_u8, 4) && aligned(sw_u8, 4), WANQ_E_ARG, "%s: sa_u8 and sw_u8 must be 4-byte aligned", what);
-  if (const int rc = check_gemm16_tail(what, bias, bias_dtype, gate, M, N)) return rc;
-  if (M == 0) return WANQ_OK;
-  const Gemm16Params p = gemm16_params(a, w, sa_u8, sw_u8, out, bias, bias_dtype, gate, residual, epi_flags, M, N, K);
-  hipStream_t st = (hipStream_t)stream;
-  return with_out_dtype(out_dtype, [&](auto o) {
-    return launch_tiles(gemm_tile_kernel<MxPolicy<decltype(o)::value, true, true>>, p, st, what);
+  return mx_gemm_entry(what, a, w, sa_u8, sw_u8, out, out_dtype, bias, bias_dtype, gate, residual, epi_flags, M, N, K, stream, no_rules, [&](const Gemm16Params& p, hipStream_t st) {
+    return with_out_dtype(out_dtype, [&](auto o) {
+      return launch_tiles(gemm_tile_kernel<MxPolicy<decltype(o)::value, true, true>>, p, st, what);
+    });
   });
 }
 
@@ -186,23 +178,25 @@ extern "C" int wanq_gemm_mx4_lowrank(const uint8_t* a, const uint8_t* w, const u
                                      int bias_dtype, const float* gate, const void* residual, int epi_flags, int64_t M, int N, int K,
                                      void* stream) {
   const char* what = "wanq_gemm_mx4_lowrank";
-  WANQ_REQUIRE(a && w && out && sa_u8 && sw_u8, WANQ_E_ARG, "%s: a, w, sa_u8, sw_u8 and out must be non-NULL", what);
-  WANQ_REQUIRE(t && b, WANQ_E_ARG, "%s: t and b must be non-NULL", what);
-  WANQ_REQUIRE(dtype16 == WANQ_BF16 || dtype16 == WANQ_F16, WANQ_E_ARG, "%s: dtype16=%d must be BF16 or F16", what, dtype16);
-  if (const int rc = check_gemm16_shapes(what, TKX, a, w, out, out_dtype, bias, bias_dtype, gate, residual, epi_flags, M, N, K))
-    return rc;
-  WANQ_REQUIRE(R >= 64 && R <= 256 && R % 64 == 0, WANQ_E_SHAPE, "%s: R=%d must be a multiple of 64 in [64, 256]", what, R);
-  WANQ_REQUIRE(ldt >= R && ldt % 8 == 0, WANQ_E_SHAPE, "%s: ldt=%d must be a multiple of 8 and at least R=%d", what, ldt, R);
-  WANQ_REQUIRE(aligned(sa_u8, 4) && aligned(sw_u8, 4), WANQ_E_ARG, "%s: sa_u8 and sw_u8 must be 4-byte aligned", what);
-  WANQ_REQUIRE(aligned(t, 16) && aligned(b, 16), WANQ_E_ARG, "%s: t and b must be 16-byte aligned", what);
-  if (const int rc = check_gemm16_tail(what, bias, bias_dtype, gate, M, N)) return rc;
-  if (M == 0) return WANQ_OK;
-  const GemmLrParams p{gemm16_params(a, w, sa_u8, sw_u8, out, bias, bias_dtype, gate, residual, epi_flags, M, N, K), t, b, ldt, R};
-  hipStream_t st = (hipStream_t)stream;
-  return with_out_dtype(out_dtype, [&](auto o) {
-    constexpr int OUT = decltype(o)::value;
-    return dtype16 == WANQ_F16 ? launch_tiles(gemm_tile_kernel<MxLrPolicy<OUT, true>>, p, st, what)
-                               : launch_tiles(gemm_tile_kernel<MxLrPolicy<OUT, false>>, p, st, what);
+  const auto rules = [&](MxRulesAt at) {
+    if (at == MX_BEFORE_SHAPES) {
+      WANQ_REQUIRE(t && b, WANQ_E_ARG, "%s: t and b must be non-NULL", what);
+      WANQ_REQUIRE(dtype16 == WANQ_BF16 || dtype16 == WANQ_F16, WANQ_E_ARG, "%s: dtype16=%d must be BF16 or F16", what, dtype16);
+    } else if (at == MX_AFTER_SHAPES) {
+      WANQ_REQUIRE(R >= 64 && R <= 256 && R % 64 == 0, WANQ_E_SHAPE, "%s: R=%d must be a multiple of 64 in [64, 256]", what, R);
+      WANQ_REQUIRE(ldt >= R && ldt % 8 == 0, WANQ_E_SHAPE, "%s: ldt=%d must be a multiple of 8 and at least R=%d", what, ldt, R);
+    } else {
+      WANQ_REQUIRE(aligned(t, 16) && aligned(b, 16), WANQ_E_ARG, "%s: t and b must be 16-byte aligned", what);
+    }
+    return WANQ_OK;
+  };
+  return mx_gemm_entry(what, a, w, sa_u8, sw_u8, out, out_dtype, bias, bias_dtype, gate, residual, epi_flags, M, N, K, stream, rules, [&](const Gemm16Params& p16, hipStream_t st) {
+    const GemmLrParams p{p16, t, b, ldt, R};
+    return with_out_dtype(out_dtype, [&](auto o) {
+      constexpr int OUT = decltype(o)::value;
+      return dtype16 == WANQ_F16 ? launch_tiles(gemm_tile_kernel<MxLrPolicy<OUT, true>>, p, st, what)
+                                 : launch_tiles(gemm_tile_kernel<MxLrPolicy<OUT, false>>, p, st, what);
+    });
   });
 }
 
@@ -210,19 +204,17 @@ extern "C" int wanq_gemm_mx6(const uint8_t* a, const uint8_t* w, const uint8_t* 
                              int out_dtype, const void* bias, int bias_dtype, const float* gate, const void* residual, int epi_flags,
                              int64_t M, int N, int K, void* stream) {
   const char* what = "wanq_gemm_mx6";
-  WANQ_REQUIRE(a && w && out && sa_u8 && sw_u8, WANQ_E_ARG, "%s: a, w, sa_u8, sw_u8 and out must be non-NULL", what);
-  WANQ_REQUIRE(w_fmt == WANQ_MX_E2M3 || w_fmt == WANQ_MX_E2M1, WANQ_E_ARG, "%s: w_fmt=%d must be WANQ_MX_E2M3 or WANQ_MX_E2M1", what,
-               w_fmt);
-  if (const int rc = check_gemm16_shapes(what, TKX, a, w, out, out_dtype, bias, bias_dtype, gate, residual, epi_flags, M, N, K))
-    return rc;
-  WANQ_REQUIRE(aligned(sa_u8, 4) && aligned(sw_u8, 4), WANQ_E_ARG, "%s: sa_u8 and sw_u8 must be 4-byte aligned", what);
-  if (const int rc = check_gemm16_tail(what, bias, bias_dtype, gate, M, N)) return rc;
-  if (M == 0) return WANQ_OK;
-  const Gemm16Params p = gemm16_params(a, w, sa_u8, sw_u8, out, bias, bias_dtype, gate, residual, epi_flags, M, N, K);
-  hipStream_t st = (hipStream_t)stream;
-  return with_out_dtype(out_dtype, [&](auto o) {
-    constexpr int OUT = decltype(o)::value;
-    return w_fmt == WANQ_MX_E2M1 ? launch_tiles(gemm_tile_kernel<Mx6Policy<OUT, true>>, p, st, what)
-                                 : launch_tiles(gemm_tile_kernel<Mx6Policy<OUT, false>>, p, st, what);
+  const auto rules = [&](MxRulesAt at) {
+    if (at == MX_BEFORE_SHAPES)
+      WANQ_REQUIRE(w_fmt == WANQ_MX_E2M3 || w_fmt == WANQ_MX_E2M1, WANQ_E_ARG, "%s: w_fmt=%d must be WANQ_MX_E2M3 or WANQ_MX_E2M1", what,
+                   w_fmt);
+    return WANQ_OK;
+  };
+  return mx_gemm_entry(what, a, w, sa_u8, sw_u8, out, out_dtype, bias, bias_dtype, gate, residual, epi_flags, M, N, K, stream, rules, [&](const Gemm16Params& p, hipStream_t st) {
+    return with_out_dtype(out_dtype, [&](auto o) {
+      constexpr int OUT = decltype(o)::value;
+      return w_fmt == WANQ_MX_E2M1 ? launch_tiles(gemm_tile_kernel<Mx6Policy<OUT, true>>, p, st, what)
+                                   : launch_tiles(gemm_tile_kernel<Mx6Policy<OUT, false>>, p, st, what);
+    });
   });
 }

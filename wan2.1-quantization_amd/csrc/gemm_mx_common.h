@@ -57,5 +57,33 @@ struct MxScales {
   }
 };
 
+// Where an MX GEMM entry's own rules sit among the shared ones (mx_gemm_entry)
+enum MxRulesAt {
+  MX_BEFORE_SHAPES,    // w_fmt; the branch's t, b and dtype16
+  MX_AFTER_SHAPES,     // R and ldt; n8
+  MX_AFTER_ALIGNMENT,  // the branch's alignment
+};
+
+// The host front of every MX GEMM entry, in the order the ABI tests pin: non-NULL operands, the entry's rules before the shapes, the
+// shared shape rules with K a multiple of TKX, its rules after them, the scale alignment, its rules after that, the tail, M == 0,
+// then launch(params, stream).
+template <class Rules, class Launch>
+inline int mx_gemm_entry(const char* what, const uint8_t* a, const uint8_t* w, const uint8_t* sa_u8, const uint8_t* sw_u8, void* out,
+                         int out_dtype, const void* bias, int bias_dtype, const float* gate, const void* residual, int epi_flags,
+                         int64_t M, int N, int K, void* stream, Rules rules, Launch launch) {
+  WANQ_REQUIRE(a && w && out && sa_u8 && sw_u8, WANQ_E_ARG, "%s: a, w, sa_u8, sw_u8 and out must be non-NULL", what);
+  if (const int rc = rules(MX_BEFORE_SHAPES)) return rc;
+  if (const int rc = check_gemm16_shapes(what, TKX, a, w, out, out_dtype, bias, bias_dtype, gate, residual, epi_flags, M, N, K))
+    return rc;
+  if (const int rc = rules(MX_AFTER_SHAPES)) return rc;
+  WANQ_REQUIRE(aligned(sa_u8, 4) && aligned(sw_u8, 4), WANQ_E_ARG, "%s: sa_u8 and sw_u8 must be 4-byte aligned", what);
+  if (const int rc = rules(MX_AFTER_ALIGNMENT)) return rc;
+  if (const int rc = check_gemm16_tail(what, bias, bias_dtype, gate, M, N)) return rc;
+  if (M == 0) return WANQ_OK;
+  return launch(gemm16_params(a, w, sa_u8, sw_u8, out, bias, bias_dtype, gate, residual, epi_flags, M, N, K), (hipStream_t)stream);
+}
+
+inline int no_rules(MxRulesAt) { return WANQ_OK; }
+
 }  // namespace
 }  // namespace wanq

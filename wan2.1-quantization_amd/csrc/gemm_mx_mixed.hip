@@ -129,19 +129,18 @@ extern "C" int wanq_gemm_mx_mixed(const uint8_t* a, const uint8_t* w, const uint
                                   int out_dtype, const void* bias, int bias_dtype, const float* gate, const void* residual,
                                   int epi_flags, int64_t M, int N, int K, void* stream) {
   const char* what = "wanq_gemm_mx_mixed";
-  WANQ_REQUIRE(a && w && out && sa_u8 && sw_u8, WANQ_E_ARG, "%s: a, w, sa_u8, sw_u8 and out must be non-NULL", what);
-  if (const int rc = check_gemm16_shapes(what, TKX, a, w, out, out_dtype, bias, bias_dtype, gate, residual, epi_flags, M, N, K))
-    return rc;
-  WANQ_REQUIRE(n8 >= TKX && n8 % TKX == 0 && K - n8 >= TKX, WANQ_E_SHAPE,
-               "%s: n8=%d must be a multiple of 128 with 128 <= n8 <= K - 128 (K=%d)", what, n8, K);
-  WANQ_REQUIRE(aligned(sa_u8, 4) && aligned(sw_u8, 4), WANQ_E_ARG, "%s: sa_u8 and sw_u8 must be 4-byte aligned", what);
-  if (const int rc = check_gemm16_tail(what, bias, bias_dtype, gate, M, N)) return rc;
-  if (M == 0) return WANQ_OK;
-  const Gemm16Params p = gemm16_params(a, w, sa_u8, sw_u8, out, bias, bias_dtype, gate, residual, epi_flags, M, N, K);
-  hipStream_t st = (hipStream_t)stream;
-  return with_out_dtype(out_dtype, [&](auto o) {
-    const int64_t tiles = (int64_t)((p.M + TM - 1) / TM) * p.nt;
-    hipLaunchKernelGGL(gemm_mx_mixed_kernel<decltype(o)::value>, dim3((unsigned)tiles), dim3(256), 0, st, p, n8);
-    return check_launch(what);
-  });
+  const auto rules = [&](MxRulesAt at) {
+    if (at == MX_AFTER_SHAPES)
+      WANQ_REQUIRE(n8 >= TKX && n8 % TKX == 0 && K - n8 >= TKX, WANQ_E_SHAPE,
+                   "%s: n8=%d must be a multiple of 128 with 128 <= n8 <= K - 128 (K=%d)", what, n8, K);
+    return WANQ_OK;
+  };
+  return mx_gemm_entry(what, a, w, sa_u8, sw_u8, out, out_dtype, bias, bias_dtype, gate, residual, epi_flags, M, N, K, stream, rules,
+                       [&](const Gemm16Params& p, hipStream_t st) {
+                         return with_out_dtype(out_dtype, [&](auto o) {
+                           const int64_t tiles = (int64_t)((p.M + TM - 1) / TM) * p.nt;
+                           hipLaunchKernelGGL(gemm_mx_mixed_kernel<decltype(o)::value>, dim3((unsigned)tiles), dim3(256), 0, st, p, n8);
+                           return check_launch(what);
+                         });
+                       });
 }

@@ -3,10 +3,13 @@ with `delta` / `zero_point` buffers ([G,1]) and an `init_done` flag.  All heavy 
 (viditq_extension.fused): row statistics, static quantisation and the per-token dynamic quantiser; the [G]-sized
 parameter arithmetic is plain fp32 torch (IEEE, bit-identical to the reference's CPU result).
 Tensors must live on the GPU: there is no CPU path."""
+from typing import NamedTuple
+
 import torch
 import torch.nn as nn
 
 from viditq_extension import fused
+from viditq_extension._C import MX_BLOCK_BYTES  # bytes of a block's 32 codes in a row of the operand, by format name
 
 from ..config import ListConfig
 
@@ -249,6 +252,44 @@ E2M3_VALUES = tuple((c & 7) / 8 if c < 8 else 2.0 ** ((c >> 3) - 1) * (1 + (c & 
 
 def mx_fmt_code(fmt):
     return _MX_SPEC[fmt][2]
+
+
+# ---- the built operand pairs ------------------------------------------------------------------------------------------------------
+# The ONE table of which (weight format, activation format) pairs have a GEMM: the config checks (quant_layer.py), simulation mode's
+# forward, kernel mode's layer (wan/quant_wanx_hip.py: HipLinearMx, _Src.rows) and the checkpoint (wan/quant_wanx.py) read it.  A new pair is a new row.
+
+
+class MxPair(NamedTuple):
+    w_fmt: str
+    a_fmt: str
+    gemm: str         # the qgemm entry (and, + "_refusal", its shape rules)
+    takes_w_fmt: bool  # the entry has a `w_fmt` argument (C code: mx_fmt_code), and is one C entry for several weight formats
+    act_form: str     # the name of the quantised activation consumers share (+ "_h32" behind the block rotation)
+    had32: bool = False     # the options the pair admits: mx.block_hadamard,
+    low_rank: bool = False  # weight.low_rank / set_low_rank (qgemm.mx4_lowrank_linear),
+    n8: bool = False        # mx.outlier_channels (qgemm.mx_mixed_linear)
+
+    @property
+    def w_bytes(self):
+        return MX_BLOCK_BYTES[self.w_fmt]
+
+    @property
+    def a_bytes(self):
+        return MX_BLOCK_BYTES[self.a_fmt]
+
+
+MX_PAIRS = {(p.w_fmt, p.a_fmt): p for p in (
+    MxPair(MXFP8_FORMAT, MXFP8_FORMAT, "mx_linear", True, "mxfp8"),
+    MxPair(MXFP4_FORMAT, MXFP8_FORMAT, "mx_linear", True, "mxfp8"),
+    MxPair(MXFP4_FORMAT, MXFP4_FORMAT, "mx4_linear", False, "mxfp4", had32=True, low_rank=True, n8=True),
+    MxPair(MXFP6_FORMAT, MXFP6_FORMAT, "mx6_linear", True, "mxfp6"),
+    MxPair(MXFP4_FORMAT, MXFP6_FORMAT, "mx6_linear", True, "mxfp6"),
+)}
+
+
+def mx_pair(w_fmt, a_fmt):
+    """The row of the built pair (weight format, activation format), or None: no GEMM takes it."""
+    return MX_PAIRS.get((w_fmt, a_fmt))
 
 
 def _pow2_f64(e):

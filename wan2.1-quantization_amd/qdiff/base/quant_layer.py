@@ -18,7 +18,7 @@ from viditq_extension import fused, qgemm
 from ..config import ListConfig
 from ..quarot import quarot_utils
 from .base_quantizer import (FP8_FORMAT, MX_BLOCK, MX_FORMATS, MXFP4_FORMAT, MXFP6_FORMAT, MXFP8_FORMAT, DynamicQuantizer, Fp8Quantizer, MxQuantizer,
-                             StaticQuantizer, _pow2_f64, fp8_decode, mx_decode, mx_decode_mixed, mx_quant_rows_mixed)
+                             StaticQuantizer, _pow2_f64, fp8_decode, mx_decode, mx_decode_mixed, mx_pair, mx_quant_rows_mixed)
 from .gptq import BLOCK_MAX, gptq_prepare, gptq_section, gptq_solve
 from .low_rank import RANK_MAX, LowRankBranch, fit_low_rank, padded_rank
 from .mixed_precision_quantizer import MixedPrecisionDynamicQuantizer, MixedPrecisionStaticQuantizer
@@ -126,33 +126,11 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
                                       "QuantizedLinear)")
 
     def _check_mx_format(self, name, wq, aq, fw, fa):
-        """The accepted OCP MX pairs are (weight mxfp8_e4m3, act mxfp8_e4m3), (weight mxfp4_e2m1, act mxfp8_e4m3), the W4A4 pair
-        (weight mxfp4_e2m1, act mxfp4_e2m1) and the two with e2m3 activations, W6A6 (weight mxfp6_e2m3fn, act mxfp6_e2m3fn) and W4A6
-        (weight mxfp4_e2m1, act mxfp6_e2m3fn), with n_bits 8 / 6 / 4, sym True and weight.group_size absent or 32 (the format's
-        block); everything else is refused by layer name."""
-        if MXFP6_FORMAT in (fw, fa):
-            built = (f"(the built pairs with {MXFP6_FORMAT} are weight {MXFP6_FORMAT} n_bits 6 or weight {MXFP4_FORMAT} n_bits 4 against "
-                     f"act {MXFP6_FORMAT} n_bits 6: wanq_gemm_mx6)")
-            if fw == MXFP6_FORMAT and fa in (MXFP8_FORMAT, MXFP4_FORMAT, FP8_FORMAT):
-                raise NotImplementedError(f"{name}: weight.format: {MXFP6_FORMAT} against act.format: {fa} is not supported: no GEMM takes "
-                                          f"e2m3 weights against {'8-bit' if fa != MXFP4_FORMAT else 'e2m1'} activations {built}")
-            if fa == MXFP6_FORMAT and fw in (MXFP8_FORMAT, FP8_FORMAT):
-                raise NotImplementedError(f"{name}: act.format: {MXFP6_FORMAT} against weight.format: {fw} is not supported: an e4m3 "
-                                          f"weight would hold the matrix cores to the fp8 rate {built}")
-        if fa == MXFP4_FORMAT:
-            built = f"(the built pair is weight {MXFP4_FORMAT} n_bits 4 against act {MXFP4_FORMAT} n_bits 4)"
-            if not isinstance(aq["n_bits"], ListConfig) and aq["n_bits"] == 8:
-                raise NotImplementedError(f"{name}: act.format: {MXFP4_FORMAT} with act.n_bits: 8 is not supported: no fp4 activation "
-                                          f"quantiser path is built yet for 8-bit codes {built}")
-            if fw in (MXFP8_FORMAT, FP8_FORMAT):
-                raise NotImplementedError(f"{name}: act.format: {MXFP4_FORMAT} against weight.format: {fw} is not supported: no fp4 "
-                                          f"activation quantiser path is built yet for an e4m3 weight {built}")
-        if fw not in MX_FORMATS or fa not in MX_FORMATS:
-            sec, other = ("weight", fw) if fw not in MX_FORMATS else ("act", fa)
-            raise NotImplementedError(f"{name}: an MX format on one side needs an MX format on the other ({sec}.format is "
-                                      f"{other!r}): the MX GEMMs take block-scaled codes on both sides, weight {MXFP8_FORMAT} or "
-                                      f"{MXFP4_FORMAT} against act {MXFP8_FORMAT}, or weight {MXFP4_FORMAT} against act {MXFP4_FORMAT}, or weight "
-                                      f"{MXFP6_FORMAT} or {MXFP4_FORMAT} against act {MXFP6_FORMAT}")
+        """The accepted OCP MX pairs are the rows of base_quantizer.MX_PAIRS, with n_bits 8 / 6 / 4, sym True and weight.group_size
+        absent or 32 (the format's block); everything else is refused by layer name."""
+        a4_as_8 = fa == MXFP4_FORMAT and not isinstance(aq["n_bits"], ListConfig) and aq["n_bits"] == 8
+        if mx_pair(fw, fa) is None or a4_as_8:
+            raise NotImplementedError(f"{name}: {self._mx_pair_refusal(a4_as_8, fw, fa)}")
         self._check_format_sections(name, (("weight", wq, fw), ("act", aq, fa)))
         g = wq.get("group_size", None)
         if g is not None and (isinstance(g, bool) or g != MX_BLOCK):
@@ -161,6 +139,32 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         self._refuse_format_on_a_transformed_layer(name)
         if self.in_features % MX_BLOCK:
             raise ValueError(f"{name}: weight.format: {fw} needs in_features={self.in_features} to be a multiple of {MX_BLOCK}")
+
+    @staticmethod
+    def _mx_pair_refusal(a4_as_8, fw, fa):
+        """The words for a (weight format, act format) that is no row of MX_PAIRS, or for e2m1 activations declared 8 bits wide: what
+        the nearest built pair lacks."""
+        if MXFP6_FORMAT in (fw, fa):
+            built = (f"(the built pairs with {MXFP6_FORMAT} are weight {MXFP6_FORMAT} n_bits 6 or weight {MXFP4_FORMAT} n_bits 4 against "
+                     f"act {MXFP6_FORMAT} n_bits 6: wanq_gemm_mx6)")
+            if fw == MXFP6_FORMAT and fa in (MXFP8_FORMAT, MXFP4_FORMAT, FP8_FORMAT):
+                return (f"weight.format: {MXFP6_FORMAT} against act.format: {fa} is not supported: no GEMM takes e2m3 weights against "
+                        f"{'8-bit' if fa != MXFP4_FORMAT else 'e2m1'} activations {built}")
+            if fa == MXFP6_FORMAT and fw in (MXFP8_FORMAT, FP8_FORMAT):
+                return (f"act.format: {MXFP6_FORMAT} against weight.format: {fw} is not supported: an e4m3 weight would hold the matrix "
+                        f"cores to the fp8 rate {built}")
+        if fa == MXFP4_FORMAT:
+            built = f"(the built pair is weight {MXFP4_FORMAT} n_bits 4 against act {MXFP4_FORMAT} n_bits 4)"
+            if a4_as_8:
+                return (f"act.format: {MXFP4_FORMAT} with act.n_bits: 8 is not supported: no fp4 activation quantiser path is built yet "
+                        f"for 8-bit codes {built}")
+            if fw in (MXFP8_FORMAT, FP8_FORMAT):
+                return (f"act.format: {MXFP4_FORMAT} against weight.format: {fw} is not supported: no fp4 activation quantiser path is "
+                        f"built yet for an e4m3 weight {built}")
+        sec, other = ("weight", fw) if fw not in MX_FORMATS else ("act", fa)
+        return (f"an MX format on one side needs an MX format on the other ({sec}.format is {other!r}): the MX GEMMs take block-scaled "
+                f"codes on both sides, weight {MXFP8_FORMAT} or {MXFP4_FORMAT} against act {MXFP8_FORMAT}, or weight {MXFP4_FORMAT} against "
+                f"act {MXFP4_FORMAT}, or weight {MXFP6_FORMAT} or {MXFP4_FORMAT} against act {MXFP6_FORMAT}")
 
     def _checked_mx_section(self, quant_config, module_name):
         """`mx.block_hadamard` of the config (False without the section): both sides of the layer are quantised behind a 32-point
@@ -182,7 +186,7 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
             raise NotImplementedError(f"{name}: mx.block_hadamard: True is not supported with weight.format {self.mx!r} against "
                                       f"act.format {self.mx_act!r}: no rotating e2m3 quantiser is built; the block rotation is built for "
                                       f"the W4A4 pair only (weight.format: {MXFP4_FORMAT} against act.format: {MXFP4_FORMAT})")
-        if on and not (self.mx == MXFP4_FORMAT and self.mx_act == MXFP4_FORMAT):
+        if on and not self._mx_admits("had32"):
             pair = f"weight.format {self.mx!r} against act.format {self.mx_act!r}" if self.mx else "no MX format"
             raise NotImplementedError(f"{name}: mx.block_hadamard: True is not supported with {pair}: the block rotation is built for "
                                       f"the W4A4 pair only (weight.format: {MXFP4_FORMAT} against act.format: {MXFP4_FORMAT})")
@@ -195,7 +199,7 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         n8 = sec.get("outlier_channels", None)
         if n8 is None:
             return None
-        if not self._mx4_pair:
+        if not self._mx_admits("n8"):
             pair = f"weight.format {self.mx!r} against act.format {self.mx_act!r}" if self.mx else "no MX format"
             raise NotImplementedError(f"{name}: mx.outlier_channels is not supported with {pair}: the outlier channels are built for "
                                       f"the W4A4 pair only (weight.format: {MXFP4_FORMAT} against act.format: {MXFP4_FORMAT})")
@@ -225,7 +229,8 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
             raise ValueError(f"{name}: weight.low_rank={r!r} must be a positive integer")
         aq = quant_config.get("act", None)
         # the W4A4 MX pair carries the branch too (wanq_gemm_mx4_lowrank); every other quantised activation is refused as before
-        mx4 = aq is not None and wq.get("format", None) == MXFP4_FORMAT and aq.get("format", None) == MXFP4_FORMAT
+        pair = None if aq is None else mx_pair(wq.get("format", None), aq.get("format", None))
+        mx4 = pair is not None and pair.low_rank
         if aq is not None and not mx4:
             raise NotImplementedError(f"{name}: weight.low_rank with an `act:` section is not supported: the low-rank branch is summed "
                                       "in the weight-only GEMM (16-bit activations); the int8, fp8 and MX GEMMs have none")
@@ -282,7 +287,7 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         if self.mx_n8 is not None:
             raise NotImplementedError(f"{self._lr_name()}: set_low_rank with mx.outlier_channels is not supported: wanq_gemm_mx_mixed "
                                       "sums no low-rank branch")
-        if self._mx4_pair and not (self.uses_mask or self.uses_rotation):
+        if self._mx_admits("low_rank") and not (self.uses_mask or self.uses_rotation):
             return
         if self.w_quantizer is None or self.a_quantizer is not None or self.fp8 or self.mx or self.uses_mask or self.uses_rotation \
                 or not isinstance(self.w_quantizer, StaticQuantizer):
@@ -315,10 +320,10 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
             raise ValueError(f"{name}: weight.group_size={g} does not divide in_features={self.in_features}")
         return g
 
-    @property
-    def _mx4_pair(self):
-        """The W4A4 MX pair: the second host of the low-rank branch."""
-        return self.mx == MXFP4_FORMAT and self.mx_act == MXFP4_FORMAT
+    def _mx_admits(self, option):
+        """Whether this layer's MX pair admits `option` ("had32", "low_rank", "n8": the columns of base_quantizer.MX_PAIRS)."""
+        pair = mx_pair(self.mx, self.mx_act)
+        return pair is not None and getattr(pair, option)
 
     # ---- weight side --------------------------------------------------------------------------------
     def _requantize(self, w, precomputed=None):
@@ -537,15 +542,14 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         dequantised activation and the dequantised weight, in fp32."""
         if self.mx_n8 is not None:
             return self._forward_mx_mixed(x2, out_dtype, bias)
-        if self._mx4_pair and (self.low_rank is not None or self._adapter is not None):
+        if self._mx_admits("low_rank") and (self.low_rank is not None or self._adapter is not None):
             return self._forward_mx4_low_rank(x2, out_dtype, bias)
         a_q, a_s = self.a_quantizer.codes_and_scale(x2)
-        refusal, gemm, fmt = (qgemm.mx6_linear_refusal, qgemm.mx6_linear, (self.mx,)) if self.mx_act == MXFP6_FORMAT else \
-            (qgemm.mx4_linear_refusal, qgemm.mx4_linear, ()) if self.mx_act == MXFP4_FORMAT else \
-            (qgemm.mx_linear_refusal, qgemm.mx_linear, (self.mx,)) if self.mx else (qgemm.fp8_linear_refusal, qgemm.fp8_linear, ())
-        if x2.is_cuda and refusal(x2.shape[0], self.out_features, self.in_features, *fmt) is None:
+        pair = mx_pair(self.mx, self.mx_act)   # (None: fp8)
+        gemm, fmt = (pair.gemm, (self.mx,) if pair.takes_w_fmt else ()) if pair is not None else ("fp8_linear", ())
+        if x2.is_cuda and getattr(qgemm, gemm + "_refusal")(x2.shape[0], self.out_features, self.in_features, *fmt) is None:
             w_s = self.w_quantizer.scale_u8 if self.mx else self.w_quantizer.delta.reshape(-1).float().contiguous()
-            return gemm(a_q, self._codes, a_s, w_s, *fmt, bias, out_dtype=out_dtype)
+            return getattr(qgemm, gemm)(a_q, self._codes, a_s, w_s, *fmt, bias, out_dtype=out_dtype)
         # (with mx.block_hadamard the decoded activation and weight.data are both in the rotated domain: their product is x w^T's)
         a = mx_decode(a_q, a_s, self.mx_act) if self.mx else fp8_decode(a_q) * a_s.unsqueeze(-1)
         return F.linear(a, self.weight.data.float(), bias).to(out_dtype)

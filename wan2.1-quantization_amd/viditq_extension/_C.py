@@ -42,6 +42,8 @@ _vp, _i, _i64, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_floa
 MX_FMT = {"mxfp8_e4m3": 0, "mxfp4_e2m1": 1}
 # `w_fmt` codes of wanq_gemm_mx6 (WANQ_MX_E2M3, WANQ_MX_E2M1); wanq_quant_rows_mx6 writes the first
 MX6_FMT = {"mxfp6_e2m3fn": 2, "mxfp4_e2m1": 1}
+# bytes of a block's 32 codes in a row of an MX operand, by format name: the one statement of the row widths
+MX_BLOCK_BYTES = {"mxfp8_e4m3": 32, "mxfp6_e2m3fn": 24, "mxfp4_e2m1": 16}
 
 PROTOTYPES = {
     "wanq_quant_rows": [_vp, _i, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _vp],

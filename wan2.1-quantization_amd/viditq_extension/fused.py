@@ -91,6 +91,10 @@ def quant_rows_fp8(x, gelu=False):
     return codes, scale
 
 
+# fmt -> (C entry, its format-code argument if it takes one (it then has a `_had32` twin))
+_MX_ROW_ENTRY = {"mxfp6_e2m3fn": ("wanq_quant_rows_mx6", ()), **{f: ("wanq_quant_rows_mx", (c,)) for f, c in _C.MX_FMT.items()}}
+
+
 def quant_rows_mx(x, fmt="mxfp8_e4m3", gelu=False, had32=False):
     """OCP MX block quantisation (wanq_quant_rows_mx): -> (codes uint8, scale bytes uint8 [rows, cols / 32]), one E8M0 scale per block
     of 32 columns: s = clamp(E(amax) - emax, 0, 254), codes = rne(clamp(x 2^(127 - s), -max, max)).  fmt "mxfp8_e4m3": codes of x's
@@ -100,48 +104,20 @@ def quant_rows_mx(x, fmt="mxfp8_e4m3", gelu=False, had32=False):
     in front of the block maximum.
     fmt "mxfp6_e2m3fn" (wanq_quant_rows_mx6, no `had32`): [rows, 3 cols / 4], 32 six-bit e2m3 codes per 24 bytes, element j of a block
     in bits 6 j .. 6 j + 5 of its little-endian string; the scale bytes are those of "mxfp4_e2m1"."""
-    if fmt == "mxfp6_e2m3fn":
-        return _quant_rows_mx6(x, gelu, had32)
-    if fmt not in _C.MX_FMT:
+    if fmt not in _MX_ROW_ENTRY:
         raise RuntimeError(f"quant_rows_mx: fmt={fmt!r} must be one of {tuple(_C.MX_FMT)}")
+    entry, code = _MX_ROW_ENTRY[fmt]
+    if had32 and not code:
+        raise RuntimeError(f"quant_rows_mx: fmt={fmt!r} has no had32 form (the block rotation is built for mxfp4_e2m1 / mxfp8_e4m3)")
     rows, cols = _rows_cols("x", x)
     if cols % 32:
         raise RuntimeError(f"quant_rows_mx: cols={cols} must be a multiple of 32")
-    code = _C.MX_FMT[fmt]
-    codes = torch.empty((*x.shape[:-1], cols // 2 if code else cols), dtype=torch.uint8, device=x.device)
+    codes = torch.empty((*x.shape[:-1], cols // 32 * _C.MX_BLOCK_BYTES[fmt]), dtype=torch.uint8, device=x.device)
     scale = torch.empty((*x.shape[:-1], cols // 32), dtype=torch.uint8, device=x.device)
     with torch.cuda.device(x.device):
-        _C.call("wanq_quant_rows_mx_had32" if had32 else "wanq_quant_rows_mx", _C.ptr(x), _C.dt(x), _C.ptr(codes), _C.ptr(scale), rows,
-                cols, code, 1 if gelu else 0, _C.stream())
+        _C.call(entry + "_had32" if had32 else entry, _C.ptr(x), _C.dt(x), _C.ptr(codes), _C.ptr(scale), rows, cols, *code,
+                1 if gelu else 0, _C.stream())
     return codes, scale
-
-
-def _quant_rows_mx6(x, gelu, had32):
-    if had32:
-        raise RuntimeError("quant_rows_mx: fmt='mxfp6_e2m3fn' has no had32 form (the block rotation is built for mxfp4_e2m1 / mxfp8_e4m3)")
-    rows, cols = _rows_cols("x", x)
-    if cols % 32:
-        raise RuntimeError(f"quant_rows_mx: cols={cols} must be a multiple of 32")
-    codes = torch.empty((*x.shape[:-1], cols // 4 * 3), dtype=torch.uint8, device=x.device)
-    scale = torch.empty((*x.shape[:-1], cols // 32), dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        _C.call("wanq_quant_rows_mx6", _C.ptr(x), _C.dt(x), _C.ptr(codes), _C.ptr(scale), rows, cols, 1 if gelu else 0, _C.stream())
-    return codes, scale
-
-
-def quant_rows_mxfp6(x, gelu=False):
-    """`quant_rows_mx` to packed e2m3 codes: the activation form "mxfp6" of a W6A6 / W4A6 layer."""
-    return quant_rows_mx(x, "mxfp6_e2m3fn", gelu)
-
-
-def quant_rows_mxfp4(x, gelu=False):
-    """`quant_rows_mx` to packed e2m1 codes: the activation form "mxfp4" of a W4A4 layer."""
-    return quant_rows_mx(x, "mxfp4_e2m1", gelu)
-
-
-def quant_rows_mxfp4_h32(x, gelu=False):
-    """`quant_rows_mx` to packed e2m1 codes behind the block Hadamard rotation: the activation form "mxfp4_h32"."""
-    return quant_rows_mx(x, "mxfp4_e2m1", gelu, had32=True)
 
 
 def quant_rows_mx_mixed(x, perm, n8, gelu=False):
@@ -169,7 +145,7 @@ def quant_rows_mx_mixed(x, perm, n8, gelu=False):
 
 
 def quant_rows_mxfp4_project(x, a16, gelu=False, had32=False, ldt=None, out=None):
-    """`quant_rows_mxfp4` (`had32`: `quant_rows_mxfp4_h32`) and, in the same pass over x, the down-projection of a 16-bit low-rank
+    """`quant_rows_mx` to "mxfp4_e2m1" (with its `had32`) and, in the same pass over x, the down-projection of a 16-bit low-rank
     branch (wanq_quant_rows_mx4_project, csrc/quant_project.hip): -> (codes, scales, t).  codes and scales are the plain quantiser's,
     bit for bit.  a16 [R, cols] bf16 or fp16;  t [rows, R] of a16's dtype, t = round(round(gelu(x)) @ a16^T): the row is rounded once to
     a16's dtype behind the GELU and in front of the rotation, the product is summed in fp32 and rounded once.  With `ldt` (>= R, a

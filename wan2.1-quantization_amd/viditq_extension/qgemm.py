@@ -496,6 +496,30 @@ def fp8_linear_refusal(M, N, K):
 MX_K_STEP = 128  # wanq_gemm_mx's K multiple: one K-tile = one 128-deep MFMA = four blocks of 32
 
 
+def _mx_mats(name, a_q, w_q, a_scale, w_scale):
+    """The four operands of the MX entry `name`, each a uint8 matrix on the GPU -> M, N"""
+    for nm, t in (("a_q", a_q), ("w_q", w_q), ("a_scale", a_scale), ("w_scale", w_scale)):
+        if t is None:
+            raise RuntimeError(f"{name}: {nm} must be given")
+        _check_mat(nm, t, torch.uint8)
+    return a_q.shape[0], w_q.shape[0]
+
+
+def _mx_launch(name, entry, mats, M, N, K, a_cols, w_cols, why, lead, more, bias, out_dtype, gelu, gate, residual, out):
+    """What the MX entries share once they know K: the refusal `why` (None: accepted), the operands' shapes -- a_q [M, a_cols], w_q
+    [N, w_cols], both scales [., K / 32], then `more`, (name, tensor, shape or None) of the operands `lead` points at -- and the launch
+    of `entry` with `lead` between the scales and `out`."""
+    if why is not None:
+        raise RuntimeError(f"{name}: {why}")
+    for (nm, rows, cols), t in zip((("a_q", M, a_cols), ("w_q", N, w_cols), ("a_scale", M, K // 32), ("w_scale", N, K // 32)), mats):
+        _C.check_shape(nm, t, rows, cols)
+    for nm, t, shape in more:
+        if shape is not None:
+            _C.check_shape(nm, t, *shape)
+    return _launch16(entry, (*(_C.ptr(t) for t in mats), *lead), (*mats, *(t for _, t, _ in more)), bias, out_dtype or torch.bfloat16, gelu,
+                     gate, residual, out, M, N, K)
+
+
 def mx_linear(a_q, w_q, a_scale, w_scale, w_fmt="mxfp8_e4m3", bias=None, out_dtype=None, gelu=False, gate=None, residual=None,
               out=None):
     """y = epilogue(sum over blocks of 2^(a_scale - 127) 2^(w_scale - 127) a_q @ w_q^T) on the block-scaled matrix cores (wanq_gemm_mx,
@@ -506,21 +530,10 @@ def mx_linear(a_q, w_q, a_scale, w_scale, w_fmt="mxfp8_e4m3", bias=None, out_dty
     sits in the launch.  Not counted by the int8 timer (`set_timer`)."""
     if w_fmt not in _C.MX_FMT:
         raise RuntimeError(f"mx_linear: w_fmt={w_fmt!r} must be one of {tuple(_C.MX_FMT)}")
-    fp4 = _C.MX_FMT[w_fmt] == 1
-    for name, t in (("a_q", a_q), ("w_q", w_q), ("a_scale", a_scale), ("w_scale", w_scale)):
-        if t is None:
-            raise RuntimeError(f"mx_linear: {name} must be given")
-        _check_mat(name, t, torch.uint8)
-    M, K = a_q.shape
-    N = w_q.shape[0]
-    why = mx_linear_refusal(M, N, K, w_fmt)
-    if why is not None:
-        raise RuntimeError(f"mx_linear: {why}")
-    _C.check_shape("w_q", w_q, N, K // 2 if fp4 else K)
-    _C.check_shape("a_scale", a_scale, M, K // 32)
-    _C.check_shape("w_scale", w_scale, N, K // 32)
-    return _launch16("wanq_gemm_mx", (_C.ptr(a_q), _C.ptr(w_q), _C.ptr(a_scale), _C.ptr(w_scale), _C.MX_FMT[w_fmt]),
-                     (a_q, w_q, a_scale, w_scale), bias, out_dtype or torch.bfloat16, gelu, gate, residual, out, M, N, K)
+    M, N = _mx_mats("mx_linear", a_q, w_q, a_scale, w_scale)
+    K = a_q.shape[1]
+    return _mx_launch("mx_linear", "wanq_gemm_mx", (a_q, w_q, a_scale, w_scale), M, N, K, K, K // 32 * _C.MX_BLOCK_BYTES[w_fmt],
+                      mx_linear_refusal(M, N, K, w_fmt), (_C.MX_FMT[w_fmt],), (), bias, out_dtype, gelu, gate, residual, out)
 
 
 def mx_linear_refusal(M, N, K, w_fmt="mxfp8_e4m3"):
@@ -537,20 +550,10 @@ def mx4_linear(a_q, w_q, a_scale, w_scale, bias=None, out_dtype=None, gelu=False
     e2m1 nibbles, a_scale uint8 [M, K / 32], w_scale uint8 [N, K / 32], all as `fused.quant_rows_mx(fmt="mxfp4_e2m1")` writes them (both
     sides with `had32`, or neither).  The accumulation, epilogue, shape rules (K % 128 == 0, N % 8 == 0) and determinism are
     `mx_linear`'s.  Not counted by the int8 timer (`set_timer`)."""
-    for name, t in (("a_q", a_q), ("w_q", w_q), ("a_scale", a_scale), ("w_scale", w_scale)):
-        if t is None:
-            raise RuntimeError(f"mx4_linear: {name} must be given")
-        _check_mat(name, t, torch.uint8)
-    M, K = a_q.shape[0], a_q.shape[1] * 2
-    N = w_q.shape[0]
-    why = mx4_linear_refusal(M, N, K)
-    if why is not None:
-        raise RuntimeError(f"mx4_linear: {why}")
-    _C.check_shape("w_q", w_q, N, K // 2)
-    _C.check_shape("a_scale", a_scale, M, K // 32)
-    _C.check_shape("w_scale", w_scale, N, K // 32)
-    return _launch16("wanq_gemm_mx4", (_C.ptr(a_q), _C.ptr(w_q), _C.ptr(a_scale), _C.ptr(w_scale)), (a_q, w_q, a_scale, w_scale), bias,
-                     out_dtype or torch.bfloat16, gelu, gate, residual, out, M, N, K)
+    M, N = _mx_mats("mx4_linear", a_q, w_q, a_scale, w_scale)
+    K = a_q.shape[1] * 2
+    return _mx_launch("mx4_linear", "wanq_gemm_mx4", (a_q, w_q, a_scale, w_scale), M, N, K, K // 2, K // 2, mx4_linear_refusal(M, N, K), (),
+                      (), bias, out_dtype, gelu, gate, residual, out)
 
 
 def mx4_linear_refusal(M, N, K):
@@ -566,19 +569,12 @@ def mx_mixed_linear(a_q, w_q, a_scale, w_scale, n8, bias=None, out_dtype=None, g
     order; a_scale uint8 [M, K / 32], w_scale uint8 [N, K / 32], as `fused.quant_rows_mx_mixed` writes them.  One K loop: n8 / 128 tiles
     at the fp8 rate, then (K - n8) / 128 at the fp4 rate, into the same accumulators.  The accumulation, epilogue, shape rules (K % 128
     == 0, N % 8 == 0) and determinism are `mx_linear`'s, and n8 % 128 == 0, 128 <= n8 <= K - 128.  Not counted by the int8 timer."""
-    for name, t in (("a_q", a_q), ("w_q", w_q), ("a_scale", a_scale), ("w_scale", w_scale)):
-        if t is None:
-            raise RuntimeError(f"mx_mixed_linear: {name} must be given")
-        _check_mat(name, t, torch.uint8)
-    M, N, K = a_q.shape[0], w_q.shape[0], a_scale.shape[1] * 32
+    M, N = _mx_mats("mx_mixed_linear", a_q, w_q, a_scale, w_scale)
+    K = a_scale.shape[1] * 32   # (a row of a_q holds n8 + (K - n8) / 2 bytes)
     why = mx_mixed_linear_refusal(M, N, K, n8)
-    if why is not None:
-        raise RuntimeError(f"mx_mixed_linear: {why}")
-    _C.check_shape("a_q", a_q, M, n8 + (K - n8) // 2)
-    _C.check_shape("w_q", w_q, N, n8 + (K - n8) // 2)
-    _C.check_shape("w_scale", w_scale, N, K // 32)
-    return _launch16("wanq_gemm_mx_mixed", (_C.ptr(a_q), _C.ptr(w_q), _C.ptr(a_scale), _C.ptr(w_scale), int(n8)),
-                     (a_q, w_q, a_scale, w_scale), bias, out_dtype or torch.bfloat16, gelu, gate, residual, out, M, N, K)
+    cols = None if why is not None else n8 + (K - n8) // 2
+    return _mx_launch("mx_mixed_linear", "wanq_gemm_mx_mixed", (a_q, w_q, a_scale, w_scale), M, N, K, cols, cols, why, (n8,), (), bias,
+                      out_dtype, gelu, gate, residual, out)
 
 
 def mx_mixed_linear_refusal(M, N, K, n8):
@@ -597,12 +593,8 @@ def mx4_lowrank_linear(a_q, w_q, a_scale, w_scale, t, b, bias=None, out_dtype=No
     y = epilogue(y0 + t[M,R] @ b[N,R]^T), y0 what `mx4_linear` has before its bias.  `t` (from `fused.quant_rows_mxfp4_project`) and `b`
     share a dtype, bf16 or fp16; `t` may be a column window [M, R] of a wider buffer (stride(1) == 1, stride(0) % 8 == 0, 16-byte
     aligned).  R % 64 == 0, 64 <= R <= 256 (zero pad a smaller rank).  The branch is added before GELU and gate + residual."""
-    for name, x in (("a_q", a_q), ("w_q", w_q), ("a_scale", a_scale), ("w_scale", w_scale)):
-        if x is None:
-            raise RuntimeError(f"mx4_lowrank_linear: {name} must be given")
-        _check_mat(name, x, torch.uint8)
-    M, K = a_q.shape[0], a_q.shape[1] * 2
-    N = w_q.shape[0]
+    M, N = _mx_mats("mx4_lowrank_linear", a_q, w_q, a_scale, w_scale)
+    K = a_q.shape[1] * 2
     for name, x in (("t", t), ("b", b)):
         _C.check_gpu(name, x)
         _C.check_dtype(name, x, torch.bfloat16, torch.float16)
@@ -611,18 +603,12 @@ def mx4_lowrank_linear(a_q, w_q, a_scale, w_scale, t, b, bias=None, out_dtype=No
     _C.check_contig("b", b)
     R = b.shape[1]
     why = mx4_lowrank_refusal(M, N, K, R)
-    if why is not None:
-        raise RuntimeError(f"mx4_lowrank_linear: {why}")
-    if t.dtype != b.dtype or tuple(t.shape) != (M, R) or t.stride(1) != 1 or t.stride(0) < R or t.stride(0) % 8:
-        raise RuntimeError(f"mx4_lowrank_linear: t must be [{M}, {R}] of b's dtype with unit column stride and a row pitch that is a "
-                           f"multiple of 8 (got {tuple(t.shape)} {t.dtype}, strides {tuple(t.stride())})")
-    _C.check_shape("w_q", w_q, N, K // 2)
-    _C.check_shape("a_scale", a_scale, M, K // 32)
-    _C.check_shape("w_scale", w_scale, N, K // 32)
-    _C.check_shape("b", b, N, R)
-    return _launch16("wanq_gemm_mx4_lowrank", (_C.ptr(a_q), _C.ptr(w_q), _C.ptr(a_scale), _C.ptr(w_scale), _C.ptr(t), int(t.stride(0)),
-                                               _C.ptr(b), _C.dt(b), int(R)),
-                     (a_q, w_q, a_scale, w_scale, t, b), bias, out_dtype or torch.bfloat16, gelu, gate, residual, out, M, N, K)
+    if why is None and (t.dtype != b.dtype or tuple(t.shape) != (M, R) or t.stride(1) != 1 or t.stride(0) < R or t.stride(0) % 8):
+        why = (f"t must be [{M}, {R}] of b's dtype with unit column stride and a row pitch that is a multiple of 8 (got {tuple(t.shape)} "
+               f"{t.dtype}, strides {tuple(t.stride())})")
+    return _mx_launch("mx4_lowrank_linear", "wanq_gemm_mx4_lowrank", (a_q, w_q, a_scale, w_scale), M, N, K, K // 2, K // 2, why,
+                      (_C.ptr(t), int(t.stride(0)), _C.ptr(b), _C.dt(b), int(R)), (("t", t, None), ("b", b, (N, R))), bias, out_dtype, gelu,
+                      gate, residual, out)
 
 
 def mx4_lowrank_refusal(M, N, K, R):
@@ -647,22 +633,12 @@ def mx6_linear(a_q, w_q, a_scale, w_scale, w_fmt="mxfp6_e2m3fn", bias=None, out_
     rules (K % 128 == 0, N % 8 == 0) and determinism are `mx_linear`'s.  Not counted by the int8 timer (`set_timer`)."""
     if w_fmt not in _C.MX6_FMT:
         raise RuntimeError(f"mx6_linear: w_fmt={w_fmt!r} must be one of {tuple(_C.MX6_FMT)}")
-    for name, t in (("a_q", a_q), ("w_q", w_q), ("a_scale", a_scale), ("w_scale", w_scale)):
-        if t is None:
-            raise RuntimeError(f"mx6_linear: {name} must be given")
-        _check_mat(name, t, torch.uint8)
+    M, N = _mx_mats("mx6_linear", a_q, w_q, a_scale, w_scale)
     if a_q.shape[1] % 3:
         raise RuntimeError(f"mx6_linear: a_q has {a_q.shape[1]} bytes per row, not 3 K / 4 of any K")
-    M, K = a_q.shape[0], a_q.shape[1] // 3 * 4
-    N = w_q.shape[0]
-    why = mx6_linear_refusal(M, N, K, w_fmt)
-    if why is not None:
-        raise RuntimeError(f"mx6_linear: {why}")
-    _C.check_shape("w_q", w_q, N, K // 2 if _C.MX6_FMT[w_fmt] == 1 else K // 4 * 3)
-    _C.check_shape("a_scale", a_scale, M, K // 32)
-    _C.check_shape("w_scale", w_scale, N, K // 32)
-    return _launch16("wanq_gemm_mx6", (_C.ptr(a_q), _C.ptr(w_q), _C.ptr(a_scale), _C.ptr(w_scale), _C.MX6_FMT[w_fmt]),
-                     (a_q, w_q, a_scale, w_scale), bias, out_dtype or torch.bfloat16, gelu, gate, residual, out, M, N, K)
+    K = a_q.shape[1] // 3 * 4
+    return _mx_launch("mx6_linear", "wanq_gemm_mx6", (a_q, w_q, a_scale, w_scale), M, N, K, K // 4 * 3, K // 32 * _C.MX_BLOCK_BYTES[w_fmt],
+                      mx6_linear_refusal(M, N, K, w_fmt), (_C.MX6_FMT[w_fmt],), (), bias, out_dtype, gelu, gate, residual, out)
 
 
 def mx6_linear_refusal(M, N, K, w_fmt="mxfp6_e2m3fn"):

@@ -7,19 +7,53 @@ Simulation mode = the qdiff drop-in layers inside the unmodified WanAttentionBlo
 kernel mode = every block replaced by WanAttentionBlockWithHipKernel (fused producers / epilogues around the GEMMs)."""
 import logging
 import math
+from types import SimpleNamespace
 
 import torch
 import torch.nn as nn
 
+from qdiff.base.base_quantizer import mx_fmt_code, mx_pair
 from qdiff.base.quant_layer import QuantizedLinear
 from qdiff.base.quant_model import QuantModel
-from viditq_extension import _C
 
 from .modules.model import WanModel
 from .quant_wanx_hip import WanAttentionBlockWithHipKernel, _FpSrc
 from . import ops
 
 logger = logging.getLogger(__name__)
+
+
+def _mx_state(layer):
+    """What decides the optional MX records of a layer in the integer checkpoint, read off a QuantizedLinear (the writer) or off the
+    kernel-mode layer built from it (the loader): its row of MX_PAIRS (None: not an MX layer), the rotation, n8 and the channel order."""
+    sim = isinstance(layer, QuantizedLinear)
+    return SimpleNamespace(pair=mx_pair(layer.mx, layer.mx_act if sim else getattr(layer, "a_fmt", None)),
+                           had32=bool(layer.mx_had32 if sim else getattr(layer, "had32", False)),
+                           n8=layer.mx_n8 if sim else getattr(layer, "n8", None), perm=getattr(layer, "mx_perm", None))
+
+
+def _said_fmt(v):
+    return "no mx_fmt (not an MXFP6 layer)" if v is None else f"mx_fmt {v}"
+
+
+# The optional MX records, one row each: key; present when; value (of an _mx_state); what the loader compares between the file's record
+# and the layer's (None: the record is only loaded), each reduced to a plain value with None / False for "absent"; the mismatch text.
+#   mx_had32: the codes were made behind the block Hadamard rotation (a file without it: unrotated)
+#   mx_fmt:   the (weight, act) format codes of an e2m3-activation layer; no other layer has the key
+#   mx_perm, mx_n8: mx.outlier_channels, the channel order and the count of the mixed codes; the order is loaded, the count compared
+_MX_RECORDS = (
+    ("mx_had32", lambda s: s.had32, lambda s: torch.ones(1, dtype=torch.uint8), lambda v: v is not None and bool(v.reshape(-1)[0] != 0),
+     lambda f, o: f"holds codes quantised {'behind' if f else 'without'} the block Hadamard rotation (mx.block_hadamard) and the model's "
+                  f"layer was built {'with' if o else 'without'} it: the two are not interchangeable"),
+    ("mx_fmt", lambda s: s.pair is not None and s.pair.act_form == "mxfp6",
+     lambda s: torch.tensor([mx_fmt_code(s.pair.w_fmt), mx_fmt_code(s.pair.a_fmt)], dtype=torch.uint8),
+     lambda v: None if v is None else v.reshape(-1).tolist(),
+     lambda f, o: f"was saved with {_said_fmt(f)} and the model's layer was built with {_said_fmt(o)} ((weight, act) codes of "
+                  "wanq_gemm_mx6: 2 = mxfp6_e2m3fn, 1 = mxfp4_e2m1)"),
+    ("mx_perm", lambda s: s.n8 is not None, lambda s: s.perm.detach().to(torch.int32).cpu().clone(), None, None),
+    ("mx_n8", lambda s: s.n8 is not None, lambda s: torch.tensor([s.n8], dtype=torch.int32), lambda v: None if v is None else int(v.reshape(-1)[0]),
+     lambda f, o: f"was saved with mx.outlier_channels {f} and the model's layer was built with {o}"),
+)
 
 
 class QuantWanModel(WanModel, QuantModel):
@@ -119,13 +153,8 @@ class QuantWanModel(WanModel, QuantModel):
                                                    else wq.zero_point.reshape(-1).float().clone())
                     if mod.bias is not None:
                         sd[name + ".bias"] = mod.bias.detach().float().clone()
-                    if mod.mx_act == "mxfp6_e2m3fn":  # W6A6 / W4A6: the (weight, act) format codes of wanq_gemm_mx6, recorded with the layer
-                        sd[name + ".mx_fmt"] = torch.tensor([_C.MX6_FMT[mod.mx], _C.MX6_FMT[mod.mx_act]], dtype=torch.uint8)
-                    if mod.mx_had32:  # codes made behind the block Hadamard rotation (mx.block_hadamard): recorded with the layer
-                        sd[name + ".mx_had32"] = torch.ones(1, dtype=torch.uint8)
-                    if mod.mx_n8 is not None:  # mx.outlier_channels: the channel order and the count, recorded with the mixed codes
-                        sd[name + ".mx_perm"] = mod.mx_perm.detach().to(torch.int32).cpu().clone()
-                        sd[name + ".mx_n8"] = torch.tensor([mod.mx_n8], dtype=torch.int32)
+                    state = _mx_state(mod)
+                    sd.update({f"{name}.{k}": value(state) for k, when, value, _, _ in _MX_RECORDS if when(state)})
                     if mod.low_rank is not None:  # the LoRC factors, fp32 [Rp, K] / [N, Rp] (an adapter is not part of the weights)
                         sd[name + ".lr_a"] = mod.lr_a.detach().float().clone()
                         sd[name + ".lr_b"] = mod.lr_b.detach().float().clone()
@@ -218,33 +247,18 @@ class QuantWanModel(WanModel, QuantModel):
                     if weight_only and f"{base}.scale_weight" in sd and sd[f"{base}.scale_weight"].dtype == torch.float16:
                         raise NotImplementedError(f"{load_path}: {base} is a weight-only layer and the file is in the reference's "
                                                   "int_weight.pt format, which is W8A8 only (save with reference_format=False)")
-                    # an MX layer's codes are those of one rotation setting: `<name>.mx_had32` says the file's (absent: unrotated)
-                    rec = sd.get(f"{base}.mx_had32", None)
-                    had_file, had_layer = rec is not None and bool(rec.reshape(-1)[0] != 0), bool(getattr(lin, "had32", False))
-                    if had_file != had_layer:
-                        raise ValueError(f"{load_path}: {base} holds codes quantised {'behind' if had_file else 'without'} the block "
-                                         f"Hadamard rotation (mx.block_hadamard) and the model's layer was built "
-                                         f"{'with' if had_layer else 'without'} it: the two are not interchangeable")
-                    # an e2m3-activation layer records its (weight, act) formats in `<name>.mx_fmt`; no other layer has the key
-                    rec, own = sd.get(f"{base}.mx_fmt", None), getattr(lin, "mx_fmt", None)
-                    if (rec is None) != (own is None) or (rec is not None and rec.reshape(-1).tolist() != own.reshape(-1).tolist()):
-                        said = lambda v: "no mx_fmt (not an MXFP6 layer)" if v is None else f"mx_fmt {v.reshape(-1).tolist()}"  # noqa: E731
-                        raise ValueError(f"{load_path}: {base} was saved with {said(rec)} and the model's layer was built with "
-                                         f"{said(own)} ((weight, act) codes of wanq_gemm_mx6: 2 = mxfp6_e2m3fn, 1 = mxfp4_e2m1)")
-                    # an outlier-channel layer's codes are those of one (n8, order): the file says its n8, the order is loaded
-                    n8_file, n8_layer = sd.get(f"{base}.mx_n8", None), getattr(lin, "n8", None)
-                    n8_file = None if n8_file is None else int(n8_file.reshape(-1)[0])
-                    if n8_file != n8_layer:
-                        raise ValueError(f"{load_path}: {base} was saved with mx.outlier_channels {n8_file} and the model's layer was "
-                                         f"built with {n8_layer}")
+                    state = _mx_state(lin)
+                    for k, when, value, plain, text in _MX_RECORDS:
+                        if plain is None:
+                            continue
+                        in_file, in_layer = plain(sd.get(f"{base}.{k}", None)), plain(value(state) if when(state) else None)
+                        if in_file != in_layer:
+                            raise ValueError(f"{load_path}: {base} {text(in_file, in_layer)}")
                     for buf, k, required in (("weight", "weight", True), ("scale_weight", "scale_weight", True),
-                                             ("mx_fmt", "mx_fmt", own is not None),
                                              ("zp_weight", "zp_weight", lin.zp_weight is not None),
                                              ("bias", "bias", lin.bias is not None),
                                              ("act_premul", "act_premul", lin.act_premul is not None),
-                                             ("mx_had32", "mx_had32", had_layer),
-                                             ("mx_perm", "mx_perm", getattr(lin, "n8", None) is not None),
-                                             ("mx_n8", "mx_n8", getattr(lin, "n8", None) is not None),
+                                             *((k, k, when(state)) for k, when, _, _, _ in _MX_RECORDS),
                                              ("lr_a", "lr_a", getattr(lin, "lr_a", None) is not None),
                                              ("lr_b", "lr_b", getattr(lin, "lr_b", None) is not None)):
                         dst = getattr(lin, buf, None)

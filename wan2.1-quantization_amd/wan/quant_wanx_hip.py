@@ -15,8 +15,9 @@ WanSelfAttentionWithCudaKernel :331-474, WANT2VCrossAttentionWithCudaKernel :477
 import torch
 import torch.nn as nn
 
+from qdiff.base.base_quantizer import MX_PAIRS, mx_fmt_code, mx_pair
 from qdiff.base.low_rank import LowRankBranch, padded_rank
-from viditq_extension import _C, fused, qgemm
+from viditq_extension import fused, qgemm
 
 from . import ops
 from .modules.model import WanModel
@@ -387,59 +388,51 @@ class HipLinearFp8(_HipLinearCodes):
 
 
 class HipLinearMx(LowRankBranch, _HipLinearCodes):
-    """An OCP MX Linear (`format: mxfp8_e4m3` activations against `mxfp8_e4m3` / `mxfp4_e2m1` weights, or with `a_fmt` "mxfp4_e2m1"
-    the W4A4 pair): `weight` uint8 [N, K] e4m3 bytes or [N, K / 2] packed e2m1 nibbles, `scale_weight` uint8 [N, K / 32] E8M0 bytes,
-    both from wanq_quant_rows_mx; `bias` fp32.  Its input is the block's activation quantised per block of 32 channels by the same
-    entry (codes + scale bytes), and the product is qgemm.mx_linear, or qgemm.mx4_linear for e2m1 activations (csrc/gemm_mx.hip),
-    with GELU and gate + residual in its epilogue.  `had32` (W4A4 only, the config's `mx.block_hadamard`): the weight codes were
-    made behind the block Hadamard rotation and the input is quantised behind it too (activation form "mxfp4_h32"); the layer then
-    holds the one-element uint8 buffer `mx_had32`, which travels with its codes in the integer checkpoint.  `a_fmt` "mxfp6_e2m3fn"
-    (W6A6 / W4A6): `weight` uint8 [N, 3 K / 4] packed e2m3 codes (w_fmt "mxfp6_e2m3fn", from wanq_quant_rows_mx6) or the packed e2m1
-    nibbles, the input quantised to e2m3 (activation form "mxfp6"), the product qgemm.mx6_linear; the layer then holds the uint8
-    buffer `mx_fmt` = (w_fmt code, a_fmt code), which records the formats in the integer checkpoint.
-    With a `low_rank` (W4A4 only, the config's `weight.low_rank`) the buffers `lr_a` [Rp, K] / `lr_b` [N, Rp] hold the LoRC factors in
-    `act_dtype` (qdiff/base/low_rank.py), `set_low_rank` attaches a user adapter behind them, the input comes from the source's
-    `project` -- the quantiser and the down-projection t = x A16^T in one pass (fused.quant_rows_mxfp4_project), one launch for all
-    consumers of the source -- and the product is qgemm.mx4_lowrank_linear: the branch is summed in the GEMM's own accumulators.
-    Under --dit_fsdp the factors are replicated (`sharded` names the codes and the scale bytes only).
-    With `n8` (W4A4 only, the config's `mx.outlier_channels`) the layer holds the int32 buffer `mx_perm` [K], its channel order, and
-    `mx_n8`; `weight` is uint8 [N, n8 + (K - n8) / 2] in the mixed MX row format (include/wanq_hip.h), the input is made by
-    fused.quant_rows_mx_mixed in the same order (activation form "mxmix<n8>", one launch for every consumer of the source; consumers
-    under one form must hold the same order) and the product is qgemm.mx_mixed_linear (csrc/gemm_mx_mixed.hip).  Both buffers travel
-    with the codes in the integer checkpoint and are replicated under --dit_fsdp."""
+    """An OCP MX Linear of one of the built (weight format, activation format) pairs -- the rows of qdiff/base/base_quantizer.py's
+    MX_PAIRS, which say its row widths, its qgemm entry, its activation form and the options it admits.  `weight` uint8 [N, K / 32 *
+    the format's block bytes] and `scale_weight` uint8 [N, K / 32] E8M0 bytes, both as fused.quant_rows_mx writes them; `bias` fp32.  Its
+    input is the block's activation quantised by the same entry (one copy per activation form for every consumer), and the product is
+    the pair's entry with GELU and gate + residual in its epilogue.  What a layer holds beyond that:
+    `had32` (the config's `mx.block_hadamard`): the weight codes were made behind the block Hadamard rotation and the input is
+    quantised behind it too (activation form + "_h32"); the one-element uint8 buffer `mx_had32` travels with the codes in the integer
+    checkpoint.  e2m3 activations: the uint8 buffer `mx_fmt` = (w_fmt code, a_fmt code) records the formats there.
+    `low_rank` (the config's `weight.low_rank`): the buffers `lr_a` [Rp, K] / `lr_b` [N, Rp] hold the LoRC factors in `act_dtype`
+    (qdiff/base/low_rank.py), `set_low_rank` attaches a user adapter behind them, the input comes from the source's `project` -- the
+    quantiser and the down-projection t = x A16^T in one pass (fused.quant_rows_mxfp4_project), one launch for all consumers of the
+    source -- and the product is qgemm.mx4_lowrank_linear: the branch is summed in the GEMM's own accumulators.  Under --dit_fsdp the
+    factors are replicated (`sharded` names the codes and the scale bytes only).
+    `n8` (the config's `mx.outlier_channels`): the int32 buffer `mx_perm` [K], its channel order, and `mx_n8`; `weight` is uint8
+    [N, n8 + (K - n8) / 2] in the mixed MX row format (include/wanq_hip.h), the input is made by fused.quant_rows_mx_mixed in the same
+    order (activation form "mxmix<n8>", one launch for every consumer of the source; consumers under one form must hold the same
+    order) and the product is qgemm.mx_mixed_linear (csrc/gemm_mx_mixed.hip).  Both buffers travel with the codes in the integer
+    checkpoint and are replicated under --dit_fsdp."""
     act_form = act_key = "mxfp8"
     sharded = ("weight", "scale_weight")   # the scale bytes are a thirty-second or a sixteenth of the weight's
 
     def __init__(self, in_features, out_features, bias=True, w_fmt="mxfp8_e4m3", name="linear", a_fmt="mxfp8_e4m3", had32=False,
                  low_rank=None, act_dtype=torch.bfloat16, n8=None):
         self.name = name
-        a4, a6, w6 = a_fmt == "mxfp4_e2m1", a_fmt == "mxfp6_e2m3fn", w_fmt == "mxfp6_e2m3fn"
-        if a_fmt not in ("mxfp8_e4m3", "mxfp4_e2m1", "mxfp6_e2m3fn") or (a4 and w_fmt != "mxfp4_e2m1") or (had32 and not a4) or \
-                (a6 and w_fmt not in ("mxfp6_e2m3fn", "mxfp4_e2m1")) or (w6 and not a6):
+        pair = mx_pair(w_fmt, a_fmt)
+        if pair is None or (had32 and not pair.had32):
             raise NotImplementedError(f"{name}: no MX GEMM takes weight {w_fmt} against act {a_fmt}" + (" behind the block rotation" if had32 else ""))
-        if n8 is not None and (not a4 or had32 or low_rank):
+        if n8 is not None and (not pair.n8 or had32 or low_rank):
             raise NotImplementedError(f"{name}: mx.outlier_channels goes with the plain W4A4 pair only (no block rotation, no low-rank "
                                       f"branch; weight {w_fmt} against act {a_fmt})")
-        why = qgemm.mx6_linear_refusal(1, out_features, in_features, w_fmt) if a6 else \
-            qgemm.mx_mixed_linear_refusal(1, out_features, in_features, n8) if n8 is not None else \
-            qgemm.mx4_linear_refusal(1, out_features, in_features) if a4 else qgemm.mx_linear_refusal(1, out_features, in_features, w_fmt)
-        super().__init__(in_features, out_features, bias, w_fmt, why,
-                         n8 + (in_features - n8) // 2 if n8 is not None else
-                         in_features // 2 if w_fmt == "mxfp4_e2m1" else in_features // 4 * 3 if w6 else in_features,
+        # the entry this layer calls (by name: read from qgemm at each call) and what it takes between the scales and the bias
+        self._gemm, self._lead = ("mx_mixed_linear", (n8,)) if n8 is not None else (pair.gemm, (w_fmt,) if pair.takes_w_fmt else ())
+        super().__init__(in_features, out_features, bias, w_fmt, getattr(qgemm, self._gemm + "_refusal")(1, out_features, in_features, *self._lead),
+                         n8 + (in_features - n8) // 2 if n8 is not None else in_features // 32 * pair.w_bytes,
                          (out_features, in_features // 32), torch.uint8, name)
         self.mx, self.a_fmt, self.had32, self.n8 = w_fmt, a_fmt, bool(had32), n8
-        if a4:
-            self.act_form = self.act_key = "mxfp4_h32" if had32 else "mxfp4"
+        self.act_form = self.act_key = f"mxmix{n8}" if n8 is not None else pair.act_form + ("_h32" if had32 else "")
         if n8 is not None:
-            self.act_form = self.act_key = f"mxmix{n8}"
             self.register_buffer("mx_perm", torch.arange(in_features, dtype=torch.int32))
             self.register_buffer("mx_n8", torch.tensor([n8], dtype=torch.int32))
-        if a6:
-            self.act_form = self.act_key = "mxfp6"
-            self.register_buffer("mx_fmt", torch.tensor([_C.MX6_FMT[w_fmt], _C.MX6_FMT[a_fmt]], dtype=torch.uint8))
+        if pair.act_form == "mxfp6":
+            self.register_buffer("mx_fmt", torch.tensor([mx_fmt_code(w_fmt), mx_fmt_code(a_fmt)], dtype=torch.uint8))
         if had32:
             self.register_buffer("mx_had32", torch.ones(1, dtype=torch.uint8))
-        if low_rank and not a4:
+        if low_rank and not pair.low_rank:
             raise NotImplementedError(f"{name}: weight.low_rank goes with the W4A4 pair only (weight {w_fmt} against act {a_fmt})")
         if act_dtype not in (torch.bfloat16, torch.float16):
             raise ValueError(f"{name}: the low-rank branch takes bf16 or fp16 factors (act_dtype {act_dtype})")
@@ -449,7 +442,7 @@ class HipLinearMx(LowRankBranch, _HipLinearCodes):
         self.register_buffer("lr_b", torch.zeros(out_features, rp, dtype=act_dtype) if low_rank else None)
 
     def _refuse_adapter(self):
-        if self.a_fmt != "mxfp4_e2m1":
+        if not mx_pair(self.mx, self.a_fmt).low_rank:
             raise NotImplementedError(f"{self._lr_name()}: set_low_rank needs the W4A4 pair (weight {self.mx} against act {self.a_fmt}): "
                                       "only wanq_gemm_mx4_lowrank sums a low-rank branch")
 
@@ -491,17 +484,8 @@ class HipLinearMx(LowRankBranch, _HipLinearCodes):
             _, b16 = self.low_rank_operands(self.act_dtype, a_q.device)
             return qgemm.mx4_lowrank_linear(a_q, self.weight, a_scale, self.scale_weight, t, b16, self.bias, out_dtype, gelu=gelu,
                                             gate=gate, residual=residual, out=out)
-        if self.n8 is not None:
-            return qgemm.mx_mixed_linear(a_q, self.weight, a_scale, self.scale_weight, self.n8, self.bias, out_dtype, gelu=gelu,
-                                         gate=gate, residual=residual, out=out)
-        if self.a_fmt == "mxfp6_e2m3fn":
-            return qgemm.mx6_linear(a_q, self.weight, a_scale, self.scale_weight, self.mx, self.bias, out_dtype, gelu=gelu, gate=gate,
-                                    residual=residual, out=out)
-        if self.a_fmt == "mxfp4_e2m1":
-            return qgemm.mx4_linear(a_q, self.weight, a_scale, self.scale_weight, self.bias, out_dtype, gelu=gelu, gate=gate,
-                                    residual=residual, out=out)
-        return qgemm.mx_linear(a_q, self.weight, a_scale, self.scale_weight, self.mx, self.bias, out_dtype, gelu=gelu, gate=gate,
-                               residual=residual, out=out)
+        return getattr(qgemm, self._gemm)(a_q, self.weight, a_scale, self.scale_weight, *self._lead, self.bias, out_dtype, gelu=gelu,
+                                          gate=gate, residual=residual, out=out)
 
 
 # QuantizedLinear.kind -> the layer class that takes it over ("fp": the layer's FP module, below)
@@ -526,9 +510,11 @@ def _to_hip_linear(lin, n_bits, sym, act_dtype, fp_gemm="torch", name="linear"):
     return HipLinearW8A8.from_float(lin.weight.data, lin.bias.data if lin.bias is not None else None, n_bits, sym)
 
 
-# activation form -> the fused row quantiser that makes it, (codes, scales) = f(rows, gelu=); a new form adds its entry here
-_ROW_QUANTISERS = {"fp8": "quant_rows_fp8", "mxfp8": "quant_rows_mx", "mxfp4": "quant_rows_mxfp4", "mxfp4_h32": "quant_rows_mxfp4_h32",
-                   "mxfp6": "quant_rows_mxfp6"}
+# activation form -> the fused row quantiser that makes it and its arguments, (codes, scales) = f(rows, gelu=, **arguments): fp8, and
+# the form of every MX pair (base_quantizer.MX_PAIRS), plain and -- where the pair admits it -- behind the block rotation
+_ROW_QUANTISERS = {"fp8": ("quant_rows_fp8", {}),
+                   **{p.act_form: ("quant_rows_mx", {"fmt": p.a_fmt}) for p in MX_PAIRS.values()},
+                   **{p.act_form + "_h32": ("quant_rows_mx", {"fmt": p.a_fmt, "had32": True}) for p in MX_PAIRS.values() if p.had32}}
 
 
 class _Src:
@@ -539,7 +525,8 @@ class _Src:
         HipLinearMx: e4m3, packed e2m3 or packed e2m1 codes + E8M0 scale bytes), quantised from what `_plain_row` hands over."""
         if form not in self.cache:
             x, gelu = self._plain_row()
-            self.cache[form] = getattr(fused, _ROW_QUANTISERS[form])(x, gelu=gelu)
+            name, args = _ROW_QUANTISERS[form]
+            self.cache[form] = getattr(fused, name)(x, gelu=gelu, **args)
         return self.cache[form]
 
     def rows_mixed(self, lin):
