@@ -113,6 +113,26 @@ int wanq_quant_rows_mx(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8
 int wanq_quant_rows_mx_had32(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int fmt, int act,
                              void* stream);
 
+/* The MXFP4 (e2m1) row quantiser under the block-scale rule `search` (config `block_scale: search`): wanq_quant_rows_mx with fmt
+ * WANQ_MX_E2M1 -- with had32 = 1 wanq_quant_rows_mx_had32 -- except for the choice of each block's byte.  OCP's rule s0 = clamp(E(amax)
+ * - 2, 0, 254) puts the block maximum in [4, 8) and e2m1 ends at 6, so (6, 8) clips; s0 + 1 puts it in [2, 4), where nothing clips and
+ * the small elements get twice the step.  Both bytes are legal MXFP4 and every GEMM reads the result unchanged.  For a candidate s:
+ *   t_i  = x_i 2^(127 - s)                          exact (x after the optional GELU and rotation, in that order)
+ *   c_i  = the e2m1 code of clamp(t_i, -6, 6)       wanq_quant_rows_mx's rounding: the seven midpoints, ties to the even code
+ *   d_i  = |t_i| - |value(c_i)|                     exact in fp32
+ *   e(s) = sum_i d_i^2  in fp32, ONE order: each square rounded on its own (no fused multiply-add), then a butterfly tree over the
+ *          block's 32 elements with h = 1, 2, 4, 8, 16 -- at step h the partial sums at i and i + h (bit h of i clear) are added.
+ *          That is: adjacent pairs are added, five times.
+ * The block takes s0 + 1 exactly when 4 e(s0 + 1) < e(s0) in fp32 (the factor brings both to the units of s0; a tie keeps s0), else
+ * s0.  s0 is kept without a search, and q and scale_u8 are wanq_quant_rows_mx's bit for bit, for an all-zero block, for a block whose
+ * maximum is infinite, and for s0 = 254 (a guard that can never fire: with emax = 2 the byte is at most 253, for an infinite maximum,
+ * so no test builds it).  A NaN element makes both sums NaN and the comparison false: s0.
+ * q: [rows, cols / 2] packed e2m1 nibbles, scale_u8: uint8 [rows, cols / 32]; arguments, alignment and refusals as wanq_quant_rows_mx,
+ * and had32 must be 0 or 1.  One pass over x; a row's bytes do not depend on rows or on the row's place in the launch.
+ * Bit-identical to the host expression mx_quant_rows_host(fmt "mxfp4_e2m1", search=True).  No reference counterpart. */
+int wanq_quant_rows_mx4_search(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int act, int had32,
+                               void* stream);
+
 /* The MXFP4 (e2m1) row quantiser and, in the same pass over x, the down-projection of a 16-bit low-rank branch (csrc/quant_project.hip;
  * the producer of wanq_gemm_mx4_lowrank):
  *   q, scale_u8   what wanq_quant_rows_mx (fmt WANQ_MX_E2M1) writes for the same x and act -- with had32 = 1 what

@@ -420,6 +420,43 @@ __global__ __launch_bounds__(256) void quant_rows_mx_kernel(const MxRowParams p)
   }
 }
 
+// The e2m1 quantiser under the block-scale rule `search` (wanq_quant_rows_mx4_search; the rule: mx_block.h).  The frame, the ladder,
+// the GELU and the rotation of quant_rows_mx_kernel, and still one pass over x with no LDS and no barrier: per chunk slot a lane scales
+// its eight elements by both candidate bytes (two exact v_ldexp_f32), rounds each to e2m1 by one magic-number addition that leaves the
+// code in the sum's low bits and the residual one subtraction away, and keeps both packed code dwords and both error sums in
+// registers.  The two 32-wide error sums take the quad exchanges of the block maximum (two DPP steps each), so all four lanes of the
+// quad hold the same two sums and make the same choice without a broadcast; then one dword store of the winning nibbles per lane and
+// one byte from the quad's first lane, as in the plain kernel.  The exchanges run before the `ok` test: a quad is in the row or past it
+// as a whole, and a slot past the row end is a zero block.
+template <int WPR, int NCH, bool HAD>
+__global__ __launch_bounds__(256) void quant_rows_mx4_search_kernel(const MxRowParams p) {
+  RowFrame<WPR, NCH> f;
+  if (f.surplus(p.rows)) return;
+  const int C = p.cols;
+  const int64_t rbase = f.row * (int64_t)C;
+
+  float v[NCH][8];
+  bool ok[NCH];
+  f.load(p.x, p.x_dtype, rbase, C, v, ok);
+  if (p.act == 1) {
+#pragma unroll
+    for (int i = 0; i < NCH; ++i)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[i][j] = gelu_tanh_fast_f32(v[i][j]);  // (a slot past the row end stays 0)
+  }
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+    if constexpr (HAD) mx_block_hadamard<MxQuadLanes>(v[i], f.lane);
+    const float m = mx_block_amax<MxQuadLanes>(v[i]);
+    uint32_t w;
+    const int s = mx4_block_search<MxQuadLanes>(v[i], m, w);
+    if (!ok[i]) continue;
+    const int col = f.col(i);
+    *reinterpret_cast<uint32_t*>(p.q + ((rbase + col) >> 1)) = w;
+    if ((f.lane & 3) == 0) p.scale[((rbase + col) >> 5)] = (uint8_t)s;
+  }
+}
+
 // x * premul (-> LayerNorm + modulate first when `ln`) -> fp output and / or int8 quantise: the transform entry points of
 // rotate.hip with had_k == 0 (channel scale without rotation: SmoothQuant, Q/smooth_quant/sq_quant_layer.py:52-60).
 int premul_quant_rows(bool ln, const void* x, int x_dtype, const void* gamma, const void* mshift, const void* mscale,
@@ -511,6 +548,26 @@ extern "C" int wanq_quant_rows_mx(const void* x, int x_dtype, uint8_t* q, uint8_
 extern "C" int wanq_quant_rows_mx_had32(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int fmt,
                                         int act, void* stream) {
   return quant_rows_mx_entry<true>("wanq_quant_rows_mx_had32", x, x_dtype, q, scale_u8, rows, cols, fmt, act, stream);
+}
+
+extern "C" int wanq_quant_rows_mx4_search(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int act,
+                                          int had32, void* stream) {
+  const char* what = "wanq_quant_rows_mx4_search";
+  WANQ_REQUIRE(x && q && scale_u8, WANQ_E_ARG, "%s: x, q and scale_u8 must be non-NULL", what);
+  WANQ_REQUIRE(is_fp(x_dtype), WANQ_E_ARG, "%s: bad x dtype %d", what, x_dtype);
+  WANQ_REQUIRE(act == 0 || act == 1, WANQ_E_ARG, "%s: act must be 0 or 1", what);
+  WANQ_REQUIRE(had32 == 0 || had32 == 1, WANQ_E_ARG, "%s: had32 must be 0 or 1", what);
+  if (int e = check_rows_cols(what, rows, cols)) return e;
+  WANQ_REQUIRE(cols % 32 == 0, WANQ_E_SHAPE, "%s: cols=%d must be a multiple of 32 (one scale per block of 32)", what, cols);
+  WANQ_REQUIRE((reinterpret_cast<uintptr_t>(q) & 15) == 0, WANQ_E_ARG, "%s: q must be 16-byte aligned", what);
+  if (rows == 0) return WANQ_OK;
+  const MxRowParams p{x, x_dtype, q, scale_u8, rows, cols, act};
+  row_ladder(cols, rows, [&](auto wpr, auto nch, dim3 grid) {
+    constexpr int W = decltype(wpr)::value, NC = decltype(nch)::value;
+    if (had32) hipLaunchKernelGGL((quant_rows_mx4_search_kernel<W, NC, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((quant_rows_mx4_search_kernel<W, NC, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
+  });
+  return check_launch(what);
 }
 
 extern "C" int wanq_quant_rows_mx6(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int act,

@@ -342,17 +342,42 @@ def mx_hadamard32_host(x):
     return v.reshape(x.shape)
 
 
-def mx_quant_rows_host(x, fmt, gelu=False, had32=False):
+BLOCK_SCALES = ("floor", "search")   # the `block_scale` key of a `weight:` / `act:` section: OCP's rule (default), or the search below
+
+
+def _e2m1_mag(a):
+    """the e2m1 magnitude code of a >= 0 (float64): seven midpoints, ties to the even code"""
+    return ((a > 0.25).to(torch.uint8) + (a >= 0.75) + (a > 1.25) + (a >= 1.75) + (a > 2.5) + (a >= 3.5) + (a > 5.0)).to(torch.uint8)
+
+
+def mx4_block_err2_host(xb, s):
+    """e(s) of include/wanq_hip.h (wanq_quant_rows_mx4_search) for blocks xb [..., 32] fp32 and candidate bytes s [...]: t = x 2^(127 - s)
+    and d = |t| - |value(code)|, both exact in fp32; each d^2 rounded to fp32 on its own; then adjacent pairs added, five times, in
+    fp32 -- the butterfly tree h = 1, 2, 4, 8, 16 of the kernel's chunk sums and quad exchanges."""
+    t = (xb.double() * _pow2_f64(127 - s).unsqueeze(-1)).float().abs().double()
+    lut = torch.tensor(E2M1_VALUES, dtype=torch.float64, device=xb.device)
+    d = (t - lut[_e2m1_mag(t.clamp(max=6.0)).long()]).float()
+    q = d * d
+    while q.shape[-1] > 1:
+        q = q[..., 0::2] + q[..., 1::2]
+    return q[..., 0]
+
+
+def mx_quant_rows_host(x, fmt, gelu=False, had32=False, search=False):
     """(codes uint8, scale bytes uint8 [rows, cols / 32]) of the block quantiser, in torch on x's device.  Per block: amax, E = its
     biased fp32 exponent field, s = clamp(E - emax, 0, 254), c = rne(clamp(x 2^(127 - s), -max, max)).  The scaling is done in
     float64, where it is exact; the one rounding is the cast to e4m3fn (this torch build rounds to nearest even and keeps subnormals)
     or, for e2m1, the comparison against the seven midpoints with ties to the even code, or, for e2m3 (`mxfp6_e2m3fn`, include/wanq_hip.h:
     wanq_quant_rows_mx6), rne(|t| / q) with the binade's quantum q = 1/8 for |t| < 2, 1/4 for |t| < 4, else 1/2 -- the magnitude codes
     ascend with the value, so the code is that integer plus 0, 8 or 16 and the tie goes to the even code.  `had32`: the blocks go
-    through mx_hadamard32_host behind the GELU and in front of the block maximum (wanq_quant_rows_mx_had32; not for e2m3)."""
+    through mx_hadamard32_host behind the GELU and in front of the block maximum (wanq_quant_rows_mx_had32; not for e2m3).
+    `search` (e2m1 only; the config's `block_scale: search`, wanq_quant_rows_mx4_search): a block's byte is s or s + 1, s + 1 exactly
+    when 4 e(s + 1) < e(s) in fp32 with e = mx4_block_err2_host; s is kept for an all-zero block, a non-finite amax and s = 254."""
     emax, vmax, _ = _MX_SPEC[fmt]
     if had32 and fmt == MXFP6_FORMAT:
         raise ValueError(f"mx_quant_rows: {MXFP6_FORMAT} has no had32 form")
+    if search and fmt != MXFP4_FORMAT:
+        raise ValueError(f"mx_quant_rows: the block-scale search is built for {MXFP4_FORMAT} only (fmt={fmt!r})")
     x = x.float()
     if gelu:
         x = torch.nn.functional.gelu(x, approximate="tanh")
@@ -364,6 +389,9 @@ def mx_quant_rows_host(x, fmt, gelu=False, had32=False):
     xb = x.reshape(rows, cols // MX_BLOCK, MX_BLOCK)
     amax = xb.abs().amax(dim=-1).contiguous()
     s = (((amax.view(torch.int32) >> 23) & 0xff) - emax).clamp(0, 254)
+    if search:
+        up = (amax > 0) & torch.isfinite(amax) & (s < 254) & (4.0 * mx4_block_err2_host(xb, s + 1) < mx4_block_err2_host(xb, s))
+        s = s + up.to(s.dtype)
     t = (xb.double() * _pow2_f64(127 - s).unsqueeze(-1)).clamp(-vmax, vmax).reshape(rows, cols)
     if fmt == MXFP8_FORMAT:
         codes = t.float().to(torch.float8_e4m3fn).view(torch.uint8)
@@ -372,18 +400,18 @@ def mx_quant_rows_host(x, fmt, gelu=False, had32=False):
         mag = torch.where(a < 2, torch.round(a * 8), torch.where(a < 4, torch.round(a * 4) + 8, torch.round(a * 2) + 16))
         codes = mx_pack_e2m3(mag.to(torch.uint8) | (torch.signbit(t).to(torch.uint8) << 5))
     else:
-        a = t.abs()
-        mag = ((a > 0.25).to(torch.uint8) + (a >= 0.75) + (a > 1.25) + (a >= 1.75) + (a > 2.5) + (a >= 3.5) + (a > 5.0)).to(torch.uint8)
-        codes = mx_pack_e2m1(mag | (torch.signbit(t).to(torch.uint8) << 3))
+        codes = mx_pack_e2m1(_e2m1_mag(t.abs()) | (torch.signbit(t).to(torch.uint8) << 3))
     return codes, s.to(torch.uint8)
 
 
-def mx_quant_rows(x, fmt, gelu=False, had32=False):
-    """The block quantiser: on the GPU wanq_quant_rows_mx (`had32`: wanq_quant_rows_mx_had32), in host memory the host expression it is
-    bit-equal to."""
+def mx_quant_rows(x, fmt, gelu=False, had32=False, search=False):
+    """The block quantiser: on the GPU wanq_quant_rows_mx (`had32`: wanq_quant_rows_mx_had32; `search`: wanq_quant_rows_mx4_search), in
+    host memory the host expression it is bit-equal to."""
+    if search and fmt != MXFP4_FORMAT:
+        raise ValueError(f"mx_quant_rows: the block-scale search is built for {MXFP4_FORMAT} only (fmt={fmt!r})")
     if x.is_cuda:
-        return fused.quant_rows_mx(x.contiguous(), fmt, gelu, had32)
-    return mx_quant_rows_host(x, fmt, gelu, had32)
+        return fused.quant_rows_mx4_search(x.contiguous(), gelu, had32) if search else fused.quant_rows_mx(x.contiguous(), fmt, gelu, had32)
+    return mx_quant_rows_host(x, fmt, gelu, had32, search)
 
 
 def mx_decode(codes, scale_u8, fmt, dtype=torch.float32):
@@ -414,19 +442,23 @@ def mx_mixed_check(cols, perm, n8, what="mx_mixed"):
         raise ValueError(f"{what}: perm must be an integer permutation of range({cols})")
 
 
-def mx_quant_rows_mixed_host(x, perm, n8, gelu=False):
+def mx_quant_rows_mixed_host(x, perm, n8, gelu=False, search=False, quant=None):
     """(codes uint8 [rows, n8 + (cols - n8) / 2], scale bytes uint8 [rows, cols / 32]) of the mixed MX row format: nothing more than
     mx_quant_rows_host applied to the two column gathers, concatenated -- mxfp8_e4m3 of x[:, perm[:n8]], then mxfp4_e2m1 of
-    x[:, perm[n8:]].  The GELU is elementwise, so it is applied by the two calls."""
+    x[:, perm[n8:]].  The GELU is elementwise, so it is applied by the two calls.  `search`: the block-scale search on the MXFP4
+    gather (the MXFP8 one has no such rule).  `quant`: the row quantiser the gathers go through (default mx_quant_rows_host)."""
     mx_mixed_check(x.shape[-1], perm, n8, "mx_quant_rows_mixed")
-    p = perm.long()
-    c8, s8 = mx_quant_rows_host(x[:, p[:n8]], MXFP8_FORMAT, gelu)
-    c4, s4 = mx_quant_rows_host(x[:, p[n8:]], MXFP4_FORMAT, gelu)
+    p, quant = perm.long(), quant or mx_quant_rows_host
+    c8, s8 = quant(x[:, p[:n8]], MXFP8_FORMAT, gelu)
+    c4, s4 = quant(x[:, p[n8:]], MXFP4_FORMAT, gelu, search=search)
     return torch.cat((c8, c4), dim=1), torch.cat((s8, s4), dim=1)
 
 
-def mx_quant_rows_mixed(x, perm, n8, gelu=False):
-    """The mixed quantiser: on the GPU wanq_quant_rows_mx_mixed, in host memory the host expression it is bit-equal to."""
+def mx_quant_rows_mixed(x, perm, n8, gelu=False, search=False):
+    """The mixed quantiser: on the GPU wanq_quant_rows_mx_mixed, in host memory the host expression it is bit-equal to.  `search` (a
+    weight at conversion; the fused producer keeps OCP's rule): the same two gathers through mx_quant_rows on x's device."""
+    if search:
+        return mx_quant_rows_mixed_host(x, perm, n8, gelu, True, mx_quant_rows)
     if x.is_cuda:
         return fused.quant_rows_mx_mixed(x.contiguous(), perm.to(device=x.device, dtype=torch.int32), n8, gelu)
     return mx_quant_rows_mixed_host(x, perm, n8, gelu)
@@ -451,12 +483,15 @@ class MxQuantizer(BaseQuantizer):
         super().__init__(quant_config)
         self.format = quant_config["format"]
         self.had32, self.weight_side = bool(had32), bool(weight_side)
+        # the section's `block_scale: search` (mxfp4_e2m1 only; quant_layer.py refuses the rest by layer name): each block's byte is
+        # OCP's or the next one, by the smaller squared error (mx_quant_rows_host)
+        self.search = quant_config.get("block_scale", BLOCK_SCALES[0]) == "search"
         self.register_buffer("scale_u8", None, persistent=False)
 
     def codes_and_scale(self, x, gelu=False):
         if self.had32 and self.weight_side:
             x = x.float() * 0.03125
-        codes, s = mx_quant_rows(x, self.format, gelu, self.had32)
+        codes, s = mx_quant_rows(x, self.format, gelu, self.had32, self.search)
         self.scale_u8 = s
         self.delta = _pow2_f64(s.long() - 127).float()
         self.zero_point = torch.zeros_like(self.delta)

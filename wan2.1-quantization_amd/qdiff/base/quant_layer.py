@@ -17,8 +17,8 @@ from viditq_extension import fused, qgemm
 
 from ..config import ListConfig
 from ..quarot import quarot_utils
-from .base_quantizer import (FP8_FORMAT, MX_BLOCK, MX_FORMATS, MXFP4_FORMAT, MXFP6_FORMAT, MXFP8_FORMAT, DynamicQuantizer, Fp8Quantizer, MxQuantizer,
-                             StaticQuantizer, _pow2_f64, fp8_decode, mx_decode, mx_decode_mixed, mx_pair, mx_quant_rows_mixed)
+from .base_quantizer import (BLOCK_SCALES, FP8_FORMAT, MX_BLOCK, MX_FORMATS, MXFP4_FORMAT, MXFP6_FORMAT, MXFP8_FORMAT, DynamicQuantizer, Fp8Quantizer,
+                             MxQuantizer, StaticQuantizer, _pow2_f64, fp8_decode, mx_decode, mx_decode_mixed, mx_pair, mx_quant_rows_mixed)
 from .gptq import BLOCK_MAX, gptq_prepare, gptq_section, gptq_solve
 from .low_rank import RANK_MAX, LowRankBranch, fit_low_rank, padded_rank
 from .mixed_precision_quantizer import MixedPrecisionDynamicQuantizer, MixedPrecisionStaticQuantizer
@@ -50,6 +50,8 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         self.register_buffer("mx_perm", None, persistent=False)  # int32 [K], chosen from calibration statistics (select_outlier_perm)
         self.fp8 = self._checked_format(quant_config, module_name)
         self.mx_had32 = self._checked_mx_section(quant_config, module_name)  # `mx: {block_hadamard: True}`, W4A4 MX layers only
+        # `block_scale: search` of the `weight:` / `act:` section, each side for itself (mxfp4_e2m1 sides only)
+        self.mx_search_w, self.mx_search_act = self._checked_block_scale(quant_config, module_name)
         # (an MX layer's `weight.group_size: 32` names the format's own block: there is no integer group-wise path behind it)
         self.group_size = None if self.mx else self._checked_group_size(quant_config, module_name, fp_module.weight.device)
         self.gptq = self._checked_gptq(quant_config, module_name)  # the `gptq:` section when it names this layer (gptq.py), or None
@@ -215,6 +217,29 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
                              f"(in_features={K}, a multiple of 128)")
         return n8
 
+    def _checked_block_scale(self, quant_config, module_name):
+        """(weight side, act side): whether the section says `block_scale: search` -- each block of 32 takes OCP's scale byte or the
+        next one, whichever has the smaller squared error (base_quantizer.mx_quant_rows_host; wanq_quant_rows_mx4_search).  `floor`,
+        the default, is OCP's rule.  Accepted where that side's format is mxfp4_e2m1; on the act side not together with
+        `weight.low_rank` or `mx.outlier_channels`, whose fused producers quantise by OCP's rule (the weight side is quantised
+        offline and goes with both).  Everything else is refused by layer name."""
+        name = module_name or type(self).__name__
+        on = []
+        for sec, fmt in (("weight", self.mx), ("act", self.mx_act)):
+            q = quant_config.get(sec, None)
+            rule = BLOCK_SCALES[0] if q is None else q.get("block_scale", BLOCK_SCALES[0])
+            if rule not in BLOCK_SCALES:
+                raise ValueError(f"{name}: {sec}.block_scale={rule!r} must be one of {BLOCK_SCALES}")
+            if rule == "search" and fmt != MXFP4_FORMAT:
+                raise NotImplementedError(f"{name}: {sec}.block_scale: search is not supported with {sec}.format {fmt!r}: the block-scale "
+                                          f"search is built for {MXFP4_FORMAT}, where OCP's rule clips a quarter of the top binade")
+            on.append(rule == "search")
+        if on[1] and (self.low_rank is not None or self.mx_n8 is not None):
+            opt = "weight.low_rank" if self.low_rank is not None else "mx.outlier_channels"
+            raise NotImplementedError(f"{name}: act.block_scale: search with {opt} is not supported: that option's fused activation "
+                                      "producer quantises by OCP's rule (weight.block_scale: search goes with it)")
+        return tuple(on)
+
     def _checked_low_rank(self, quant_config, module_name):
         """`weight.low_rank` of the config (None: no low-rank branch), or the refusal of what has none, before any weight is
         quantised: the message names the layer and the key.  The branch has two hosts: the weight-only GEMM (a plain QuantizedLinear
@@ -287,6 +312,9 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         if self.mx_n8 is not None:
             raise NotImplementedError(f"{self._lr_name()}: set_low_rank with mx.outlier_channels is not supported: wanq_gemm_mx_mixed "
                                       "sums no low-rank branch")
+        if self.mx_search_act:
+            raise NotImplementedError(f"{self._lr_name()}: set_low_rank with act.block_scale: search is not supported: the fused "
+                                      "quantise + project producer quantises by OCP's rule")
         if self._mx_admits("low_rank") and not (self.uses_mask or self.uses_rotation):
             return
         if self.w_quantizer is None or self.a_quantizer is not None or self.fp8 or self.mx or self.uses_mask or self.uses_rotation \
@@ -353,7 +381,7 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         if self.mx_perm is None:
             self.weight.data, self.int_weight = w.detach().float(), None
             return
-        codes, s = mx_quant_rows_mixed(w.detach().float(), self.mx_perm, self.mx_n8)
+        codes, s = mx_quant_rows_mixed(w.detach().float(), self.mx_perm, self.mx_n8, search=self.mx_search_w)
         deq = torch.empty_like(w, dtype=torch.float32)
         deq[:, self.mx_perm.long()] = mx_decode_mixed(codes, s, self.mx_n8)
         self.weight.data, self.int_weight = deq, codes

@@ -21,6 +21,10 @@ and `mx.block_hadamard` with either are refused by layer name.
 `mx: {block_hadamard: True}`, a top-level section: both sides of every MX Linear are quantised behind the unnormalised 32-point
 Hadamard transform of each block of 32 input channels (wanq_quant_rows_mx_had32; the weight as w / 32, so the product is unchanged and
 nothing is rotated back).  Accepted only with the W4A4 pair; with any other pair, or without a format, refused by layer name.
+`block_scale: search` in the `weight:` and / or the `act:` section (default `floor`, OCP's rule), each side for itself, where that
+side's format is mxfp4_e2m1: every block of 32 takes OCP's scale byte or the next one, whichever has the smaller squared
+reconstruction error (wanq_quant_rows_mx4_search; the weight once at conversion).  Refused by layer name: another format on that
+side, another value, and `act.block_scale: search` together with `weight.low_rank` or `mx.outlier_channels`.
 `weight.low_rank: r` (a positive int, r <= min(N, K), at most 256 after padding to a multiple of 64): the best rank-r approximation
 of the quantisation error W - W_hat is kept in 16 bits beside the integer codes and added inside the weight-only GEMM
 (qdiff/base/low_rank.py, wanq_gemm_wq16_lowrank).  For a weight-only integer config only, per channel or with `group_size`: with an

@@ -63,6 +63,7 @@ PROTOTYPES = {
     "wanq_quant_rows_mx": [_vp, _i, _vp, _vp, _i64, _i, _i, _i, _vp],
     "wanq_gemm_mx": [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
     "wanq_quant_rows_mx_had32": [_vp, _i, _vp, _vp, _i64, _i, _i, _i, _vp],
+    "wanq_quant_rows_mx4_search": [_vp, _i, _vp, _vp, _i64, _i, _i, _i, _vp],
     "wanq_gemm_mx4": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
     "wanq_quant_rows_mx4_project": [_vp, _i, _vp, _vp, _vp, _i, _i, _vp, _i, _i64, _i, _i, _i, _vp],
     "wanq_gemm_mx4_lowrank": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],

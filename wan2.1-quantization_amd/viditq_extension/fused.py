@@ -120,6 +120,22 @@ def quant_rows_mx(x, fmt="mxfp8_e4m3", gelu=False, had32=False):
     return codes, scale
 
 
+def quant_rows_mx4_search(x, gelu=False, had32=False):
+    """`quant_rows_mx` to "mxfp4_e2m1" (with its `gelu` and `had32`) under the block-scale rule `search`
+    (wanq_quant_rows_mx4_search): every block takes OCP's byte s0 or s0 + 1, whichever has the smaller squared reconstruction error
+    (4 e(s0 + 1) < e(s0) in fp32, a tie keeps s0; include/wanq_hip.h states the sums' order).  -> (codes uint8 [rows, cols / 2], scale
+    bytes uint8 [rows, cols / 32]), the layout of `quant_rows_mx`: every consumer of MXFP4 rows reads them unchanged."""
+    rows, cols = _rows_cols("x", x)
+    if cols % 32:
+        raise RuntimeError(f"quant_rows_mx4_search: cols={cols} must be a multiple of 32")
+    codes = torch.empty((*x.shape[:-1], cols // 2), dtype=torch.uint8, device=x.device)
+    scale = torch.empty((*x.shape[:-1], cols // 32), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _C.call("wanq_quant_rows_mx4_search", _C.ptr(x), _C.dt(x), _C.ptr(codes), _C.ptr(scale), rows, cols, 1 if gelu else 0,
+                1 if had32 else 0, _C.stream())
+    return codes, scale
+
+
 def quant_rows_mx_mixed(x, perm, n8, gelu=False):
     """The row quantiser of the mixed MX format (wanq_quant_rows_mx_mixed, csrc/quant_mixed.hip): -> (codes uint8 [rows, n8 + (cols -
     n8) / 2], scale bytes uint8 [rows, cols / 32]).  The row is gathered into the channel order `perm` (int32 [cols], a permutation,

@@ -29,7 +29,8 @@ def _mx_state(layer):
     sim = isinstance(layer, QuantizedLinear)
     return SimpleNamespace(pair=mx_pair(layer.mx, layer.mx_act if sim else getattr(layer, "a_fmt", None)),
                            had32=bool(layer.mx_had32 if sim else getattr(layer, "had32", False)),
-                           n8=layer.mx_n8 if sim else getattr(layer, "n8", None), perm=getattr(layer, "mx_perm", None))
+                           n8=layer.mx_n8 if sim else getattr(layer, "n8", None), perm=getattr(layer, "mx_perm", None),
+                           search=bool(layer.mx_search_act if sim else getattr(layer, "search", False)))
 
 
 def _said_fmt(v):
@@ -39,12 +40,16 @@ def _said_fmt(v):
 # The optional MX records, one row each: key; present when; value (of an _mx_state); what the loader compares between the file's record
 # and the layer's (None: the record is only loaded), each reduced to a plain value with None / False for "absent"; the mismatch text.
 #   mx_had32: the codes were made behind the block Hadamard rotation (a file without it: unrotated)
+#   mx_search: the layer's activations are quantised under `act.block_scale: search` (a file without it: OCP's rule)
 #   mx_fmt:   the (weight, act) format codes of an e2m3-activation layer; no other layer has the key
 #   mx_perm, mx_n8: mx.outlier_channels, the channel order and the count of the mixed codes; the order is loaded, the count compared
 _MX_RECORDS = (
     ("mx_had32", lambda s: s.had32, lambda s: torch.ones(1, dtype=torch.uint8), lambda v: v is not None and bool(v.reshape(-1)[0] != 0),
      lambda f, o: f"holds codes quantised {'behind' if f else 'without'} the block Hadamard rotation (mx.block_hadamard) and the model's "
                   f"layer was built {'with' if o else 'without'} it: the two are not interchangeable"),
+    ("mx_search", lambda s: s.search, lambda s: torch.ones(1, dtype=torch.uint8), lambda v: v is not None and bool(v.reshape(-1)[0] != 0),
+     lambda f, o: f"was saved {'with' if f else 'without'} act.block_scale: search and the model's layer was built "
+                  f"{'with' if o else 'without'} it: the checkpoint and the config must name the same activation rule"),
     ("mx_fmt", lambda s: s.pair is not None and s.pair.act_form == "mxfp6",
      lambda s: torch.tensor([mx_fmt_code(s.pair.w_fmt), mx_fmt_code(s.pair.a_fmt)], dtype=torch.uint8),
      lambda v: None if v is None else v.reshape(-1).tolist(),

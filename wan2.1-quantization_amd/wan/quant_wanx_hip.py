@@ -41,7 +41,7 @@ class _HipLinear(nn.Module):
     fp8 = False
     mx = None              # HipLinearMx: the weight's MX format name
     weight_only = False
-    act_form = "fp"        # what its input is made into: "fp" (16 bits, no quantiser), "int8", "fp8", "mxfp8", "mxfp6", "mxfp4" or "mxfp4_h32"
+    act_form = "fp"        # what its input is made into: "fp" (16 bits, no quantiser), "int8", "fp8", "mxfp8", "mxfp6", "mxfp4", "mxfp4_h32" or either + "_s"
     act_key = "fp"         # layers with the same key share one copy of their input
     plain_rows = False     # its quantiser takes the source's row without a transform, so it can apply the FFN's GELU itself
     rot = act_quantizer = None
@@ -395,7 +395,9 @@ class HipLinearMx(LowRankBranch, _HipLinearCodes):
     the pair's entry with GELU and gate + residual in its epilogue.  What a layer holds beyond that:
     `had32` (the config's `mx.block_hadamard`): the weight codes were made behind the block Hadamard rotation and the input is
     quantised behind it too (activation form + "_h32"); the one-element uint8 buffer `mx_had32` travels with the codes in the integer
-    checkpoint.  e2m3 activations: the uint8 buffer `mx_fmt` = (w_fmt code, a_fmt code) records the formats there.
+    checkpoint.  `search` (the config's `act.block_scale: search`): the input is quantised by fused.quant_rows_mx4_search (activation
+    form + "_s"; the GEMM entry is unchanged) and the one-element uint8 buffer `mx_search` records the rule in the checkpoint; the
+    weight side's rule only chose the codes' scale bytes and leaves no trace here.  e2m3 activations: the uint8 buffer `mx_fmt` = (w_fmt code, a_fmt code) records the formats there.
     `low_rank` (the config's `weight.low_rank`): the buffers `lr_a` [Rp, K] / `lr_b` [N, Rp] hold the LoRC factors in `act_dtype`
     (qdiff/base/low_rank.py), `set_low_rank` attaches a user adapter behind them, the input comes from the source's `project` -- the
     quantiser and the down-projection t = x A16^T in one pass (fused.quant_rows_mxfp4_project), one launch for all consumers of the
@@ -410,7 +412,7 @@ class HipLinearMx(LowRankBranch, _HipLinearCodes):
     sharded = ("weight", "scale_weight")   # the scale bytes are a thirty-second or a sixteenth of the weight's
 
     def __init__(self, in_features, out_features, bias=True, w_fmt="mxfp8_e4m3", name="linear", a_fmt="mxfp8_e4m3", had32=False,
-                 low_rank=None, act_dtype=torch.bfloat16, n8=None):
+                 low_rank=None, act_dtype=torch.bfloat16, n8=None, search=False):
         self.name = name
         pair = mx_pair(w_fmt, a_fmt)
         if pair is None or (had32 and not pair.had32):
@@ -418,13 +420,17 @@ class HipLinearMx(LowRankBranch, _HipLinearCodes):
         if n8 is not None and (not pair.n8 or had32 or low_rank):
             raise NotImplementedError(f"{name}: mx.outlier_channels goes with the plain W4A4 pair only (no block rotation, no low-rank "
                                       f"branch; weight {w_fmt} against act {a_fmt})")
+        if search and (a_fmt != "mxfp4_e2m1" or low_rank or n8 is not None):
+            raise NotImplementedError(f"{name}: act.block_scale: search goes with plain mxfp4_e2m1 activations only (no low-rank branch, "
+                                      f"no outlier channels; act {a_fmt})")
         # the entry this layer calls (by name: read from qgemm at each call) and what it takes between the scales and the bias
         self._gemm, self._lead = ("mx_mixed_linear", (n8,)) if n8 is not None else (pair.gemm, (w_fmt,) if pair.takes_w_fmt else ())
         super().__init__(in_features, out_features, bias, w_fmt, getattr(qgemm, self._gemm + "_refusal")(1, out_features, in_features, *self._lead),
                          n8 + (in_features - n8) // 2 if n8 is not None else in_features // 32 * pair.w_bytes,
                          (out_features, in_features // 32), torch.uint8, name)
         self.mx, self.a_fmt, self.had32, self.n8 = w_fmt, a_fmt, bool(had32), n8
-        self.act_form = self.act_key = f"mxmix{n8}" if n8 is not None else pair.act_form + ("_h32" if had32 else "")
+        self.search = bool(search)
+        self.act_form = self.act_key = f"mxmix{n8}" if n8 is not None else pair.act_form + ("_h32" if had32 else "") + ("_s" if search else "")
         if n8 is not None:
             self.register_buffer("mx_perm", torch.arange(in_features, dtype=torch.int32))
             self.register_buffer("mx_n8", torch.tensor([n8], dtype=torch.int32))
@@ -432,6 +438,8 @@ class HipLinearMx(LowRankBranch, _HipLinearCodes):
             self.register_buffer("mx_fmt", torch.tensor([mx_fmt_code(w_fmt), mx_fmt_code(a_fmt)], dtype=torch.uint8))
         if had32:
             self.register_buffer("mx_had32", torch.ones(1, dtype=torch.uint8))
+        if search:
+            self.register_buffer("mx_search", torch.ones(1, dtype=torch.uint8))
         if low_rank and not pair.low_rank:
             raise NotImplementedError(f"{name}: weight.low_rank goes with the W4A4 pair only (weight {w_fmt} against act {a_fmt})")
         if act_dtype not in (torch.bfloat16, torch.float16):
@@ -442,6 +450,9 @@ class HipLinearMx(LowRankBranch, _HipLinearCodes):
         self.register_buffer("lr_b", torch.zeros(out_features, rp, dtype=act_dtype) if low_rank else None)
 
     def _refuse_adapter(self):
+        if self.search:
+            raise NotImplementedError(f"{self._lr_name()}: set_low_rank with act.block_scale: search is not supported: the fused quantise "
+                                      "+ project producer quantises by OCP's rule")
         if not mx_pair(self.mx, self.a_fmt).low_rank:
             raise NotImplementedError(f"{self._lr_name()}: set_low_rank needs the W4A4 pair (weight {self.mx} against act {self.a_fmt}): "
                                       "only wanq_gemm_mx4_lowrank sums a low-rank branch")
@@ -458,7 +469,8 @@ class HipLinearMx(LowRankBranch, _HipLinearCodes):
             raise RuntimeError(f"{name}: mx.outlier_channels needs calibration activation statistics and none were given: the layer "
                                "has no channel order yet (PTQ: get_channel_mask(act_mask) / select_outlier_perm)")
         m = cls(ql.in_features, ql.out_features, ql.bias is not None, ql.mx, name, ql.mx_act, ql.mx_had32, ql.low_rank,
-                act_dtype if act_dtype in (torch.bfloat16, torch.float16) else torch.bfloat16, ql.mx_n8).to(ql.fp_module.weight.device)
+                act_dtype if act_dtype in (torch.bfloat16, torch.float16) else torch.bfloat16, ql.mx_n8,
+                ql.mx_search_act).to(ql.fp_module.weight.device)
         if ql.mx_n8 is not None:
             m.mx_perm.copy_(ql.mx_perm)
         if ql.low_rank is not None:
@@ -514,7 +526,9 @@ def _to_hip_linear(lin, n_bits, sym, act_dtype, fp_gemm="torch", name="linear"):
 # the form of every MX pair (base_quantizer.MX_PAIRS), plain and -- where the pair admits it -- behind the block rotation
 _ROW_QUANTISERS = {"fp8": ("quant_rows_fp8", {}),
                    **{p.act_form: ("quant_rows_mx", {"fmt": p.a_fmt}) for p in MX_PAIRS.values()},
-                   **{p.act_form + "_h32": ("quant_rows_mx", {"fmt": p.a_fmt, "had32": True}) for p in MX_PAIRS.values() if p.had32}}
+                   **{p.act_form + "_h32": ("quant_rows_mx", {"fmt": p.a_fmt, "had32": True}) for p in MX_PAIRS.values() if p.had32},
+                   # e2m1 activations under `act.block_scale: search`: a form of their own, so that only layers of the same rule share
+                   "mxfp4_s": ("quant_rows_mx4_search", {}), "mxfp4_h32_s": ("quant_rows_mx4_search", {"had32": True})}
 
 
 class _Src:
