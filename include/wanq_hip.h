@@ -184,6 +184,31 @@ int wanq_quant_rows_mx_mixed(const void* x, int x_dtype, const int32_t* perm, in
  * Bit-identical to the host expression mx_quant_rows_host(fmt "mxfp6_e2m3fn").  No reference counterpart. */
 int wanq_quant_rows_mx6(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int act, void* stream);
 
+/* LayerNorm + modulate in front of the fp8 / MX row quantisers, in one pass over x: the producers of a block's norm1 -> q / k / v,
+ * norm3 -> cross-attention q and norm2 -> ffn.0 inputs when those Linears are fp8 or MX.
+ *   y = (x - mean) * rstd * gamma;  y = y * (1 + mscale[b]) + mshift[b]      (b = row / rows_per_batch; wanq_layernorm_rows's y)
+ *   q, scale = the quantiser of y
+ * and q and scale are, BIT FOR BIT, what the quantiser writes when it reads y from an fp32 tensor that wanq_layernorm_rows wrote
+ * (out_dtype F32, mod_dtype F32): the LayerNorm arithmetic is one device function for both (csrc/rowwise.hip, ln_modulate_row, every
+ * rounding written out), the quantiser's is its own kernel's, and y stays in the registers x was loaded into -- the fp32 row is never
+ * stored.  The quantisers: wanq_quant_rows_fp8;  wanq_quant_rows_mx (fmt WANQ_MX_E4M3 | WANQ_MX_E2M1, had32 = 1:
+ * wanq_quant_rows_mx_had32) and wanq_quant_rows_mx6 (fmt WANQ_MX_E2M3, had32 must be 0);  wanq_quant_rows_mx4_search (fmt must be
+ * WANQ_MX_E2M1).  No GELU: nothing in the block puts one behind a LayerNorm.
+ * x: F16 | BF16 | F32 [rows, cols].  gamma [cols], mshift / mscale [batch, cols] with mod_stride elements between batches: fp32, any of
+ * them NULL (identity).  rows_per_batch >= 1, mod_stride >= 0, eps >= 0.  cols: the quantiser's rule (% 8 for fp8, % 32 for MX), at most
+ * 16384.  q 16-byte aligned; q and scale in the quantiser's layout.  rows == 0 returns WANQ_OK.  Anything else is refused (WANQ_E_ARG /
+ * WANQ_E_SHAPE, the message names the value).  A row's bytes do not depend on rows or on the row's place in the launch.
+ * No reference counterpart (the reference fuses its LayerNorm with the int8 quantiser only). */
+int wanq_layernorm_quant_rows_fp8(const void* x, int x_dtype, const float* gamma, const float* mshift, const float* mscale,
+                                  int64_t mod_stride, int64_t rows_per_batch, float eps, uint8_t* q, float* scale, int64_t rows,
+                                  int cols, void* stream);
+int wanq_layernorm_quant_rows_mx(const void* x, int x_dtype, const float* gamma, const float* mshift, const float* mscale,
+                                 int64_t mod_stride, int64_t rows_per_batch, float eps, uint8_t* q, uint8_t* scale_u8, int64_t rows,
+                                 int cols, int fmt, int had32, void* stream);
+int wanq_layernorm_quant_rows_mx4_search(const void* x, int x_dtype, const float* gamma, const float* mshift, const float* mscale,
+                                         int64_t mod_stride, int64_t rows_per_batch, float eps, uint8_t* q, uint8_t* scale_u8,
+                                         int64_t rows, int cols, int fmt, int had32, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * LayerNorm (no bias, optional gamma) -> optional adaLN modulate -> fp output OR int8 quant (+sum).
  *   y = (x - mean) * rstd * gamma;  y = y * (1 + mscale[b]) + mshift[b]   (b = row / rows_per_batch)

@@ -5,10 +5,9 @@
 
 namespace wanq {
 
-struct RowParams {
-  const void* x;
-  int x_dtype;
-  // layernorm
+// The LayerNorm + modulate front end of a row kernel (ln_modulate_row): gamma [cols], mshift / mscale [batch, cols] with mod_stride
+// elements between batches, any of them NULL (identity); row r reads batch r / rows_per_batch.
+struct LnFront {
   const void* gamma;
   const void* mshift;
   const void* mscale;
@@ -16,6 +15,15 @@ struct RowParams {
   int64_t mod_stride;
   int64_t rows_per_batch;
   float eps;
+};
+// a kernel argument that is the front end's arguments in the LN instantiations and nothing in the others
+template <bool LN> struct LnArg : LnFront {};
+template <> struct LnArg<false> {};
+
+struct RowParams {
+  const void* x;
+  int x_dtype;
+  LnFront ln;
   // outputs
   void* out_fp;
   int out_dtype;
@@ -37,6 +45,7 @@ struct RowParams {
 enum { MOD_MUL = 0, MOD_MUL1P = 1, MOD_ADD = 2 };
 template <typename T, int OP, int WPR, int NCH>
 __device__ __forceinline__ void mod_row_t(const RowFrame<WPR, NCH>& f, const void* m, int64_t mbase, float (&v)[NCH][8], const bool (&ok)[NCH]) {
+#pragma clang fp contract(off)
 #pragma unroll
   for (int i = 0; i < NCH; ++i)
     if (ok[i]) {
@@ -46,11 +55,64 @@ __device__ __forceinline__ void mod_row_t(const RowFrame<WPR, NCH>& f, const voi
       for (int j = 0; j < 8; ++j) v[i][j] = OP == MOD_MUL ? v[i][j] * t[j] : OP == MOD_MUL1P ? v[i][j] * (1.0f + t[j]) : v[i][j] + t[j];
     }
 }
-template <int OP, int WPR, int NCH>
+// (ONLY_F32: the caller's vectors are fp32 by its contract, and the kernel carries no branch on dt)
+template <int OP, bool ONLY_F32, int WPR, int NCH>
 __device__ __forceinline__ void mod_row(const RowFrame<WPR, NCH>& f, const void* m, int dt, int64_t mbase, float (&v)[NCH][8], const bool (&ok)[NCH]) {
-  if (dt == WANQ_F32) mod_row_t<F32, OP>(f, m, mbase, v, ok);
+  if (ONLY_F32 || dt == WANQ_F32) mod_row_t<F32, OP>(f, m, mbase, v, ok);
   else if (dt == WANQ_BF16) mod_row_t<BF16, OP>(f, m, mbase, v, ok);
   else mod_row_t<F16, OP>(f, m, mbase, v, ok);
+}
+
+// v <- LayerNorm(v) (* gamma) (* (1 + mscale)) (+ mshift) for the row a frame holds in registers: the one definition of that arithmetic
+// for rowwise_kernel<.., LN> and for the fp8 / MX quantisers behind a LayerNorm, whose codes must equal, bit for bit, those of the
+// quantiser run on what rowwise_kernel stores as fp32.  The row mean, the centred variance, rstd = 1 / sqrt(var + eps), then one
+// multiplication or addition per step, each rounded on its own.  Two reductions over the row (ids 0 and 1 of `red`).
+// Every rounding is written out (contraction is off in here), because the compiler's own choice depends on the code around it.  The
+// one-chunk form (NCH = 1, cols <= 512) has summed its squares as fma(d0, d0, d1 d1), then fma(d_j, d_j, .) for even j and a rounded
+// square for odd j, since rowwise_kernel was first built; that order is pinned here.  The other forms round every square.
+template <bool ONLY_F32 = false, int WPR, int NCH>
+__device__ __forceinline__ void ln_modulate_row(const RowFrame<WPR, NCH>& f, const RowReduce<WPR>& red, const LnFront& ln, int C,
+                                                float (&v)[NCH][8], const bool (&ok)[NCH]) {
+#pragma clang fp contract(off)
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < NCH; ++i)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) s += v[i][j];
+  const float mean = red.template reduce<OpSum>(s, 0) / (float)C;
+  float s2 = 0.f;
+  if constexpr (NCH == 1) {
+    if (ok[0]) {
+      float d[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) d[j] = v[0][j] - mean;
+      s2 = __builtin_fmaf(d[0], d[0], d[1] * d[1]);
+#pragma unroll
+      for (int j = 2; j < 8; j += 2) s2 = __builtin_fmaf(d[j], d[j], s2) + d[j + 1] * d[j + 1];
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < NCH; ++i)
+      if (ok[i]) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float d = v[i][j] - mean;
+          s2 += d * d;
+        }
+      }
+  }
+  const float var = red.template reduce<OpSum>(s2, 1) / (float)C;
+  const float rstd = 1.0f / sqrtf(var + ln.eps);
+  const int64_t mb = (f.row / ln.rows_per_batch) * ln.mod_stride;
+#pragma unroll
+  for (int i = 0; i < NCH; ++i)
+    if (ok[i]) {  // chunks past the row end stay zero: they take part in the row max and sum
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[i][j] = (v[i][j] - mean) * rstd;
+    }
+  if (ln.gamma) mod_row<MOD_MUL, ONLY_F32>(f, ln.gamma, ln.mod_dtype, 0, v, ok);
+  if (ln.mscale) mod_row<MOD_MUL1P, ONLY_F32>(f, ln.mscale, ln.mod_dtype, mb, v, ok);
+  if (ln.mshift) mod_row<MOD_ADD, ONLY_F32>(f, ln.mshift, ln.mod_dtype, mb, v, ok);
 }
 
 template <int WPR, int NCH, bool LN>
@@ -68,34 +130,7 @@ __global__ __launch_bounds__(256) void rowwise_kernel(const RowParams p) {
   f.load(p.x, p.x_dtype, rbase, C, v, ok);
 
   if (LN) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s += v[i][j];
-    const float mean = red.template reduce<OpSum>(s, 0) / (float)C;
-    float s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-      if (ok[i]) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float d = v[i][j] - mean;
-          s2 += d * d;
-        }
-      }
-    const float var = red.template reduce<OpSum>(s2, 1) / (float)C;
-    const float rstd = 1.0f / sqrtf(var + p.eps);
-    const int64_t mb = (row / p.rows_per_batch) * p.mod_stride;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-      if (ok[i]) {  // chunks past the row end stay zero: they take part in the row max and sum
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[i][j] = (v[i][j] - mean) * rstd;
-      }
-    if (p.gamma) mod_row<MOD_MUL>(f, p.gamma, p.mod_dtype, 0, v, ok);
-    if (p.mscale) mod_row<MOD_MUL1P>(f, p.mscale, p.mod_dtype, mb, v, ok);
-    if (p.mshift) mod_row<MOD_ADD>(f, p.mshift, p.mod_dtype, mb, v, ok);
+    ln_modulate_row(f, red, p.ln, C, v, ok);
   } else if (p.act == 1) {
 #pragma unroll
     for (int i = 0; i < NCH; ++i)
@@ -288,9 +323,12 @@ struct Fp8RowParams {
 
 constexpr float FP8_E4M3_MAX = 448.0f;
 
-template <int WPR, int NCH>
-__global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const Fp8RowParams p) {
-  __shared__ float red_slots[4];
+// LN (wanq_layernorm_quant_rows_fp8): x is the residual stream and the row goes through ln_modulate_row between the load and the
+// row maximum, in the registers it was loaded into: what wanq_layernorm_rows would store as fp32 and this kernel would read back is
+// never written.  Three reductions then (two sums, the maximum), each with its own LDS slots in the four-wave form; no GELU.
+template <int WPR, int NCH, bool LN = false>
+__global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const Fp8RowParams p, const LnArg<LN> ln) {
+  __shared__ float red_slots[LN ? 3 * 4 : 4];
   RowFrame<WPR, NCH> f;
   if (f.surplus(p.rows)) return;
   const RowReduce<WPR> red{red_slots, f.wave};
@@ -300,7 +338,9 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const Fp8RowParams 
   float v[NCH][8];
   bool ok[NCH];
   f.load(p.x, p.x_dtype, rbase, C, v, ok);
-  if (p.act == 1) {
+  if constexpr (LN) {
+    ln_modulate_row<true>(f, red, ln, C, v, ok);
+  } else if (p.act == 1) {
 #pragma unroll
     for (int i = 0; i < NCH; ++i)
 #pragma unroll
@@ -311,7 +351,7 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const Fp8RowParams 
   for (int i = 0; i < NCH; ++i)
 #pragma unroll
     for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(v[i][j]));
-  const float scale = dyn_scale(red.template reduce<OpMax>(m, 0), FP8_E4M3_MAX, 1e-6f);
+  const float scale = dyn_scale(red.template reduce<OpMax>(m, LN ? 2 : 0), FP8_E4M3_MAX, 1e-6f);
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
     if (!ok[i]) continue;
@@ -367,8 +407,11 @@ __device__ __forceinline__ uint32_t quad_next_dpp(uint32_t v) {
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x39, 0xf, 0xf, true);  // quad_perm:[1,2,3,0]
 }
 
-template <int WPR, int NCH, bool FP4, bool HAD = false, bool FP6 = false>
-__global__ __launch_bounds__(256) void quant_rows_mx_kernel(const MxRowParams p) {
+// LN (wanq_layernorm_quant_rows_mx): the row goes through ln_modulate_row between the load and the blocks, as in the fp8 kernel.  Its
+// two sums are the only reductions over the row (the four-wave form: 32 B of LDS, two barriers); behind them a block is still the
+// business of its quad alone.
+template <int WPR, int NCH, bool FP4, bool HAD = false, bool FP6 = false, bool LN = false>
+__global__ __launch_bounds__(256) void quant_rows_mx_kernel(const MxRowParams p, const LnArg<LN> ln) {
   static_assert(!(FP6 && (FP4 || HAD)), "e2m3 is a format of its own, without the rotation");
   RowFrame<WPR, NCH> f;
   if (f.surplus(p.rows)) return;
@@ -379,7 +422,10 @@ __global__ __launch_bounds__(256) void quant_rows_mx_kernel(const MxRowParams p)
   float v[NCH][8];
   bool ok[NCH];
   f.load(p.x, p.x_dtype, rbase, C, v, ok);
-  if (p.act == 1) {
+  if constexpr (LN) {
+    __shared__ float red_slots[2 * 4];
+    ln_modulate_row<true>(f, RowReduce<WPR>{red_slots, f.wave}, ln, C, v, ok);
+  } else if (p.act == 1) {
 #pragma unroll
     for (int i = 0; i < NCH; ++i)
 #pragma unroll
@@ -428,8 +474,9 @@ __global__ __launch_bounds__(256) void quant_rows_mx_kernel(const MxRowParams p)
 // quad hold the same two sums and make the same choice without a broadcast; then one dword store of the winning nibbles per lane and
 // one byte from the quad's first lane, as in the plain kernel.  The exchanges run before the `ok` test: a quad is in the row or past it
 // as a whole, and a slot past the row end is a zero block.
-template <int WPR, int NCH, bool HAD>
-__global__ __launch_bounds__(256) void quant_rows_mx4_search_kernel(const MxRowParams p) {
+// LN (wanq_layernorm_quant_rows_mx4_search): ln_modulate_row between the load and the blocks, as in quant_rows_mx_kernel.
+template <int WPR, int NCH, bool HAD, bool LN = false>
+__global__ __launch_bounds__(256) void quant_rows_mx4_search_kernel(const MxRowParams p, const LnArg<LN> ln) {
   RowFrame<WPR, NCH> f;
   if (f.surplus(p.rows)) return;
   const int C = p.cols;
@@ -438,7 +485,10 @@ __global__ __launch_bounds__(256) void quant_rows_mx4_search_kernel(const MxRowP
   float v[NCH][8];
   bool ok[NCH];
   f.load(p.x, p.x_dtype, rbase, C, v, ok);
-  if (p.act == 1) {
+  if constexpr (LN) {
+    __shared__ float red_slots[2 * 4];
+    ln_modulate_row<true>(f, RowReduce<WPR>{red_slots, f.wave}, ln, C, v, ok);
+  } else if (p.act == 1) {
 #pragma unroll
     for (int i = 0; i < NCH; ++i)
 #pragma unroll
@@ -457,6 +507,29 @@ __global__ __launch_bounds__(256) void quant_rows_mx4_search_kernel(const MxRowP
   }
 }
 
+// the three quantisers through the ladder, plain (LN false, `ln` empty) or behind the LayerNorm front end
+template <bool LN>
+static int launch_quant_rows_fp8(const char* what, const Fp8RowParams& p, const LnArg<LN>& ln, hipStream_t st) {
+  row_ladder(p.cols, p.rows, [&](auto wpr, auto nch, dim3 grid) {
+    hipLaunchKernelGGL((quant_rows_fp8_kernel<decltype(wpr)::value, decltype(nch)::value, LN>), grid, dim3(256), 0, st, p, ln);
+  });
+  return check_launch(what);
+}
+template <bool FP4, bool HAD, bool FP6, bool LN>
+static int launch_quant_rows_mx(const char* what, const MxRowParams& p, const LnArg<LN>& ln, hipStream_t st) {
+  row_ladder(p.cols, p.rows, [&](auto wpr, auto nch, dim3 grid) {
+    hipLaunchKernelGGL((quant_rows_mx_kernel<decltype(wpr)::value, decltype(nch)::value, FP4, HAD, FP6, LN>), grid, dim3(256), 0, st, p, ln);
+  });
+  return check_launch(what);
+}
+template <bool HAD, bool LN>
+static int launch_quant_rows_mx4_search(const char* what, const MxRowParams& p, const LnArg<LN>& ln, hipStream_t st) {
+  row_ladder(p.cols, p.rows, [&](auto wpr, auto nch, dim3 grid) {
+    hipLaunchKernelGGL((quant_rows_mx4_search_kernel<decltype(wpr)::value, decltype(nch)::value, HAD, LN>), grid, dim3(256), 0, st, p, ln);
+  });
+  return check_launch(what);
+}
+
 // x * premul (-> LayerNorm + modulate first when `ln`) -> fp output and / or int8 quantise: the transform entry points of
 // rotate.hip with had_k == 0 (channel scale without rotation: SmoothQuant, Q/smooth_quant/sq_quant_layer.py:52-60).
 int premul_quant_rows(bool ln, const void* x, int x_dtype, const void* gamma, const void* mshift, const void* mscale,
@@ -466,8 +539,8 @@ int premul_quant_rows(bool ln, const void* x, int x_dtype, const void* gamma, co
   if (rows == 0) return WANQ_OK;
   RowParams p{};
   p.levels = 127.0f; p.floor = 1e-6f;
-  p.x = x; p.x_dtype = x_dtype; p.gamma = gamma; p.mshift = mshift; p.mscale = mscale; p.mod_dtype = WANQ_F32;
-  p.mod_stride = mod_stride; p.rows_per_batch = rows_per_batch; p.eps = eps; p.out_fp = out_fp; p.out_dtype = out_dtype;
+  p.x = x; p.x_dtype = x_dtype; p.ln.gamma = gamma; p.ln.mshift = mshift; p.ln.mscale = mscale; p.ln.mod_dtype = WANQ_F32;
+  p.ln.mod_stride = mod_stride; p.ln.rows_per_batch = rows_per_batch; p.ln.eps = eps; p.out_fp = out_fp; p.out_dtype = out_dtype;
   p.q = q; p.scale = scale; p.sum = sum; p.vec_dtype = vec_dtype; p.rows = rows; p.cols = cols; p.premul = premul;
   return ln ? launch_rowwise<true>(p, st, what) : launch_rowwise<false>(p, st, what);
 }
@@ -488,7 +561,7 @@ extern "C" int wanq_quant_rows(const void* x, int x_dtype, int8_t* q, void* scal
   RowParams p{};
   p.levels = 127.0f; p.floor = 1e-6f;
   p.x = x; p.x_dtype = x_dtype; p.q = q; p.scale = scale; p.sum = sum; p.vec_dtype = vec_dtype;
-  p.rows = rows; p.cols = cols; p.act = act; p.static_amax = static_amax; p.rows_per_batch = 1;
+  p.rows = rows; p.cols = cols; p.act = act; p.static_amax = static_amax; p.ln.rows_per_batch = 1;
   return launch_rowwise<false>(p, (hipStream_t)stream, "wanq_quant_rows");
 }
 
@@ -502,7 +575,7 @@ extern "C" int wanq_quant_rows_levels(const void* x, int x_dtype, int8_t* q, voi
   if (rows == 0) return WANQ_OK;
   RowParams p{};
   p.x = x; p.x_dtype = x_dtype; p.q = q; p.scale = scale; p.sum = sum; p.vec_dtype = vec_dtype;
-  p.rows = rows; p.cols = cols; p.rows_per_batch = 1; p.levels = (float)n_levels; p.floor = floor;
+  p.rows = rows; p.cols = cols; p.ln.rows_per_batch = 1; p.levels = (float)n_levels; p.floor = floor;
   return launch_rowwise<false>(p, (hipStream_t)stream, "wanq_quant_rows_levels");
 }
 
@@ -513,11 +586,7 @@ extern "C" int wanq_quant_rows_fp8(const void* x, int x_dtype, uint8_t* q, float
   WANQ_REQUIRE(act == 0 || act == 1, WANQ_E_ARG, "wanq_quant_rows_fp8: act must be 0 or 1");
   if (int e = check_rows_cols("wanq_quant_rows_fp8", rows, cols)) return e;
   if (rows == 0) return WANQ_OK;
-  const Fp8RowParams p{x, x_dtype, q, scale, rows, cols, act};
-  row_ladder(cols, rows, [&](auto wpr, auto nch, dim3 grid) {
-    hipLaunchKernelGGL((quant_rows_fp8_kernel<decltype(wpr)::value, decltype(nch)::value>), grid, dim3(256), 0, (hipStream_t)stream, p);
-  });
-  return check_launch("wanq_quant_rows_fp8");
+  return launch_quant_rows_fp8<false>("wanq_quant_rows_fp8", {x, x_dtype, q, scale, rows, cols, act}, {}, (hipStream_t)stream);
 }
 
 template <bool HAD>
@@ -532,12 +601,8 @@ static int quant_rows_mx_entry(const char* what, const void* x, int x_dtype, uin
   WANQ_REQUIRE((reinterpret_cast<uintptr_t>(q) & 15) == 0, WANQ_E_ARG, "%s: q must be 16-byte aligned", what);
   if (rows == 0) return WANQ_OK;
   const MxRowParams p{x, x_dtype, q, scale_u8, rows, cols, act};
-  row_ladder(cols, rows, [&](auto wpr, auto nch, dim3 grid) {
-    constexpr int W = decltype(wpr)::value, NC = decltype(nch)::value;
-    if (fmt == WANQ_MX_E2M1) hipLaunchKernelGGL((quant_rows_mx_kernel<W, NC, true, HAD>), grid, dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((quant_rows_mx_kernel<W, NC, false, HAD>), grid, dim3(256), 0, (hipStream_t)stream, p);
-  });
-  return check_launch(what);
+  return fmt == WANQ_MX_E2M1 ? launch_quant_rows_mx<true, HAD, false, false>(what, p, {}, (hipStream_t)stream)
+                             : launch_quant_rows_mx<false, HAD, false, false>(what, p, {}, (hipStream_t)stream);
 }
 
 extern "C" int wanq_quant_rows_mx(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int fmt, int act,
@@ -562,12 +627,8 @@ extern "C" int wanq_quant_rows_mx4_search(const void* x, int x_dtype, uint8_t* q
   WANQ_REQUIRE((reinterpret_cast<uintptr_t>(q) & 15) == 0, WANQ_E_ARG, "%s: q must be 16-byte aligned", what);
   if (rows == 0) return WANQ_OK;
   const MxRowParams p{x, x_dtype, q, scale_u8, rows, cols, act};
-  row_ladder(cols, rows, [&](auto wpr, auto nch, dim3 grid) {
-    constexpr int W = decltype(wpr)::value, NC = decltype(nch)::value;
-    if (had32) hipLaunchKernelGGL((quant_rows_mx4_search_kernel<W, NC, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((quant_rows_mx4_search_kernel<W, NC, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
-  });
-  return check_launch(what);
+  return had32 ? launch_quant_rows_mx4_search<true, false>(what, p, {}, (hipStream_t)stream)
+               : launch_quant_rows_mx4_search<false, false>(what, p, {}, (hipStream_t)stream);
 }
 
 extern "C" int wanq_quant_rows_mx6(const void* x, int x_dtype, uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int act,
@@ -580,12 +641,66 @@ extern "C" int wanq_quant_rows_mx6(const void* x, int x_dtype, uint8_t* q, uint8
   WANQ_REQUIRE(cols % 32 == 0, WANQ_E_SHAPE, "%s: cols=%d must be a multiple of 32 (one scale per block of 32)", what, cols);
   WANQ_REQUIRE((reinterpret_cast<uintptr_t>(q) & 15) == 0, WANQ_E_ARG, "%s: q must be 16-byte aligned", what);
   if (rows == 0) return WANQ_OK;
-  const MxRowParams p{x, x_dtype, q, scale_u8, rows, cols, act};
-  row_ladder(cols, rows, [&](auto wpr, auto nch, dim3 grid) {
-    hipLaunchKernelGGL((quant_rows_mx_kernel<decltype(wpr)::value, decltype(nch)::value, false, false, true>), grid, dim3(256), 0,
-                       (hipStream_t)stream, p);
-  });
-  return check_launch(what);
+  return launch_quant_rows_mx<false, false, true, false>(what, {x, x_dtype, q, scale_u8, rows, cols, act}, {}, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------ LayerNorm + modulate in front of the fp8 / MX quantisers
+// What the three entries below share: the source, the front end's arguments (fp32 vectors) and the shape, checked on the host.
+static int check_ln_quant_rows(const char* what, const void* x, int x_dtype, const void* q, const void* scale, int64_t mod_stride,
+                               int64_t rows_per_batch, float eps, int64_t rows, int cols, int block) {
+  WANQ_REQUIRE(x && q && scale, WANQ_E_ARG, "%s: x, q and scale must be non-NULL", what);
+  WANQ_REQUIRE(is_fp(x_dtype), WANQ_E_ARG, "%s: bad x dtype %d", what, x_dtype);
+  WANQ_REQUIRE(rows_per_batch >= 1, WANQ_E_ARG, "%s: rows_per_batch=%lld must be >= 1", what, (long long)rows_per_batch);
+  WANQ_REQUIRE(mod_stride >= 0, WANQ_E_ARG, "%s: mod_stride=%lld must be >= 0", what, (long long)mod_stride);
+  WANQ_REQUIRE(eps >= 0.f, WANQ_E_ARG, "%s: eps=%g must be >= 0", what, (double)eps);
+  if (int e = check_rows_cols(what, rows, cols)) return e;
+  WANQ_REQUIRE(cols % block == 0, WANQ_E_SHAPE, "%s: cols=%d must be a multiple of %d (one scale per block of %d)", what, cols, block, block);
+  WANQ_REQUIRE((reinterpret_cast<uintptr_t>(q) & 15) == 0, WANQ_E_ARG, "%s: q must be 16-byte aligned", what);
+  return WANQ_OK;
+}
+
+extern "C" int wanq_layernorm_quant_rows_fp8(const void* x, int x_dtype, const float* gamma, const float* mshift, const float* mscale,
+                                             int64_t mod_stride, int64_t rows_per_batch, float eps, uint8_t* q, float* scale,
+                                             int64_t rows, int cols, void* stream) {
+  const char* what = "wanq_layernorm_quant_rows_fp8";
+  if (int e = check_ln_quant_rows(what, x, x_dtype, q, scale, mod_stride, rows_per_batch, eps, rows, cols, 8)) return e;
+  if (rows == 0) return WANQ_OK;
+  return launch_quant_rows_fp8<true>(what, {x, x_dtype, q, scale, rows, cols, 0},
+                                     {{gamma, mshift, mscale, WANQ_F32, mod_stride, rows_per_batch, eps}}, (hipStream_t)stream);
+}
+
+extern "C" int wanq_layernorm_quant_rows_mx(const void* x, int x_dtype, const float* gamma, const float* mshift, const float* mscale,
+                                            int64_t mod_stride, int64_t rows_per_batch, float eps, uint8_t* q, uint8_t* scale_u8,
+                                            int64_t rows, int cols, int fmt, int had32, void* stream) {
+  const char* what = "wanq_layernorm_quant_rows_mx";
+  WANQ_REQUIRE(fmt == WANQ_MX_E4M3 || fmt == WANQ_MX_E2M1 || fmt == WANQ_MX_E2M3, WANQ_E_ARG,
+               "%s: fmt=%d must be WANQ_MX_E4M3, WANQ_MX_E2M1 or WANQ_MX_E2M3", what, fmt);
+  WANQ_REQUIRE(had32 == 0 || had32 == 1, WANQ_E_ARG, "%s: had32=%d must be 0 or 1", what, had32);
+  WANQ_REQUIRE(!(had32 && fmt == WANQ_MX_E2M3), WANQ_E_ARG, "%s: had32=1 does not go with fmt=%d (WANQ_MX_E2M3 has no rotated form)", what, fmt);
+  if (int e = check_ln_quant_rows(what, x, x_dtype, q, scale_u8, mod_stride, rows_per_batch, eps, rows, cols, 32)) return e;
+  if (rows == 0) return WANQ_OK;
+  const MxRowParams p{x, x_dtype, q, scale_u8, rows, cols, 0};
+  const LnArg<true> ln{{gamma, mshift, mscale, WANQ_F32, mod_stride, rows_per_batch, eps}};
+  hipStream_t st = (hipStream_t)stream;
+  if (fmt == WANQ_MX_E2M3) return launch_quant_rows_mx<false, false, true, true>(what, p, ln, st);
+  if (fmt == WANQ_MX_E2M1) return had32 ? launch_quant_rows_mx<true, true, false, true>(what, p, ln, st)
+                                        : launch_quant_rows_mx<true, false, false, true>(what, p, ln, st);
+  return had32 ? launch_quant_rows_mx<false, true, false, true>(what, p, ln, st) : launch_quant_rows_mx<false, false, false, true>(what, p, ln, st);
+}
+
+extern "C" int wanq_layernorm_quant_rows_mx4_search(const void* x, int x_dtype, const float* gamma, const float* mshift,
+                                                    const float* mscale, int64_t mod_stride, int64_t rows_per_batch, float eps,
+                                                    uint8_t* q, uint8_t* scale_u8, int64_t rows, int cols, int fmt, int had32,
+                                                    void* stream) {
+  const char* what = "wanq_layernorm_quant_rows_mx4_search";
+  WANQ_REQUIRE(fmt == WANQ_MX_E2M1, WANQ_E_ARG, "%s: fmt=%d must be WANQ_MX_E2M1 (the scale search is e2m1's)", what, fmt);
+  WANQ_REQUIRE(had32 == 0 || had32 == 1, WANQ_E_ARG, "%s: had32=%d must be 0 or 1", what, had32);
+  if (int e = check_ln_quant_rows(what, x, x_dtype, q, scale_u8, mod_stride, rows_per_batch, eps, rows, cols, 32)) return e;
+  if (rows == 0) return WANQ_OK;
+  const MxRowParams p{x, x_dtype, q, scale_u8, rows, cols, 0};
+  const LnArg<true> ln{{gamma, mshift, mscale, WANQ_F32, mod_stride, rows_per_batch, eps}};
+  return had32 ? launch_quant_rows_mx4_search<true, true>(what, p, ln, (hipStream_t)stream)
+               : launch_quant_rows_mx4_search<false, true>(what, p, ln, (hipStream_t)stream);
 }
 
 extern "C" int wanq_layernorm_rows(const void* x, int x_dtype, const void* gamma, const void* mshift,
@@ -602,8 +717,8 @@ extern "C" int wanq_layernorm_rows(const void* x, int x_dtype, const void* gamma
   if (rows == 0) return WANQ_OK;
   RowParams p{};
   p.levels = 127.0f; p.floor = 1e-6f;
-  p.x = x; p.x_dtype = x_dtype; p.gamma = gamma; p.mshift = mshift; p.mscale = mscale; p.mod_dtype = mod_dtype;
-  p.mod_stride = mod_stride; p.rows_per_batch = rows_per_batch; p.eps = eps; p.out_fp = out_fp; p.out_dtype = out_dtype;
+  p.x = x; p.x_dtype = x_dtype; p.ln.gamma = gamma; p.ln.mshift = mshift; p.ln.mscale = mscale; p.ln.mod_dtype = mod_dtype;
+  p.ln.mod_stride = mod_stride; p.ln.rows_per_batch = rows_per_batch; p.ln.eps = eps; p.out_fp = out_fp; p.out_dtype = out_dtype;
   p.q = q; p.scale = scale; p.sum = sum; p.vec_dtype = vec_dtype; p.rows = rows; p.cols = cols;
   return launch_rowwise<true>(p, (hipStream_t)stream, "wanq_layernorm_rows");
 }

@@ -70,6 +70,9 @@ PROTOTYPES = {
     "wanq_quant_rows_mx_mixed": [_vp, _i, _vp, _i, _vp, _vp, _i64, _i, _i, _vp],
     "wanq_gemm_mx_mixed": [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
     "wanq_quant_rows_mx6": [_vp, _i, _vp, _vp, _i64, _i, _i, _vp],
+    "wanq_layernorm_quant_rows_fp8": [_vp, _i, _vp, _vp, _vp, _i64, _i64, _f, _vp, _vp, _i64, _i, _vp],
+    "wanq_layernorm_quant_rows_mx": [_vp, _i, _vp, _vp, _vp, _i64, _i64, _f, _vp, _vp, _i64, _i, _i, _i, _vp],
+    "wanq_layernorm_quant_rows_mx4_search": [_vp, _i, _vp, _vp, _vp, _i64, _i64, _f, _vp, _vp, _i64, _i, _i, _i, _vp],
     "wanq_gemm_mx6": [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
     "wanq_lincomb":[_i, _i, _vp, _vp, _vp, _i64, _vp],
     "wanq_linear_f32": [_vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp],

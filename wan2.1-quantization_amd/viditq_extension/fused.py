@@ -276,6 +276,78 @@ def layernorm_nobias_t2i_quant_sum_fuse(output, input, weight, shift_msa, scale_
     _layernorm(output, input, weight, shift_msa, scale_msa, sum_output, scaling, epsilon, True)
 
 
+# ---- LayerNorm + modulate in front of the fp8 / MX row quantisers: layernorm_nobias_t2i_fuse into an fp32 tensor followed by
+#      quant_rows_fp8 / quant_rows_mx / quant_rows_mx4_search, bit for bit, in one launch and without the fp32 tensor
+def _ln_front(input, weight, shift_msa, scale_msa):
+    """-> (rows, cols, the front end's arguments of the C entries between x's dtype and eps): fp32 vectors as in layernorm_rotate_quant"""
+    rows, cols = _rows_cols("input", input)
+    for m in (weight, shift_msa, scale_msa):
+        if m is not None:
+            _C.check_gpu("weight/shift/scale", m)
+            _C.check_dtype("weight/shift/scale", m, torch.float32)
+    if weight is not None:
+        _C.check_shape("weight", weight, cols)
+        weight = weight.contiguous()
+    batch, mod_stride = 1, 0
+    ref = shift_msa if shift_msa is not None else scale_msa
+    if ref is not None:
+        if ref.dim() != 2 or ref.shape[1] != cols or rows % ref.shape[0]:
+            raise RuntimeError(f"shift_msa / scale_msa must be [batch, {cols}] with rows={rows} a multiple of batch")
+        batch, mod_stride = ref.shape[0], ref.stride(0)
+        for m in (shift_msa, scale_msa):
+            if m is not None and (m.shape != ref.shape or m.stride(1) != 1 or m.stride(0) != mod_stride):
+                raise RuntimeError("shift_msa / scale_msa must be [batch, cols] views with equal strides")
+    _C.check_same_device(input, weight, shift_msa, scale_msa)
+    return rows, cols, (_C.ptr(weight), _C.ptr(shift_msa), _C.ptr(scale_msa), mod_stride, rows // batch)
+
+
+def layernorm_quant_rows_fp8(input, weight, shift_msa, scale_msa, epsilon):
+    """`quant_rows_fp8` of LayerNorm(input) (* weight) (* (1 + scale_msa)) (+ shift_msa) (wanq_layernorm_quant_rows_fp8): -> (codes,
+    scale), the bits `quant_rows_fp8` gives for the fp32 tensor `layernorm_nobias_t2i_fuse` writes, in one pass over input."""
+    rows, cols, front = _ln_front(input, weight, shift_msa, scale_msa)
+    codes = torch.empty(input.shape, dtype=torch.uint8, device=input.device)
+    scale = torch.empty(rows, dtype=torch.float32, device=input.device)
+    with torch.cuda.device(input.device):
+        _C.call("wanq_layernorm_quant_rows_fp8", _C.ptr(input), _C.dt(input), *front, float(epsilon), _C.ptr(codes), _C.ptr(scale), rows,
+                cols, _C.stream())
+    return codes, scale
+
+
+_MX_ALL_FMT = {**_C.MX_FMT, **_C.MX6_FMT}
+
+
+def layernorm_quant_rows_mx(input, weight, shift_msa, scale_msa, epsilon, fmt="mxfp8_e4m3", had32=False):
+    """`quant_rows_mx(fmt=, had32=)` of the LayerNorm + modulate of `layernorm_quant_rows_fp8` (wanq_layernorm_quant_rows_mx): ->
+    (codes, scale bytes) in that function's layouts and with its bits, in one pass over input."""
+    if fmt not in _MX_ALL_FMT:
+        raise RuntimeError(f"layernorm_quant_rows_mx: fmt={fmt!r} must be one of {tuple(_MX_ALL_FMT)}")
+    if had32 and fmt not in _C.MX_FMT:
+        raise RuntimeError(f"layernorm_quant_rows_mx: fmt={fmt!r} has no had32 form (the block rotation is built for mxfp4_e2m1 / mxfp8_e4m3)")
+    rows, cols, front = _ln_front(input, weight, shift_msa, scale_msa)
+    if cols % 32:
+        raise RuntimeError(f"layernorm_quant_rows_mx: cols={cols} must be a multiple of 32")
+    codes = torch.empty((*input.shape[:-1], cols // 32 * _C.MX_BLOCK_BYTES[fmt]), dtype=torch.uint8, device=input.device)
+    scale = torch.empty((*input.shape[:-1], cols // 32), dtype=torch.uint8, device=input.device)
+    with torch.cuda.device(input.device):
+        _C.call("wanq_layernorm_quant_rows_mx", _C.ptr(input), _C.dt(input), *front, float(epsilon), _C.ptr(codes), _C.ptr(scale), rows,
+                cols, _MX_ALL_FMT[fmt], 1 if had32 else 0, _C.stream())
+    return codes, scale
+
+
+def layernorm_quant_rows_mx4_search(input, weight, shift_msa, scale_msa, epsilon, had32=False):
+    """`quant_rows_mx4_search(had32=)` of the LayerNorm + modulate of `layernorm_quant_rows_fp8`
+    (wanq_layernorm_quant_rows_mx4_search): -> (codes, scale bytes) with that function's bits, in one pass over input."""
+    rows, cols, front = _ln_front(input, weight, shift_msa, scale_msa)
+    if cols % 32:
+        raise RuntimeError(f"layernorm_quant_rows_mx4_search: cols={cols} must be a multiple of 32")
+    codes = torch.empty((*input.shape[:-1], cols // 2), dtype=torch.uint8, device=input.device)
+    scale = torch.empty((*input.shape[:-1], cols // 32), dtype=torch.uint8, device=input.device)
+    with torch.cuda.device(input.device):
+        _C.call("wanq_layernorm_quant_rows_mx4_search", _C.ptr(input), _C.dt(input), *front, float(epsilon), _C.ptr(codes), _C.ptr(scale),
+                rows, cols, _C.MX_FMT["mxfp4_e2m1"], 1 if had32 else 0, _C.stream())
+    return codes, scale
+
+
 def gate_residual_fuse(input, gate_msa, residual, out_dtype=None):
     """input * gate_msa[b] + residual.  input/residual: [batch*tokens, hidden]; gate_msa: [batch, hidden]."""
     rows, cols = _rows_cols("input", input)

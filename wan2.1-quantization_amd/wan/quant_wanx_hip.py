@@ -641,9 +641,21 @@ class _LnSrc(_Src):
         for i, lin in enumerate(todo):
             self.cache[lin.act_key] = (qs[i], vec[i, 0], vec[i, 1])
 
+    def prefetch_rows(self, lins):
+        """Materialise every plain-row form (a key of _ROW_QUANTISERS: fp8, the MX forms, rotated and scale-searched) among the
+        consumers `lins` by the fused LayerNorm + modulate + quantise producer of that form (fused.layernorm_quant_rows_*), once per
+        form: one pass over x and no fp32 row in memory, with the bits of `rows`'s two launches.  Consumers that take the mixed
+        (outlier-channel) form or carry a low-rank branch are left to `rows_mixed` / `project`, which read the fp32 row."""
+        for lin in lins:
+            form = lin.act_form
+            if form in self.cache or form not in _ROW_QUANTISERS or not lin.plain_rows or getattr(lin, "has_branch", False) or \
+                    lin.act_quantizer is not None:
+                continue
+            name, args = _ROW_QUANTISERS[form]
+            self.cache[form] = getattr(fused, "layernorm_" + name)(self.x, self.gamma, self.shift, self.scale, self.blk.eps, **args)
+
     def _plain_row(self):
-        """The fp32 row, what a simulation-mode quantiser sees.  (A fused LayerNorm + modulate + fp8 / MX producer would save the
-        fp32 round trip.)"""
+        """The fp32 row, what a simulation-mode quantiser sees: the lazy path of a consumer that `prefetch_rows` did not serve."""
         return self.fp32(), False
 
     def fp(self):
@@ -979,6 +991,7 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         h = _LnSrc(self, x, None, e[:, 0], e[:, 1])
         h.prefetch([sa.q, sa.k, sa.v])  # one pass over x for the three ViDiT-transformed int8 inputs
         h.project([sa.q, sa.k, sa.v])   # ... and for the three W4A4 inputs with a low-rank branch: codes and all three t
+        h.prefetch_rows([sa.q, sa.k, sa.v])  # ... and for fp8 / MX inputs: LayerNorm + modulate + quantise, no fp32 row in between
         q = self._linear(sa.q, h)
         if sp is not None and sp.size > 1:
             o = self._self_attention_ulysses(q, h, rope, seq_len, sp)
@@ -991,6 +1004,7 @@ class WanAttentionBlockWithHipKernel(nn.Module):
 
         # ---- cross attention: LN_affine -> q; k,v from the text context
         h = _LnSrc(self, x, self.norm3_weight, self.norm3_bias.view(1, -1), None)
+        h.prefetch_rows([ca.q])
         q = self._linear(ca.q, h)
         k, v = self._context_kv(ctx)
         # cross_attn.attn_map under sequence parallelism: a rank's queries are a token shard here (the cross-attention is not
@@ -1011,6 +1025,7 @@ class WanAttentionBlockWithHipKernel(nn.Module):
         # the GELU in the GEMM epilogue, whose store loop is vector-bound; cfg-B, tools/probes/ffn_gelu_placement.py); with a
         # rotation in front of ffn.2, or a floating-point ffn.2, it stays in ffn.0's epilogue.
         h = _LnSrc(self, x, None, e[:, 3], e[:, 4])
+        h.prefetch_rows([self.ffn0])
         late_gelu = _late_gelu(self.ffn0, self.ffn2)
         hid = self._linear(self.ffn0, h, gelu=not late_gelu)
         self._linear(self.ffn2, _FpSrc(hid, gelu=late_gelu), gate=e[0, 5].contiguous(), residual=x)
