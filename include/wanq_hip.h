@@ -80,6 +80,20 @@ int wanq_quant_rows_levels(const void* x, int x_dtype, int8_t* q, void* scale, v
  * No reference counterpart: the reference's Linear formats are integer ones. */
 int wanq_quant_rows_fp8(const void* x, int x_dtype, uint8_t* q, float* scale, int64_t rows, int cols, int act, void* stream);
 
+/* The same quantiser with one scale per row AND per group of `group` = 128 consecutive columns (fine-grained fp8): the activation
+ * quantiser and, once at conversion time, the weight quantiser (rows = output channels) of wanq_gemm_fp8_grouped.  For row r and
+ * group g (columns 128 g .. 128 g + 127):
+ *   scale[r,g] = max(absmax over the group / 448, 1e-6)
+ *   q[r,c]     = e4m3fn_rne(clamp(x[r,c] / scale[r, c / 128], -448, 448))      (true division, one rounding: wanq_quant_rows_fp8's rule)
+ * q: uint8 [rows, cols].  scale: fp32 [rows, cols / 128], row-major.  act as above (this library's GELU first).  A group of zeros
+ * gets scale 1e-6 and codes 0, whatever its neighbours hold.  Every element is read once and written once; a group's maximum is a
+ * DPP reduction over the 16 lanes that hold its 16 chunks.
+ * Refused: group != 128 (WANQ_E_ARG); cols % 128 != 0 or cols > 16384 (WANQ_E_SHAPE); the NULL, dtype and act rules above.
+ * Bit-identical to wanq_quant_rows_fp8 applied to x viewed as [rows * cols / 128, 128] -- the definition; on the host
+ * qdiff/base/base_quantizer.py::fp8_quant_rows_grouped.  No reference counterpart. */
+int wanq_quant_rows_fp8_grouped(const void* x, int x_dtype, uint8_t* q, float* scale, int64_t rows, int cols, int group, int act,
+                                void* stream);
+
 /* OCP Microscaling (MX) block quantisation: one E8M0 power-of-two scale per block of 32 consecutive columns.  The activation
  * quantiser (fmt e4m3) and, once at conversion time, the weight quantiser (a weight [N, K] goes through it as rows = N, either
  * format) of wanq_gemm_mx.  For row r and block b (columns 32 b .. 32 b + 31):
@@ -669,6 +683,25 @@ int wanq_gemm_w8a8_grouped(const int8_t* a, const void* w, int w_bits, const flo
  * No reference counterpart (its 8-bit Linears are int8: ViDiT-Q/kernels/csrc/qgemm/w8a8/w8a8_gemm_cuda.cu). */
 int wanq_gemm_fp8(const uint8_t* a, const uint8_t* w, const float* sa, const float* sw, void* out, int out_dtype, const void* bias,
                   int bias_dtype, const float* gate, const void* residual, int epi_flags, int64_t M, int N, int K, void* stream);
+
+/* Fine-grained fp8 W8A8 GEMM: e4m3 activations and weights with one fp32 scale per 128 input channels on BOTH sides (both operands
+ * from wanq_quant_rows_fp8_grouped), partial sums promoted to the fp32 accumulator once per group.  wanq_gemm_fp8's kernel with
+ * another MFMA block: a K-tile is one group.  G = K / 128.
+ *   a: e4m3fn bytes [M, K];  w: e4m3fn bytes [N, K];  sa: fp32 [M, G], as the quantiser writes it;  sw: fp32 [G, N] -- GROUP-MAJOR, the
+ *   quantiser's [N, G] transposed once at conversion, so that a lane's four consecutive channels of a group are one 16-byte load.
+ *   part_g[m,n] = sum_{k in group g} a[m,k] * w[n,k]      (one v_mfma_scale_f32_16x16x128_f8f6f4 from a zero C operand, unit block scales)
+ *   acc[m,n]    = fmaf(part_g[m,n] * sa[m,g], sw[g,n], acc[m,n]),  g ascending from acc = 0     (this order: the token factor, then one fma)
+ *   y = acc + bias[n];  WANQ_EPI_GELU;  WANQ_EPI_GATE_RES;  one rounding to out_dtype -- wanq_gemm_bf16's epilogue, no scale left to apply.
+ * Shapes: group == 128 (WANQ_E_ARG otherwise); K % 128 == 0 (no half-deep tile here); any M >= 1; N % 8 == 0; a, w, out, residual and
+ * sw 16-byte aligned, sa 4-byte aligned, gate and bias aligned to 4 elements.  Anything else is refused (WANQ_E_SHAPE / WANQ_E_ARG, the
+ * message names the rule).
+ * Determinism: the summation order of element (m, n) is "groups ascending, inside a group the instruction's own": it depends on K
+ * only, so a row gives the same bits at any m and in a launch of any M.  With integer-valued operands and power-of-two scales whose
+ * partial sums stay below 2^24 the result is exact.
+ * No reference counterpart. */
+int wanq_gemm_fp8_grouped(const uint8_t* a, const uint8_t* w, const float* sa, const float* sw, int group, void* out, int out_dtype,
+                          const void* bias, int bias_dtype, const float* gate, const void* residual, int epi_flags, int64_t M, int N,
+                          int K, void* stream);
 
 /* MX GEMM: MXFP8 (e4m3) activations against MXFP8 (e4m3) or MXFP4 (e2m1) weights, both from wanq_quant_rows_mx, on
  * v_mfma_scale_f32_16x16x128_f8f6f4 with the E8M0 block scales applied by the matrix cores, and the epilogue of wanq_gemm_bf16:

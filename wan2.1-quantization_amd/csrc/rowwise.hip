@@ -367,6 +367,49 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const Fp8RowParams 
   if (f.lane == 0 && f.sub == 0) p.scale[f.row] = scale;
 }
 
+// ------------------------------------------------------------------------------ the same quantiser per group of 128 columns
+// wanq_quant_rows_fp8_grouped: the rule above applied to every group of 128 consecutive columns of a row, scale [rows, cols / 128].
+// A group is 16 consecutive 8-element chunks, and chunk slot i of a lane is chunk (a multiple of 64) + lane: the group sits in the 16
+// lanes of one DPP row at one slot (group 4 sub + 4 WPR i + (lane >> 4) of the row), in the four-wave form too.  Its maximum is
+// four DPP exchanges inside the row -- no reduction over the whole row, no LDS, no barrier -- and the row's first lane stores the
+// scale.  cols % 128 == 0, so a DPP row is inside the row of the tensor or past it as a whole.
+template <int WPR, int NCH>
+__global__ __launch_bounds__(256) void quant_rows_fp8_grouped_kernel(const Fp8RowParams p) {
+  RowFrame<WPR, NCH> f;
+  if (f.surplus(p.rows)) return;
+  const int C = p.cols;
+  const int64_t rbase = f.row * (int64_t)C;
+
+  float v[NCH][8];
+  bool ok[NCH];
+  f.load(p.x, p.x_dtype, rbase, C, v, ok);
+  if (p.act == 1) {
+#pragma unroll
+    for (int i = 0; i < NCH; ++i)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[i][j] = gelu_tanh_fast_f32(v[i][j]);  // (a slot past the row end stays 0)
+  }
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+    float m = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) m = fmaxf(m, fabsf(v[i][j]));
+    m = fmaxf(m, lane_xor_dpp<1>(m)); m = fmaxf(m, lane_xor_dpp<2>(m)); m = fmaxf(m, lane_xor_dpp<4>(m)); m = fmaxf(m, lane_xor_dpp<8>(m));
+    if (!ok[i]) continue;
+    const float scale = dyn_scale(m, FP8_E4M3_MAX, 1e-6f);
+    float t[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) t[j] = __builtin_amdgcn_fmed3f(v[i][j] / scale, -FP8_E4M3_MAX, FP8_E4M3_MAX);
+    int lo = __builtin_amdgcn_cvt_pk_fp8_f32(t[0], t[1], 0, false);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(t[2], t[3], lo, true);
+    int hi = __builtin_amdgcn_cvt_pk_fp8_f32(t[4], t[5], 0, false);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(t[6], t[7], hi, true);
+    const int col = f.col(i);
+    *reinterpret_cast<uint2*>(p.q + rbase + col) = make_uint2((uint32_t)lo, (uint32_t)hi);
+    if ((f.lane & 15) == 0) p.scale[(rbase + col) >> 7] = scale;  // [rows, cols / 128] row-major: (row * cols + col) / 128
+  }
+}
+
 // ------------------------------------------------------------------------------ OCP MX block quantiser (e4m3 / e2m1 codes, E8M0 scales)
 // One power-of-two scale per block of 32 consecutive columns: s = clamp(E(amax) - emax, 0, 254), c = rne(clamp(ldexp(x, 127 - s))).
 // The row frame and ladder of the other quantisers.  A block is four consecutive 8-element chunks, and chunk slot i of a lane is
@@ -587,6 +630,25 @@ extern "C" int wanq_quant_rows_fp8(const void* x, int x_dtype, uint8_t* q, float
   if (int e = check_rows_cols("wanq_quant_rows_fp8", rows, cols)) return e;
   if (rows == 0) return WANQ_OK;
   return launch_quant_rows_fp8<false>("wanq_quant_rows_fp8", {x, x_dtype, q, scale, rows, cols, act}, {}, (hipStream_t)stream);
+}
+
+extern "C" int wanq_quant_rows_fp8_grouped(const void* x, int x_dtype, uint8_t* q, float* scale, int64_t rows, int cols, int group,
+                                           int act, void* stream) {
+  const char* what = "wanq_quant_rows_fp8_grouped";
+  WANQ_REQUIRE(x && q && scale, WANQ_E_ARG, "%s: x, q and scale must be non-NULL", what);
+  WANQ_REQUIRE(is_fp(x_dtype), WANQ_E_ARG, "%s: bad x dtype %d", what, x_dtype);
+  WANQ_REQUIRE(act == 0 || act == 1, WANQ_E_ARG, "%s: act must be 0 or 1", what);
+  WANQ_REQUIRE(group == 128, WANQ_E_ARG, "%s: group=%d must be 128 (16 chunks of 8: one DPP row)", what, group);
+  if (int e = check_rows(what, rows)) return e;
+  WANQ_REQUIRE(cols >= 128 && cols % 128 == 0 && cols <= 16384, WANQ_E_SHAPE, "%s: cols=%d must be a multiple of 128 in [128, 16384]",
+               what, cols);
+  if (rows == 0) return WANQ_OK;
+  const Fp8RowParams p{x, x_dtype, q, scale, rows, cols, act};
+  row_ladder(cols, rows, [&](auto wpr, auto nch, dim3 grid) {
+    hipLaunchKernelGGL((quant_rows_fp8_grouped_kernel<decltype(wpr)::value, decltype(nch)::value>), grid, dim3(256), 0,
+                       (hipStream_t)stream, p);
+  });
+  return check_launch(what);
 }
 
 template <bool HAD>

@@ -210,23 +210,59 @@ def fp8_quant_rows(x, gelu=False):
     return codes, s.reshape(-1)
 
 
+FP8_GROUP = 128  # `group_size: 128` beside `format: fp8_e4m3`: the one group size of the grouped fp8 quantiser and GEMM
+
+
+def fp8_quant_rows_grouped(x, group_size=FP8_GROUP, gelu=False):
+    """(codes uint8 of x's shape, scale fp32 [rows, ceil(cols / group_size)]) of the fine-grained e4m3 quantiser: `fp8_quant_rows` of
+    every group of `group_size` consecutive columns of a row, i.e. fp8_quant_rows(x.view(-1, group_size)) reshaped -- that expression
+    is the definition.  On the GPU, for cols % 128 == 0, wanq_quant_rows_fp8_grouped, bit-equal to it.  A row length that is no
+    multiple of the group leaves a shorter last group, quantised like the others (simulation mode only: the kernels take whole
+    groups)."""
+    x2 = x.reshape(-1, x.shape[-1])
+    rows, cols = x2.shape
+    full = cols // group_size * group_size
+    if x2.is_cuda and full == cols and group_size == FP8_GROUP:
+        return fused.quant_rows_fp8_grouped(x2.contiguous(), group_size, gelu)
+    c, s = fp8_quant_rows(x2[:, :full].reshape(-1, group_size), gelu) if full else (x2.new_empty(0, dtype=torch.uint8), x2.new_empty(0))
+    codes, scale = c.reshape(rows, full), s.reshape(rows, full // group_size).float()
+    if full < cols:
+        ct, st = fp8_quant_rows(x2[:, full:], gelu)
+        codes, scale = torch.cat((codes, ct), 1), torch.cat((scale, st.reshape(rows, 1)), 1)
+    return codes, scale
+
+
+def fp8_group_expand(scale, group_size, cols):
+    """[rows, groups] -> [rows, cols]: every group's scale at each of its columns."""
+    return scale.repeat_interleave(group_size, dim=-1)[..., :cols]
+
+
 class Fp8Quantizer(BaseQuantizer):
     """`format: fp8_e4m3` of a `weight:` or `act:` section (n_bits 8, sym True): one fp32 scale per row -- per output channel for a
     weight, per token for an activation -- and OCP e4m3fn codes.  `delta` [rows, 1] is the scale, `zero_point` zeros, as the integer
     quantisers keep them (save / load_quant_param_dict).  The scale is a function of the tensor alone (absmax / 448, floored at
-    1e-6): nothing is fitted or calibrated, so it is derived again at every call, for a weight too."""
+    1e-6): nothing is fitted or calibrated, so it is derived again at every call, for a weight too.
+    With `group_size: 128` in the section (QuantizedLinear accepts it on both sides only) there is one scale per row and per group
+    of 128 columns (fp8_quant_rows_grouped): `delta` and the returned scale are [rows, G]."""
 
     def __init__(self, quant_config):
         super().__init__(quant_config)
         self.format = FP8_FORMAT
+        self.group_size = quant_config.get("group_size", None)
 
     def codes_and_scale(self, x, gelu=False):
+        if self.group_size is not None:
+            codes, scale = fp8_quant_rows_grouped(x, self.group_size, gelu)
+            self.delta, self.zero_point = scale, torch.zeros_like(scale)
+            return codes, scale
         codes, scale = fp8_quant_rows(x, gelu)
         self.delta, self.zero_point = scale.unsqueeze(-1), torch.zeros(scale.shape[0], 1, device=scale.device)
         return codes, scale
 
     def codes_and_dequant(self, x, want_codes=True, want_dequant=True):
         codes, scale = self.codes_and_scale(x)
+        if self.group_size is not None:
+            return codes, (fp8_decode(codes) * fp8_group_expand(scale, self.group_size, codes.shape[-1])) if want_dequant else None
         return codes, (fp8_decode(codes) * scale.unsqueeze(-1)) if want_dequant else None
 
     def quantize(self, x):

@@ -17,8 +17,8 @@ from viditq_extension import fused, qgemm
 
 from ..config import ListConfig
 from ..quarot import quarot_utils
-from .base_quantizer import (BLOCK_SCALES, FP8_FORMAT, MX_BLOCK, MX_FORMATS, MXFP4_FORMAT, MXFP6_FORMAT, MXFP8_FORMAT, DynamicQuantizer, Fp8Quantizer,
-                             MxQuantizer, StaticQuantizer, _pow2_f64, fp8_decode, mx_decode, mx_decode_mixed, mx_pair, mx_quant_rows_mixed)
+from .base_quantizer import (BLOCK_SCALES, FP8_FORMAT, FP8_GROUP, MX_BLOCK, MX_FORMATS, MXFP4_FORMAT, MXFP6_FORMAT, MXFP8_FORMAT, DynamicQuantizer, Fp8Quantizer,
+                             MxQuantizer, StaticQuantizer, _pow2_f64, fp8_decode, fp8_group_expand, mx_decode, mx_decode_mixed, mx_pair, mx_quant_rows_mixed)
 from .gptq import BLOCK_MAX, gptq_prepare, gptq_section, gptq_solve
 from .low_rank import RANK_MAX, LowRankBranch, fit_low_rank, padded_rank
 from .mixed_precision_quantizer import MixedPrecisionDynamicQuantizer, MixedPrecisionStaticQuantizer
@@ -48,12 +48,15 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         self.mx_act = None  # ... and the activation's
         self.mx_n8 = None  # `mx: {outlier_channels: n8}`: the first n8 channels of the order `mx_perm` are kept in MXFP8
         self.register_buffer("mx_perm", None, persistent=False)  # int32 [K], chosen from calibration statistics (select_outlier_perm)
+        self.fp8_group = None  # `group_size: 128` in both sections beside `format: fp8_e4m3` (set by _checked_format): the grouped form
         self.fp8 = self._checked_format(quant_config, module_name)
         self.mx_had32 = self._checked_mx_section(quant_config, module_name)  # `mx: {block_hadamard: True}`, W4A4 MX layers only
         # `block_scale: search` of the `weight:` / `act:` section, each side for itself (mxfp4_e2m1 sides only)
         self.mx_search_w, self.mx_search_act = self._checked_block_scale(quant_config, module_name)
         # (an MX layer's `weight.group_size: 32` names the format's own block: there is no integer group-wise path behind it)
-        self.group_size = None if self.mx else self._checked_group_size(quant_config, module_name, fp_module.weight.device)
+        # (... and an fp8 layer's is the grouped fp8 form's, checked with the format: no integer group-wise path either)
+        self.group_size = None if self.mx else self.fp8_group if self.fp8 else \
+            self._checked_group_size(quant_config, module_name, fp_module.weight.device)
         self.gptq = self._checked_gptq(quant_config, module_name)  # the `gptq:` section when it names this layer (gptq.py), or None
         self.w_quantizer = self.a_quantizer = None
         self.channel_mask = None
@@ -83,8 +86,9 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
 
     def _checked_format(self, quant_config, module_name):
         """True when the config's `weight:` and `act:` sections both say `format: fp8_e4m3` (per-token dynamic e4m3 activations against
-        per-channel e4m3 weights, wanq_gemm_fp8), False when neither has the key; every other combination is refused here, before
-        any weight is quantised, and the message names the layer and the key."""
+        per-channel e4m3 weights, wanq_gemm_fp8; with `group_size: 128` in both sections too, one scale per token or channel and per
+        128 input channels, wanq_gemm_fp8_grouped: `fp8_group`), False when neither has the key; every other combination is refused
+        here, before any weight is quantised, and the message names the layer and the key."""
         wq, aq = quant_config.get("weight", None), quant_config.get("act", None)
         fw, fa = (None if wq is None else wq.get("format", None)), (None if aq is None else aq.get("format", None))
         if fw is None and fa is None:
@@ -103,10 +107,17 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
             raise NotImplementedError(f"{name}: format: {FP8_FORMAT} must be set in both the `weight:` and the `act:` section (it is "
                                       f"missing from `{'weight' if fw is None else 'act'}:`): the fp8 GEMM takes e4m3 codes on both sides")
         self._check_format_sections(name, (("weight", wq, fw), ("act", aq, fa)))
-        if wq.get("group_size", None) is not None:
-            raise NotImplementedError(f"{name}: weight.format with weight.group_size is not supported: the fp8 GEMM applies one weight "
-                                      "scale per output channel")
+        gw, ga = wq.get("group_size", None), aq.get("group_size", None)
+        built = (f"the fp8 GEMM applies one weight scale per output channel; the built fine-grained form is weight.group_size: "
+                 f"{FP8_GROUP} together with act.group_size: {FP8_GROUP} (wanq_gemm_fp8_grouped)")
+        is_group = lambda g: not isinstance(g, bool) and g == FP8_GROUP  # noqa: E731
+        if gw is not None and not (is_group(gw) and is_group(ga)):
+            raise NotImplementedError(f"{name}: weight.format with weight.group_size={gw!r} and act.group_size={ga!r} is not supported: "
+                                      f"{built}")
+        if ga is not None and gw is None:
+            raise NotImplementedError(f"{name}: act.format with act.group_size={ga!r} and no weight.group_size is not supported: {built}")
         self._refuse_format_on_a_transformed_layer(name)
+        self.fp8_group = gw
         return True
 
     def _check_format_sections(self, name, sections):
@@ -515,14 +526,16 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
     @property
     def kind(self):
         """What this layer is now, the one place that says so: "fp" (quantisation off, or no `weight:` section: the FP module),
-        "weight_only" (no `act:` section), else by its format "fp8", "mx", "int8_grouped" (a `weight.group_size`) or "int8".  `forward`
+        "weight_only" (no `act:` section), else by its format "fp8", "fp8_grouped" (fp8 with `group_size: 128` on both sides), "mx", "int8_grouped" (a `weight.group_size`) or "int8".  `forward`
         dispatches on it and kernel mode maps it to a layer class (wan/quant_wanx_hip.py::_to_hip_linear).  A SmoothQuant / QuaRot /
         ViDiT layer without an `act:` section is "weight_only" too: `forward` runs its FP module, kernel mode refuses it by name."""
         if not self.quant_mode or self.w_quantizer is None:
             return "fp"
         if self.a_quantizer is None:
             return "weight_only"
-        return "fp8" if self.fp8 else "mx" if self.mx else "int8_grouped" if self.group_size is not None else "int8"
+        if self.fp8:
+            return "fp8" if self.fp8_group is None else "fp8_grouped"
+        return "mx" if self.mx else "int8_grouped" if self.group_size is not None else "int8"
 
     def forward(self, x, *args, **kwargs):
         """x: [B, N_token, C] (or [tokens, C]) on the GPU."""
@@ -568,6 +581,8 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         these are kernel mode's two entries per format, fused.quant_rows_fp8 + qgemm.fp8_linear and fused.quant_rows_mx +
         qgemm.mx_linear / qgemm.mx4_linear.  In host memory, and for a shape the GEMM refuses, the same numbers through torch: F.linear of the
         dequantised activation and the dequantised weight, in fp32."""
+        if self.fp8_group is not None:
+            return self._forward_fp8_grouped(x2, out_dtype, bias)
         if self.mx_n8 is not None:
             return self._forward_mx_mixed(x2, out_dtype, bias)
         if self._mx_admits("low_rank") and (self.low_rank is not None or self._adapter is not None):
@@ -580,6 +595,18 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
             return getattr(qgemm, gemm)(a_q, self._codes, a_s, w_s, *fmt, bias, out_dtype=out_dtype)
         # (with mx.block_hadamard the decoded activation and weight.data are both in the rotated domain: their product is x w^T's)
         a = mx_decode(a_q, a_s, self.mx_act) if self.mx else fp8_decode(a_q) * a_s.unsqueeze(-1)
+        return F.linear(a, self.weight.data.float(), bias).to(out_dtype)
+
+    def _forward_fp8_grouped(self, x2, out_dtype, bias):
+        """`format: fp8_e4m3` with `group_size: 128` on both sides: activation and weight are quantised per row and per group of 128
+        input channels (Fp8Quantizer's group form).  On the GPU the two entries of kernel mode, fused.quant_rows_fp8_grouped and
+        qgemm.fp8_grouped_linear on the layer's codes and its scales transposed to [G, N]; in host memory, and for a shape the GEMM
+        refuses (in_features % 128 != 0: a shorter last group), F.linear of the two decoded operands in fp32."""
+        a_q, a_s = self.a_quantizer.codes_and_scale(x2)
+        if x2.is_cuda and qgemm.fp8_grouped_linear_refusal(x2.shape[0], self.out_features, self.in_features) is None:
+            return qgemm.fp8_grouped_linear(a_q, self._codes, a_s, self.w_quantizer.delta.float().t().contiguous(), self.fp8_group, bias,
+                                            out_dtype=out_dtype)
+        a = fp8_decode(a_q) * fp8_group_expand(a_s, self.fp8_group, self.in_features)
         return F.linear(a, self.weight.data.float(), bias).to(out_dtype)
 
     def _forward_mx4_low_rank(self, x2, out_dtype, bias):
@@ -613,7 +640,8 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         y = qgemm.w8a8_grouped_linear(q, codes, scale, sw, zp, self.group_size, bias, out_dtype=out_dtype, w4=w4)
         return self._add_act_zero_point_term(y, scale)
 
-    _FORWARDS = {"int8": _forward_int8, "int8_grouped": _forward_grouped, "fp8": _forward_format, "mx": _forward_format}
+    _FORWARDS = {"int8": _forward_int8, "int8_grouped": _forward_grouped, "fp8": _forward_format, "fp8_grouped": _forward_format,
+                 "mx": _forward_format}
 
     def weight_only_operands(self):
         """(codes, scale fp32 [N], zp fp32 [N] or None, w4) of wanq_gemm_wq16 for this layer's quantised weight: int8 codes, or the

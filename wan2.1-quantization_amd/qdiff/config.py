@@ -7,7 +7,9 @@ section the layer's weight must be on the GPU; QuantizedLinear refuses everythin
 `format: fp8_e4m3` in BOTH the `weight:` and the `act:` section -- OCP e4m3fn codes with one fp32 scale per output channel and per
 token (absmax / 448) instead of int8 codes, on wanq_gemm_fp8; `n_bits: 8, sym: True` stay as written.  Refused by layer name when
 the layer is built: the key in only one section, with `group_size`, with `sym: False`, with `n_bits` other than 8 or a bit-width
-list, and on a SmoothQuant / QuaRot / ViDiT layer.
+list, and on a SmoothQuant / QuaRot / ViDiT layer.  One `group_size` form is built: `group_size: 128` in BOTH sections beside the
+format -- one scale per token or output channel AND per 128 input channels, each group's partial product promoted to fp32 with its
+two scales (wanq_quant_rows_fp8_grouped, wanq_gemm_fp8_grouped); the key on one side only and any other value stay refused.
 The OCP Microscaling formats use the same key: `format: mxfp8_e4m3` (`n_bits: 8`) and `format: mxfp4_e2m1` (`n_bits: 4`) in `act:` and
 in `weight:` -- one E8M0 power-of-two scale per block of 32 input channels on both sides, applied by the matrix cores
 (wanq_quant_rows_mx, wanq_gemm_mx, wanq_gemm_mx4).  The accepted pairs are weight mxfp8_e4m3 or mxfp4_e2m1 against act mxfp8_e4m3, and

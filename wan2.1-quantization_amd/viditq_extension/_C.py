@@ -60,6 +60,8 @@ PROTOTYPES = {
     "wanq_gemm_w8a8_grouped": [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
     "wanq_quant_rows_fp8": [_vp, _i, _vp, _vp, _i64, _i, _i, _vp],
     "wanq_gemm_fp8": [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
+    "wanq_quant_rows_fp8_grouped": [_vp, _i, _vp, _vp, _i64, _i, _i, _i, _vp],
+    "wanq_gemm_fp8_grouped": [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
     "wanq_quant_rows_mx": [_vp, _i, _vp, _vp, _i64, _i, _i, _i, _vp],
     "wanq_gemm_mx": [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp],
     "wanq_quant_rows_mx_had32": [_vp, _i, _vp, _vp, _i64, _i, _i, _i, _vp],

@@ -91,6 +91,26 @@ def quant_rows_fp8(x, gelu=False):
     return codes, scale
 
 
+FP8_GROUP = 128  # the one group size of wanq_quant_rows_fp8_grouped / wanq_gemm_fp8_grouped: a K-tile of the fp8 GEMM
+
+
+def quant_rows_fp8_grouped(x, group_size=FP8_GROUP, gelu=False):
+    """`quant_rows_fp8` with one scale per row and per group of 128 consecutive columns (wanq_quant_rows_fp8_grouped): -> (codes uint8
+    of x's shape; scale fp32 [rows, cols / 128]), the bits of `quant_rows_fp8(x.view(-1, 128), gelu)` reshaped.  cols % 128 == 0.
+    Activations per token, and a weight [N, K] per output channel (its scales go to the GEMM transposed, [K / 128, N])."""
+    rows, cols = _rows_cols("x", x)
+    if group_size != FP8_GROUP:
+        raise RuntimeError(f"quant_rows_fp8_grouped: group_size={group_size!r} must be {FP8_GROUP}")
+    if cols % FP8_GROUP:
+        raise RuntimeError(f"quant_rows_fp8_grouped: cols={cols} must be a multiple of {FP8_GROUP}")
+    codes = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    scale = torch.empty(rows, cols // FP8_GROUP, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _C.call("wanq_quant_rows_fp8_grouped", _C.ptr(x), _C.dt(x), _C.ptr(codes), _C.ptr(scale), rows, cols, FP8_GROUP,
+                1 if gelu else 0, _C.stream())
+    return codes, scale
+
+
 # fmt -> (C entry, its format-code argument if it takes one (it then has a `_had32` twin))
 _MX_ROW_ENTRY = {"mxfp6_e2m3fn": ("wanq_quant_rows_mx6", ()), **{f: ("wanq_quant_rows_mx", (c,)) for f, c in _C.MX_FMT.items()}}
 

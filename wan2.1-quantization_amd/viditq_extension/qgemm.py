@@ -492,6 +492,40 @@ def fp8_linear_refusal(M, N, K):
     return _shape_refusal(M, N, K, FP8_K_STEP, bounded=True)
 
 
+FP8_GROUP = 128  # wanq_gemm_fp8_grouped's group size and K multiple: one K-tile of the fp8 kernel is one scale group
+
+
+def fp8_grouped_linear(a_q, w_q, a_scale, w_scale, group_size, bias=None, out_dtype=None, gelu=False, gate=None, residual=None,
+                       out=None):
+    """y = epilogue(sum_g a_scale[m, g] * w_scale[g, n] * a_q[M, K_g] @ w_q[N, K_g]^T) on the fp8 matrix cores (wanq_gemm_fp8_grouped,
+    csrc/gemm_fp8.hip): a_q and w_q uint8 e4m3fn bytes as `fused.quant_rows_fp8_grouped` writes them; a_scale fp32 [M, K / 128] as it
+    writes them, w_scale fp32 [K / 128, N] (its scales of the weight, transposed: group-major).  Each group's fp32 partial product
+    is folded into the result as acc = fma(part * a_scale[m, g], w_scale[g, n], acc), groups ascending; then + bias and the epilogue
+    of `fp8_linear`, one rounding to out_dtype (default bf16).  group_size == 128, K % 128 == 0, N % 8 == 0.  A row's bits do not
+    depend on M or on where the row sits in the launch.  Not counted by the int8 timer (`set_timer`)."""
+    for name, t in (("a_q", a_q), ("w_q", w_q)):
+        _check_mat(name, t, torch.uint8)
+    M, K = a_q.shape
+    N = w_q.shape[0]
+    _C.check_shape("w_q", w_q, N, K)
+    if group_size != FP8_GROUP:
+        raise RuntimeError(f"fp8_grouped_linear: group_size={group_size!r} must be {FP8_GROUP}")
+    why = fp8_grouped_linear_refusal(M, N, K)
+    if why is not None:
+        raise RuntimeError(f"fp8_grouped_linear: {why}")
+    if a_scale is None or w_scale is None:
+        raise RuntimeError("fp8_grouped_linear: a_scale and w_scale must be given")
+    _check_mat("a_scale", a_scale, torch.float32, M, K // FP8_GROUP)
+    _check_mat("w_scale", w_scale, torch.float32, K // FP8_GROUP, N)
+    return _launch16("wanq_gemm_fp8_grouped", (_C.ptr(a_q), _C.ptr(w_q), _C.ptr(a_scale), _C.ptr(w_scale), FP8_GROUP),
+                     (a_q, w_q, a_scale, w_scale), bias, out_dtype or torch.bfloat16, gelu, gate, residual, out, M, N, K)
+
+
+def fp8_grouped_linear_refusal(M, N, K):
+    """Why wanq_gemm_fp8_grouped would refuse an [M, K] x [N, K] product (None = accepted); see `fp8_linear_refusal`."""
+    return _shape_refusal(M, N, K, FP8_GROUP, bounded=True)
+
+
 # ---- OCP MX: MXFP8 (e4m3) activations x MXFP8 / MXFP4 weights, E8M0 block scales ---------------------------------------------------
 MX_K_STEP = 128  # wanq_gemm_mx's K multiple: one K-tile = one 128-deep MFMA = four blocks of 32
 

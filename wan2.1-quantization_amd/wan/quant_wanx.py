@@ -30,7 +30,9 @@ def _mx_state(layer):
     return SimpleNamespace(pair=mx_pair(layer.mx, layer.mx_act if sim else getattr(layer, "a_fmt", None)),
                            had32=bool(layer.mx_had32 if sim else getattr(layer, "had32", False)),
                            n8=layer.mx_n8 if sim else getattr(layer, "n8", None), perm=getattr(layer, "mx_perm", None),
-                           search=bool(layer.mx_search_act if sim else getattr(layer, "search", False)))
+                           search=bool(layer.mx_search_act if sim else getattr(layer, "search", False)),
+                           # (not MX, but recorded the same way: the group size of a grouped fp8 layer)
+                           fp8_group=(layer.fp8_group if sim else getattr(layer, "group_size", None)) if layer.fp8 else None)
 
 
 def _said_fmt(v):
@@ -58,6 +60,10 @@ _MX_RECORDS = (
     ("mx_perm", lambda s: s.n8 is not None, lambda s: s.perm.detach().to(torch.int32).cpu().clone(), None, None),
     ("mx_n8", lambda s: s.n8 is not None, lambda s: torch.tensor([s.n8], dtype=torch.int32), lambda v: None if v is None else int(v.reshape(-1)[0]),
      lambda f, o: f"was saved with mx.outlier_channels {f} and the model's layer was built with {o}"),
+    # fp8_group: `group_size: 128` beside `format: fp8_e4m3`; scale_weight is then [K / 128, N] (a file without it: one scale per channel)
+    ("fp8_group", lambda s: s.fp8_group is not None, lambda s: torch.tensor([s.fp8_group], dtype=torch.int32),
+     lambda v: None if v is None else int(v.reshape(-1)[0]),
+     lambda f, o: f"was saved with fp8 group_size {f} and the model's layer was built with {o}"),
 )
 
 
@@ -142,7 +148,8 @@ class QuantWanModel(WanModel, QuantModel):
                         sd[name + ".bias"] = mod.bias.detach().to(f16).clone()
                 else:
                     # 8-bit: int8 [N, K]; 4-bit: uint8 [N, K/2], the packed nibbles exactly as the GEMM reads them; format: fp8_e4m3:
-                    # uint8 [N, K], the e4m3 bytes, with their per-channel scales
+                    # uint8 [N, K], the e4m3 bytes, with their per-channel scales -- with `group_size: 128` their [K / 128, N] scales, as
+                    # the grouped GEMM reads them, and `fp8_group`
                     # (weight.group_size: the parameters as the group-wise GEMM reads them, [K / g, N]); format: mxfp8_e4m3 /
                     # mxfp4_e2m1: uint8 [N, K] e4m3 bytes / uint8 [N, K/2] packed e2m1 nibbles, scale_weight uint8 [N, K/32] E8M0 bytes;
                     # mxfp6_e2m3fn: uint8 [N, 3K/4] packed e2m3 codes, and `mx_fmt` with either weight of an e2m3-activation layer

@@ -367,22 +367,42 @@ class HipLinearFp8(_HipLinearCodes):
     """An fp8 W8A8 Linear (`format: fp8_e4m3` in the config's `weight:` and `act:` sections): `weight` uint8 [N, K], OCP e4m3fn codes
     of the weight quantised per output channel by wanq_quant_rows_fp8; `scale_weight` fp32 [N], absmax / 448; `bias` fp32.  Its input
     is the block's activation quantised per token by the same entry (codes + fp32 scale), and the product is qgemm.fp8_linear
-    (csrc/gemm_fp8.hip) with GELU and gate + residual in its epilogue."""
+    (csrc/gemm_fp8.hip) with GELU and gate + residual in its epilogue.
+    `group_size` = 128 (`group_size: 128` in both sections of the config): the fine-grained form.  `weight` is quantised per output
+    channel and per 128 input channels by wanq_quant_rows_fp8_grouped and `scale_weight` is fp32 [K / 128, N], the quantiser's
+    [N, K / 128] transposed once (`from_quantized`); the input is quantised per token and per 128 channels by the same entry
+    (activation form "fp8_g128", its scales [M, K / 128]) and the product is qgemm.fp8_grouped_linear.  The scales are a thirty-second
+    of the codes' bytes, so --dit_fsdp shards them with the codes; the one-element int32 buffer `fp8_group` records the group size in
+    the integer checkpoint."""
     fp8 = True
     act_form = act_key = "fp8"
 
-    def __init__(self, in_features, out_features, bias=True, name="linear"):
-        super().__init__(in_features, out_features, bias, "fp8_e4m3", qgemm.fp8_linear_refusal(1, out_features, in_features),
-                         in_features, (out_features,), torch.float32, name)
+    def __init__(self, in_features, out_features, bias=True, name="linear", group_size=None):
+        if group_size is not None and group_size != qgemm.FP8_GROUP:
+            raise NotImplementedError(f"{name}: format: fp8_e4m3 with group_size={group_size!r} has no kernel-mode form: the grouped "
+                                      f"fp8 GEMM takes groups of {qgemm.FP8_GROUP}")
+        grouped = group_size is not None
+        why = (qgemm.fp8_grouped_linear_refusal if grouped else qgemm.fp8_linear_refusal)(1, out_features, in_features)
+        super().__init__(in_features, out_features, bias, "fp8_e4m3" + (f" with group_size: {group_size}" if grouped else ""), why, in_features,
+                         (in_features // group_size, out_features) if grouped else (out_features,), torch.float32, name)
+        self.group_size = group_size
+        if grouped:
+            self.act_form = self.act_key = "fp8_g128"
+            self.sharded = ("weight", "scale_weight")
+            self.register_buffer("fp8_group", torch.tensor([group_size], dtype=torch.int32))
 
     @classmethod
     def from_quantized(cls, ql, name="linear"):
-        """From a plain qdiff QuantizedLinear built with `format: fp8_e4m3`: the same codes and scales."""
-        m = cls(ql.in_features, ql.out_features, ql.bias is not None, name).to(ql.fp_module.weight.device)
-        return m._take(ql, ql.w_quantizer.delta.reshape(-1).float(), name)
+        """From a plain qdiff QuantizedLinear built with `format: fp8_e4m3`: the same codes and scales (the grouped form's transposed)."""
+        m = cls(ql.in_features, ql.out_features, ql.bias is not None, name, ql.fp8_group).to(ql.fp_module.weight.device)
+        delta = ql.w_quantizer.delta.float()
+        return m._take(ql, delta.reshape(-1) if ql.fp8_group is None else delta.t(), name)
 
     def forward(self, a_q, a_scale, out_dtype=torch.bfloat16, gelu=False, gate=None, residual=None, out=None):
-        """Reads `weight` as it is now (--dit_fsdp re-points it at views of the gathered buffer)."""
+        """Reads `weight` (and the grouped form's `scale_weight`) as it is now (--dit_fsdp re-points it at views of the gathered buffer)."""
+        if self.group_size is not None:
+            return qgemm.fp8_grouped_linear(a_q, self.weight, a_scale, self.scale_weight, self.group_size, self.bias, out_dtype, gelu=gelu,
+                                            gate=gate, residual=residual, out=out)
         return qgemm.fp8_linear(a_q, self.weight, a_scale, self.scale_weight, self.bias, out_dtype, gelu=gelu, gate=gate,
                                 residual=residual, out=out)
 
@@ -502,7 +522,7 @@ class HipLinearMx(LowRankBranch, _HipLinearCodes):
 
 # QuantizedLinear.kind -> the layer class that takes it over ("fp": the layer's FP module, below)
 _HIP_LINEAR_OF = {"int8": HipLinearW8A8, "int8_grouped": HipLinearW8A8, "weight_only": HipLinearWq16, "fp8": HipLinearFp8,
-                  "mx": HipLinearMx}
+                  "fp8_grouped": HipLinearFp8, "mx": HipLinearMx}
 
 
 def _to_hip_linear(lin, n_bits, sym, act_dtype, fp_gemm="torch", name="linear"):
@@ -524,7 +544,7 @@ def _to_hip_linear(lin, n_bits, sym, act_dtype, fp_gemm="torch", name="linear"):
 
 # activation form -> the fused row quantiser that makes it and its arguments, (codes, scales) = f(rows, gelu=, **arguments): fp8, and
 # the form of every MX pair (base_quantizer.MX_PAIRS), plain and -- where the pair admits it -- behind the block rotation
-_ROW_QUANTISERS = {"fp8": ("quant_rows_fp8", {}),
+_ROW_QUANTISERS = {"fp8": ("quant_rows_fp8", {}), "fp8_g128": ("quant_rows_fp8_grouped", {}),
                    **{p.act_form: ("quant_rows_mx", {"fmt": p.a_fmt}) for p in MX_PAIRS.values()},
                    **{p.act_form + "_h32": ("quant_rows_mx", {"fmt": p.a_fmt, "had32": True}) for p in MX_PAIRS.values() if p.had32},
                    # e2m1 activations under `act.block_scale: search`: a form of their own, so that only layers of the same rule share
@@ -645,11 +665,12 @@ class _LnSrc(_Src):
         """Materialise every plain-row form (a key of _ROW_QUANTISERS: fp8, the MX forms, rotated and scale-searched) among the
         consumers `lins` by the fused LayerNorm + modulate + quantise producer of that form (fused.layernorm_quant_rows_*), once per
         form: one pass over x and no fp32 row in memory, with the bits of `rows`'s two launches.  Consumers that take the mixed
-        (outlier-channel) form or carry a low-rank branch are left to `rows_mixed` / `project`, which read the fp32 row."""
+        (outlier-channel) form or carry a low-rank branch are left to `rows_mixed` / `project`, which read the fp32 row; so is a form
+        whose quantiser has no fused twin (fp8_g128: `rows` makes it from the fp32 row, two launches)."""
         for lin in lins:
             form = lin.act_form
             if form in self.cache or form not in _ROW_QUANTISERS or not lin.plain_rows or getattr(lin, "has_branch", False) or \
-                    lin.act_quantizer is not None:
+                    lin.act_quantizer is not None or not hasattr(fused, "layernorm_" + _ROW_QUANTISERS[form][0]):
                 continue
             name, args = _ROW_QUANTISERS[form]
             self.cache[form] = getattr(fused, "layernorm_" + name)(self.x, self.gamma, self.shift, self.scale, self.blk.eps, **args)
