@@ -420,6 +420,28 @@ int wanq_gptq_block_gidx(float* w, int64_t w_stride, const float* u, int64_t u_s
                          const int32_t* g_idx, int G, int qmin, int qmax, int8_t* codes, float* err, int64_t N, int K, int c0,
                          int cols, void* stream);
 
+/* The clip search of the integer weight quantisers (AWQ's auto-clip; StaticQuantizer.search_clip drives it; csrc/clip_search.hip): per
+ * quantiser row the grid of wanq_weight_quant with the row's extremes scaled by r_s = 1 - s / steps, s = 0 .. n_cand-1, and of
+ * those the one with the smallest objective (a tie, and a NaN objective, keep the lower s; s = 0 is the un-clipped grid).
+ * A candidate, every operation one fp32 IEEE operation, never contracted:
+ *   sym != 0:  delta = (absmax r) / (2^(n_bits-1) - 1), zp = 0
+ *   sym == 0:  hi' = max(hi, 0) r, lo' = min(lo, 0) r, delta = (hi' - lo') / (2^n_bits - 1), zp = rne(lo' / delta) + 2^n_bits / 2
+ *   q = clamp(rne(w / delta) - zp, qmin, qmax),  e = fma(-(q + zp), delta, w)  (the exact error, rounded once)
+ * Outputs: delta, zp fp32 [R], sel int32 [R] (the chosen s), and, when table is not NULL, the objectives fp32 [R, n_cand].
+ * wanq_clip_search: w fp32 [rows, cols] (R = rows; for a group-wise quantiser the weight viewed as [N K / g, g]); objective
+ *   sum_j h_j e_j^2 with h = 1 (chan_w NULL) or h_j = chan_w[(row % (chan_len / cols)) * cols + j], chan_w fp32 [chan_len] (the
+ *   Hessian's diagonal): summed in fp32 down a lane's elements, then over the lanes, then over the waves of the row.
+ * wanq_clip_search_blocks: w fp32 [N, K] (R = N K / g, row n K / g + gi); objective e H e^T with H = hblocks[gi], the g x g diagonal
+ *   block of the layer's Hessian, hblocks fp32 [K / g, g, g] contiguous; T = e H on v_mfma_f32_32x32x2_f32, then sum_c T[c] e[c].
+ * Refused before any launch (WANQ_E_ARG / WANQ_E_SHAPE, the message names the rule): NULL or misaligned (16 bytes) w / chan_w /
+ * hblocks, NULL delta / zp / sel, n_bits outside 2..8, a range that is not an int8 range, steps outside 1..64, n_cand outside
+ * 1..steps, cols no multiple of 8 in [8, 16384], chan_len no multiple of cols, g other than 32 / 64 / 128, K no multiple of g.
+ * rows == 0 / N == 0: WANQ_OK. */
+int wanq_clip_search(const float* w, const float* chan_w, int chan_len, int n_bits, int sym, int qmin, int qmax, int steps,
+                     int n_cand, float* delta, float* zp, int32_t* sel, float* table, int64_t rows, int cols, void* stream);
+int wanq_clip_search_blocks(const float* w, const float* hblocks, int g, int n_bits, int sym, int qmin, int qmax, int steps,
+                            int n_cand, float* delta, float* zp, int32_t* sel, float* table, int64_t N, int K, void* stream);
+
 /* H += x^T x in fp32, in place: the Hessian of a Linear's calibration inputs (csrc/gram.hip).
  *   x  row-major [rows, C], WANQ_BF16 or WANQ_F16, read as it lies (no transposed copy);  H  fp32 [C, C], row stride C.
  * The contraction runs over the rows on v_mfma_f32_16x16x32_{bf16,f16}, 32 rows a step from row 0 upwards; rows past `rows` in the

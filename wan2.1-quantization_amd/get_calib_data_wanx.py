@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Calibration data collection -- entry point 2/4 (ViDiT-Q/examples/Wan2.1/get_calib_data_wanx.py): run the FP model
 with a forward hook on every nn.Linear that keeps the per-input-channel absmax (HIP reduction, running max on the
-device), and save {layer_name: [1, C_in]} to quant_config.calib_data.save_path.  With --hessian, or a `gptq:` section in the quant
-config, a second hook accumulates H = X^T X of the inputs (wan/calib.py GramHook) and {layer_name: fp32 [C_in, C_in]} is saved to
+device), and save {layer_name: [1, C_in]} to quant_config.calib_data.save_path.  With --hessian, or a `gptq:` section or a
+`weight.clip` search of `diag` / `hessian` in the quant config, a second hook accumulates H = X^T X of the inputs (wan/calib.py GramHook) and {layer_name: fp32 [C_in, C_in]} is saved to
 calib_data.hessian_path (--hessian_path), for ptq_wanx.py's GPTQ solve."""
 import logging
 import os
@@ -12,6 +12,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch  # noqa: E402
 
 from qdiff import config as qcfg  # noqa: E402
+from qdiff.base.gptq import clip_needs_hessian  # noqa: E402
 from wan import calib, cli  # noqa: E402
 from wan.configs import SIZE_CONFIGS  # noqa: E402
 from wan.text2video import WanT2V  # noqa: E402
@@ -33,12 +34,13 @@ def main(args):
     logging.info("hooked %d Linear layers", len(hooks))
     # --hessian (implied by a `gptq:` section): H = X^T X of every Linear input the section names, for ptq_wanx.py's GPTQ solve
     gptq = quant_config.get("gptq", None)
+    clip = clip_needs_hessian(quant_config)  # weight.clip.search: diag / hessian reads them too, for every quantised Linear
     gram_hooks = None
-    if args.hessian or gptq is not None:
+    if args.hessian or gptq is not None or clip:
         hessian_path = args.hessian_path or (quant_config.get("calib_data", None) or {}).get("hessian_path", None)
         if hessian_path is None:
             raise ValueError("--hessian needs a place to save to: --hessian_path, or calib_data.hessian_path in the quant config")
-        gram_hooks = calib.add_gram_hooks(t2v.model, "" if gptq is None else gptq.get("layer_name_regex", ""))
+        gram_hooks = calib.add_gram_hooks(t2v.model, "" if gptq is None or clip else gptq.get("layer_name_regex", ""))
         logging.info("collecting Hessians of %d Linear layers", len(gram_hooks))
     prompts = cli.read_prompts(args)
     if sharded:

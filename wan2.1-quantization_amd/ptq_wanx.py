@@ -38,13 +38,21 @@ def main(args):
                                  if (m.uses_mask or m.uses_rotation or m.mx_n8 is not None) else None, full_name="", calib_data=calib_data)
     if quant_config.get("mixed_precision", None) is not None:
         model.bitwidth_refactor()
-    if quant_config.get("gptq", None) is not None:
-        # GPTQ (qdiff/base/gptq.py): the layers the section names get their codes from the solver, on the Hessians that
-        # get_calib_data_wanx.py --hessian saved; scales and zero points stay the round-to-nearest ones
+    if quant_config.get("gptq", None) is not None or gptq.clip_needs_hessian(quant_config):
         hp = args.hessian_path or (quant_config.get("calib_data", None) or {}).get("hessian_path", None)
         if hp is None:
-            raise ValueError("a `gptq:` section needs the Hessian file: --hessian_path, or calib_data.hessian_path in the quant config")
-        n = gptq.requantize_model_(model, quant_config, gptq.load_hessians(hp), hp)
+            raise ValueError("a `gptq:` section and weight.clip.search: diag / hessian need the Hessian file: --hessian_path, or "
+                             "calib_data.hessian_path in the quant config")
+        hessians = gptq.load_hessians(hp)
+    if gptq.clip_needs_hessian(quant_config):
+        # the clip search (StaticQuantizer.search_clip): delta / zero_point of every such layer are fitted on its Hessian, first,
+        # so that GPTQ below solves on the clipped grid
+        n = gptq.clip_model_(model, hessians, hp)
+        logging.info("clip search: fitted the grids of %d Linear layers on the Hessians of %s", n, hp)
+    if quant_config.get("gptq", None) is not None:
+        # GPTQ (qdiff/base/gptq.py): the layers the section names get their codes from the solver, on the Hessians that
+        # get_calib_data_wanx.py --hessian saved; scales and zero points stay the grid's (round-to-nearest's, or the clip search's)
+        n = gptq.requantize_model_(model, quant_config, hessians, hp)
         logging.info("GPTQ: solved %d Linear layers on the Hessians of %s", n, hp)
     model.set_init_done()
     params = model.save_quant_param_dict()

@@ -3,6 +3,7 @@ with `delta` / `zero_point` buffers ([G,1]) and an `init_done` flag.  All heavy 
 (viditq_extension.fused): row statistics, static quantisation and the per-token dynamic quantiser; the [G]-sized
 parameter arithmetic is plain fp32 torch (IEEE, bit-identical to the reference's CPU result).
 Tensors must live on the GPU: there is no CPU path."""
+import math
 from typing import NamedTuple
 
 import torch
@@ -12,6 +13,7 @@ from viditq_extension import fused
 from viditq_extension._C import MX_BLOCK_BYTES  # bytes of a block's 32 codes in a row of the operand, by format name
 
 from ..config import ListConfig
+from .gptq import stored_range
 
 
 class BaseQuantizer(nn.Module):
@@ -49,15 +51,50 @@ def static_params(x, n_bits, sym):
     return delta, torch.round(lo / delta) + n_levels / 2
 
 
+CLIP_SEARCHES = ("mse", "diag", "hessian")  # the `search` key of a `weight.clip` section: the row objective (StaticQuantizer)
+CLIP_STEPS_MAX = 64                         # the kernels' bound on `steps`
+CLIP_BLOCK_GROUPS = (32, 64, 128)           # the group sizes wanq_clip_search_blocks takes (`search: hessian`)
+
+
+def clip_candidates(steps, max_shrink):
+    """The number of candidates of a `clip:` section, floor(max_shrink steps): s = 0 .. that - 1."""
+    return int(math.floor(max_shrink * steps + 1e-9))
+
+
+def clip_ratios(steps, n_cand, device=None):
+    """r_s = 1 - s / steps for s < n_cand, fp32 [n_cand]: the one expression of a candidate's ratio (csrc/clip_search.hip evaluates
+    the same two fp32 operations)."""
+    s = torch.arange(n_cand, dtype=torch.float32, device=device)
+    return 1.0 - s / _full(s, steps)
+
+
+def clip_params(lo, hi, r, n_bits, sym):
+    """(delta, zero_point) of `static_params` with the row extremes lo / hi scaled by the ratio r (fp32 tensors that broadcast):
+    the grid of a clip candidate, bit-equal to what wanq_clip_search / wanq_clip_search_blocks return.  r = 1 is static_params."""
+    if sym:
+        am = torch.maximum(lo.abs(), hi.abs()) * r
+        return am / _full(am, 2 ** (n_bits - 1) - 1), torch.zeros_like(am)
+    n_levels = 2 ** n_bits
+    hi, lo = hi.clamp_min(0.0) * r, lo.clamp_max(0.0) * r
+    delta = (hi - lo) / _full(hi, n_levels - 1)
+    return delta, torch.round(lo / delta) + n_levels / 2
+
+
 class StaticQuantizer(BaseQuantizer):
     """Per-row (output channel) static quantizer for weights.
     `group_size` g (the `weight.group_size` key): one (delta, zero_point) per row and per group of g input channels -- this same
     quantiser on w.view(N K / g, g), the [N_group, -1] input the reference's quantisers are written for (base_quantizer.py:72).
-    `delta` / `zero_point` are then [N, K / g]; codes and the dequantised weight keep w's shape."""
+    `delta` / `zero_point` are then [N, K / g]; codes and the dequantised weight keep w's shape.
+    `clip` (the `weight.clip` key, checked by QuantizedLinear._checked_clip): every row's extremes are scaled by the ratio
+    1 - s / steps, s < floor(max_shrink steps), that minimises the row's objective (csrc/clip_search.hip).  `search: mse` needs the
+    weight alone and is part of init_quant_params; `diag` / `hessian` need the layer's Hessian: init_quant_params gives the s = 0
+    grid (today's) and `search_clip(w, H)` is the PTQ step.  A clipped quantiser clamps to the stored range of its bit width."""
 
     def __init__(self, quant_config):
         super().__init__(quant_config)
         self.group_size = quant_config.get("group_size", None)
+        c = quant_config.get("clip", None)
+        self.clip = None if c is None else {"search": c["search"], "steps": c.get("steps", 20), "max_shrink": c.get("max_shrink", 0.5)}
 
     def _group_rows(self, x):
         """x [N, K] as the quantiser's rows: itself, or [N K / g, g]"""
@@ -70,17 +107,45 @@ class StaticQuantizer(BaseQuantizer):
         return x.view(-1, g)
 
     def init_quant_params(self, x):
+        if getattr(self, "clip", None) is not None and self.clip["search"] == "mse":
+            self.search_clip(x)
+            return
         delta, zp = static_params(self._group_rows(x), self.n_bits, self.sym)
+        self._set_params(x, delta, zp)
+
+    def _set_params(self, x, delta, zp):
         if not torch.all(delta > 1e-6):
             raise AssertionError("unexpected small delta exists")  # the reference drops into ipdb here (:94-97)
         self.delta, self.zero_point = delta.view(x.shape[0], -1), zp.view(x.shape[0], -1)  # [N, 1], or [N, K / g]
+
+    def search_clip(self, x, H=None, want_table=False):
+        """Fit delta / zero_point of the weight x [N, K] by the `clip` search: -> (the chosen s int32, the objectives fp32 or None),
+        both per quantiser row ([N K / g], [N K / g, S]).  `mse`: no H.  `diag`: H's diagonal weighs the squared errors.  `hessian`:
+        e H_gg e^T on the g x g diagonal blocks of H, which are cut from H (fp32 [K, K], possibly memory mapped) one at a time: the
+        whole matrix never moves."""
+        c = self.clip
+        n_cand = clip_candidates(c["steps"], c["max_shrink"])
+        args = (self.n_bits, self.sym, *stored_range(self), c["steps"], n_cand)
+        x = x.detach().float().contiguous()
+        if c["search"] == "hessian":
+            g = self.group_size
+            blocks = torch.stack([H[k:k + g, k:k + g] for k in range(0, x.shape[1], g)]).to(device=x.device, dtype=torch.float32)
+            delta, zp, s, table = fused.clip_search_blocks(x, blocks.contiguous(), *args, want_table=want_table)
+        else:
+            h = None if c["search"] == "mse" else torch.diagonal(H).to(device=x.device, dtype=torch.float32).contiguous()
+            delta, zp, s, table = fused.clip_search(self._group_rows(x), *args, chan_w=h, want_table=want_table)
+        self._set_params(x, delta, zp)
+        return s, table
 
     def codes_and_dequant(self, x, want_codes=True, want_dequant=True):
         if self.init_done is not True:
             self.init_quant_params(x)
         n = self.n_levels
+        lo, hi = -n - 1, n
+        if getattr(self, "clip", None) is not None:  # clipping is the point: the fake-quant value saturates where the codes do
+            lo, hi = stored_range(self)
         codes, deq = fused.weight_quant(self._group_rows(x), self.delta.reshape(-1).float().contiguous(),
-                                        self.zero_point.reshape(-1).float().contiguous(), -n - 1, n, want_codes, want_dequant)
+                                        self.zero_point.reshape(-1).float().contiguous(), lo, hi, want_codes, want_dequant)
         codes, deq = (None if t is None else t.view(x.shape) for t in (codes, deq))
         if codes is not None and self.n_bits < 8:
             # The reference's clamp is one level looser than the bit-width (SURVEY D9): a row whose extremes tie exactly at a

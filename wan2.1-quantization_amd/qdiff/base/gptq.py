@@ -228,6 +228,30 @@ def requantize_model_(model, quant_config, hessians, path):
     return done
 
 
+def clip_needs_hessian(quant_config):
+    """Whether the config's `weight.clip` search reads the Hessians (`search: diag` / `hessian`): it then implies --hessian in
+    get_calib_data_wanx.py for every quantised Linear, as a `gptq:` section does for the layers it names."""
+    wq = quant_config.get("weight", None) if quant_config is not None else None
+    sec = None if wq is None else wq.get("clip", None)
+    return sec is not None and sec.get("search", None) in ("diag", "hessian")
+
+
+def clip_model_(model, hessians, path):
+    """ptq_wanx.py, before requantize_model_: the `weight.clip` search (`diag` / `hessian`) on every QuantizedLinear that has one,
+    with its Hessian from `hessians` (the file at `path`).  -> the number of layers fitted.  A layer without a Hessian in the file is
+    a KeyError that names both."""
+    from .quant_layer import QuantizedLinear
+
+    done = 0
+    for name, mod in model.named_modules():
+        if isinstance(mod, QuantizedLinear) and mod.clip is not None and mod.clip["search"] != "mse" and mod.quant_mode:
+            if name not in hessians:
+                raise KeyError(f"{name}: no Hessian for this layer in {path} (collect it with get_calib_data_wanx.py --hessian)")
+            mod.requantize_clip_(hessians[name])
+            done += 1
+    return done
+
+
 def load_codes_(model, state_dict, path):
     """Simulation mode of a GPTQ checkpoint: a QuantizedLinear re-derives its codes from the FP weight by round-to-nearest, so the
     layers the `gptq:` section names take theirs from the integer checkpoint instead (`<name>.weight` of int_weight.pt)."""

@@ -17,7 +17,7 @@ from viditq_extension import fused, qgemm
 
 from ..config import ListConfig
 from ..quarot import quarot_utils
-from .base_quantizer import (BLOCK_SCALES, FP8_FORMAT, FP8_GROUP, MX_BLOCK, MX_FORMATS, MXFP4_FORMAT, MXFP6_FORMAT, MXFP8_FORMAT, DynamicQuantizer, Fp8Quantizer,
+from .base_quantizer import (CLIP_BLOCK_GROUPS, CLIP_SEARCHES, CLIP_STEPS_MAX, clip_candidates, BLOCK_SCALES, FP8_FORMAT, FP8_GROUP, MX_BLOCK, MX_FORMATS, MXFP4_FORMAT, MXFP6_FORMAT, MXFP8_FORMAT, DynamicQuantizer, Fp8Quantizer,
                              MxQuantizer, StaticQuantizer, _pow2_f64, fp8_decode, fp8_group_expand, mx_decode, mx_decode_mixed, mx_pair, mx_quant_rows_mixed)
 from .gptq import BLOCK_MAX, gptq_prepare, gptq_section, gptq_solve
 from .low_rank import RANK_MAX, LowRankBranch, fit_low_rank, padded_rank
@@ -58,6 +58,7 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         self.group_size = None if self.mx else self.fp8_group if self.fp8 else \
             self._checked_group_size(quant_config, module_name, fp_module.weight.device)
         self.gptq = self._checked_gptq(quant_config, module_name)  # the `gptq:` section when it names this layer (gptq.py), or None
+        self.clip = self._checked_clip(quant_config, module_name)  # the `weight.clip` section (StaticQuantizer.search_clip), or None
         self.w_quantizer = self.a_quantizer = None
         self.channel_mask = None
         self.rotation_signs = None
@@ -319,6 +320,43 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
             raise ValueError(f"{name}: gptq with weight.group_size={self.group_size} needs an even group size and an even gptq.block")
         return sec
 
+    def _checked_clip(self, quant_config, module_name):
+        """The `weight.clip` section, `{search: mse | diag | hessian, steps: 20, max_shrink: 0.5}` (None without the key), or the
+        refusal of what the clip search has no form for, before any weight is quantised: the message names the layer and the key.
+        The search scales the extremes a plain QuantizedLinear's StaticQuantizer takes its grid from."""
+        wq = quant_config.get("weight", None)
+        sec = None if wq is None else wq.get("clip", None)
+        if sec is None:
+            return None
+        name = module_name or type(self).__name__
+        if self.uses_mask or self.uses_rotation:
+            raise NotImplementedError(f"{name}: weight.clip with {type(self).__name__} is not supported: the SmoothQuant / QuaRot / "
+                                      "ViDiT layer classes re-derive their weight after a transform (leave the layer to the plain "
+                                      "QuantizedLinear)")
+        if wq.get("format", None) is not None:
+            raise NotImplementedError(f"{name}: weight.clip with weight.format={wq.get('format')!r} is not supported: the clip search "
+                                      f"scales an integer grid's extremes ({MXFP4_FORMAT} has weight.block_scale: search)")
+        if isinstance(wq["n_bits"], ListConfig):
+            raise NotImplementedError(f"{name}: weight.clip with a bit-width list (MixedPrecisionStaticQuantizer) is not supported")
+        unknown = [k for k in sec.keys() if k not in ("search", "steps", "max_shrink")]
+        if unknown:
+            raise ValueError(f"{name}: weight.clip.{unknown[0]} is not a known key of the `clip:` section (it has three: search, steps, "
+                             "max_shrink)")
+        search, steps, shrink = sec.get("search", None), sec.get("steps", 20), sec.get("max_shrink", 0.5)
+        if search not in CLIP_SEARCHES:
+            raise ValueError(f"{name}: weight.clip.search={search!r} must be one of {CLIP_SEARCHES}")
+        if isinstance(steps, bool) or not isinstance(steps, int) or not 1 <= steps <= CLIP_STEPS_MAX:
+            raise ValueError(f"{name}: weight.clip.steps={steps!r} must be an integer in 1..{CLIP_STEPS_MAX}")
+        if isinstance(shrink, bool) or not isinstance(shrink, (int, float)) or not 0 < shrink <= 1 or clip_candidates(steps, shrink) < 1:
+            raise ValueError(f"{name}: weight.clip.max_shrink={shrink!r} must be a number in (0, 1] with floor(max_shrink * steps) >= 1 "
+                             f"(steps={steps})")
+        if search == "hessian" and self.group_size not in CLIP_BLOCK_GROUPS:
+            why = ("a whole-row block is in_features x in_features per row; `search: diag` is the per-channel form"
+                   if self.group_size is None else "the block is held in LDS")
+            raise NotImplementedError(f"{name}: weight.clip.search: hessian needs weight.group_size in {CLIP_BLOCK_GROUPS} (it is "
+                                      f"{self.group_size!r}): {why}")
+        return {"search": search, "steps": steps, "max_shrink": shrink}
+
     def _refuse_adapter(self):
         if self.mx_n8 is not None:
             raise NotImplementedError(f"{self._lr_name()}: set_low_rank with mx.outlier_channels is not supported: wanq_gemm_mx_mixed "
@@ -440,7 +478,8 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         w = self.fp_module.weight.data.detach().float()
         if tuple(H.shape) != (self.in_features, self.in_features):
             raise ValueError(f"{name}: the Hessian is {tuple(H.shape)}, expected {(self.in_features, self.in_features)}")
-        self.w_quantizer.init_quant_params(w)
+        if self.clip is None or self.clip["search"] == "mse":
+            self.w_quantizer.init_quant_params(w)  # (a `diag` / `hessian` clip layer keeps the grid requantize_clip_ fitted)
         self.w_quantizer.init_done = True
         damp, block = float(self.gptq.get("damp", 0.01)), int(self.gptq.get("block", BLOCK_MAX))
         if self.gptq.get("act_order", False):  # channels in order of descending diag H; codes and deq come back in the original order
@@ -450,6 +489,23 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
             U, w0 = gptq_prepare(H, w, damp)
             codes, deq = gptq_solve(w0, U, self.w_quantizer, block)
         self._requantize(w, (codes, deq))
+        return self
+
+    def requantize_clip_(self, H):
+        """Fit the layer's grid by the `weight.clip` search on its calibration Hessian H = X^T X (fp32 [K, K], from
+        get_calib_data_wanx.py --hessian; `search: diag` reads its diagonal, `hessian` its g x g diagonal blocks), then re-derive
+        codes and weight.data by round-to-nearest on that grid.  A PTQ step: it runs before requantize_gptq_, which then solves on
+        the clipped grid; delta / zero_point travel in the quant-parameter file.  In place; -> self."""
+        name = self.module_name or type(self).__name__
+        if self.clip is None or self.clip["search"] == "mse":
+            raise NotImplementedError(f"{name}: requantize_clip_ needs weight.clip.search: diag or hessian (`mse` needs no Hessian and "
+                                      "is part of the quantiser's initialisation)")
+        if tuple(H.shape) != (self.in_features, self.in_features):
+            raise ValueError(f"{name}: the Hessian is {tuple(H.shape)}, expected {(self.in_features, self.in_features)}")
+        w = self.fp_module.weight.data.detach().float()
+        self.w_quantizer.search_clip(w, H)
+        self.w_quantizer.init_done = True
+        self._requantize(w)
         return self
 
     def set_codes_(self, codes):

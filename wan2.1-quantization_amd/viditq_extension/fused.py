@@ -536,6 +536,51 @@ def gram_accumulate_onepass_(H, x):
     return H
 
 
+def _clip_search(entry, w, side, side_shape, R, head, tail, n_bits, sym, qmin, qmax, steps, n_cand, want_table):
+    for n, t, shape in (("w", w, None), side + (side_shape,)):
+        if t is None:
+            continue
+        _C.check_gpu(n, t)
+        _C.check_dtype(n, t, torch.float32)
+        _C.check_contig(n, t)
+        if shape is not None:
+            _C.check_shape(n, t, *shape)
+    _C.check_same_device(w, side[1])
+    out = torch.empty(2, R, dtype=torch.float32, device=w.device)
+    sel = torch.empty(R, dtype=torch.int32, device=w.device)
+    table = torch.empty(R, int(n_cand), dtype=torch.float32, device=w.device) if want_table else None
+    with torch.cuda.device(w.device):
+        _C.call(entry, _C.ptr(w), _C.ptr(side[1]), *head, int(n_bits), int(bool(sym)), int(qmin), int(qmax), int(steps), int(n_cand),
+                _C.ptr(out[0]), _C.ptr(out[1]), _C.ptr(sel), _C.ptr(table), *tail, _C.stream())
+    return out[0], out[1], sel, table
+
+
+def clip_search(w, n_bits, sym, qmin, qmax, steps, n_cand, chan_w=None, want_table=False):
+    """The elementwise clip search (wanq_clip_search): w fp32 [R, cols], the quantiser's rows; per row the grid of the candidate
+    s < n_cand (extremes scaled by 1 - s / steps) with the smallest sum_j h_j e_j^2, h = 1 or, with chan_w fp32 [a multiple of
+    cols], the channel weights of row r at chan_w[(r % (len / cols)) * cols ..].  -> (delta fp32 [R], zp fp32 [R], s int32 [R],
+    the objectives fp32 [R, n_cand] or None)."""
+    if w.dim() != 2:
+        raise RuntimeError(f"Tensor w must be a matrix, got {tuple(w.shape)}")
+    R, cols = w.shape
+    if chan_w is not None and (chan_w.dim() != 1 or chan_w.numel() % cols):
+        raise RuntimeError(f"Tensor chan_w must be a vector of a multiple of {cols} values, got {tuple(chan_w.shape)}")
+    return _clip_search("wanq_clip_search", w, ("chan_w", chan_w), None, R, (0 if chan_w is None else chan_w.numel(),), (R, cols),
+                        n_bits, sym, qmin, qmax, steps, n_cand, want_table)
+
+
+def clip_search_blocks(w, hblocks, n_bits, sym, qmin, qmax, steps, n_cand, want_table=False):
+    """The block clip search (wanq_clip_search_blocks): w fp32 [N, K], hblocks fp32 [K / g, g, g] the diagonal blocks of the layer's
+    Hessian (g = 32, 64, 128); per (weight row, group) the candidate with the smallest e H_gg e^T.  The outputs are those of
+    clip_search on w.view(-1, g): row n K / g + gi."""
+    if w.dim() != 2 or hblocks is None or hblocks.dim() != 3:
+        raise RuntimeError("clip_search_blocks: w must be a matrix and hblocks [K / g, g, g]")
+    N, K = w.shape
+    g = hblocks.shape[-1]
+    return _clip_search("wanq_clip_search_blocks", w, ("hblocks", hblocks), (K // g if g else 0, g, g), N * (K // g if g else 0), (g,),
+                        (N, K), n_bits, sym, qmin, qmax, steps, n_cand, want_table)
+
+
 def _check_gptq(w, u, err, c0, cols):
     for n, t in (("w", w), ("u", u), ("err", err)):
         _C.check_gpu(n, t)

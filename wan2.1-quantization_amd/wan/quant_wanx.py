@@ -133,6 +133,10 @@ class QuantWanModel(WanModel, QuantModel):
                         raise NotImplementedError(f"{name}: the reference's int_weight.pt format derives its codes from the FP weight "
                                                   "by the reference's own half-precision equation; a `gptq:` layer's codes come "
                                                   "from the solver (save with reference_format=False)")
+                    if mod.clip is not None:
+                        raise NotImplementedError(f"{name}: the reference's int_weight.pt format derives its grid from the FP "
+                                                  "weight's extremes; a `weight.clip` layer's grid comes from the clip search (save "
+                                                  "with reference_format=False)")
                     if mod.group_size is not None:
                         raise NotImplementedError(f"{name}: the reference's int_weight.pt format has one scale per output channel "
                                                   "(weight.group_size is set; save with reference_format=False)")
