@@ -348,6 +348,29 @@ int wanq_gemm_wq16_lowrank(const void* a, const void* w, int dtype, int w_bits, 
                            const void* t, const void* b, int R, void* out, int out_dtype, const void* bias, int bias_dtype,
                            const float* gate, const void* residual, int epi_flags, int64_t M, int N, int K, void* stream);
 
+/* W4A16 MXFP4: 16-bit activations against OCP MXFP4 weights, the weight-only cell of the MX grid (csrc/gemm_wq16_mx.hip).  a is
+ * [M, K] of `dtype` (WANQ_BF16 or WANQ_F16); w is packed e2m1 [N, K/2] in wanq_gemm_mx's layout (element k in byte k / 2, even k in
+ * the low nibble -- not wanq_pack_w4's); sw_u8 is E8M0 bytes [N, K/32]; row_exp is uint8 [N], one reference exponent per output
+ * channel, chosen by the caller (kernel mode: clamp(max_b sw_u8[n, b] - 13, 0, 254), bytes of 255 ignored):
+ *   r          = sw_u8[n, k/32] - row_exp[n]
+ *   op[n,k]    = e2m1(w[n,k]) * 2^r         if RLO <= r <= 13, written exactly into the 16-bit operand (sign, table, exponent add)
+ *              = 0                          if r < RLO          (RLO = -13 for fp16, -112 for bf16: below it the product leaves the
+ *                                                                normal range of the operand type; the whole block is flushed)
+ *   acc        = sum_k a[m,k] * op[n,k]     fp32, on v_mfma_f32_16x16x32_{bf16,f16}, wanq_gemm_bf16's summation order
+ *   y          = fma(acc, 2^(row_exp[n] - 127), bias[n]);  GELU, gate + residual and the one rounding to out_dtype as above.
+ * e2m1(c) 2^r has at most two significant bits, so it is a number of the operand type and every product is exact in fp32; the scale
+ * rides in the operand's exponent field and there is no per-block fp32 fold.  The factor 2^(row_exp - 127) is exact in fp32 (row_exp
+ * = 0: the subnormal 2^-127; 255: +inf).  For r > 13 -- a byte the layer's row_exp never leaves -- the result is unspecified, but every
+ * access stays in bounds.  Scale byte 255 (OCP's NaN) is read as the host's mx_decode reads it, as the exponent 2^128, r = 255 -
+ * row_exp: no NaN is made of it.
+ * Any M >= 1; N % 8 == 0; K % 64 == 0; a, w, out, residual, sw_u8 and row_exp 16-byte aligned, gate and bias aligned to 4 elements.
+ * Anything else is refused before any launch (WANQ_E_SHAPE / WANQ_E_ARG, the message names the rule).
+ * Determinism: with row_exp = 127 and bias NULL the output is bit-equal to wanq_gemm_bf16 on op cast to `dtype`; a row gives the
+ * same bits in any launch. */
+int wanq_gemm_wq16_mx(const void* a, const uint8_t* w, int dtype, const uint8_t* sw_u8, const uint8_t* row_exp, void* out,
+                      int out_dtype, const void* bias, int bias_dtype, const float* gate, const void* residual, int epi_flags,
+                      int64_t M, int N, int K, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * PTQ calibration reduction: running per-channel absmax over tokens,
  *   colmax[c] = max(colmax[c], max_r |x[r,c]|)        (colmax fp32[cols], caller zero-initialises)

@@ -2,7 +2,8 @@
 // channel scales) and gemm_mx.hip (OCP MX: e4m3 tokens against e4m3 or packed e2m1 weights, E8M0 block scales) copy BOTH halves of
 // a K-tile into LDS and are one kernel, gemm_tile_kernel below, with a policy each (gemm_mx.hip's W4A4 form, packed e2m1 on both
 // sides, and its W6A6 / W4A6 forms, packed e2m3 tokens, are further policies of it); gemm_wq16.hip (integer weight codes converted
-// in registers, plain and group-wise) copies the token half only and has its own loop.  All four use the tile geometry, Frame, the
+// in registers, plain and group-wise) copies the token half only and has its own loop, and so does gemm_wq16_mx.hip (packed e2m1
+// codes decoded in registers with the E8M0 block scale in the operand's exponent).  All of them use the tile geometry, Frame, the
 // LDS-DMA sources and issue, the fragment addresses and reads, epilogue16, the launch parameters and helpers and the argument rules
 // of the extern "C" entries; gemm_tile_kernel is used by the first three.
 //
@@ -197,17 +198,28 @@ __device__ __forceinline__ void zero_acc(v4f (&acc)[4][4]) {
 
 // epilogue, fp32: acc + bias, or with SCALED acc * sw + bias in one fma, or with TOKEN (gemm_fp8.hip) (acc * sa[m]) * sw + bias, the
 // per-token factor first and then one fma; with LOWRANK (gemm_wq16.hip) + lr, a second accumulator set, one fp32 add behind the bias;
-// GELU; residual + y * gate; one rounding to OUT
-template <int OUT, bool SCALED, bool TOKEN, bool LOWRANK>
+// GELU; residual + y * gate; one rounding to OUT.  EXP8 (gemm_wq16_mx.hip, with SCALED): sw is uint8 [N] biased exponents, the factor
+// 2^(sw[n] - 127) built in the fp32 exponent field (byte 0: the subnormal 2^-127)
+template <int OUT, bool SCALED, bool TOKEN, bool LOWRANK, bool EXP8 = false>
 __device__ __forceinline__ void epilogue16(const v4f (&acc)[4][4], const v4f (&lr)[4][4], const Frame& f, const Gemm16Params& p) {
   static_assert(!TOKEN || SCALED, "the per-token factor comes with the per-channel one");
+  static_assert(!EXP8 || (SCALED && !TOKEN), "the exponent bytes are the per-channel factor");
   const bool gelu = p.epi & WANQ_EPI_GELU, gres = p.epi & WANQ_EPI_GATE_RES;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int n = f.n0 + f.wn * 64 + j * 16 + f.fq * 4;
     if (n >= p.N) continue;
     float s4[4], b4[4] = {0.f, 0.f, 0.f, 0.f}, g4[4] = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (SCALED) load4_ch(p.sw, WANQ_F32, n, s4);
+    if constexpr (EXP8) {
+      const uint32_t e4 = *reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(p.sw) + n);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const uint32_t b = (e4 >> (8 * e)) & 0xffu;
+        s4[e] = __uint_as_float(b ? b << 23 : 0x00400000u);
+      }
+    } else if constexpr (SCALED) {
+      load4_ch(p.sw, WANQ_F32, n, s4);
+    }
     if (p.bias) load4_any(p.bias, p.bias_dtype, n, b4);
     if (gres) load4_ch(p.gate, WANQ_F32, n, g4);
 #pragma unroll

@@ -43,6 +43,7 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
     def __init__(self, in_features, out_features, bias, device, quant_config, fp_module, module_name=None):
         super().__init__(in_features, out_features, bias, device)
         self.fp_module, self.q_cfg = fp_module, quant_config
+        self.mx_weight_only = self._checked_weight_only(quant_config, module_name)  # `weight.weight_only: True`: the W4A16 MXFP4 form
         self.low_rank = self._checked_low_rank(quant_config, module_name)  # `weight.low_rank`: the LoRC rank (low_rank.py), or None
         self.mx = None  # the weight's MX format name (`format: mxfp8_e4m3` / `mxfp4_e2m1`), set by _checked_format
         self.mx_act = None  # ... and the activation's
@@ -85,6 +86,41 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         self.quant_mode = True
         self.module_name = module_name
 
+    def _checked_weight_only(self, quant_config, module_name):
+        """`weight.weight_only` of the config (False without the key): the opt-in to MXFP4 weights against unquantised 16-bit
+        activations, `weight: {format: mxfp4_e2m1, n_bits: 4, sym: True, weight_only: True}` and no `act:` section (W4A16 MXFP4,
+        wanq_gemm_wq16_mx).  Without it an MX weight format without an MX `act:` section stays refused as before.  What the form has
+        no kernel for is refused here, before any weight is quantised, and the message names the layer: an `act:` section, any other
+        weight format, `mx.block_hadamard` (the activation side would need the rotation), `mx.outlier_channels`, `weight.low_rank`,
+        and the SmoothQuant / QuaRot / ViDiT layer classes.  `weight.block_scale: search` is offline and weight-side: it goes with it."""
+        wq = quant_config.get("weight", None)
+        on = False if wq is None else wq.get("weight_only", False)
+        name = module_name or type(self).__name__
+        if not isinstance(on, bool):
+            raise ValueError(f"{name}: weight.weight_only={on!r} must be True or False")
+        if not on:
+            return False
+        why = None
+        mx = quant_config.get("mx", None)
+        if quant_config.get("act", None) is not None:
+            why = "together with an `act:` section is not supported: the form leaves the activations unquantised (drop the section, or drop the key)"
+        elif wq.get("format", None) != MXFP4_FORMAT:
+            why = (f"with weight.format={wq.get('format', None)!r} is not supported: the key opts in to {MXFP4_FORMAT} weights, whose "
+                   "block scale is exact in a 16-bit operand's exponent (integer weight-only configs need no key; an e2m3 or e4m3 value "
+                   "times a power of two is not exact in fp16)")
+        elif mx is not None and mx.get("block_hadamard", False):
+            why = "with mx.block_hadamard is not supported: the activation side would need the rotation, and it is not quantised"
+        elif mx is not None and mx.get("outlier_channels", None) is not None:
+            why = "with mx.outlier_channels is not supported: the outlier channels are built for the W4A4 pair only"
+        elif wq.get("low_rank", None) is not None:
+            why = "with weight.low_rank is not supported: wanq_gemm_wq16_mx sums no low-rank branch"
+        elif self.uses_mask or self.uses_rotation:
+            why = (f"with {type(self).__name__} is not supported: the SmoothQuant / QuaRot / ViDiT layer classes condition an activation "
+                   "quantiser (leave the layer to the plain QuantizedLinear)")
+        if why is not None:
+            raise NotImplementedError(f"{name}: weight.weight_only: True {why}")
+        return True
+
     def _checked_format(self, quant_config, module_name):
         """True when the config's `weight:` and `act:` sections both say `format: fp8_e4m3` (per-token dynamic e4m3 activations against
         per-channel e4m3 weights, wanq_gemm_fp8; with `group_size: 128` in both sections too, one scale per token or channel and per
@@ -100,6 +136,11 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
                 raise ValueError(f"{name}: {sec}.format={f!r} is not a known format (the format keys are {FP8_FORMAT!r}, "
                                  f"{MXFP8_FORMAT!r} and {MXFP4_FORMAT!r}); OCP MXFP6 e2m3, a finite-only format, is spelled "
                                  f"{MXFP6_FORMAT!r}")
+        if self.mx_weight_only:  # (no `act:` section and fw mxfp4_e2m1: _checked_weight_only) the weight side's rules alone
+            self._check_format_sections(name, (("weight", wq, fw),))
+            self._check_mx_layer(name, wq, fw)
+            self.mx = fw
+            return False
         if fw in MX_FORMATS or fa in MX_FORMATS:
             self._check_mx_format(name, wq, aq, fw, fa)
             self.mx, self.mx_act = fw, fa
@@ -146,6 +187,10 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         if mx_pair(fw, fa) is None or a4_as_8:
             raise NotImplementedError(f"{name}: {self._mx_pair_refusal(a4_as_8, fw, fa)}")
         self._check_format_sections(name, (("weight", wq, fw), ("act", aq, fa)))
+        self._check_mx_layer(name, wq, fw)
+
+    def _check_mx_layer(self, name, wq, fw):
+        """What an MX weight format asks of its layer beyond the sections' own rules, with or without an `act:` section."""
         g = wq.get("group_size", None)
         if g is not None and (isinstance(g, bool) or g != MX_BLOCK):
             raise NotImplementedError(f"{name}: weight.format: {fw} with weight.group_size={g!r} is not supported: an MX block is "
@@ -587,8 +632,8 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
         ViDiT layer without an `act:` section is "weight_only" too: `forward` runs its FP module, kernel mode refuses it by name."""
         if not self.quant_mode or self.w_quantizer is None:
             return "fp"
-        if self.a_quantizer is None:
-            return "weight_only"
+        if self.a_quantizer is None:  # ("weight_only_mx": `weight.weight_only: True`, MXFP4 codes against 16-bit activations)
+            return "weight_only_mx" if self.mx_weight_only else "weight_only"
         if self.fp8:
             return "fp8" if self.fp8_group is None else "fp8_grouped"
         return "mx" if self.mx else "int8_grouped" if self.group_size is not None else "int8"
@@ -600,6 +645,8 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
             return self.fp_module(x, *args, **kwargs)
         if kind == "weight_only":
             return self._forward_weight_only(x)
+        if kind == "weight_only_mx":
+            return self._forward_weight_only_mx(x)
         out_dtype = x.dtype if x.dtype in (torch.float16, torch.bfloat16, torch.float32) else torch.float32
         bias = None if self.bias is None else self.bias.detach().float().contiguous()
         y = self._FORWARDS[kind](self, x.reshape(-1, x.shape[-1]), out_dtype, bias)
@@ -740,6 +787,15 @@ class QuantizedLinear(LowRankBranch, nn.Linear):
                 else:
                     y = qgemm.wq16_linear(x2.contiguous(), codes, sw, zp, bias, w4=w4)
                 return y.view(*x.shape[:-1], self.out_features)
+        w = self.weight if self.weight.dtype == x.dtype else self.weight.to(x.dtype)
+        b = self.bias if self.bias is None or self.bias.dtype == x.dtype else self.bias.to(x.dtype)
+        return F.linear(x, w, b)
+
+    def _forward_weight_only_mx(self, x):
+        """`weight: {format: mxfp4_e2m1, weight_only: True}` without an `act:` section (W4A16 MXFP4): the weight was quantised by
+        MxQuantizer and the activation is left alone, y = F.linear(x, mx_decode(codes, scales), bias) -- `_forward_weight_only`'s
+        expression on the decoded MX weight, which `_requantize` keeps in weight.data (fp32; every value is exact in bf16, and in
+        fp16 wherever it is a normal fp16 number).  Kernel mode (HipLinearWq16Mx) runs wanq_gemm_wq16_mx on the codes."""
         w = self.weight if self.weight.dtype == x.dtype else self.weight.to(x.dtype)
         b = self.bias if self.bias is None or self.bias.dtype == x.dtype else self.bias.to(x.dtype)
         return F.linear(x, w, b)

@@ -365,6 +365,37 @@ def wq16_linear_refusal(M, N, K, group_size=None):
     return None
 
 
+def wq16_mx_linear(input, weight, scale_weight, row_exp, bias=None, out_dtype=None, gelu=False, gate=None, residual=None, out=None):
+    """y = epilogue(2^(row_exp[n] - 127) * input[M,K] @ op[N,K]^T) on the bf16 / fp16 matrix cores (wanq_gemm_wq16_mx,
+    csrc/gemm_wq16_mx.hip), the W4A16 MXFP4 product: `input` bf16 or fp16, `weight` uint8 [N, K/2] packed e2m1 codes in `mx_linear`'s
+    layout (not pack_w4's), `scale_weight` uint8 [N, K/32] E8M0 bytes, `row_exp` uint8 [N] (`wq16_mx_row_exp`).  op[n,k] = e2m1(code)
+    2^(scale_weight[n, k/32] - row_exp[n]) is written exactly into the 16-bit operand (blocks more than 13 binades below row_exp in
+    fp16, 112 in bf16, are flushed to zero); epilogue as `fp_linear`.  Not counted by the int8 timer (`set_timer`)."""
+    M, N, K = _check_operands16(input, "weight", weight, torch.uint8)
+    _C.check_shape("weight", weight, N, K // 2)
+    why = wq16_mx_linear_refusal(M, N, K)
+    if why is not None:
+        raise RuntimeError(f"wq16_mx_linear: {why}")
+    _check_mat("scale_weight", scale_weight, torch.uint8, N, K // 32)
+    _check_vec("row_exp", row_exp, N, (torch.uint8,))
+    return _launch16("wanq_gemm_wq16_mx", (_C.ptr(input), _C.ptr(weight), _C.dt(input), _C.ptr(scale_weight), _C.ptr(row_exp)),
+                     (input, weight, scale_weight, row_exp), bias, out_dtype or input.dtype, gelu, gate, residual, out, M, N, K)
+
+
+def wq16_mx_linear_refusal(M, N, K):
+    """Why wanq_gemm_wq16_mx would refuse an [M, K] x [N, K] product (None = accepted): `wq16_linear_refusal`'s rules."""
+    return _shape_refusal(M, N, K, 64)
+
+
+def wq16_mx_row_exp(scale_weight):
+    """The reference exponents kernel mode gives `wq16_mx_linear`: clamp(max_b scale_weight[n, b] - 13, 0, 254) over the bytes below
+    255, uint8 [N].  The row's largest block then sits at r = 13, the top of the 16-bit operand's window, and the 26 binades below it
+    are exact in fp16 (125 in bf16)."""
+    s = scale_weight.to(torch.int16)
+    top = torch.where(s < 255, s, torch.zeros_like(s)).amax(dim=1)
+    return (top - 13).clamp(0, 254).to(torch.uint8).contiguous()
+
+
 LOWRANK_MAX = 256  # the largest (padded) rank wanq_gemm_wq16_lowrank takes; ranks are padded to multiples of 64
 
 

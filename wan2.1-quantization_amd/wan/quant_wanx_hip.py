@@ -520,9 +520,51 @@ class HipLinearMx(LowRankBranch, _HipLinearCodes):
                                           gate=gate, residual=residual, out=out)
 
 
+class HipLinearWq16Mx(_HipLinearCodes):
+    """A W4A16 MXFP4 Linear (`weight: {format: mxfp4_e2m1, weight_only: True}` and no `act:` section): HipLinearMx's `weight` uint8
+    [N, K / 2] packed e2m1 codes, `scale_weight` uint8 [N, K / 32] E8M0 bytes and fp32 `bias` -- the same checkpoint keys, the same
+    `sharded` -- against the block's 16-bit activations as HipLinearWq16 consumes them (the source's `fp()`: layernorm_nobias_t2i_fuse
+    for an _LnSrc, the tensor itself for an _FpSrc), through qgemm.wq16_mx_linear (csrc/gemm_wq16_mx.hip): the codes become MFMA
+    fragments in registers with the block scale in their exponent field, GELU and gate + residual in the epilogue.  No activation
+    quantiser, no transform, so ffn.0 keeps the FFN's GELU in its epilogue.  `row_exp` uint8 [N] (qgemm.wq16_mx_row_exp) is no
+    checkpoint key: it is derived from `scale_weight` when the layer is built and again after a checkpoint was loaded
+    (`refresh_zp_gemm`), and stays replicated under --dit_fsdp."""
+    weight_only = True
+    plain_rows = False
+    sharded = ("weight", "scale_weight")
+    w_fmt = "mxfp4_e2m1"  # (`mx` stays None: this is no row of MX_PAIRS, and the checkpoint's optional MX records do not apply)
+
+    def __init__(self, in_features, out_features, bias=True, name="linear"):
+        self.name = name
+        super().__init__(in_features, out_features, bias, self.w_fmt + " with weight_only: True",
+                         qgemm.wq16_mx_linear_refusal(1, out_features, in_features), in_features // 2, (out_features, in_features // 32),
+                         torch.uint8, name)
+        self.register_buffer("row_exp", torch.zeros(out_features, dtype=torch.uint8), persistent=False)
+
+    @classmethod
+    def from_quantized(cls, ql, name="linear", act_dtype=torch.bfloat16):
+        """From a plain qdiff QuantizedLinear built with the weight-only MXFP4 form: the same codes and scale bytes."""
+        m = cls(ql.in_features, ql.out_features, ql.bias is not None, name).to(ql.fp_module.weight.device)
+        m._take(ql, ql.w_quantizer.scale_u8, name)
+        m.refresh_zp_gemm()
+        return m
+
+    def refresh_zp_gemm(self):
+        """After scale_weight was set or loaded from a checkpoint."""
+        self.row_exp.copy_(qgemm.wq16_mx_row_exp(self.scale_weight))
+
+    def operands(self, src):
+        return (src.fp(),)
+
+    def forward(self, x, out_dtype=None, gelu=False, gate=None, residual=None, out=None):
+        """Reads `weight` and `scale_weight` as they are now (--dit_fsdp re-points them at views of the gathered buffer)."""
+        return qgemm.wq16_mx_linear(x, self.weight, self.scale_weight, self.row_exp, self.bias, out_dtype, gelu=gelu, gate=gate,
+                                    residual=residual, out=out)
+
+
 # QuantizedLinear.kind -> the layer class that takes it over ("fp": the layer's FP module, below)
 _HIP_LINEAR_OF = {"int8": HipLinearW8A8, "int8_grouped": HipLinearW8A8, "weight_only": HipLinearWq16, "fp8": HipLinearFp8,
-                  "fp8_grouped": HipLinearFp8, "mx": HipLinearMx}
+                  "fp8_grouped": HipLinearFp8, "mx": HipLinearMx, "weight_only_mx": HipLinearWq16Mx}
 
 
 def _to_hip_linear(lin, n_bits, sym, act_dtype, fp_gemm="torch", name="linear"):
@@ -530,9 +572,9 @@ def _to_hip_linear(lin, n_bits, sym, act_dtype, fp_gemm="torch", name="linear"):
 
     if isinstance(lin, QuantizedLinear):
         cls = _HIP_LINEAR_OF.get(lin.kind)
-        if cls is HipLinearWq16 and act_dtype not in (torch.bfloat16, torch.float16):
+        if cls in (HipLinearWq16, HipLinearWq16Mx) and act_dtype not in (torch.bfloat16, torch.float16):
             raise ValueError(f"{name}: the weight-only GEMM takes bf16 or fp16 activations (act_dtype {act_dtype})")
-        if cls is HipLinearWq16 or cls is HipLinearMx:
+        if cls in (HipLinearWq16, HipLinearMx, HipLinearWq16Mx):
             return cls.from_quantized(lin, name, act_dtype)
         if cls is not None:
             return cls.from_quantized(lin, name)
